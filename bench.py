@@ -12,9 +12,10 @@ env of the rank's shard) over one batch of actions that is already resident in H
 CyberBattleChain size=10, 65 536 envs, attacker only, goal own 100 %, auto-reset, episodes truncated at 2 000
 steps (marlon's max_timesteps, attack_wrapper.py:38); actions are valid random actions in the style of
 CyberBattleEnv.sample_valid_action, recorded by an untimed rollout of the same engine and replayed from an
-HBM ring (the replay is exact: attacker-only Chain has no randomness).  Weak scaling: every rank owns its own
+HBM ring (the replay is exact: attacker-only Chain has no randomness; in a plain run the ring holds at most one
+episode's length of steps and is cycled beyond it, so any K fits).  Weak scaling: every rank owns its own
 65 536 envs (global env ids rank*E ..), no collective on the data path; the only collectives are the timing
-barrier / MAX / gathers and an all_gather of episode returns after the timed region.
+barrier / MAX / gathers and, with --full, an all_gather of episode returns after the timed region.
 
 The timed region replays the K steps from a hipGraph (launch-bound inner loop captured once), bracketed by
 barrier + synchronize on both sides (barrier, synchronize, K steps, synchronize, barrier; every rank times its own K steps between the two
@@ -26,7 +27,12 @@ events on the launch stream bracketing that timed region (/ K) and reported as a
 this process makes is a graph replay of the same shape (the recording rollout runs as ONE mcbs_rollout_random launch — a different kernel —
 and the per-launch event-pair cross-check is behind --event-pairs), so `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-extras
 --no-cpu-baseline` reports the same regime (profiles/round3_bench_headline*.json).
-Beside the headline (never as `value`): `configs` — the step kernels of BASELINE.json's configs 3, 4 (one GPU's shard) and
+
+A plain run does only that: set up, rehearse, warm up, time the K steps and print the line, whose `roofline` block is computed from
+the same timed region and the committed profiles.  `--dump-outputs DIR` then also writes what the last timed step returned to its
+caller, the per-env reward and terminated flag, as DIR/reward.npy and DIR/terminated.npy (float32; `_rank<r>` appended at N > 1):
+the inputs are seeded, so two builds can be compared output for output.
+With `--full`, beside the headline (never as `value`): `step_many`; `configs` — the step kernels of BASELINE.json's configs 3, 4 (one GPU's shard) and
 5 (one GPU's shard) timed the same way, with their roofline fraction from MEASURED HBM bytes (profiles/round2_step_*.json,
 tied to the kernel sources by a hash); `observe` — the observation tier; `cpu_baseline` — the CPU oracle (oracle/, a port of
 the reference's algorithm, NOT the product) timed on the host cores on a bounded sample of the same action ring, its rewards
@@ -55,6 +61,7 @@ B_STEP = 348            # algorithmic bytes per env-step, SURVEY.md section 8(d)
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
 METRIC = "env-steps/sec at 65536 envs, CyberBattleChain-10; bit-exact vs CPU ref"
 HEADLINE_KERNEL = "mcbs::step_kernel<0, 0, false, 0>"   # <PHASE whole step, packed sets, hot image through L1/L2, no defender>
+DUMP_MAX_BYTES = 64 << 20   # --dump-outputs: beyond this, a fixed seeded sample of the envs is written
 
 
 def parse_args(argv=None):
@@ -63,21 +70,31 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=1000)
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
-    ap.add_argument("--max-episode-steps", type=int, default=2000)
-    ap.add_argument("--cpu-envs", type=int, default=65536)
-    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="CPU oracle sample: repeat the recorded steps until about this long (1 core; half of it on all cores)")
+    ap.add_argument("--max-episode-steps", type=int, default=2000, help="truncation; also the most steps a plain run's action ring holds")
+    ap.add_argument("--full", action="store_true", help="after the headline, everything else bench.py measures and checks: step_many, the "
+                    "other configurations, resets, batch sweep, observation and wrapper tiers, the CPU oracle baseline and its comparison")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (per-env reward and terminated flag) "
+                    "to DIR/<name>.npy as float32")
+    ap.add_argument("--cpu-envs", type=int, default=65536, help="(--full) envs of the CPU oracle sample")
+    ap.add_argument("--cpu-seconds", type=float, default=8.0, help="(--full) CPU oracle sample: repeat the recorded steps until about this long "
+                    "(1 core; half of it on all cores)")
     ap.add_argument("--no-graph", action="store_true", help="time eager launches instead of a hipGraph replay")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--event-pairs", action="store_true", help="also replay the K steps eagerly with one HIP event pair per launch (cross-check; "
-                    "adds eager launches of the headline kernel to the process: leave off under rocprofv3)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the `configs` and `observe` legs (they run at N = 1 only)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU oracle baseline")
+    ap.add_argument("--event-pairs", action="store_true", help="(--full) also replay the K steps eagerly with one HIP event pair per launch "
+                    "(cross-check; adds eager launches of the headline kernel to the process: leave off under rocprofv3)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the legs beside the headline other than step_many and the CPU baseline")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend of the timing collectives for N>1 (nccl = RCCL; gloo is the "
                     "agreed fallback when RCCL cannot be brought up on every rank)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal on a one-GPU box: every rank uses cuda:0")
     ap.add_argument("--rehearse", action="store_true", help="launcher / collective / JSON plumbing only, NO engine and no GPU (CPU-safe: "
                     "tests/test_distributed_gloo.py); prints value null")
     ap.add_argument("--master-port", type=int, default=0, help="self-launch only: rendezvous port (0 = pick a free one)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.event_pairs and not args.full:
+        ap.error("--event-pairs is a cross-check of --full")
+    return args
 
 
 def free_port() -> int:
@@ -207,10 +224,10 @@ def rehearse(args, world, rank, local_rank) -> int:
         gathered = [torch.empty_like(mine) for _ in range(world)]
         dist.all_gather(gathered, mine)
         assert [float(g[0]) for g in gathered] == [float(r) for r in range(world)]
-    # the `configs` legs of a multi-rank run (configs 4 and 5: every rank its shard): one barrier-bracketed region and one gather of
-    # times per configuration, in the same order on every rank
+    # the `configs` legs of a multi-rank --full run (configs 4 and 5: every rank its shard): one barrier-bracketed region and one gather
+    # of times per configuration, in the same order on every rank
     cfg_rows = []
-    for i, name in enumerate(("config4", "config5") if world > 1 else ("config3", "config4", "config5")):
+    for i, name in enumerate(() if not args.full else ("config4", "config5") if world > 1 else ("config3", "config4", "config5")):
         if world > 1:
             dist.barrier()
         c0 = time.perf_counter()
@@ -225,7 +242,7 @@ def rehearse(args, world, rank, local_rank) -> int:
         cfg_rows.append({"name": name, "n_gpus": world, "ms_host_clock_max_over_ranks": el * 1e3, "env_steps_per_s": None})
     if rank == 0:
         print(json.dumps({"metric": METRIC, "value": None, "unit": "env-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-                          "configs": cfg_rows,
+                          **({"configs": cfg_rows} if args.full else {}), "full": args.full,
                           "ms_per_step": None, "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "int32",
                           "data": "synthetic", "rehearsal": "launcher and collectives only: no engine, no GPU, nothing measured",
                           "collective_backend": backend, "ranks_in_group": dist.get_world_size() if world > 1 else 1,
@@ -270,27 +287,37 @@ def main() -> int:
     # ---- headline: 65 536 Chain-10 envs per GPU, attacker only ----
     eng, topo, spec, desc = W.make_engine("headline", n_envs=E, env_id_base=rank * E, device=f"cuda:{local_rank}",
                                           max_episode_steps=args.max_episode_steps, seed=12345)
-    # untimed: W+K batches of valid random actions recorded into an HBM ring by ONE launch of the looping step kernel (the random agent
-    # sampled inside it: the actions mcbs_sample_actions(valid, seed, t) + mcbs_step would give, tests/test_gpu_parity.py)
-    ring = eng.rollout_random(Wm + K, valid=True, seed=12345, first_step=0, record_actions=True)[2]
+    # untimed: batches of valid random actions recorded into an HBM ring by ONE launch of the looping step kernel (the random agent
+    # sampled inside it: the actions mcbs_sample_actions(valid, seed, t) + mcbs_step would give, tests/test_gpu_parity.py).  A plain run
+    # records at most one episode's length (--max-episode-steps) and cycles the ring beyond it (timed_leg), so that its memory and graph
+    # capture stay bounded whatever K is: an env that ran to truncation is reset at that step and meets the recorded states again.
+    # --full records all W + K steps: its cross-checks replay them through other paths
+    ring_steps = Wm + K if args.full else min(Wm + K, args.max_episode_steps)
+    ring = eng.rollout_random(ring_steps, valid=True, seed=12345, first_step=0, record_actions=True)[2]
     torch.cuda.synchronize()
     leg = W.timed_leg(eng, ring, Wm, K, graph=not args.no_graph, barrier=barrier, restore=eng.rewind)
     elapsed_mine, region_us, rewards, dones = leg["elapsed_s"], leg["region_us"], leg["rewards"], leg["dones"]
     elapsed, per_rank = gather_times(elapsed_mine, world, coll_dev, group)
-    reward_sum_timed = rewards.double().sum(dim=0)          # per-env return over the K timed steps
-    done_cnt_timed = dones.long().sum(dim=0)                # per-env `terminated` flags raised in the K timed steps
-    n_done = int(done_cnt_timed.sum().item())
-    same = leg["rehearsal_equal"]
+    if args.dump_outputs:
+        last = (K - 1) % rewards.shape[0]                   # the row the last timed step wrote
+        dump_outputs(args.dump_outputs, {"reward": rewards[last], "terminated": dones[last]}, "" if world == 1 else f"_rank{rank}",
+                     DUMP_MAX_BYTES // world)
+    same = leg["rehearsal_equal"]                           # None: W or K exceeded the ring and the rehearsal replayed each graph once
     kernel_us = region_us
-    lib, h, dev = eng.lib, eng._h, eng.device
-    st = torch.cuda.current_stream().cuda_stream
+    pair_us = many = None
 
-    def launch(t_ring: int, t_out: int, stream: int) -> None:
-        rc = lib.mcbs_step(h, ring[t_ring].data_ptr(), rewards[t_out].data_ptr(), dones[t_out].data_ptr(), None, stream)
-        if rc != 0:
-            raise RuntimeError(lib.mcbs_last_error().decode())
+    if args.full:
+        reward_sum_timed = rewards.double().sum(dim=0)      # per-env return over the K timed steps
+        done_cnt_timed = dones.long().sum(dim=0)            # per-env `terminated` flags raised in the K timed steps
+        n_done = int(done_cnt_timed.sum().item())
+        lib, h, dev = eng.lib, eng._h, eng.device
+        st = torch.cuda.current_stream().cuda_stream
 
-    pair_us = None
+        def launch(t_ring: int, t_out: int, stream: int) -> None:
+            rc = lib.mcbs_step(h, ring[t_ring].data_ptr(), rewards[t_out].data_ptr(), dones[t_out].data_ptr(), None, stream)
+            if rc != 0:
+                raise RuntimeError(lib.mcbs_last_error().decode())
+
     if args.event_pairs:
         # cross-check (off by default: its K eager launches of the same kernel would mix a second regime into a rocprofv3 trace of
         # this process): one HIP event pair around EACH launch, same K steps, eager, from the same start state.  The pair itself
@@ -307,29 +334,35 @@ def main() -> int:
         pair_us = kernel_ms * 1e3 / max(1, launches)
         same = same and bool(torch.equal(rewards.double().sum(dim=0), reward_sum_timed) and torch.equal(dones.long().sum(dim=0), done_cnt_timed))
 
-    # ---- extra, NOT the headline: the same K recorded steps through mcbs_step_many (one launch, no per-step launch cost) ----
-    eng.reset()
-    if Wm:
-        eng.step_many(ring[:Wm])
-    many_r = torch.empty((K, E), dtype=torch.float32, device=dev)
-    many_d = torch.empty((K, E), dtype=torch.uint8, device=dev)
-    torch.cuda.synchronize()
-    m0, m1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    m0.record()
-    eng.step_many(ring[Wm:Wm + K], many_r, many_d)
-    m1.record()
-    torch.cuda.synchronize()
-    many_us = m0.elapsed_time(m1) * 1e3 / K
-    many_same = bool(torch.equal(many_r.double().sum(dim=0), reward_sum_timed) and torch.equal(many_d.long().sum(dim=0), done_cnt_timed))
+    if args.full:
+        # ---- extra, NOT the headline: the same K recorded steps through mcbs_step_many (one launch, no per-step launch cost) ----
+        eng.reset()
+        if Wm:
+            eng.step_many(ring[:Wm])
+        many_r = torch.empty((K, E), dtype=torch.float32, device=dev)
+        many_d = torch.empty((K, E), dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        m0, m1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        m0.record()
+        eng.step_many(ring[Wm:Wm + K], many_r, many_d)
+        m1.record()
+        torch.cuda.synchronize()
+        many_us = m0.elapsed_time(m1) * 1e3 / K
+        many_same = bool(torch.equal(many_r.double().sum(dim=0), reward_sum_timed) and torch.equal(many_d.long().sum(dim=0), done_cnt_timed))
+        # scripted-sequence entry point (no reference counterpart): K steps in ONE launch; reported beside, never as, `value`.
+        # Under the contract's 348 B model it exceeds the HBM peak (frac > 1): the state never leaves the caches between steps
+        many = {"us_per_step": many_us, "env_steps_per_s_rank0": E / (many_us * 1e-6), "rewards_and_dones_equal_timed_region": many_same,
+                "frac_by_348B_model": B_STEP * E / (many_us * 1e-6) / 1e9 / HBM_PEAK_GBS}
+        del many_r, many_d
 
-    # ---- optional logging collective (not on the data path): episode returns of every rank ----
-    if world > 1:
-        mine = reward_sum_timed.to(coll_dev)
-        gathered = [torch.empty_like(mine) for _ in range(world)]
-        dist.all_gather(gathered, mine, group=group)
+        # ---- optional logging collective (not on the data path): episode returns of every rank ----
+        if world > 1:
+            mine = reward_sum_timed.to(coll_dev)
+            gathered = [torch.empty_like(mine) for _ in range(world)]
+            dist.all_gather(gathered, mine, group=group)
 
     result = None
-    parity_ok = same and many_same
+    parity_ok = same is not False and (many is None or many["rewards_and_dones_equal_timed_region"])
     if rank == 0:
         bytes_per_launch = float(B_STEP) * E
         achieved = bytes_per_launch / (kernel_us * 1e-6) / 1e9
@@ -354,8 +387,7 @@ def main() -> int:
             "data": "synthetic",
             "config": {"workload": f"CyberBattleChain size=10, {E} envs per GPU, attacker-only, recorded valid random actions, "
                                    f"auto-reset, truncation at {args.max_episode_steps} steps",
-                       "envs_per_gpu": E, "launch": "hipGraph replay" if not args.no_graph else "eager",
-                       "episodes_ended_in_timed_region_rank0": n_done,
+                       "envs_per_gpu": E, "launch": "hipGraph replay" if not args.no_graph else "eager", "action_ring_steps": ring_steps,
                        # where the host clock's region goes: the device's share (HIP events) and the host's calls around it
                        "timed_region_breakdown_us_rank0": leg["host_breakdown"]},
             "collective_backend": backend, "ranks_in_group": world,
@@ -379,25 +411,25 @@ def main() -> int:
                          # the committed profile): latency, not bandwidth — the 10 MB of state are L2 / Infinity-Cache resident
                          "binding": binding,
                          "replay_rewards_and_dones_equal_timed_region": same},
-            # scripted-sequence entry point (no reference counterpart): K steps in ONE launch; reported beside, never as, `value`.
-            # Under the contract's 348 B model it exceeds the HBM peak (frac > 1): the state never leaves the caches between steps
-            "step_many": {"us_per_step": many_us, "env_steps_per_s_rank0": E / (many_us * 1e-6), "rewards_and_dones_equal_timed_region": many_same,
-                          "frac_by_348B_model": B_STEP * E / (many_us * 1e-6) / 1e9 / HBM_PEAK_GBS},
+            "full": args.full,
         }
+        if args.full:
+            result["config"]["episodes_ended_in_timed_region_rank0"] = n_done
+            result["step_many"] = many
     ring_cpu = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         n = min(args.cpu_envs, E)
         ring_cpu = ring[:, :n].cpu().numpy()
         ref_sum, ref_done = reward_sum_timed[:n].cpu().numpy(), done_cnt_timed[:n].cpu().numpy().astype(np.int32)
     eng.close()
-    del ring, rewards, dones, many_r, many_d, leg
+    del ring, rewards, dones, leg
     torch.cuda.empty_cache()
 
     # ---- beside the headline, every rank: the step kernels of the other BASELINE.json configurations.  N = 1: configs 3, 4 (one GPU's
     # shard) and 5 (one GPU's shard); N > 1: configs 4 and 5 are DEFINED as shards over the GPUs of a node, so every rank runs its own
     # shard (global env ids rank * shard ..) inside the same barrier / synchronize / MAX-over-ranks bracket and rank 0 reports the
     # aggregate env-steps/s ----
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         try:
             cfgs = extras_configs(W, world, rank, local_rank, barrier, lambda x: gather_times(x, world, coll_dev, group)[0])
             if rank == 0:
@@ -408,7 +440,7 @@ def main() -> int:
             parity_ok = False
     # ---- rank 0 only (the other ranks wait at the closing barrier): the headline kernel with episodes ending inside the timed
     # region, the observation tier and the wrapper tier ----
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         try:
             result["headline_with_resets"] = extras_resets(W, E, K if K <= 1000 else 1000, Wm, f"cuda:{local_rank}", not args.no_graph)
             parity_ok = parity_ok and result["headline_with_resets"]["rewards_dones_and_episodes_equal_rehearsal"]
@@ -484,6 +516,20 @@ def gather_times(elapsed_mine: float, world: int, coll_dev, group):
 
 def max_over_ranks(x: float, world: int, coll_dev, group) -> float:
     return gather_times(x, world, coll_dev, group)[0]
+
+
+def dump_outputs(out_dir: str, arrays: dict, suffix: str, max_bytes: int) -> None:
+    """Per-env device tensors [E] as float32 `out_dir/<name><suffix>.npy`.  When they hold more than max_bytes, the same fixed seeded
+    sample of env indices is taken from each, and the indices are written beside them (`env_index<suffix>.npy`, float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    host = {k: v.float().cpu().numpy() for k, v in arrays.items()}
+    n = len(next(iter(host.values())))
+    if 4 * len(host) * n > max_bytes:
+        idx = np.sort(np.random.default_rng(0).choice(n, max_bytes // (4 * len(host) + 8), replace=False))
+        host = {**{k: v[idx] for k, v in host.items()}, "env_index": idx.astype(np.float64)}
+    for k, v in host.items():
+        np.save(os.path.join(out_dir, f"{k}{suffix}.npy"), v)
 
 
 def layout_bytes_per_env_step(n_nodes: int) -> int:

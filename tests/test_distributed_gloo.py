@@ -101,7 +101,7 @@ def test_bench_self_launches_ranks_when_invoked_plainly():
     """`python bench.py --gpus 2` with no launcher in the environment (how the driver invokes N = 1) must start the two ranks
     itself and print rank 0's JSON line.  --rehearse keeps it CPU-safe: launcher, backend agreement, barrier / MAX / gathers and
     the JSON assembly run for real, the engine does not (value null)."""
-    p, line = _run_bench(["--gpus", "2", "--steps", "7", "--warmup", "2", "--rehearse"])
+    p, line = _run_bench(["--gpus", "2", "--steps", "7", "--warmup", "2", "--rehearse", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     assert line is not None and line["n_gpus"] == 2 and line["ranks_in_group"] == 2 and line["steps"] == 7 and line["warmup"] == 2
     assert line["self_launched"] is True and line["collective_backend"] == "gloo" and line["value"] is None
@@ -123,6 +123,7 @@ def test_bench_under_an_external_launcher_and_rank_failure_is_an_error():
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1 and '"self_launched": false' in lines[0]
+    assert '"full": false' in lines[0] and '"configs"' not in lines[0]      # a plain run has no legs beside the headline
     cmd[cmd.index("--gpus") + 1] = "4"                      # 2 ranks started, 4 announced
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode != 0

@@ -1,5 +1,5 @@
 """The driver's benchmark contract, exercised on the GPU box: `python bench.py --gpus 1 --steps K --warmup W` prints ONE JSON line with the
-fields the contract names, the parity flags hold (the metric says "bit-exact vs CPU ref": a run whose checks fail prints value null and exits
+fields the contract names (a plain run: the headline alone, and what its last step returned with --dump-outputs); with --full the parity flags hold (the metric says "bit-exact vs CPU ref": a run whose checks fail prints value null and exits
 non-zero), the roofline block is consistent with the timed region, and the counter files under profiles/ belong to the kernels being timed."""
 import json
 import os
@@ -14,7 +14,7 @@ REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 
 def test_bench_line_contract_small_run():
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "40", "--warmup", "10", "--cpu-seconds", "1",
-                        "--envs-per-gpu", "65536"], capture_output=True, text=True, timeout=600)
+                        "--envs-per-gpu", "65536", "--full"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -60,7 +60,7 @@ def test_bench_two_ranks_on_one_gpu():
     cuda:0), the ranks agree on a collective backend (RCCL refuses two ranks on one device, so gloo), each owns its own 65 536-env shard
     (global env ids rank * E ...), and rank 0 reports the whole-job throughput from the MAX of the per-rank times."""
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--single-device", "--steps", "60", "--warmup", "10",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -83,3 +83,40 @@ def test_build_then_smoke_in_one_process():
     HIP runtime the library brought in — the wrong one unless load_library imports torch first ("no ROCm-capable device is detected")."""
     out = subprocess.run([sys.executable, "-c", "import __graft_entry__ as g; g.build(); g.smoke()"], cwd=REPO, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0 and "smoke ok" in out.stdout, (out.stdout[-1500:], out.stderr[-1500:])
+
+
+@pytest.mark.parametrize("steps,warmup,episode", [(40, 10, 2000), (150, 20, 64)])
+def test_plain_run_is_the_headline_alone_and_dumps_its_last_step(tmp_path, steps, warmup, episode):
+    """`bench.py` without --full prints the headline line and nothing beside it; --dump-outputs writes what the last timed step returned
+    (reward, terminated: float32, one value per env), equal to the same W + K recorded steps replayed in this process through
+    mcbs_step_many.  At (150, 20, 64) the W + K steps exceed the episode length, so the action ring (64 steps) is cycled: two whole
+    passes and a remainder of timed steps."""
+    import numpy as np
+    import torch
+    from tools import workloads as W
+    E = 4096
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                        "--envs-per-gpu", str(E), "--max-episode-steps", str(episode), "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [ln for ln in p.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    b = json.loads(lines[0])
+    assert b["full"] is False and b["steps"] == steps and b["warmup"] == warmup and b["parity_ok"] is True and b["value"] is not None
+    assert b["unit"] == "env-steps/s" and b["higher_is_better"] is True and b["dtype"] == "int32"
+    assert abs(b["value"] - E * steps / (b["ms_per_step"] * steps * 1e-3)) / b["value"] < 1e-6
+    ring_steps = min(steps + warmup, episode)
+    assert b["config"]["action_ring_steps"] == ring_steps
+    assert b["roofline"]["replay_rewards_and_dones_equal_timed_region"] is (True if ring_steps == steps + warmup else None)
+    assert not {"step_many", "configs", "headline_with_resets", "batch_sweep", "observe", "wrapper", "cpu_baseline"} & set(b)
+    reward, terminated = np.load(tmp_path / "reward.npy"), np.load(tmp_path / "terminated.npy")
+    assert reward.dtype == terminated.dtype == np.float32 and reward.shape == terminated.shape == (E,)
+    eng, _, _, _ = W.make_engine("headline", n_envs=E, max_episode_steps=episode, seed=12345)
+    ring = eng.rollout_random(ring_steps, valid=True, seed=12345, first_step=0, record_actions=True)[2]
+    eng.rewind()
+    r, d = eng.step_many(ring[torch.arange(warmup + steps, device=ring.device) % ring_steps].contiguous())
+    torch.cuda.synchronize()
+    np.testing.assert_array_equal(reward, r[-1].float().cpu().numpy())
+    np.testing.assert_array_equal(terminated, d[-1].float().cpu().numpy())
+    assert float(r.sum()) > 0
+    eng.close()

@@ -173,6 +173,26 @@ def test_no_unbound_names_in_host_code():
     assert not [p for p in problems if p[1]], [p for p in problems if p[1]]
 
 
+def test_bench_dump_outputs_writes_float32_and_samples_beyond_its_cap(tmp_path):
+    """bench.py --dump-outputs: per-env tensors as float32 .npy; beyond the byte cap the same fixed seeded sample of envs from each,
+    with the sampled indices beside them, identical from run to run."""
+    import bench
+    r, d = torch.arange(1000, dtype=torch.float32) * 0.5, (torch.arange(1000) % 3 == 0).to(torch.uint8)
+    bench.dump_outputs(str(tmp_path / "all"), {"reward": r, "terminated": d}, "", bench.DUMP_MAX_BYTES)
+    out = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in ("reward", "terminated")}
+    assert all(v.dtype == np.float32 for v in out.values()) and sorted(os.listdir(tmp_path / "all")) == ["reward.npy", "terminated.npy"]
+    np.testing.assert_array_equal(out["reward"], r.numpy())
+    np.testing.assert_array_equal(out["terminated"], d.numpy())
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), {"reward": r, "terminated": d}, "_rank1", 1600)
+    idx = np.load(tmp_path / "a" / "env_index_rank1.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100 and np.all(np.diff(idx) > 0)          # 1600 B / (4 + 4 + 8 B per env)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "reward_rank1.npy"), r.numpy()[idx.astype(np.int64)])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "terminated_rank1.npy"), d.numpy()[idx.astype(np.int64)])
+    for k in ("env_index", "reward", "terminated"):
+        np.testing.assert_array_equal(np.load(tmp_path / "a" / f"{k}_rank1.npy"), np.load(tmp_path / "b" / f"{k}_rank1.npy"))
+
+
 def test_lazy_info_list_is_a_list_of_dicts_built_on_demand():
     """MarlonVecEnv's infos (marlon_amd/vecenv.py _InfoList): a real `list` whose per-env dicts — DummyVecEnv's keys, VecMonitor's
     `episode`, `terminal_observation` — only exist once somebody indexes or iterates it (SB3's _update_info_buffer does), built from

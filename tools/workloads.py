@@ -98,22 +98,27 @@ def graph_replay_us(eng, ring, K: int):
 
 
 def timed_leg(eng, ring, Wm: int, K: int, graph: bool, barrier, restore):
-    """W warm-up steps (ring[:W]) then EXACTLY K timed steps (ring[W:W+K]) of mcbs_step on `eng`, from the state restore() leaves.
-    Both step sequences are captured as hipGraphs (graph=True) and REHEARSED once, untimed; restore() then puts the engine back to the
-    start state, the warm-up graph is replayed, and the K timed steps run between barrier + synchronize on both sides with HIP events
-    on the launch stream around them.  Returns elapsed_s (host clock, this rank), region_us (event time / K), rewards / dones [K, E]
-    of the timed replay, rehearsal_equal (the rehearsal's per-env sums equal the timed replay's: the replay is deterministic)."""
+    """W warm-up steps then EXACTLY K timed steps of mcbs_step on `eng`, from the state restore() leaves.  Step s of the W + K (warm-up
+    first) replays ring[s % len(ring)]: a ring of W + K rows is replayed once, a shorter one is cycled (memory and capture time then
+    stay bounded whatever K is).  Both step sequences are captured as hipGraphs (graph=True; longer than the ring: one graph per ring
+    cycle, replayed once per cycle, and one for the remainder) and REHEARSED once, untimed; restore() then puts the engine back to the
+    start state, the warm-up is replayed, and the K timed steps run between barrier + synchronize on both sides with HIP events on the
+    launch stream around them.  Returns elapsed_s (host clock, this rank), region_us (event time / K), rewards / dones of the timed
+    replay ([min(K, len(ring)), E]: timed step t writes row t % min(K, len(ring)), so the last step's row is (K - 1) % that),
+    rehearsal_equal (the rehearsal's per-env sums equal the timed replay's: the replay is deterministic; None when a sequence is longer
+    than the ring, as the rehearsal then replays each graph once rather than the whole sequence)."""
     import torch
     E, dev = eng.E, eng.device
     lib, h = eng.lib, eng._h
-    rewards = torch.empty((K, E), dtype=torch.float32, device=dev)
-    dones = torch.empty((K, E), dtype=torch.uint8, device=dev)
-    wr = torch.empty((max(Wm, 1), E), dtype=torch.float32, device=dev)
-    wd = torch.empty((max(Wm, 1), E), dtype=torch.uint8, device=dev)
+    R = ring.shape[0]
+    rewards = torch.empty((min(K, R), E), dtype=torch.float32, device=dev)
+    dones = torch.empty((min(K, R), E), dtype=torch.uint8, device=dev)
+    wr = torch.empty((max(min(Wm, R), 1), E), dtype=torch.float32, device=dev)
+    wd = torch.empty((max(min(Wm, R), 1), E), dtype=torch.uint8, device=dev)
 
-    def run_steps(t0: int, n: int, r, d, stream: int) -> None:
+    def run_steps(s0: int, n: int, r, d, stream: int) -> None:
         for t in range(n):
-            if lib.mcbs_step(h, ring[t0 + t].data_ptr(), r[t].data_ptr(), d[t].data_ptr(), None, stream) != 0:
+            if lib.mcbs_step(h, ring[(s0 + t) % R].data_ptr(), r[t % r.shape[0]].data_ptr(), d[t % d.shape[0]].data_ptr(), None, stream) != 0:
                 raise RuntimeError(lib.mcbs_last_error().decode())
 
     def capture(t0: int, n: int, r, d):
@@ -127,20 +132,30 @@ def timed_leg(eng, ring, Wm: int, K: int, graph: bool, barrier, restore):
         torch.cuda.synchronize()
         return g          # capture does not execute: the engine's state is untouched
 
-    if graph:
-        g_warm = capture(0, Wm, wr, wd) if Wm else None
-        g_timed = capture(Wm, K, rewards, dones)
-        warm = (lambda: g_warm.replay()) if Wm else (lambda: None)
-        timed = lambda: g_timed.replay()
-    else:
+    def sequence(s0: int, n: int, r, d):
+        """(run, rehearse) of steps s0 .. s0 + n - 1: `reps` whole passes of c = min(n, R) steps (each pass starts at ring row s0 % R
+        again), then the remaining `tail` steps; rehearse() runs each distinct pass once."""
+        c = min(n, R)
+        reps, tail = divmod(n, c) if n else (0, 0)
+        if graph:
+            gs = [(capture(s0, m, r, d), k) for m, k in ((c, reps), (tail, 1)) if m]
+
+            def run():
+                for g, k in gs:
+                    for _ in range(k):
+                        g.replay()
+            return run, lambda: [g.replay() for g, _ in gs]
         st = torch.cuda.current_stream().cuda_stream
-        warm = lambda: run_steps(0, Wm, wr, wd, st)
-        timed = lambda: run_steps(Wm, K, rewards, dones, st)
+        return (lambda: run_steps(s0, n, r, d, st)), (lambda: [run_steps(s0, m, r, d, st) for m in (c, tail)])
+
+    warm, warm_rehearse = sequence(0, Wm, wr, wd)
+    timed, timed_rehearse = sequence(Wm, K, rewards, dones)
+    whole = Wm <= R and K <= R                        # the rehearsal is then the whole W + K steps
 
     # rehearsal (untimed) from the start state, then back to it
     restore()
-    warm()
-    timed()
+    warm_rehearse()
+    timed_rehearse()
     torch.cuda.synchronize()
     reh_r, reh_d = rewards.double().sum(dim=0), dones.long().sum(dim=0)
     rewards.zero_()
@@ -168,7 +183,7 @@ def timed_leg(eng, ring, Wm: int, K: int, graph: bool, barrier, restore):
     elapsed = t4 - t0                                 # this rank's K steps, device work drained; the MAX over ranks is the job's time
     barrier()                                         # (the closing barrier brackets the region; its own latency is not part of the K steps)
     region_us = ev0.elapsed_time(ev1) * 1e3 / K       # device time per launch over the timed region, launch gaps included
-    same = bool(torch.equal(rewards.double().sum(dim=0), reh_r) and torch.equal(dones.long().sum(dim=0), reh_d))
+    same = bool(torch.equal(rewards.double().sum(dim=0), reh_r) and torch.equal(dones.long().sum(dim=0), reh_d)) if whole else None
     host = {"event_record_us": (t1 - t0) * 1e6, "enqueue_us": (t2 - t1) * 1e6, "event_record2_us": (t3 - t2) * 1e6, "synchronize_us": (t4 - t3) * 1e6,
             "device_region_us": region_us * K, "host_region_us": elapsed * 1e6}
     return {"elapsed_s": elapsed, "region_us": region_us, "rewards": rewards, "dones": dones, "rehearsal_equal": same, "host_breakdown": host}
