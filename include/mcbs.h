@@ -376,6 +376,26 @@ int  mcbs_decode_attacker_actions(mcbs_batch*, const int64_t* multidiscrete, con
 uint64_t mcbs_discrete_action_count(const mcbs_batch*);
 int  mcbs_mask_logits(mcbs_batch*, void* logits, int32_t dtype, size_t row_stride, float fill, void* stream);
 
+/* ---- bit-packed Discrete action masks: stored per rollout step, applied at update time (MaskablePPO's evaluate_actions) ----
+ * Format: row e covers env (or stored sample) e, device uint32_t [rows, row_words].  Bit a of a row is bit (a & 31) of word (a >> 5),
+ * set iff action a is allowed in MaskedDiscreteAttackerWrapper's order (connect ((s*N+t)*P+p)*C+c, then local s*L+l, then remote
+ * (s*N+t)*R+r: the order of mcbs_mask_logits and mask_discrete).  W = ceil(A / 32) words carry the mask, A =
+ * mcbs_discrete_action_count; bits from A on in word W-1 are zero; words from W up to row_words are never touched.
+ *
+ * mcbs_pack_action_mask: the packed mask of the LAST observation of every env, rebuilt from the per-env digest exactly like
+ *   mcbs_mask_logits (same preconditions: MCBS_ESTATE under MCBS_DEFENDER_RANDOM_EVENTS and while the digests cannot be trusted).
+ *   MCBS_EINVAL when bits is NULL or row_words < W.
+ * mcbs_apply_packed_mask: logits[i, a] = bit(i, a) ? logits[i, a] : fill for i < n_rows, a < A.  n_rows is any count (e.g. a shuffled
+ *   minibatch gathered from stored masks); the batch only supplies the device and A, so no digest is needed (ExternalRandomEvents
+ *   batches too, given bits packed by the caller).  dtype, the write-only contract (logits never read, allowed actions left alone)
+ *   and the bfloat16 rounding of `fill` are those of mcbs_mask_logits.  logits_row_stride in elements, >= A.
+ * mcbs_unpack_action_mask: out[i, a] = bit(i, a) as a 0 / 1 byte for i < n_rows, a < A; bytes from A up to out_row_stride are untouched. */
+int  mcbs_pack_action_mask(mcbs_batch*, uint32_t* bits, size_t row_words, void* stream);
+int  mcbs_apply_packed_mask(const mcbs_batch*, const uint32_t* bits, size_t bits_row_words, void* logits, int32_t dtype, size_t logits_row_stride,
+                            uint64_t n_rows, float fill, void* stream);
+int  mcbs_unpack_action_mask(const mcbs_batch*, const uint32_t* bits, size_t bits_row_words, uint8_t* out, size_t out_row_stride,
+                             uint64_t n_rows, void* stream);
+
 /* ---- learned defender: marlon/baseline_models/env_wrappers/defend_wrapper.py:197-327,329-412,492-534
  * and marlon/defender_agents/defender.py:31-107, for batches created with MCBS_DEFENDER_EXTERNAL ---- */
 typedef struct mcbs_defender_obs {   /* DefenderEnvWrapper.observe: four MultiBinary fields, int8, network node order */

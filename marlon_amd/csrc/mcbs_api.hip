@@ -17,6 +17,7 @@
 #include "mcbs_aux.hip"
 #include "mcbs_defend.hip"
 #include "mcbs_logits.hip"
+#include "mcbs_packed_mask.hip"
 #include "mcbs_wrapper_fused.hip"
 
 using namespace mcbs;
@@ -1182,24 +1183,43 @@ extern "C" uint64_t mcbs_discrete_action_count(const mcbs_batch* b) {
     return N * N * b->C.P * C + N * b->C.L + N * N * b->C.R;
 }
 
+// The Discrete mask of the last observation is rebuilt from the per-env digests (mcbs_mask_logits, mcbs_pack_action_mask): refused
+// under ExternalRandomEvents and while the digests cannot be trusted
+static int digest_usable(const mcbs_batch* b, const char* who) {
+    if (b->cfg.defender_kind == MCBS_DEFENDER_RANDOM_EVENTS)
+        return fail(MCBS_ESTATE, "%s: under ExternalRandomEvents a node's local-vulnerability mask changes with the defender's "
+                                 "edits and is not part of the observation digest; use the materialised mask (mcbs_observe)", who);
+    if (b->digest_state != 1)
+        return fail(MCBS_ESTATE, b->digest_state == 0 ? "%s: no observation has been taken since the batch was created, wholly reset or given a state "
+                                                        "(the mask is rebuilt from the digest the last observation left per env)"
+                                                      : "%s: envs were reset by mask and not re-observed (mcbs_observe_masked) since", who);
+    return MCBS_OK;
+}
+
+static int discrete_geom(const mcbs_batch* b, LogitsGeom& G) {
+    const uint64_t A64 = mcbs_discrete_action_count(b);
+    if (A64 >= (1ull << 31)) return fail(MCBS_ELIMIT, "Discrete action space too large for one launch");
+    G.N = b->cfg.maximum_node_count; G.C = b->cfg.maximum_total_credentials; G.L = b->C.L; G.R = b->C.R; G.RL = b->C.P * G.C;
+    G.M = G.N * G.N * G.RL; G.ML = G.N * G.L; G.A = (uint32_t)A64;
+    G.dRL = fast_div_host(G.RL); G.dC = fast_div_host(G.C); G.dN = fast_div_host(G.N); G.dL = fast_div_host(G.L); G.dR = fast_div_host(G.R);
+    return MCBS_OK;
+}
+
+static uint16_t bf16_fill(float fill) {                  // float -> bfloat16, round to nearest even
+    uint32_t bits;
+    memcpy(&bits, &fill, 4);
+    return (bits & 0x7FFFFFFFu) > 0x7F800000u ? (uint16_t)((bits >> 16) | 0x40u) : (uint16_t)((bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16);
+}
+
 extern "C" int mcbs_mask_logits(mcbs_batch* b, void* logits, int32_t dtype, size_t row_stride, float fill, void* stream) {
     if (!b || !logits) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
     if (dtype != MCBS_LOGITS_F32 && dtype != MCBS_LOGITS_BF16) return fail(MCBS_EINVAL, "logits dtype must be MCBS_LOGITS_F32 or MCBS_LOGITS_BF16");
-    if (b->cfg.defender_kind == MCBS_DEFENDER_RANDOM_EVENTS)
-        return fail(MCBS_ESTATE, "mcbs_mask_logits: under ExternalRandomEvents a node's local-vulnerability mask changes with the defender's "
-                                 "edits and is not part of the observation digest; use the materialised mask (mcbs_observe)");
-    if (b->digest_state != 1)
-        return fail(MCBS_ESTATE, b->digest_state == 0 ? "mcbs_mask_logits: no observation has been taken since the batch was created, wholly reset or given a state "
-                                                        "(the mask is rebuilt from the digest the last observation left per env)"
-                                                      : "mcbs_mask_logits: envs were reset by mask and not re-observed (mcbs_observe_masked) since");
-    const uint64_t A64 = mcbs_discrete_action_count(b);
-    if (A64 >= (1ull << 31)) return fail(MCBS_ELIMIT, "Discrete action space too large for one launch");
-    if (row_stride < A64) return fail(MCBS_EINVAL, "row_stride %zu is shorter than the %llu Discrete actions", row_stride, (unsigned long long)A64);
+    int rc;
+    if ((rc = digest_usable(b, "mcbs_mask_logits"))) return rc;
     LogitsGeom G;
-    G.N = b->cfg.maximum_node_count; G.C = b->cfg.maximum_total_credentials; G.L = b->C.L; G.R = b->C.R; G.RL = b->C.P * G.C;
-    G.M = G.N * G.N * G.RL; G.ML = G.N * G.L; G.A = (uint32_t)A64;
-    G.dRL = fast_div_host(G.RL); G.dC = fast_div_host(G.C); G.dN = fast_div_host(G.N); G.dL = fast_div_host(G.L); G.dR = fast_div_host(G.R);
+    if ((rc = discrete_geom(b, G))) return rc;
+    if (row_stride < G.A) return fail(MCBS_EINVAL, "row_stride %zu is shorter than the %u Discrete actions", row_stride, G.A);
     hipStream_t st = (hipStream_t)stream;
     const uintptr_t p0 = reinterpret_cast<uintptr_t>(logits);
     // one wavefront per env, four per workgroup; very large action spaces split their chunks of 64 spans over grid.x
@@ -1212,9 +1232,7 @@ extern "C" int mcbs_mask_logits(mcbs_batch* b, void* logits, int32_t dtype, size
         if ((row_stride * 4) % 16 == 0 && p0 % 16 == 0) MCBS_LOGITS_LAUNCH(float, 4u, true, lp, fill);
         else MCBS_LOGITS_LAUNCH(float, 4u, false, lp, fill);
     } else {
-        uint32_t bits;                                   // float -> bfloat16, round to nearest even
-        memcpy(&bits, &fill, 4);
-        const uint16_t f16 = (bits & 0x7FFFFFFFu) > 0x7F800000u ? (uint16_t)((bits >> 16) | 0x40u) : (uint16_t)((bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16);
+        const uint16_t f16 = bf16_fill(fill);
         uint16_t* lp = static_cast<uint16_t*>(logits);
         if ((row_stride * 2) % 16 == 0 && p0 % 16 == 0) MCBS_LOGITS_LAUNCH(uint16_t, 8u, true, lp, f16);
         else if ((row_stride * 2) % 8 == 0 && p0 % 8 == 0) MCBS_LOGITS_LAUNCH(uint16_t, 4u, true, lp, f16);     // rows only 8-byte aligned (Chain-10: 14 172 actions)
@@ -1222,6 +1240,76 @@ extern "C" int mcbs_mask_logits(mcbs_batch* b, void* logits, int32_t dtype, size
     }
 #undef MCBS_LOGITS_LAUNCH
     return launch_ok("mask logits");
+}
+
+// ------------------------------------------------------------------ bit-packed action masks
+extern "C" int mcbs_pack_action_mask(mcbs_batch* b, uint32_t* bits, size_t row_words, void* stream) {
+    if (!b || !bits) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    int rc;
+    if ((rc = digest_usable(b, "mcbs_pack_action_mask"))) return rc;
+    LogitsGeom G;
+    if ((rc = discrete_geom(b, G))) return rc;
+    const uint32_t W = (G.A + 31u) / 32u;
+    if (row_words < W) return fail(MCBS_EINVAL, "row_words %zu is shorter than the %u words of %u Discrete actions", row_words, W, G.A);
+    hipLaunchKernelGGL(pack_mask_kernel, dim3((b->S.E + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, b->S, b->T, b->C_dev, b->digest, bits, row_words, G);
+    return launch_ok("pack action mask");
+}
+
+// rows of the two caller-side kernels: one wavefront per row, four per workgroup along grid.x; the kernels loop over rows beyond
+// 4 * grid.x (gridDim.x * blockDim.x must stay below 2^32), so n_rows is not limited by the launch
+static dim3 packed_rows_grid(uint64_t n_rows, uint32_t pieces) {
+    const uint64_t blocks = (n_rows + 3u) / 4u;
+    const uint32_t chunks = (pieces + 63u) / 64u;       // very long rows split their pieces over grid.y
+    return dim3(blocks < 65536u ? (uint32_t)blocks : 65536u, chunks < 64u ? chunks : 64u);
+}
+
+extern "C" int mcbs_apply_packed_mask(const mcbs_batch* b, const uint32_t* bits, size_t bits_row_words, void* logits, int32_t dtype,
+                                      size_t logits_row_stride, uint64_t n_rows, float fill, void* stream) {
+    if (!b || !bits || !logits) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    if (dtype != MCBS_LOGITS_F32 && dtype != MCBS_LOGITS_BF16) return fail(MCBS_EINVAL, "logits dtype must be MCBS_LOGITS_F32 or MCBS_LOGITS_BF16");
+    const uint64_t A64 = mcbs_discrete_action_count(b);
+    if (A64 >= (1ull << 31)) return fail(MCBS_ELIMIT, "Discrete action space too large for one launch");
+    const uint32_t A = (uint32_t)A64, W = (A + 31u) / 32u;
+    if (bits_row_words < W) return fail(MCBS_EINVAL, "bits_row_words %zu is shorter than the %u words of %u Discrete actions", bits_row_words, W, A);
+    if (logits_row_stride < A) return fail(MCBS_EINVAL, "logits_row_stride %zu is shorter than the %u Discrete actions", logits_row_stride, A);
+    if (n_rows == 0) return MCBS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(logits);
+    const dim3 block(256);
+#define MCBS_APPLY_LAUNCH(LT_, GW_, VEC_, PTR_, FILL_)                                                                               \
+    do {                                                                                                                             \
+        const dim3 grid = packed_rows_grid(n_rows, ((A + GW_ - 1u) / GW_ + 31u + 63u) / 64u);   /* spans shifted by < 32 groups */      \
+        hipLaunchKernelGGL((apply_packed_kernel<LT_, GW_, VEC_>), grid, block, 0, st, bits, bits_row_words, PTR_, logits_row_stride, n_rows, FILL_, A); \
+    } while (0)
+    if (dtype == MCBS_LOGITS_F32) {
+        float* lp = static_cast<float*>(logits);
+        if ((logits_row_stride * 4) % 16 == 0 && p0 % 16 == 0) MCBS_APPLY_LAUNCH(float, 4u, true, lp, fill);
+        else MCBS_APPLY_LAUNCH(float, 4u, false, lp, fill);
+    } else {
+        const uint16_t f16 = bf16_fill(fill);
+        uint16_t* lp = static_cast<uint16_t*>(logits);
+        if ((logits_row_stride * 2) % 16 == 0 && p0 % 16 == 0) MCBS_APPLY_LAUNCH(uint16_t, 8u, true, lp, f16);
+        else if ((logits_row_stride * 2) % 8 == 0 && p0 % 8 == 0) MCBS_APPLY_LAUNCH(uint16_t, 4u, true, lp, f16);
+        else MCBS_APPLY_LAUNCH(uint16_t, 4u, false, lp, f16);
+    }
+#undef MCBS_APPLY_LAUNCH
+    return launch_ok("apply packed mask");
+}
+
+extern "C" int mcbs_unpack_action_mask(const mcbs_batch* b, const uint32_t* bits, size_t bits_row_words, uint8_t* out, size_t out_row_stride,
+                                       uint64_t n_rows, void* stream) {
+    if (!b || !bits || !out) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    const uint64_t A64 = mcbs_discrete_action_count(b);
+    if (A64 >= (1ull << 31)) return fail(MCBS_ELIMIT, "Discrete action space too large for one launch");
+    const uint32_t A = (uint32_t)A64, W = (A + 31u) / 32u;
+    if (bits_row_words < W) return fail(MCBS_EINVAL, "bits_row_words %zu is shorter than the %u words of %u Discrete actions", bits_row_words, W, A);
+    if (out_row_stride < A) return fail(MCBS_EINVAL, "out_row_stride %zu is shorter than the %u Discrete actions", out_row_stride, A);
+    if (n_rows == 0) return MCBS_OK;
+    hipLaunchKernelGGL(unpack_mask_kernel, packed_rows_grid(n_rows, (A + 15u + 15u) / 16u), dim3(256), 0, (hipStream_t)stream, bits, bits_row_words, out, out_row_stride, n_rows, A);
+    return launch_ok("unpack action mask");
 }
 
 // ------------------------------------------------------------------ learned defender

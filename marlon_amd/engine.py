@@ -25,6 +25,7 @@ EXPORTS = [
     "mcbs_step_many", "mcbs_rollout_random", "mcbs_attacker_wrapper_post", "mcbs_attacker_wrapper_clear", "mcbs_defender_wrapper_post", "mcbs_sample_actions", "mcbs_decode_attacker_actions", "mcbs_defender_step", "mcbs_defender_observe", "mcbs_set_draw_tape", "mcbs_state_record_bytes", "mcbs_get_state", "mcbs_set_state",
     "mcbs_timing_enable", "mcbs_timing_read", "mcbs_mask_logits", "mcbs_discrete_action_count", "mcbs_copy_rows_masked", "mcbs_attacker_wrapper_finish", "mcbs_attacker_wrapper_step",
     "mcbs_attacker_wrapper_step_launches", "mcbs_set_mask_discrete_stride", "mcbs_defender_wrapper_step",
+    "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask",
 ]
 
 _lib = None
@@ -89,6 +90,9 @@ def load_library(path: Optional[str] = None):
     lib.mcbs_discrete_action_count.restype = C.c_uint64
     lib.mcbs_discrete_action_count.argtypes = [C.c_void_p]
     lib.mcbs_mask_logits.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t, C.c_float, C.c_void_p]
+    lib.mcbs_pack_action_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mcbs_apply_packed_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_size_t, C.c_uint64, C.c_float, C.c_void_p]
+    lib.mcbs_unpack_action_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]
     lib.mcbs_copy_rows_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mcbs_attacker_wrapper_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -441,6 +445,67 @@ class BatchEngine:
         _check(self.lib, self.lib.mcbs_mask_logits(self._h, logits.data_ptr(), 0 if logits.dtype == t.float32 else 1, logits.stride(0),
                                                    float(fill), self._stream()), "mcbs_mask_logits")
         return logits
+
+    # -- bit-packed Discrete action masks (include/mcbs.h): int32 tensors [rows, row_words], bit a of a row = bit (a & 31) of word a >> 5 --
+    def packed_mask_words(self):
+        """-> (W, row_words): W = ceil(A / 32) words carry a row's mask; row_words = W rounded up to whole 16-byte groups (the rows
+        pack_action_mask allocates)."""
+        W = (self.discrete_action_count() + 31) // 32
+        return W, (W + 3) // 4 * 4
+
+    def _packed_rows(self, bits, what: str):
+        t = self.torch
+        if bits.dtype != t.int32 or bits.dim() != 2 or bits.stride(1) != 1 or bits.device != self.device:
+            raise ValueError(f"{what} must be a device int32 tensor [n, >= W] with contiguous rows")
+        if bits.shape[1] < self.packed_mask_words()[0]:
+            raise ValueError(f"{what} rows hold {bits.shape[1]} words, the mask needs {self.packed_mask_words()[0]}")
+        return bits
+
+    def pack_action_mask(self, out=None):
+        """The Discrete action mask of the LAST observation call as one bit per action, rebuilt on the device from that call's per-env
+        digest (the preconditions of mask_logits).  out: device int32 [E, >= W] with contiguous rows (e.g. buffer[t] of a
+        [T, E, row_words] rollout buffer), or None for a new zeroed [E, row_words] tensor.  Words from W on are not written."""
+        t = self.torch
+        if out is None:
+            out = t.zeros((self.E, self.packed_mask_words()[1]), dtype=t.int32, device=self.device)
+        self._packed_rows(out, "out")
+        if out.shape[0] != self.E:
+            raise ValueError(f"out must have {self.E} rows, got {out.shape[0]}")
+        _check(self.lib, self.lib.mcbs_pack_action_mask(self._h, out.data_ptr(), out.stride(0), self._stream()), "mcbs_pack_action_mask")
+        return out
+
+    def apply_packed_mask(self, bits, logits, fill: float = -1e8):
+        """In place: logits[i, a] = bit(i, a) ? logits[i, a] : fill for every row i of bits [n, >= W] and logits float32 / bfloat16
+        [n, >= A] (any n: a minibatch gathered from stored masks).  Write-only, like mask_logits; no digest involved."""
+        t = self.torch
+        self._packed_rows(bits, "bits")
+        if logits.dtype not in (t.float32, t.bfloat16):
+            raise ValueError("logits must be float32 or bfloat16")
+        if logits.dim() != 2 or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < self.discrete_action_count():
+            raise ValueError(f"logits must be a device tensor [n, >= {self.discrete_action_count()}] with contiguous rows")
+        if logits.shape[0] != bits.shape[0]:
+            raise ValueError(f"bits has {bits.shape[0]} rows, logits {logits.shape[0]}")
+        if bits.shape[0]:
+            _check(self.lib, self.lib.mcbs_apply_packed_mask(self._h, bits.data_ptr(), bits.stride(0), logits.data_ptr(),
+                                                             0 if logits.dtype == t.float32 else 1, logits.stride(0), bits.shape[0],
+                                                             float(fill), self._stream()), "mcbs_apply_packed_mask")
+        return logits
+
+    def unpack_action_mask(self, bits, out=None):
+        """bits [n, >= W] -> the bool mask [n, A] (out: device bool / uint8 [n, >= A] with contiguous rows; bytes from A on untouched)."""
+        t = self.torch
+        self._packed_rows(bits, "bits")
+        A = self.discrete_action_count()
+        if out is None:
+            out = t.empty((bits.shape[0], A), dtype=t.bool, device=self.device)
+        if out.dtype not in (t.bool, t.uint8) or out.dim() != 2 or out.stride(1) != 1 or out.device != self.device or out.shape[1] < A:
+            raise ValueError(f"out must be a device bool or uint8 tensor [n, >= {A}] with contiguous rows")
+        if out.shape[0] != bits.shape[0]:
+            raise ValueError(f"bits has {bits.shape[0]} rows, out {out.shape[0]}")
+        if bits.shape[0]:
+            _check(self.lib, self.lib.mcbs_unpack_action_mask(self._h, bits.data_ptr(), bits.stride(0), out.data_ptr(), out.stride(0),
+                                                              bits.shape[0], self._stream()), "mcbs_unpack_action_mask")
+        return out
 
     # -- learned defender (batches created with defender=("external",)) --
     def alloc_defender_obs(self) -> dict:

@@ -319,6 +319,11 @@ class MarlonVecEnv:
         """The [num_envs, A] mask array in one piece (what np.stack(env_method("action_masks")) yields, without the Python list)."""
         return self._out(self.venv.action_masks())
 
+    def action_masks_packed(self):
+        """The packed masks of every env, [num_envs, row_words] int32 (AttackerVecEnv.action_masks_packed: bit a of a row = bit (a & 31)
+        of word a >> 5): 8x smaller than action_masks(), and available when the masks are not materialised."""
+        return self._out(self.venv.action_masks_packed())
+
     def get_attr(self, attr_name: str, indices=None) -> List[Any]:
         val = getattr(self.venv, attr_name)
         idx = self._indices(indices)

@@ -157,6 +157,21 @@ class AttackerVecEnv:
         with action_masks() (train_marl_multi.py:259-293), straight from the digest of the observation this env last returned."""
         return self.engine.mask_logits(logits, fill)
 
+    def action_masks_packed(self, out=None):
+        """action_masks() as one bit per action: device int32 [n_envs, row_words] (engine.pack_action_mask), bit a of row e = bit
+        (a & 31) of word a >> 5.  Works whether or not the masks are materialised (with materialize_masks=False the step stays one
+        launch and this is a second).  out=: write straight into a preallocated buffer, e.g. buffer[t] of a [T, n_envs, row_words]
+        rollout buffer, for apply_packed_mask at update time."""
+        return self.engine.pack_action_mask(out)
+
+    def apply_packed_mask(self, bits, logits, fill: float = -1e8):
+        """`where(mask, logits, fill)` in place for stored packed masks bits [n, >= W] and logits [n, >= A], any n."""
+        return self.engine.apply_packed_mask(bits, logits, fill)
+
+    def unpack_action_mask(self, bits, out=None):
+        """Packed masks [n, >= W] -> bool [n, A] (what action_masks() returns for the same step)."""
+        return self.engine.unpack_action_mask(bits, out)
+
     # -- VecEnv surface --
     def reset(self):
         self.engine.reset()
