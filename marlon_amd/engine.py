@@ -440,8 +440,10 @@ class BatchEngine:
         t = self.torch
         if logits.dtype not in (t.float32, t.bfloat16):
             raise ValueError("logits must be float32 or bfloat16")
-        if logits.dim() != 2 or logits.shape[0] != self.E or logits.stride(1) != 1 or logits.device != self.device:
-            raise ValueError(f"logits must be a device tensor [{self.E}, A] with contiguous rows")
+        # the C side sees only the row stride: a view narrower than A (wide[:, :A-1]) would have its rows written past their end
+        if (logits.dim() != 2 or logits.shape[0] != self.E or logits.stride(1) != 1 or logits.device != self.device
+                or logits.shape[1] < self.discrete_action_count()):
+            raise ValueError(f"logits must be a device tensor [{self.E}, >= {self.discrete_action_count()}] with contiguous rows")
         _check(self.lib, self.lib.mcbs_mask_logits(self._h, logits.data_ptr(), 0 if logits.dtype == t.float32 else 1, logits.stride(0),
                                                    float(fill), self._stream()), "mcbs_mask_logits")
         return logits
