@@ -532,6 +532,21 @@ size_t mcbs_state_record_bytes(const mcbs_batch*);
 int  mcbs_get_state(mcbs_batch*, void* host_buf, size_t nbytes);
 int  mcbs_set_state(mcbs_batch*, const void* host_buf, size_t nbytes);
 
+/* Which compiled variant this batch's calls dispatch to, decided at batch creation (tests assert the cell they reach).  Read-only: the
+ * query changes no dispatch decision.  Per-call conditions are not included (mcbs_defender_step also needs 16-byte aligned observation
+ * arrays for the fused observation; mcbs_attacker_wrapper_step's single launch also needs no mask field and aligned rows). */
+typedef struct mcbs_batch_variant_info {   /* 32 bytes */
+    uint32_t packed;              /* 1: packed sets (16-bit fields, 4-byte rows): N <= 16 and few credentials */
+    uint32_t words_per_set;       /* 1, 2 or 4: 64-bit words of a per-env node / credential set in the general layout */
+    uint32_t wide;                /* 1: the cached-triple set lives in a column of its own (more than 256 cacheable credentials) */
+    uint32_t coop;                /* 1: mcbs_step runs the G-lanes-per-env kernel (G = words_per_set) */
+    uint32_t lds_topo;            /* 1: the step kernel stages the topology's hot image in LDS (MCBS_LDS_TOPO=1 and it fits) */
+    uint32_t defender_kind;       /* MCBS_DEFENDER_* of the batch */
+    uint32_t fused_wrapper;       /* 1: the batch admits the one-launch mcbs_attacker_wrapper_step */
+    uint32_t fused_defender_obs;  /* 1: learned-defender turns can write the observation themselves (N <= 32, at most 256 services) */
+} mcbs_batch_variant_info;
+int  mcbs_batch_variant(const mcbs_batch*, mcbs_batch_variant_info* out);
+
 /* Kernel timing hook for bench.py: HIP events recorded on `stream` around each mcbs_step launch
  * while enabled; mcbs_timing_read synchronises and returns the summed kernel milliseconds. */
 int  mcbs_timing_enable(mcbs_batch*, int32_t on);

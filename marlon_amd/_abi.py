@@ -60,6 +60,12 @@ class DefenderObs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("infected_nodes", "incoming_firewall_status", "outgoing_firewall_status", "services_status")]
 
 
+class BatchVariantInfo(C.Structure):
+    """mcbs_batch_variant_info (include/mcbs.h): the compiled variant a batch dispatches to"""
+    _fields_ = [(n, C.c_uint32) for n in ("packed", "words_per_set", "wide", "coop", "lds_topo", "defender_kind", "fused_wrapper",
+                                          "fused_defender_obs")]
+
+
 class InfoBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("network_availability", "step_count", "truncated", "out_of_bound", "raw_reward")]
 

@@ -1316,6 +1316,10 @@ extern "C" int mcbs_unpack_action_mask(const mcbs_batch* b, const uint32_t* bits
 // The observation written by the turn kernel's own workgroups (one launch per turn): topologies of up to 32 nodes and 256 services,
 // output arrays on 16-byte boundaries (the 128 envs of a workgroup are one contiguous region of each array, stored as 16-byte vectors).
 // MCBS_NO_FUSED_DEFENDER_OBS=1: the separate launch.
+static bool fused_defender_obs_batch_ok(const mcbs_batch* b) {
+    return b->S.N <= 32u && b->C.n_services <= 256u && !b->no_fused_defender_obs;
+}
+
 static DefObs fused_defender_obs(const mcbs_batch* b, const mcbs_defender_obs* o) {
     DefObs d{};
     if (!o) return d;
@@ -1325,8 +1329,23 @@ static DefObs fused_defender_obs(const mcbs_batch* b, const mcbs_defender_obs* o
     d.dN = fast_div_host(N); d.d6N = fast_div_host(6u * N); d.dS = fast_div_host(d.n_services ? d.n_services : 1u);
     auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
     const bool aligned = al(d.infected) && al(d.fw_in) && al(d.fw_out) && al(d.services);
-    d.fused = (b->S.N <= 32u && d.n_services <= 256u && aligned && !b->no_fused_defender_obs) ? 1u : 0u;
+    d.fused = (fused_defender_obs_batch_ok(b) && aligned) ? 1u : 0u;
     return d;
+}
+
+extern "C" int mcbs_batch_variant(const mcbs_batch* b, mcbs_batch_variant_info* out) {
+    if (!b || !out) return fail(MCBS_EINVAL, "null argument");
+    mcbs_batch_variant_info v{};
+    v.packed = b->S.packed;
+    v.words_per_set = b->S.WT;
+    v.wide = b->S.wide;
+    v.coop = b->coop ? 1u : 0u;
+    v.lds_topo = (b->lds_topo && b->C.hot_bytes <= 60000u) ? 1u : 0u;       // the staged step kernel's own condition
+    v.defender_kind = b->cfg.defender_kind;
+    v.fused_wrapper = fused_wrapper_batch_ok(b) ? 1u : 0u;
+    v.fused_defender_obs = (b->cfg.defender_kind == MCBS_DEFENDER_EXTERNAL && fused_defender_obs_batch_ok(b)) ? 1u : 0u;
+    *out = v;
+    return MCBS_OK;
 }
 
 static int launch_defender_obs(mcbs_batch* b, const mcbs_defender_obs* o, hipStream_t st) {

@@ -13,7 +13,7 @@ from typing import Dict, Iterable, Optional
 
 import numpy as np
 
-from ._abi import BatchCfg, DefenderObs, EnvSpec, InfoBuffers, ObsBuffers, split_state, state_record_bytes
+from ._abi import BatchCfg, BatchVariantInfo, DefenderObs, EnvSpec, InfoBuffers, ObsBuffers, split_state, state_record_bytes
 from .flatten import FlatTopology
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -25,7 +25,7 @@ EXPORTS = [
     "mcbs_step_many", "mcbs_rollout_random", "mcbs_attacker_wrapper_post", "mcbs_attacker_wrapper_clear", "mcbs_defender_wrapper_post", "mcbs_sample_actions", "mcbs_decode_attacker_actions", "mcbs_defender_step", "mcbs_defender_observe", "mcbs_set_draw_tape", "mcbs_state_record_bytes", "mcbs_get_state", "mcbs_set_state",
     "mcbs_timing_enable", "mcbs_timing_read", "mcbs_mask_logits", "mcbs_discrete_action_count", "mcbs_copy_rows_masked", "mcbs_attacker_wrapper_finish", "mcbs_attacker_wrapper_step",
     "mcbs_attacker_wrapper_step_launches", "mcbs_set_mask_discrete_stride", "mcbs_defender_wrapper_step",
-    "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask",
+    "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant",
 ]
 
 _lib = None
@@ -100,6 +100,7 @@ def load_library(path: Optional[str] = None):
     lib.mcbs_attacker_wrapper_step_launches.restype = C.c_int32
     lib.mcbs_attacker_wrapper_step_launches.argtypes = [C.c_void_p, C.c_int32]
     lib.mcbs_set_mask_discrete_stride.argtypes = [C.c_void_p, C.c_size_t]
+    lib.mcbs_batch_variant.argtypes = [C.c_void_p, C.POINTER(BatchVariantInfo)]
     lib.mcbs_timing_enable.argtypes = [C.c_void_p, C.c_int32]
     lib.mcbs_timing_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     for name in EXPORTS:
@@ -563,6 +564,13 @@ class BatchEngine:
         raw[:, o:o + 2 * N] = np.ascontiguousarray(order.astype("<u2")).view(np.uint8).reshape(self.E, 2 * N)
         raw[:, o + 2 * N:o + 2 * N + 2 * Cm] = np.ascontiguousarray(cache.astype("<u2")).view(np.uint8).reshape(self.E, 2 * Cm)
         _check(self.lib, self.lib.mcbs_set_state(self._h, raw.ctypes.data, raw.size), "mcbs_set_state")
+
+    def variant(self) -> dict:
+        """The compiled variant this batch dispatches to (mcbs_batch_variant): packed, words_per_set, wide, coop, lds_topo, defender_kind,
+        fused_wrapper, fused_defender_obs.  Decided at creation; the query changes nothing."""
+        v = BatchVariantInfo()
+        _check(self.lib, self.lib.mcbs_batch_variant(self._h, C.byref(v)), "mcbs_batch_variant")
+        return {name: int(getattr(v, name)) for name, _ in BatchVariantInfo._fields_}
 
     def timing_enable(self, on: bool = True) -> None:
         _check(self.lib, self.lib.mcbs_timing_enable(self._h, int(on)), "mcbs_timing_enable")

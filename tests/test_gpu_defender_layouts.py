@@ -1,0 +1,511 @@
+"""The random-events and learned defenders on every state layout, against the CPU oracle (oracle/oracle.py) or a float64 NumPy
+restatement, with Philox draws and bitwise equality (availability and fp64 rewards as uint64 bit patterns).
+
+Each step kernel is compiled per state layout (packed: N <= 16; general with 1, 2 or 4 words per set; wide: more than 256 cacheable
+credentials) x defender kind x entry point.  Every test asserts BatchEngine.variant() before it steps, so a moved threshold fails
+loudly instead of quietly testing another cell.
+
+| cell | test | comparison |
+|---|---|---|
+| ExternalRandomEvents x packed (ToyCtf) | test_random_events_engine_vs_oracle[toyctf] | oracle: every output every step, observations, state |
+| ExternalRandomEvents x general WT 1 (ToyCtf with MCBS_NO_PACKED_SETS=1, Random-24) | ...[toyctf_general], [random24] | same |
+| ExternalRandomEvents x general WT 2 (Random-65, Random-100, Chain-100) | ...[random65], [random100], [chain100] | same |
+| ExternalRandomEvents x general WT 4 (Random-129) | ...[random129] | same |
+| ExternalRandomEvents x wide (ActiveDirectory-6) | ...[ad6] | same, whole observation |
+| ExternalRandomEvents x step_many / rollout_random, WT 1, 2, 4 | test_random_events_step_many_and_rollout_against_oracle | oracle replay of the actions |
+| ExternalRandomEvents through AttackerVecEnv (decode_step1_kernel / step2_finish_kernel, three launches) | test_random_events_attacker_vec_env_against_oracle | oracle + wrapper semantics |
+| ExternalRandomEvents on Random-200 / Random-256: firewall overlay beyond 64 KB | test_random_events_refused_beyond_the_overlay | refused with MCBS_ELIMIT |
+| learned defender (defender_kernel<WT>) x WT 4, wide | tests/test_gpu_facades.py::test_defender_step_batch_against_oracle[random129], [ad6] | oracle |
+| DefenderVecEnv.step (defender_turn_post_kernel<WT>) WT 1 fused obs, WT 2 and WT 4 separate obs | test_defender_vec_env_shaping_against_numpy | oracle turn + NumPy shaping |
+| ScanAndReimage x wide | tests/test_gpu_parity.py::test_engine_matches_oracle_batched[ad6_wide_scan-*] | oracle |
+
+mcbs_get_state does not carry the random-events overlay (vulnerability keys, service flags, firewall lists), so the tests make the
+channels it drives sensitive: non-dyadic node and service SLA weights (availability fingerprints each env's service flags), mask_local
+(the env's own keys), connect outcomes and rewards.
+"""
+import numpy as np
+import pytest
+
+from tests import parity
+
+pytestmark = pytest.mark.gpu
+
+SMALL = ["scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel"]
+DEF_KEYS = ["infected_nodes", "incoming_firewall_status", "outgoing_firewall_status", "services_status"]
+
+
+def _engine():
+    from marlon_amd import engine
+    return engine
+
+
+def _model_env(name):
+    from marlon_amd import model
+    from marlon_amd.samples import active_directory, chainpattern, random_net, toy_ctf
+    if name.startswith("toyctf"):
+        return toy_ctf.new_environment()
+    if name == "chain100":
+        return chainpattern.new_environment(100)
+    if name == "ad6":
+        return active_directory.new_random_environment(6)
+    return random_net.build(model, int(name[6:]), 7)
+
+
+def _weighted_topology(name):
+    """The topology with distinct non-dyadic node and service SLA weights: availability then fingerprints the env's service flags."""
+    from marlon_amd import flatten as F
+    env = _model_env(name)
+    nw = [0.1, 0.3, 0.7, 1.9, 2.3, 0.6, 1.1, 3.3, 0.35]
+    sw = [0.3, 0.6, 1.7, 0.9, 0.1, 2.2, 1.3]
+    k = 0
+    for i, (_, info) in enumerate(env.nodes()):
+        info.sla_weight = nw[i % len(nw)]
+        for s in info.services:
+            s.sla_weight = sw[k % len(sw)]
+            k += 1
+    topo = F.flatten(env)
+    assert int(topo.header()["avail_any_order"]) == 0
+    return topo
+
+
+def _ere_spec(topo, E, **over):
+    from marlon_amd._abi import RNG_PHILOX, EnvSpec
+    h = topo.header()
+    kw = dict(n_envs=E, maximum_node_count=topo.n_nodes + 2, maximum_total_credentials=max(1, len(topo.triples)),
+              maximum_discoverable_credentials_per_action=max(8, int(h["max_leak_per_action"])),
+              attacker_goal=dict(own_atleast_percent=1.0), maintain_sla=0.0, defender=("random_events",), auto_reset=True,
+              max_episode_steps=30, rng_kind=RNG_PHILOX, seed=777, env_id_base=31)
+    kw.update(over)
+    return EnvSpec(**kw)
+
+
+def _assert_variant(eng, **want):
+    v = eng.variant()
+    got = {k: v[k] for k in want}
+    assert got == want, f"batch dispatches to {v}, the test expects {want}"
+    return v
+
+
+def _compare_states(a, b, ctx):
+    for x, y, what in zip(a, b, ("header", "nodes", "order", "cache")):
+        if x.dtype.names:
+            for f in x.dtype.names:
+                if not f.startswith("pad"):
+                    np.testing.assert_array_equal(x[f], y[f], err_msg=f"{ctx}: state {what}.{f}")
+        else:
+            np.testing.assert_array_equal(x, y, err_msg=f"{ctx}: state {what}")
+
+
+def _compare_outputs(eng, r, d, o, ctx):
+    np.testing.assert_array_equal(r.double().cpu().numpy(), o["reward"], err_msg=ctx + " reward")
+    np.testing.assert_array_equal(eng.info["raw_reward"].double().cpu().numpy(), o["raw_reward"], err_msg=ctx + " raw reward")
+    np.testing.assert_array_equal(d.cpu().numpy(), o["terminated"], err_msg=ctx + " terminated")
+    np.testing.assert_array_equal(eng.info["truncated"].cpu().numpy(), o["truncated"], err_msg=ctx + " truncated")
+    np.testing.assert_array_equal(eng.info["out_of_bound"].cpu().numpy(), o["oob"], err_msg=ctx + " oob")
+    np.testing.assert_array_equal(eng.info["step_count"].cpu().numpy(), o["step_count"], err_msg=ctx + " step_count")
+    av = eng.info["network_availability"].cpu().numpy()
+    np.testing.assert_array_equal(av.view(np.uint64), o["availability"].view(np.uint64), err_msg=ctx + " availability bits")
+    return av
+
+
+# name: (E, expected variant)
+LAYOUTS = {
+    "toyctf": (337, dict(packed=1, words_per_set=1, wide=0)),
+    "toyctf_general": (337, dict(packed=0, words_per_set=1, wide=0)),
+    "random24": (337, dict(packed=0, words_per_set=1, wide=0)),
+    "random65": (133, dict(packed=0, words_per_set=2, wide=0)),
+    "random100": (133, dict(packed=0, words_per_set=2, wide=0)),
+    "chain100": (133, dict(packed=0, words_per_set=2, wide=0)),
+    "random129": (133, dict(packed=0, words_per_set=4, wide=0)),
+    "ad6": (133, dict(packed=0, words_per_set=2, wide=1)),
+}
+
+
+def _local_mask_changes(topo, Lcols, mask_local, hdr_nodes_order):
+    """(rows that differ from the topology's static local mask, rows that show a column outside it) over the owned rows of every env.
+    Under random events keys are only patched away or library columns planted, and library columns are always visible: an owned row
+    is a subset of the static row."""
+    _, nodes, order, _ = hdr_nodes_order
+    from marlon_amd import flatten as F
+    nt = topo.node_table()
+    off = int(topo.header()["off_ere"])
+    lib = int(np.frombuffer(topo.blob, np.uint8)[off:off + F.ERE_DT.itemsize].view(F.ERE_DT)[0]["lib_cols"])
+    static = (nt["local_mask"].astype(np.uint64) | np.uint64(lib)) & np.uint64((1 << Lcols) - 1)
+    bits = (mask_local.astype(np.uint64) << np.arange(Lcols, dtype=np.uint64)).sum(axis=2)        # [E, Nmax] row as a bit mask
+    E, N = order.shape
+    differ = outside = 0
+    for e in range(E):
+        for i in range(N):
+            n = int(order[e, i])
+            if n == 0xFFFF or not nodes["installed"][e, n]:
+                continue
+            differ += int(bits[e, i] != static[n])
+            outside += int(bits[e, i] & ~static[n] != 0)
+    return differ, outside
+
+
+@pytest.mark.parametrize("name", sorted(LAYOUTS))
+def test_random_events_engine_vs_oracle(name, monkeypatch):
+    """mcbs_step / mcbs_step_observe under ExternalRandomEvents on every state layout, batches that leave the last wavefront partial,
+    auto-reset after short episodes (the reset restores the overlay), valid and uniform device-sampled actions: every output every step,
+    the canonical state every 25 steps, the small observation fields and mask_local every 10th step (the whole observation where
+    N <= 33).  The run must have exercised the overlay: many distinct availabilities, some below the initial one; owned rows of
+    mask_local that differ from the static local mask; episodes that ended."""
+    from oracle.oracle import Oracle
+    E, want = LAYOUTS[name]
+    topo = _weighted_topology(name)
+    spec = _ere_spec(topo, E)
+    if name == "toyctf_general":
+        monkeypatch.setenv("MCBS_NO_PACKED_SETS", "1")
+    eng = _engine().BatchEngine(topo, spec)
+    monkeypatch.delenv("MCBS_NO_PACKED_SETS", raising=False)
+    _assert_variant(eng, defender_kind=3, coop=0, fused_wrapper=0, lds_topo=0, **want)
+    orc = Oracle(topo, spec)
+    fields = SMALL + (["mask_local", "mask_remote", "mask_connect"] if topo.n_nodes <= 33 else ["mask_local"])
+    L = len(topo.local_vulnerabilities)
+    full = float(topo.header()["full_availability"])
+    distinct, ended, differ, outside, owned_rows = set(), 0, 0, 0, 0
+    T = 100
+    for t in range(T):
+        a = eng.sample_actions(t % 3 != 2, seed=13, step=t)
+        an = a.cpu().numpy()
+        ctx = f"{name} step {t}"
+        if t % 10 == 9:
+            obs, oo = eng.alloc_obs(fields), orc.alloc_obs(fields)
+            r, d = eng.step_observe(a, obs)
+            o = orc.step(an, obs=oo)
+            for f in fields:
+                np.testing.assert_array_equal(obs[f].cpu().numpy(), oo[f], err_msg=f"{ctx} obs {f}")
+            st = orc.get_state()
+            dd, oc = _local_mask_changes(topo, L, oo["mask_local"], st)
+            differ += dd
+            outside += oc
+            owned_rows += int(st[1]["installed"].sum())
+        else:
+            r, d = eng.step(a)
+            o = orc.step(an)
+        av = _compare_outputs(eng, r, d, o, ctx)
+        distinct.update(np.unique(av).tolist())
+        ended += int(d.sum()) + int(eng.info["truncated"].sum())
+        if t % 25 == 24:
+            _compare_states(eng.get_state(), orc.get_state(), ctx)
+    assert len(distinct) > 20 and min(distinct) < full, f"availability took {len(distinct)} values, min {min(distinct)}"
+    assert differ > 0 and outside == 0, f"mask_local: {differ} owned rows changed by the overlay, {outside} outside the static mask"
+    assert owned_rows > 0 and ended >= E, f"{ended} episode ends for {E} envs"
+    eng.close()
+
+
+@pytest.mark.parametrize("n_nodes", [200, 256])
+def test_random_events_refused_beyond_the_overlay(n_nodes):
+    """The random-events overlay addresses its firewall lists with 16-bit offsets: Random-200 / Random-256 need more than 64 KB and
+    batch creation refuses them with MCBS_ELIMIT (no crash); a batch created next on the same device works (Random-129 still fits)."""
+    from marlon_amd import flatten as F, model
+    from marlon_amd.samples import random_net
+    from oracle.oracle import Oracle
+    topo = F.flatten(random_net.build(model, n_nodes, 7))
+    with pytest.raises(_engine().McbsError, match=r"\(-2\): firewall rule lists too large for the random-events overlay"):
+        _engine().BatchEngine(topo, _ere_spec(topo, 64, maximum_node_count=n_nodes))
+    topo = _weighted_topology("random129")
+    spec = _ere_spec(topo, 65)
+    eng = _engine().BatchEngine(topo, spec)
+    _assert_variant(eng, defender_kind=3, packed=0, words_per_set=4, wide=0)
+    orc = Oracle(topo, spec)
+    for t in range(12):
+        a = eng.sample_actions(True, seed=3, step=t)
+        r, d = eng.step(a)
+        _compare_outputs(eng, r, d, orc.step(a.cpu().numpy()), f"random129 after a refusal, step {t}")
+    eng.close()
+
+
+@pytest.mark.parametrize("name", ["random24", "random65", "random129"])
+def test_random_events_step_many_and_rollout_against_oracle(name):
+    """mcbs_step_many (K = 25 pre-sampled actions per launch, twice) and mcbs_rollout_random (actions recorded, valid then uniform) under
+    ExternalRandomEvents at 1, 2 and 4 words per set, replayed through the oracle: rewards and terminations of every step, final
+    canonical state.  Episodes truncate inside the launches."""
+    from oracle.oracle import Oracle
+    topo = _weighted_topology(name)
+    E, want = 133, LAYOUTS[name][1]
+    spec = _ere_spec(topo, E, max_episode_steps=20)
+    many = _engine().BatchEngine(topo, spec)
+    _assert_variant(many, defender_kind=3, coop=0, **want)
+    t = many.torch
+    K = 25
+    # pre-sampled from the initial state (valid then, stale later) and uniform rows, before anything is stepped
+    ring = t.stack([many.sample_actions(k % 2 == 0, seed=41, step=k) for k in range(2 * K)])
+    orc = Oracle(topo, spec)
+    ended = 0
+    for c in range(2):
+        r, d = many.step_many(ring[c * K:(c + 1) * K])
+        rn, dn, an = r.double().cpu().numpy(), d.cpu().numpy(), ring[c * K:(c + 1) * K].cpu().numpy()
+        for k in range(K):
+            o = orc.step(an[k])
+            np.testing.assert_array_equal(rn[k], o["reward"], err_msg=f"{name} step_many step {c * K + k} reward")
+            np.testing.assert_array_equal(dn[k], o["terminated"], err_msg=f"{name} step_many step {c * K + k} terminated")
+            ended += int(o["truncated"].sum())
+    _compare_states(many.get_state(), orc.get_state(), f"{name} after step_many")
+    assert ended >= E
+    many.close()
+
+    roll = _engine().BatchEngine(topo, spec)
+    _assert_variant(roll, defender_kind=3, coop=0, **want)
+    orc = Oracle(topo, spec)
+    first = 0
+    for valid, n in ((True, 30), (False, 15)):
+        r, d, acts = roll.rollout_random(n, valid=valid, seed=5, first_step=first, record_actions=True)
+        rn, dn, an = r.double().cpu().numpy(), d.cpu().numpy(), acts.cpu().numpy()
+        for k in range(n):
+            o = orc.step(an[k])
+            np.testing.assert_array_equal(rn[k], o["reward"], err_msg=f"{name} rollout valid={valid} step {first + k} reward")
+            np.testing.assert_array_equal(dn[k], o["terminated"], err_msg=f"{name} rollout valid={valid} step {first + k} terminated")
+        first += n
+    _compare_states(roll.get_state(), orc.get_state(), f"{name} after rollout_random")
+    roll.close()
+
+
+def _rows_of(a, n_disc):
+    """marlon's MultiDiscrete attacker action -> engine row and validity (attack_wrapper.py:286-308: undiscovered indices are intercepted)."""
+    E = a.shape[0]
+    kind = a[:, 0]
+    src = np.where(kind == 0, a[:, 1], np.where(kind == 1, a[:, 3], a[:, 6]))
+    tgt = np.where(kind == 0, 0, np.where(kind == 1, a[:, 4], a[:, 7]))
+    valid = (src < n_disc) & ((kind == 0) | (tgt < n_disc))
+    rows = np.zeros((E, 5), np.int32)
+    rows[:, 0] = np.where(valid, kind, 3)
+    rows[:, 1] = src
+    rows[:, 2] = np.where(kind == 0, a[:, 2], tgt)
+    rows[:, 3] = np.where(kind == 1, a[:, 5], np.where(kind == 2, a[:, 8], 0))
+    rows[:, 4] = np.where(kind == 2, a[:, 9], 0)
+    return rows, valid
+
+
+def _draw_attacker(rng, nvec, n_disc, share):
+    E = n_disc.shape[0]
+    a = (rng.random((E, 10)) * nvec).astype(np.int64)
+    fix = rng.random(E) < share
+    for i in (1, 3, 4, 6, 7):
+        a[fix, i] = (rng.random(fix.sum()) * n_disc[fix]).astype(np.int64)
+    return a
+
+
+@pytest.mark.parametrize("masks", [True, False])
+@pytest.mark.parametrize("name", ["toyctf", "random24", "chain100", "random129"])
+def test_random_events_attacker_vec_env_against_oracle(name, masks):
+    """AttackerVecEnv under ExternalRandomEvents: the wrapper step is three launches (decode_step1_kernel<WT, RANDOM_EVENTS>, the
+    observation, step2_finish_kernel<WT, RANDOM_EVENTS>).  Host-drawn MultiDiscrete actions (some intercepted), truncation and auto-reset,
+    the oracle as checker: rewards, flags, interception, the small observation fields and (materialised) the Discrete mask of envs that
+    did not end, the terminal observation of envs that did, and the steps after an env's reset against an oracle env reset with
+    orc.reset(i).  attack_wrapper.py:255-372, action_masking.py:90-110."""
+    from marlon_amd import cyberbattle_env as ce
+    from marlon_amd.cyberbattle_env import SCALAR_KEYS
+    from marlon_amd.wrappers import AttackerVecEnv
+    from oracle.oracle import Oracle
+    topo = _weighted_topology(name)
+    big = topo.n_nodes > 64
+    E, T, MAXT = (24, 50, 20) if big else (64, 70, 25)
+    Nm, Cm = topo.n_nodes + 2, max(1, len(topo.triples))
+    K = max(8, int(topo.header()["max_leak_per_action"]))
+    env = AttackerVecEnv(topo, E, maximum_node_count=Nm, maximum_total_credentials=Cm, maximum_discoverable_credentials_per_action=K,
+                         attacker_goal=ce.AttackerGoal(own_atleast_percent=0.7), defender_agent=ce.ExternalRandomEvents(),
+                         defender_constraint=ce.DefenderConstraint(0.0), max_timesteps=MAXT, seed=17, materialize_masks=masks)
+    assert env.engine.wrapper_step_launches(masks) == 3
+    want = {"toyctf": dict(packed=1, words_per_set=1), "random24": dict(packed=0, words_per_set=1),
+            "chain100": dict(packed=0, words_per_set=2), "random129": dict(packed=0, words_per_set=4)}[name]
+    _assert_variant(env.engine, defender_kind=3, fused_wrapper=0, wide=0, **want)
+    orc = Oracle(topo, env.spec)
+    orc.reset()                                          # the wrapper's reset() began episode 1 (the episode index feeds the Philox counter)
+    mask_fields = ["mask_connect", "mask_local", "mask_remote"]
+    rng = np.random.Generator(np.random.PCG64(23))
+    timesteps = np.zeros(E, np.int64)
+    n_disc = np.ones(E, np.int64)
+    checked = terminal_checked = after_reset = 0
+    was_reset = np.zeros(E, bool)
+    for t in range(T):
+        a = _draw_attacker(rng, env.nvec, n_disc, 0.8)
+        rows, valid = _rows_of(a, n_disc)
+        with_masks = masks and (not big or t % 5 == 4)
+        oo = orc.alloc_obs(SMALL + (mask_fields if with_masks else []))
+        obs, r, term, trunc, info = env.step(a)
+        o = orc.step(rows, obs=oo)
+        timesteps += 1
+        ctx = f"{name} masks={masks} step {t}"
+        np.testing.assert_array_equal(r.double().cpu().numpy(), o["reward"] + np.where(valid, 0.0, -1.0), err_msg=ctx + " reward")
+        np.testing.assert_array_equal(term.cpu().numpy(), o["terminated"], err_msg=ctx + " terminated")
+        np.testing.assert_array_equal(trunc.cpu().numpy(), (timesteps >= MAXT).astype(np.uint8), err_msg=ctx + " truncated")
+        np.testing.assert_array_equal(info["invalid_action"].cpu().numpy(), ~valid, err_msg=ctx + " interception")
+        dones = (o["terminated"] != 0) | (timesteps >= MAXT)
+        flat = None
+        if with_masks:
+            flat = np.concatenate([oo["mask_connect"].reshape(E, -1), oo["mask_local"].reshape(E, -1), oo["mask_remote"].reshape(E, -1)], axis=1) != 0
+        for view, sel, what in ((env.observation, np.flatnonzero(valid & ~dones), "observation"),
+                                (env.terminal_observation, np.flatnonzero(valid & dones), "terminal observation")):
+            if not sel.size:
+                continue
+            got = np.stack([view[k].cpu().numpy() for k in SCALAR_KEYS], axis=1)
+            np.testing.assert_array_equal(got[sel], oo["scalars"][sel], err_msg=f"{ctx} {what} scalars")
+            for k in SMALL[1:]:
+                np.testing.assert_array_equal(view[k].cpu().numpy().reshape(E, -1)[sel], oo[k].reshape(E, -1)[sel], err_msg=f"{ctx} {what} {k}")
+            if flat is not None:
+                m = np.concatenate([view["connect"].cpu().numpy().reshape(E, -1), view["local_vulnerability"].cpu().numpy().reshape(E, -1),
+                                    view["remote_vulnerability"].cpu().numpy().reshape(E, -1)], axis=1) != 0
+                np.testing.assert_array_equal(m[sel], flat[sel], err_msg=f"{ctx} {what} Discrete action mask")
+            if what == "observation":
+                checked += sel.size
+                after_reset += int(was_reset[sel].sum())
+            else:
+                terminal_checked += sel.size
+        for i in np.flatnonzero(dones):
+            orc.reset(int(i))
+        was_reset |= dones
+        timesteps[dones] = 0
+        n_disc = obs["discovered_node_count"].cpu().numpy().astype(np.int64)
+        _, _, order, _ = orc.get_state()
+        np.testing.assert_array_equal(n_disc, (order != 0xFFFF).sum(axis=1), err_msg=ctx + " discovered count after reset")
+    assert checked > E * T // 3 and terminal_checked > 0 and after_reset > 0
+    env.close()
+
+
+def _shape(s, valid, avail, won, has_cyber, last_cyber, c):
+    """DefenderEnvWrapper.step's reward shaping (defend_wrapper.py:228-282) in float64 NumPy, one env at a time, updating the wrapper
+    state s (dict of arrays) in place; returns reward, terminated, truncated, breached."""
+    E = valid.shape[0]
+    reward = np.zeros(E, np.float64)
+    term = np.zeros(E, bool)
+    trunc = np.zeros(E, bool)
+    breached = np.zeros(E, bool)
+    branch = dict(first=0, worse=0, recover=0, won=0, trunc=0)
+    for e in range(E):
+        r = 0.0
+        if not valid[e]:
+            s["invalid"][e] += 1
+            r += float(c["invalid_action_penalty"])
+        else:
+            s["valid"][e] += 1
+        cur = float(avail[e])
+        worsening = float(s["prev"][e] - cur)
+        if has_cyber[e]:
+            r += float(-1 * float(last_cyber[e]))
+        if cur < c["maintain_sla"]:
+            breached[e] = True
+            if not s["had"][e]:
+                r += float(c["loss_reward"])
+                term[e] = bool(c["reset_on_constraint_broken"])
+                s["had"][e] = True
+                branch["first"] += 1
+            elif worsening > 0:
+                r += float(-c["sla_worsening_penalty_scale"] * worsening)
+                branch["worse"] += 1
+        else:
+            if s["had"][e]:
+                branch["recover"] += 1
+            s["had"][e] = False
+        s["prev"][e] = cur
+        if won[e]:
+            r = c["winning_reward"]
+            term[e] = True
+            branch["won"] += 1
+        s["t"][e] += 1
+        if s["t"][e] >= c["max_timesteps"]:
+            trunc[e] = True
+            branch["trunc"] += 1
+        reward[e] = r
+    return reward, term, trunc, breached, branch
+
+
+@pytest.mark.parametrize("n_nodes,want", [(24, dict(words_per_set=1, fused_defender_obs=1)), (70, dict(words_per_set=2, fused_defender_obs=0)),
+                                          (129, dict(words_per_set=4, fused_defender_obs=0))])
+def test_defender_vec_env_shaping_against_numpy(n_nodes, want):
+    """DefenderVecEnv.step (mcbs_defender_wrapper_step: defender_turn_post_kernel<WT>, the turn and the reward shaping in one launch, the
+    observation fused into it or a launch of its own) next to AttackerVecEnv(learned_defender=True) beyond ToyCtf, with random defender
+    actions (kinds -1 and -2 included, some aimed at the attacker's nodes) against the oracle's turn and a float64 NumPy restatement of
+    the shaping fed by the oracle's defender_step and the attacker's last environment reward: reward bits, terminated, truncated,
+    sla_breached, defender_won, the valid / invalid counts and the four observation arrays.  SLA, loss_reward and worsening scale make
+    every branch fire: a first breach, a worsening penalty while breached, recovery, eviction and truncation."""
+    from marlon_amd import cyberbattle_env as ce, flatten as F, model
+    from marlon_amd.samples import random_net
+    from marlon_amd.wrappers import AttackerVecEnv, DefenderVecEnv
+    from oracle.oracle import Oracle
+    env_m = random_net.build(model, n_nodes, 5)
+    for _, info in env_m.nodes():
+        info.reimagable = True                        # the entry node too: the defender can evict the attacker
+    topo = F.flatten(env_m)
+    E, T, MAXT_A, MAXT_D = 133, 60, 23, 17
+    sla = {24: 0.9, 70: 0.95, 129: 0.97}[n_nodes]
+    att = AttackerVecEnv(topo, E, maximum_node_count=n_nodes, maximum_total_credentials=max(1, len(topo.triples)),
+                         maximum_discoverable_credentials_per_action=8, attacker_goal=ce.AttackerGoal(own_atleast_percent=1.0),
+                         defender_constraint=ce.DefenderConstraint(sla), losing_reward=0.0, max_timesteps=MAXT_A, seed=29,
+                         learned_defender=True, materialize_masks=False)
+    c = dict(invalid_action_penalty=-3.0, loss_reward=-700.0, sla_worsening_penalty_scale=137.0, maintain_sla=sla, winning_reward=5000.0,
+             reset_on_constraint_broken=False, max_timesteps=MAXT_D)
+    dfd = DefenderVecEnv(att, max_timesteps=MAXT_D, invalid_action_reward=c["invalid_action_penalty"], reset_on_constraint_broken=False,
+                         loss_reward=c["loss_reward"], sla_worsening_penalty_scale=c["sla_worsening_penalty_scale"])
+    _assert_variant(att.engine, defender_kind=2, packed=0, wide=0, **want)
+    orc = Oracle(topo, att.spec)
+    orc.reset()                                          # as the attacker wrapper's reset() did
+    rng = np.random.Generator(np.random.PCG64(31))
+    N = topo.n_nodes
+    full = float(orc.get_state()[0]["availability"][0])
+    s = dict(t=np.zeros(E, np.int64), valid=np.zeros(E, np.int64), invalid=np.zeros(E, np.int64), had=np.zeros(E, bool),
+             prev=np.full(E, full))
+    att_t = np.zeros(E, np.int64)
+    n_disc = np.ones(E, np.int64)
+    counts = dict(first=0, worse=0, recover=0, won=0, trunc=0)
+    for t in range(T):
+        a = _draw_attacker(rng, att.nvec, n_disc, 0.8)
+        rows, valid = _rows_of(a, n_disc)
+        obs, r, term, trunc, info = att.step(a)
+        o = orc.step(rows)
+        att_t += 1
+        ctx = f"random_net({n_nodes}) step {t}"
+        np.testing.assert_array_equal(r.double().cpu().numpy(), o["reward"] + np.where(valid, 0.0, -1.0), err_msg=ctx + " attacker reward")
+        np.testing.assert_array_equal(term.cpu().numpy(), o["terminated"], err_msg=ctx + " attacker terminated")
+        last_cyber = np.where(valid, o["reward"].astype(np.float32).astype(np.float64), 0.0)
+        a_done = (o["terminated"] != 0) | (att_t >= MAXT_A)
+        for i in np.flatnonzero(a_done):                 # the attacker wrapper reset these envs (auto_reset): so does the oracle
+            orc.reset(int(i))
+        att_t[a_done] = 0
+        n_disc = obs["discovered_node_count"].cpu().numpy().astype(np.int64)
+        hdr, nodes, _, _ = orc.get_state()
+        if a_done.any():                                 # a new episode of both agents: the defender wrapper's state too
+            dfd.reset(att.torch.as_tensor(a_done.astype(np.uint8), device=att.engine.device))
+            s["t"][a_done] = 0
+            s["valid"][a_done] = 0
+            s["invalid"][a_done] = 0
+            s["had"][a_done] = False
+            s["prev"][a_done] = hdr["availability"][a_done]
+        da = (rng.random((E, 12)) * dfd.nvec).astype(np.int64)
+        da[rng.random(E) < 0.3, 0] = 0                   # re-imaging: availability falls (breach, worsening) and recovers
+        aim = np.flatnonzero(rng.random(E) < 0.15)       # re-image a node the attacker holds: eviction
+        for e in aim:
+            held = np.flatnonzero(nodes["installed"][e])
+            if held.size:
+                da[e, 0], da[e, 1] = 0, held[rng.integers(held.size)]
+        da[rng.random(E) < 0.05, 0] = -1
+        da[rng.random(E) < 0.05, 0] = -2
+        dobs, dr, dterm, dtrunc, dinfo = dfd.step(da)
+        od = orc.defender_step(da)
+        exp_r, exp_term, exp_trunc, exp_breached, br = _shape(s, od["valid"] != 0, od["availability"], od["evicted"] != 0, ~a_done, last_cyber, c)
+        for k in counts:
+            counts[k] += br[k]
+        np.testing.assert_array_equal(dinfo["valid_action"].cpu().numpy(), od["valid"] != 0, err_msg=ctx + " defender valid")
+        np.testing.assert_array_equal(dinfo["network_availability"].cpu().numpy().view(np.uint64), od["availability"].view(np.uint64),
+                                      err_msg=ctx + " defender availability bits")
+        np.testing.assert_array_equal(dr.cpu().numpy().view(np.uint64), exp_r.view(np.uint64), err_msg=ctx + " defender reward bits")
+        np.testing.assert_array_equal(dterm.cpu().numpy() != 0, exp_term, err_msg=ctx + " defender terminated")
+        np.testing.assert_array_equal(dtrunc.cpu().numpy() != 0, exp_trunc, err_msg=ctx + " defender truncated")
+        np.testing.assert_array_equal(dinfo["sla_breached"].cpu().numpy(), exp_breached, err_msg=ctx + " sla_breached")
+        np.testing.assert_array_equal(dinfo["defender_won"].cpu().numpy(), od["evicted"] != 0, err_msg=ctx + " defender_won")
+        np.testing.assert_array_equal(dfd.valid_action_count.cpu().numpy(), s["valid"], err_msg=ctx + " valid count")
+        np.testing.assert_array_equal(dfd.invalid_action_count.cpu().numpy(), s["invalid"], err_msg=ctx + " invalid count")
+        oo = orc.defender_observe()
+        for k in DEF_KEYS:
+            np.testing.assert_array_equal(dobs[k].cpu().numpy(), oo[k], err_msg=f"{ctx} {k}")
+        d_done = exp_term | exp_trunc                    # the defender's episode ended: its wrapper state starts over
+        if d_done.any():
+            dfd.reset(att.torch.as_tensor(d_done.astype(np.uint8), device=att.engine.device))
+            s["t"][d_done] = 0
+            s["valid"][d_done] = 0
+            s["invalid"][d_done] = 0
+            s["had"][d_done] = False
+            s["prev"][d_done] = od["availability"][d_done]
+    assert all(v > 0 for v in counts.values()), f"shaping branches taken: {counts}"
+    att.close()

@@ -268,12 +268,24 @@ def test_defender_vec_env_matches_marlon_defender_wrapper(name):
     att.close()
 
 
-@pytest.mark.parametrize("case", ["toyctf", "toyctf_separate_observation", "random24", "random70"])
+DEFENDER_CASES = {   # case: the variant the batch must dispatch to
+    "toyctf": dict(packed=1, words_per_set=1, wide=0, fused_defender_obs=1),
+    "toyctf_separate_observation": dict(packed=1, words_per_set=1, wide=0, fused_defender_obs=0),
+    "random24": dict(packed=0, words_per_set=1, wide=0, fused_defender_obs=1),
+    "random70": dict(packed=0, words_per_set=2, wide=0, fused_defender_obs=0),
+    "random129": dict(packed=0, words_per_set=4, wide=0, fused_defender_obs=0),
+    "ad6": dict(packed=0, words_per_set=2, wide=1, fused_defender_obs=1),
+}
+
+
+@pytest.mark.parametrize("case", list(DEFENDER_CASES))
 def test_defender_step_batch_against_oracle(case, monkeypatch):
     """Random attacker rows and random defender vectors on a batch that does not fill its last workgroup: validity, availability bits,
     eviction, the four observation fields and the attacker's rewards equal the oracle's (which keeps real rule lists) at every step.
     ToyCtf and a 24-node instance of the config-5 generator write the observation from the turn kernel itself (round 3: one launch per
     turn), MCBS_NO_FUSED_DEFENDER_OBS=1 and the 70-node instance (two words per node set) through the separate observation launch;
+    the 129-node instance at four words per set (defender_kernel<4>, the attacker's step at WT 4, the separate observation beyond 32
+    nodes); ActiveDirectory-6 on the wide layout (821 cacheable credentials in a column of their own);
     buffers pre-filled with a sentinel.  defend_wrapper.py:329-412,492-534, defender.py:31-107."""
     from marlon_amd import flatten as F, model
     from marlon_amd._abi import EnvSpec
@@ -281,17 +293,23 @@ def test_defender_step_batch_against_oracle(case, monkeypatch):
     from oracle.oracle import Oracle
     if case.startswith("toyctf"):
         topo, nm, cm, E, T = parity.topology_for("toyctf"), 12, 10, 2048 + 37, 120
+    elif case == "ad6":
+        topo = parity.topology_for("ad6_mix_s70")
+        nm, cm, E, T = topo.n_nodes, len(topo.triples), 300 + 37, 60
     else:
         n = int(case[6:])
         topo = F.flatten(random_net.build(model, n, 5))
         nm, cm, E, T = n, max(1, len(topo.triples)), 300 + 37, 60
-    spec = EnvSpec(n_envs=E, maximum_node_count=nm, maximum_total_credentials=cm, maximum_discoverable_credentials_per_action=8,
+    spec = EnvSpec(n_envs=E, maximum_node_count=nm, maximum_total_credentials=cm,
+                   maximum_discoverable_credentials_per_action=max(8, int(topo.header()["max_leak_per_action"])),
                    attacker_goal=dict(own_atleast=6, own_atleast_percent=1.0),
                    maintain_sla=0.6, losing_reward=-5000.0, defender=("external",), auto_reset=True, max_episode_steps=80, seed=4)
     if case == "toyctf_separate_observation":
         monkeypatch.setenv("MCBS_NO_FUSED_DEFENDER_OBS", "1")
     eng = _engine_mod().BatchEngine(topo, spec)
     monkeypatch.delenv("MCBS_NO_FUSED_DEFENDER_OBS", raising=False)
+    v = eng.variant()
+    assert {k: v[k] for k in DEFENDER_CASES[case]} == DEFENDER_CASES[case] and v["defender_kind"] == 2, f"{case}: batch dispatches to {v}"
     orc = Oracle(topo, spec)
     rng = np.random.Generator(np.random.PCG64(9))
     N = int(topo.n_nodes)

@@ -79,6 +79,8 @@ CASES = {
     "sink_evict": ("sink_evict_s44", dict(), 1024, 200),
     "random24_defender": ("random24_defender_s51", dict(), 1024, 200),
     "ad6_wide_cache": ("ad6_mix_s70", dict(), 512, 200),          # 821 cacheable credentials: the set lives in memory / LDS
+    # ... with ScanAndReimage: the wide layout's re-imaging ring and `cach` column
+    "ad6_wide_scan": ("ad6_mix_s70", dict(defender=("scan_and_reimage", 0.6, 2, 3), maintain_sla=0.5), 512, 200),
     "random_s5_defender": ("random_s5_defender_s67", dict(), 512, 150),
     # ExternalRandomEvents with Philox draws: per-env vulnerability keys, service bits and firewall lists diverge between envs
     "toyctf_randomevents": ("toyctf_randomevents_s81", dict(), 1024, 200),
@@ -99,6 +101,9 @@ def test_engine_matches_oracle_batched(case, policy):
     spec = parity.spec_from_json(sj, n_envs=E, auto_reset=True, rng_kind=RNG_PHILOX, seed=0xC0FFEE + len(case),
                                  env_id_base=1000, max_episode_steps=150, **over)
     eng = _engine().BatchEngine(topo, spec)
+    if case.startswith("ad6"):
+        v = eng.variant()
+        assert v["wide"] == 1 and v["defender_kind"] == (1 if case == "ad6_wide_scan" else 0), f"{case}: batch dispatches to {v}"
     orc = Oracle(topo, spec)
     for t in range(steps):
         a = eng.sample_actions(policy == "valid", seed=77, step=t)

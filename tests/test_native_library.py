@@ -36,6 +36,22 @@ def test_abi_struct_sizes_match_header():
     assert flatten.HEADER_DT.itemsize == 192 and flatten.NODE_DT.itemsize == 64 and flatten.SLOT_DT.itemsize == 32
 
 
+def test_batch_variant_struct_matches_header():
+    """mcbs_batch_variant_info: the ctypes mirror has the header's members in the header's order, all uint32_t, 32 bytes; the query
+    refuses null arguments without a GPU."""
+    from marlon_amd._abi import BatchVariantInfo
+    text = open(os.path.join(REPO, "include", "mcbs.h")).read()
+    body = re.search(r"typedef struct mcbs_batch_variant_info \{(.*?)\} mcbs_batch_variant_info;", text, flags=re.S).group(1)
+    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
+    members = re.findall(r"(\w+)\s+(\w+);", body)
+    assert members and all(ty == "uint32_t" for ty, _ in members)
+    assert [n for _, n in members] == [n for n, _ in BatchVariantInfo._fields_]
+    assert C.sizeof(BatchVariantInfo) == 32
+    lib = engine.load_library()
+    v = BatchVariantInfo()
+    assert lib.mcbs_batch_variant(None, C.byref(v)) == -1 and b"null" in lib.mcbs_last_error()
+
+
 def test_topology_create_rejects_malformed_blobs_without_gpu():
     lib = engine.load_library()
     out = C.c_void_p()
