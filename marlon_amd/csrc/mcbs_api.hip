@@ -341,7 +341,9 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     S.TW = (h->n_triples + 63) / 64; if (!S.TW) S.TW = 1;
     S.Cmax = cfg->maximum_total_credentials;
     S.off_disc = 0;                                                             // u8 discovery order, >= 16 bytes
-    // both lists have one slack entry past their capacity: the step kernel appends unconditionally and only advances the count
+    // both lists have one slack entry past their capacity: the cooperative step kernel (mcbs_step_coop.hip) and the looping variant of
+    // mcbs_step.hip (mcbs_step_many / mcbs_rollout_random) append every leaked element and only advance the count for a new one; the
+    // other step kernels store new elements only
     S.off_cred = (uint32_t)align_up((size_t)N + 1, 16);                         // u16 credential cache, >= 32 bytes
     S.off_rows = (uint32_t)align_up((size_t)S.off_cred + (2u * (h->n_triples + 1u) > 32u ? 2u * (h->n_triples + 1u) : 32u), 16);
     const bool external = cfg->defender_kind == MCBS_DEFENDER_EXTERNAL;

@@ -39,8 +39,11 @@
 // four single-issue instructions at one wave per SIMD) whether or not any lane takes it.  The attacker's action is
 // therefore written as straight-line predicated arithmetic: indices are clamped so that every look-up is safe for
 // every lane, both the connect-side and the exploit-side tables are read, every check of the reference becomes a
-// boolean, and the state changes are masked by the conjunction (`go`).  Loads and stores are unconditional wherever
-// storing the unchanged value back is harmless.  What remains as real branches: the payload loop of leaked
+// boolean, and the state changes are masked by the conjunction (`go`).  Loads are unconditional wherever the look-up is
+// safe; stores are exec-masked to what changed, decided against the value the step loaded (registers, never a re-read): the
+// launch boundary writes back every line a step dirties, and storing every row, set and header back unchanged made that the part
+// of the step that grows with the batch (profiles/round3_notes.md section 11; the looping variant keeps unconditional stores, see
+// step_body).  What remains as real branches: the payload loop of leaked
 // credentials / nodes, list entries past the first 16, the in-env defender, and the wave-level auto-reset.
 //
 // Rules restated from the reference (citations = /root/reference/src/CyberBattleSim/cyberbattle/...):
@@ -124,6 +127,16 @@ __device__ __forceinline__ uint32_t dword_of(const uint4& r0, const uint4& r1, c
     return (uint32_t)((b3 ? s1 : s0) >> ((i & 1u) * 32u));
 }
 
+// the step stores a row, a header or a set only when its bits changed, decided against the value it loaded (registers, no re-read).
+// Such a store is written `if (MCBS_CHANGED(changed)) ...`: expecting the store to happen makes the compiler keep it as an exec-masked
+// store with no `s_cbranch_execz` around it (its branch cost model skips a block only when it expects the block's lanes to be off).
+// A macro, not a function: the hint must sit in the branch's own condition to reach it.
+#define MCBS_CHANGED(changed) __builtin_expect((bool)(changed), 1)
+__device__ __forceinline__ bool differs(const uint4& a, const uint4& b) { return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0u; }
+__device__ __forceinline__ bool differs(const double2& a, const double2& b) {   // bit patterns, not values: -0.0 + 0.0 is a change
+    return ((__double_as_longlong(a.x) ^ __double_as_longlong(b.x)) | (__double_as_longlong(a.y) ^ __double_as_longlong(b.y))) != 0;
+}
+
 // entry i (< 16) of a 16-byte vector of u8 / of two 16-byte vectors of u16 := v (64-bit mask arithmetic, see byte_of)
 __device__ __forceinline__ void put_byte(uint4& v, uint32_t i, uint32_t x) {
     uint64_t lo = (uint64_t)v.x | ((uint64_t)v.y << 32), hi = (uint64_t)v.z | ((uint64_t)v.w << 32);
@@ -165,7 +178,7 @@ struct Lane {
     // the target node's row, in registers
     uint64_t props;      // discovered properties (60 bits)
     uint32_t ever, since, tags;
-    bool row_dirty;      // (unused by the step kernel: the row is always written back)
+    bool row_dirty;      // (unused by the step kernel: it compares the row with the one it loaded)
     // learned-defender tier: this env's firewall state of source / target (12 bits per rule list, see mcbs_defend.hip), else unused
     bool learned;
     uint32_t fw_src, fw_tgt;
@@ -208,7 +221,8 @@ struct Lane {
     //            `port` / `triple` = connect arguments (0 for exploits).  Every index is valid for every lane.
     // WIDE_OK = false: the batch cannot have a wide cached-triple set (packed layout); compiles its handling out.
     // DK: the batch's defender kind; MCBS_DEFENDER_RANDOM_EVENTS consults the env's own vulnerability / service / firewall state
-    template <bool WIDE_OK, int DK, bool REC = false>
+    // GUARD = false (the looping variant, see step_body): list appends go to the slot past the end whether or not the element is new
+    template <bool WIDE_OK, int DK, bool REC = false, bool GUARD = true>
     __device__ __forceinline__ void act(bool X, double raw_nx, int kind, uint32_t src, uint32_t tgt, uint32_t col, uint32_t port, uint32_t triple) {
         const bool k2 = kind == 2;
         // ---- look-ups of both flavours (LDS) ----
@@ -324,8 +338,9 @@ struct Lane {
         __builtin_amdgcn_s_waitcnt(0x0F70);              // vmcnt(0), expcnt / lgkmcnt untouched
         auto leak = [&](const uint2 p) {                 // one LeakedCredentials / LeakedNodesId entry {node | cred << 16, triple | port << 16}
             const uint32_t pn = p.x & 0xFFFFu, pc = p.x >> 16, pt = p.y & 0xFFFFu;
-            // appends go to the slot past the list's end whether or not the element is new (the lists have one slack slot):
-            // the count only advances for a new element, so a stale write is overwritten or never read
+            // an element is appended only if it is new (an exec-masked store; nothing reads a list at or past its count, and
+            // mcbs_get_state reports 0xFFFF there; the lists keep one slack slot for !GUARD).  The record heads (REC) take every entry:
+            // registers, read below the counts only
             const bool new_n = !rget<WT>(m[M_DISC], pn);
             const bool new_g = creds & !rget<WT>(m[M_GATH], pc);
             bool new_c;
@@ -335,8 +350,8 @@ struct Lane {
                 new_c = creds & !(old & bit);
                 if (stage) *w = old | bit;
             } else new_c = creds & !rget<WT>(m[M_CACH], pt);
-            disc_list()[n_disc] = (uint8_t)pn;
-            cred_list()[n_creds] = (uint16_t)pt;
+            if (!GUARD || MCBS_CHANGED(new_n)) disc_list()[n_disc] = (uint8_t)pn;
+            if (!GUARD || MCBS_CHANGED(new_c)) cred_list()[n_creds] = (uint16_t)pt;
             if (REC) {                                   // (packed batches: both lists have fewer than 16 entries)
                 put_byte(rec_dh, n_disc & 15u, pn);
                 put_half(rec_c0, rec_c1, n_creds & 15u, pt);
@@ -484,6 +499,10 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
     constexpr bool learned = DEFK == MCBS_DEFENDER_EXTERNAL;           // firewall rules are per-env state (learned defender)
     constexpr bool ere = DEFK == MCBS_DEFENDER_RANDOM_EVENTS;          // ExternalRandomEvents: per-env vulnerability / service / firewall state
     constexpr bool def_avail = has_def || ere;                         // a defender agent exists: availability goals and the SLA constraint apply
+    // Stores only what changed (header comment) — except in the looping variant: between the steps of one launch its state stays in
+    // L2 and is written back once, at the end, so the guards would only add instructions (step_many measured ~2 % slower with them,
+    // profiles/round3_notes.md section 11).  MANY instantiations compile the unconditional stores.
+    constexpr bool GUARD = !MANY;
 
     // MANY: mcbs_step_many — n_steps consecutive steps of every env in ONE launch (action batches [n_steps, E, 5], outputs
     // [n_steps, E]); each iteration is the whole step below against the state the previous one stored (a lane reads its own
@@ -532,8 +551,9 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
         if (S.N > 12u) rw3 = rp[3];
     }
     uint64_t m0[M_COUNT][WT];        // every set is stored padded to WT words: no bounds to test, all loads independent
+    uint4 pk = make_uint4(0, 0, 0, 0);
     if (PK) {
-        const uint4 pk = reinterpret_cast<const uint4*>(S.masks)[ec];
+        pk = reinterpret_cast<const uint4*>(S.masks)[ec];
         const uint32_t f[4] = {pk.x, pk.y, pk.z, pk.w};
 #pragma unroll
         for (int k = 0; k < M_COUNT; ++k) m0[k][0] = (f[k >> 1] >> ((k & 1) * 16)) & 0xFFFFu;
@@ -555,6 +575,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
         if (PK || (def_avail && C.rng_kind == MCBS_RNG_PHILOX)) episode = S.episode[ec];
     }
     if (PHASE == 2) pending = S.pending[ec];
+    const double2 h1_in = h1;
 
     if constexpr (Hook::kFinish) hook.level1(ec);                  // its own level-1 loads (wrapper counters ...) go out behind the step's
     STAMP_NOWAIT(1);   // level-1 loads issued
@@ -643,8 +664,10 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
         }
         // ---------------- level 2: the target row (packed batches: already here) ----------------
         uint4 r0;
+        uint32_t pw0 = 0;                                       // packed: the target's row word as loaded
         if (PK) {
-            const uint32_t w = dword_of(rw0, rw1, rw2, rw3, tgt), vm = (1u << S.tiny_v) - 1u;
+            pw0 = dword_of(rw0, rw1, rw2, rw3, tgt);
+            const uint32_t w = pw0, vm = (1u << S.tiny_v) - 1u;
             r0 = make_uint4(w & ((1u << S.tiny_p) - 1u), ((w >> S.tiny_p) & 0xFu) << 28, (w >> (S.tiny_p + 4u)) & vm,
                             (w >> (S.tiny_p + 4u + S.tiny_v)) & vm);
         } else r0 = *reinterpret_cast<const uint4*>(ln.row(tgt));
@@ -657,16 +680,18 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
         ln.props = pt & ROW_PROPS_MASK; ln.tags = (uint32_t)(pt >> 60);
         ln.ever = r0.z; ln.since = r0.w;
         STAMP(3);  // row landed
-        ln.template act<!PK, DEFK, Hook::kObs>(X, skip ? -1.0 : 0.0, kind, src, tgt, X ? (k0 ? a2 : (k1 ? cL + a3 : 0u)) : 0u, (X & k2) ? a3 : 0u, triple);
-        // unchanged rows are written back as they were
+        ln.template act<!PK, DEFK, Hook::kObs, GUARD>(X, skip ? -1.0 : 0.0, kind, src, tgt, X ? (k0 ? a2 : (k1 ? cL + a3 : 0u)) : 0u, (X & k2) ? a3 : 0u, triple);
+        // the row goes back only if the action changed it (first attack / discovery of a (node, vulnerability) pair, new properties
+        // or tags); `pword` holds the row as the attacker left it either way, for reimage()
         if (PK) {
             const uint32_t w = S.tiny_pack(ln.props, ln.tags, ln.ever, ln.since);
-            reinterpret_cast<uint32_t*>(body + S.off_rows)[tgt] = w;
+            if (!GUARD || MCBS_CHANGED(w != pw0)) reinterpret_cast<uint32_t*>(body + S.off_rows)[tgt] = w;
             if (PHASE == 0) { ln.rows_in_regs = true; ln.prw0 = rw0; ln.prw1 = rw1; ln.prw2 = rw2; ln.prw3 = rw3; ln.ptgt = tgt; ln.pword = w; }
         }
         else {
             const uint64_t wpt = ln.props | ((uint64_t)ln.tags << 60);
-            *reinterpret_cast<uint4*>(ln.row(tgt)) = make_uint4((uint32_t)wpt, (uint32_t)(wpt >> 32), ln.ever, ln.since);
+            const uint4 nr = make_uint4((uint32_t)wpt, (uint32_t)(wpt >> 32), ln.ever, ln.since);
+            if (!GUARD || MCBS_CHANGED(differs(nr, r0))) *reinterpret_cast<uint4*>(ln.row(tgt)) = nr;
         }
         STAMP(4);      // attacker logic and row store done
         const uint32_t nf = (oob ? F_OOB : 0u) | ((uint32_t)ln.okind << F_KIND_SHIFT) | ((uint32_t)ln.olevel << F_LEVEL_SHIFT) |
@@ -683,7 +708,8 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
 
     if (PHASE == 1) {
         if (live) S.pending[e] = ln.raw;
-        S.h0[e] = make_uint4(step, flags, ln.n_disc | (ln.n_creds << 16), ln.owned | (ln.dclk << 16));
+        const uint4 nh0 = make_uint4(step, flags, ln.n_disc | (ln.n_creds << 16), ln.owned | (ln.dclk << 16));
+        if (!GUARD || MCBS_CHANGED(differs(nh0, h0))) S.h0[e] = nh0;     // unchanged for an env that has ended
     } else {
         double reward = 0.0;
         bool done = false;
@@ -735,19 +761,23 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
             hk_reward = (float)reward;
             hk_done = live ? done : ((old_flags & F_DONE) != 0);
             flags |= (done ? F_DONE : 0u) | (trunc ? F_TRUNC : 0u);
-            S.h0[e] = make_uint4(step, flags, ln.n_disc | (ln.n_creds << 16), ln.owned | (ln.dclk << 16));
-            S.h1[e] = h1;
+            // a live env's step counter always moves; an ended or skipped env's header and {cum_reward, availability} stay as they were,
+            // and h1 changes only with a non-zero reward or a new availability
+            const uint4 nh0 = make_uint4(step, flags, ln.n_disc | (ln.n_creds << 16), ln.owned | (ln.dclk << 16));
+            if (!GUARD || MCBS_CHANGED(differs(nh0, h0))) S.h0[e] = nh0;
+            if (!GUARD || MCBS_CHANGED(differs(h1, h1_in))) S.h1[e] = h1;
         }
     }
     {
-        // sets the phase can have changed go back whole (WT == 1: one coalesced 8-byte store per set beats a compare and a
-        // branch); an env about to be reset gets its columns rewritten below, after these stores in program order
+        // set words the phase may have changed go back only if they did (an exec-masked store; an env about to be reset gets its
+        // columns rewritten below, after these stores in program order)
         if (PK) {
             if (PHASE != 2 || has_def) {
                 uint32_t f[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) f[q] = (uint32_t)ln.m[2 * q][0] | ((uint32_t)ln.m[2 * q + 1][0] << 16);
-                reinterpret_cast<uint4*>(S.masks)[e] = make_uint4(f[0], f[1], f[2], f[3]);
+                const uint4 npk = make_uint4(f[0], f[1], f[2], f[3]);
+                if (!GUARD || MCBS_CHANGED(differs(npk, pk))) reinterpret_cast<uint4*>(S.masks)[e] = npk;
             }
         } else {
 #pragma unroll
@@ -757,7 +787,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
                 if (!((PHASE != 2 && attacker_set) || (PHASE != 1 && has_def && defender_set))) continue;
 #pragma unroll
                 for (int w = 0; w < WT; ++w)
-                    if (WT == 1 || ln.m[k][w] != m0[k][w]) S.masks[((uint32_t)k * WT + (uint32_t)w) * S.E + e] = ln.m[k][w];
+                    if ((!GUARD && WT == 1) || MCBS_CHANGED(ln.m[k][w] != m0[k][w])) S.masks[((uint32_t)k * WT + (uint32_t)w) * S.E + e] = ln.m[k][w];
             }
         }
     }
