@@ -396,6 +396,41 @@ int  mcbs_apply_packed_mask(const mcbs_batch*, const uint32_t* bits, size_t bits
 int  mcbs_unpack_action_mask(const mcbs_batch*, const uint32_t* bits, size_t bits_row_words, uint8_t* out, size_t out_row_stride,
                              uint64_t n_rows, void* stream);
 
+/* ---- feature encoder: observation rows -> the float rows a policy's first layer takes, one launch ----
+ * What Stable-Baselines3's "MultiInputPolicy" (marlon/baseline_models/ppo/train.py:79) does first with the wrappers' Dict observation
+ * (preprocess_obs + CombinedExtractor): a Discrete(n) becomes a one-hot of n, every element of a MultiDiscrete a one-hot of its own, a
+ * MultiBinary 0.0 / 1.0, all concatenated in key order.  The row layout is the caller's (marlon_amd/features.py derives it from the
+ * reference's spaces) and is handed over once:
+ *   desc[n_desc]: one word per one-hot column, in row order with the mask columns left out: bits 0-15 the column's class, bits 16-30 the
+ *     index of its source value among the row's int32 values — the five int32 fields of mcbs_obs_buffers in the struct's order,
+ *     flattened: scalars [7], leaked_credentials [K*4], credential_cache_matrix [C*2], discovered_nodes_properties [N*n_props],
+ *     nodes_privilegelevel [N] — and bit 31 set on the first column of every element.  The columns of an element are consecutive,
+ *     classes 0, 1, 2, ... of one source (MCBS_EINVAL otherwise; MCBS_ELIMIT for a source index beyond 32 767 or 65 536 classes).
+ *   mask_ranges[n_mask_ranges][3] (at most three, ascending, not overlapping): (first column of the row, columns, first bit): columns
+ *     copied as 0 / 1 from the packed action mask (the format of mcbs_pack_action_mask; bits beyond mcbs_discrete_action_count:
+ *     MCBS_EINVAL).
+ *   F = n_desc + the ranges' columns (mcbs_feature_layout_width).
+ * mcbs_encode_features: out[i, j] for i < n_rows, j < F = 1 where column j's source value of row i equals its class (its mask bit is
+ *   set), else 0, as float32 / bfloat16 / float16 (exactly 0 and 1 in each).  obs: the five int32 fields as DENSE rows of their own width,
+ *   n_rows rows (a field the layout never reads may be NULL; the mask pointers are ignored); bits [n_rows, bits_row_words >= W] is read
+ *   only when the layout has mask columns (NULL then: MCBS_EINVAL).  n_rows is any count: the live observation of the batch or a
+ *   minibatch gathered from a rollout buffer; the batch supplies the device and the geometry only — no digest is read, so every defender
+ *   kind is served.  out_row_stride in elements, >= F (MCBS_EINVAL otherwise); elements from F up to the stride are never touched, and
+ *   every column below F is written (zeros too): the buffer need not be cleared.  Rows on 16-byte boundaries are written with 16-byte
+ *   stores, rows on 8- / 4- / 2-byte boundaries with narrower ones.
+ *   A value outside [0, classes) leaves its element's columns all zero; out_of_range (optional device uint32_t) is INCREASED by the
+ *   number of such elements (not zeroed by the call). */
+#define MCBS_FEATURES_F32  0    /* = MCBS_LOGITS_F32 */
+#define MCBS_FEATURES_BF16 1    /* = MCBS_LOGITS_BF16 */
+#define MCBS_FEATURES_F16  2
+typedef struct mcbs_feature_layout mcbs_feature_layout;
+int  mcbs_feature_layout_create(const mcbs_batch*, const uint32_t* desc, size_t n_desc, const uint32_t* mask_ranges, size_t n_mask_ranges,
+                                mcbs_feature_layout** out);
+void mcbs_feature_layout_destroy(mcbs_feature_layout*);
+uint64_t mcbs_feature_layout_width(const mcbs_feature_layout*);
+int  mcbs_encode_features(const mcbs_batch*, const mcbs_feature_layout*, const mcbs_obs_buffers* obs, const uint32_t* bits, size_t bits_row_words,
+                          void* out, int32_t dtype, size_t out_row_stride, uint64_t n_rows, uint32_t* out_of_range, void* stream);
+
 /* ---- learned defender: marlon/baseline_models/env_wrappers/defend_wrapper.py:197-327,329-412,492-534
  * and marlon/defender_agents/defender.py:31-107, for batches created with MCBS_DEFENDER_EXTERNAL ---- */
 typedef struct mcbs_defender_obs {   /* DefenderEnvWrapper.observe: four MultiBinary fields, int8, network node order */

@@ -18,6 +18,7 @@
 #include "mcbs_defend.hip"
 #include "mcbs_logits.hip"
 #include "mcbs_packed_mask.hip"
+#include "mcbs_features.hip"
 #include "mcbs_wrapper_fused.hip"
 
 using namespace mcbs;
@@ -1312,6 +1313,154 @@ extern "C" int mcbs_unpack_action_mask(const mcbs_batch* b, const uint32_t* bits
     if (n_rows == 0) return MCBS_OK;
     hipLaunchKernelGGL(unpack_mask_kernel, packed_rows_grid(n_rows, (A + 15u + 15u) / 16u), dim3(256), 0, (hipStream_t)stream, bits, bits_row_words, out, out_row_stride, n_rows, A);
     return launch_ok("unpack action mask");
+}
+
+// ------------------------------------------------------------------ feature encoder
+struct mcbs_feature_layout {
+    int32_t device = 0;
+    FeatGeom G{};
+    uint32_t* desc_dev = nullptr;
+    uint2* elems_dev = nullptr;     // per source value: (first one-hot column, classes) of its element; NULL when two elements share a value
+    uint32_t fields_used = 0;       // bit k: some descriptor reads observation field k
+    uint64_t A = 0;                 // Discrete actions of the batch the layout was made for
+};
+
+extern "C" int mcbs_feature_layout_create(const mcbs_batch* b, const uint32_t* desc, size_t n_desc, const uint32_t* mask_ranges,
+                                          size_t n_mask_ranges, mcbs_feature_layout** out) {
+    if (!b || !out || (!desc && n_desc) || (!mask_ranges && n_mask_ranges)) return fail(MCBS_EINVAL, "null argument");
+    if (n_mask_ranges > FEAT_MAX_RANGES) return fail(MCBS_EINVAL, "at most %u mask ranges, got %zu", FEAT_MAX_RANGES, n_mask_ranges);
+    if (n_desc >= (1ull << 30)) return fail(MCBS_ELIMIT, "feature layout: too many columns");
+    FeatGeom G{};
+    const uint64_t lens[5] = {7u, (uint64_t)b->cfg.maximum_discoverable_credentials_per_action * 4u, (uint64_t)b->cfg.maximum_total_credentials * 2u,
+                              (uint64_t)b->cfg.maximum_node_count * b->topo->H()->n_props, b->cfg.maximum_node_count};
+    uint64_t V = 0;
+    for (int k = 0; k < 5; ++k) { G.len[k] = (uint32_t)lens[k]; G.off[k] = (uint32_t)V; V += lens[k]; }
+    uint32_t used = 0;
+    std::vector<uint2> elems((size_t)V, make_uint2(0u, 0u));
+    bool elems_ok = true;
+    uint32_t cur = 0;
+    for (size_t j = 0; j < n_desc; ++j) {
+        const uint32_t d = desc[j], cls = d & (FEAT_MAX_CLASS - 1u), s = (d >> 16) & (FEAT_MAX_SRC - 1u);
+        if (s >= V) return fail(MCBS_EINVAL, "feature layout: column %zu reads value %u of %llu per row", j, s, (unsigned long long)V);
+        if (d >> 31) {
+            if (cls != 0u) return fail(MCBS_EINVAL, "feature layout: column %zu starts an element with class %u", j, cls);
+            if (elems[s].y) elems_ok = false;
+            elems[s] = make_uint2((uint32_t)j, 1u);
+            cur = s;
+        } else {
+            const uint32_t p = j ? desc[j - 1] : 0u;
+            if (!j || ((p >> 16) & (FEAT_MAX_SRC - 1u)) != s || (p & (FEAT_MAX_CLASS - 1u)) + 1u != cls)
+                return fail(MCBS_EINVAL, "feature layout: column %zu does not continue the element before it (classes 0, 1, 2, ... of one value)", j);
+            elems[cur].y += 1u;
+        }
+        uint32_t k = 0;
+        for (uint32_t q = 1; q < 5u; ++q) k += (uint32_t)(s >= G.off[q]);
+        used |= 1u << k;
+    }
+    const uint64_t A = mcbs_discrete_action_count(b);
+    if (n_mask_ranges && A >= (1ull << 31)) return fail(MCBS_ELIMIT, "Discrete action space too large for one launch");
+    uint64_t F = n_desc, next_col = 0, top_bit = 0;
+    for (size_t r = 0; r < n_mask_ranges; ++r) {
+        const uint64_t c0 = mask_ranges[3 * r], n = mask_ranges[3 * r + 1], b0 = mask_ranges[3 * r + 2];
+        if (n == 0 || c0 < next_col) return fail(MCBS_EINVAL, "feature layout: mask range %zu is empty or not above the one before it", r);
+        if (b0 + n > A) return fail(MCBS_EINVAL, "feature layout: mask range %zu reads bits up to %llu of %llu Discrete actions", r,
+                                    (unsigned long long)(b0 + n), (unsigned long long)A);
+        G.rc0[r] = (uint32_t)c0; G.rn[r] = (uint32_t)n; G.rb0[r] = (uint32_t)b0;
+        next_col = c0 + n;
+        F += n;
+        if (b0 + n > top_bit) top_bit = b0 + n;
+    }
+    if (next_col > F) return fail(MCBS_EINVAL, "feature layout: a mask range ends at column %llu of %llu", (unsigned long long)next_col, (unsigned long long)F);
+    if (F == 0 || F >= (1ull << 30)) return fail(F ? MCBS_ELIMIT : MCBS_EINVAL, "feature layout: %llu columns", (unsigned long long)F);
+    G.F = (uint32_t)F; G.n_desc = (uint32_t)n_desc; G.V = (uint32_t)V; G.n_ranges = (uint32_t)n_mask_ranges;
+    G.W = (uint32_t)((top_bit + 31u) / 32u);
+    DeviceGuard guard(b->cfg.device);
+    if (guard.err != hipSuccess) return fail(MCBS_EHIP, "cannot select device %d: %s", b->cfg.device, hipGetErrorString(guard.err));
+    mcbs_feature_layout* l = new (std::nothrow) mcbs_feature_layout();
+    if (!l) return fail(MCBS_ENOMEM, "out of memory");
+    l->device = b->cfg.device; l->G = G; l->fields_used = used; l->A = A;
+    if (n_desc) {
+        hipError_t e = hipMalloc(&l->desc_dev, n_desc * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpy(l->desc_dev, desc, n_desc * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e == hipSuccess && elems_ok) {
+            e = hipMalloc(&l->elems_dev, elems.size() * sizeof(uint2));
+            if (e == hipSuccess) e = hipMemcpy(l->elems_dev, elems.data(), elems.size() * sizeof(uint2), hipMemcpyHostToDevice);
+        }
+        if (e != hipSuccess) {
+            if (l->desc_dev) (void)hipFree(l->desc_dev);
+            if (l->elems_dev) (void)hipFree(l->elems_dev);
+            delete l;
+            return fail(MCBS_EHIP, "feature layout: descriptor upload failed: %s", hipGetErrorString(e));
+        }
+    }
+    *out = l;
+    return MCBS_OK;
+}
+
+extern "C" void mcbs_feature_layout_destroy(mcbs_feature_layout* l) {
+    if (!l) return;
+    DeviceGuard guard(l->device);
+    if (l->desc_dev) (void)hipFree(l->desc_dev);
+    if (l->elems_dev) (void)hipFree(l->elems_dev);
+    delete l;
+}
+
+extern "C" uint64_t mcbs_feature_layout_width(const mcbs_feature_layout* l) { return l ? l->G.F : 0u; }
+
+extern "C" int mcbs_encode_features(const mcbs_batch* b, const mcbs_feature_layout* l, const mcbs_obs_buffers* obs, const uint32_t* bits,
+                                    size_t bits_row_words, void* out, int32_t dtype, size_t out_row_stride, uint64_t n_rows,
+                                    uint32_t* out_of_range, void* stream) {
+    if (!b || !l || !obs || !out) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    if (dtype != MCBS_FEATURES_F32 && dtype != MCBS_FEATURES_BF16 && dtype != MCBS_FEATURES_F16)
+        return fail(MCBS_EINVAL, "features dtype must be MCBS_FEATURES_F32, MCBS_FEATURES_BF16 or MCBS_FEATURES_F16");
+    const FeatGeom& G = l->G;
+    if (l->device != b->cfg.device || l->A != mcbs_discrete_action_count(b) || G.len[1] != b->cfg.maximum_discoverable_credentials_per_action * 4u ||
+        G.len[2] != b->cfg.maximum_total_credentials * 2u || G.len[3] != b->cfg.maximum_node_count * b->topo->H()->n_props ||
+        G.len[4] != b->cfg.maximum_node_count)
+        return fail(MCBS_EINVAL, "mcbs_encode_features: the layout was created for a batch of another device or geometry");
+    if (out_row_stride < G.F) return fail(MCBS_EINVAL, "out_row_stride %zu is shorter than the %u feature columns", out_row_stride, G.F);
+    FeatSrc src{{obs->scalars, obs->leaked_credentials, obs->credential_cache_matrix, obs->discovered_nodes_properties, obs->nodes_privilegelevel}};
+    static const char* const names[5] = {"scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel"};
+    for (uint32_t k = 0; k < 5u; ++k)
+        if (((l->fields_used >> k) & 1u) && !src.f[k]) return fail(MCBS_EINVAL, "mcbs_encode_features: the layout reads obs->%s, which is NULL", names[k]);
+    if (G.W) {
+        if (!bits) return fail(MCBS_EINVAL, "mcbs_encode_features: the layout has mask columns and bits is NULL");
+        if (bits_row_words < G.W) return fail(MCBS_EINVAL, "bits_row_words %zu is shorter than the %u words the layout's mask columns read", bits_row_words, G.W);
+    }
+    if (n_rows == 0) return MCBS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    // one wavefront per row, four per workgroup, rows beyond one grid's worth in a loop: about eight workgroups per CU keep the
+    // descriptor table's trip into LDS a small share of a workgroup's life
+    const uint64_t blocks = (n_rows + 3u) / 4u;
+    const dim3 grid(blocks < 2048u ? (uint32_t)blocks : 2048u), block(256);
+    // the per-element kernel when its LDS fits (element table + four wavefronts' one-hot rows and bit words), else column by column from memory
+    const size_t item = dtype == MCBS_FEATURES_F32 ? 4u : 2u, per = 16u / item;
+    const size_t lds = (((size_t)G.V + 1u) / 2u + 4u * (((size_t)G.n_desc + per - 1u) / per + ((size_t)G.W + 3u) / 4u)) * 16u;
+    const bool rows_kernel = l->elems_dev && lds <= 48u * 1024u;
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(out);
+#define MCBS_FEAT_LAUNCH(T_, GW_, VEC_, ONE_)                                                                                                \
+    do {                                                                                                                                     \
+        if (rows_kernel) hipLaunchKernelGGL((encode_features_rows_kernel<T_, GW_, VEC_>), grid, block, lds, st, G, src, l->elems_dev, bits,   \
+                                            bits_row_words, static_cast<T_*>(out), out_row_stride, n_rows, (T_)(ONE_), out_of_range);         \
+        else hipLaunchKernelGGL((encode_features_kernel<T_, GW_, VEC_>), grid, block, 0, st, G, src, l->desc_dev, bits,                \
+                                bits_row_words, static_cast<T_*>(out), out_row_stride, n_rows, (T_)(ONE_), out_of_range);                     \
+    } while (0)
+    if (dtype == MCBS_FEATURES_F32) {
+        const size_t rb = out_row_stride * 4u;
+        if (rb % 16 == 0 && p0 % 16 == 0) MCBS_FEAT_LAUNCH(uint32_t, 4u, true, 0x3F800000u);
+        else if (rb % 8 == 0 && p0 % 8 == 0) MCBS_FEAT_LAUNCH(uint32_t, 2u, true, 0x3F800000u);
+        else MCBS_FEAT_LAUNCH(uint32_t, 1u, true, 0x3F800000u);
+    } else {
+        const uint32_t one = dtype == MCBS_FEATURES_BF16 ? 0x3F80u : 0x3C00u;
+        const size_t rb = out_row_stride * 2u;
+        if (rb % 16 == 0 && p0 % 16 == 0) MCBS_FEAT_LAUNCH(uint16_t, 8u, true, one);
+        else if (rb % 8 == 0 && p0 % 8 == 0) MCBS_FEAT_LAUNCH(uint16_t, 4u, true, one);
+        else if (rb % 4 == 0 && p0 % 4 == 0) MCBS_FEAT_LAUNCH(uint16_t, 2u, true, one);
+        else MCBS_FEAT_LAUNCH(uint16_t, 2u, false, one);
+    }
+#undef MCBS_FEAT_LAUNCH
+    return launch_ok("encode features");
 }
 
 // ------------------------------------------------------------------ learned defender

@@ -26,6 +26,7 @@ EXPORTS = [
     "mcbs_timing_enable", "mcbs_timing_read", "mcbs_mask_logits", "mcbs_discrete_action_count", "mcbs_copy_rows_masked", "mcbs_attacker_wrapper_finish", "mcbs_attacker_wrapper_step",
     "mcbs_attacker_wrapper_step_launches", "mcbs_set_mask_discrete_stride", "mcbs_defender_wrapper_step",
     "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant",
+    "mcbs_feature_layout_create", "mcbs_feature_layout_destroy", "mcbs_feature_layout_width", "mcbs_encode_features",
 ]
 
 _lib = None
@@ -93,6 +94,13 @@ def load_library(path: Optional[str] = None):
     lib.mcbs_pack_action_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcbs_apply_packed_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_size_t, C.c_uint64, C.c_float, C.c_void_p]
     lib.mcbs_unpack_action_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]
+    lib.mcbs_feature_layout_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+    lib.mcbs_feature_layout_destroy.argtypes = [C.c_void_p]
+    lib.mcbs_feature_layout_destroy.restype = None
+    lib.mcbs_feature_layout_width.restype = C.c_uint64
+    lib.mcbs_feature_layout_width.argtypes = [C.c_void_p]
+    lib.mcbs_encode_features.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ObsBuffers), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_size_t,
+                                         C.c_uint64, C.c_void_p, C.c_void_p]
     lib.mcbs_copy_rows_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mcbs_attacker_wrapper_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -125,6 +133,29 @@ def obs_field_shapes(topo: FlatTopology, spec: EnvSpec) -> Dict[str, tuple]:
         "mask_local": ((N, L), "int8"), "mask_remote": ((N, N, R), "int8"), "mask_connect": ((N, N, P, Cm), "int8"),
         "mask_discrete": ((N * N * P * Cm + N * L + N * N * R,), "int8"),
     }
+
+
+class FeatureLayoutHandle:
+    """A `features.FeatureLayout` handed to the library (mcbs_feature_layout_create): descriptors uploaded once, freed with the object."""
+
+    def __init__(self, lib, ptr, layout):
+        self.lib, self.ptr, self.layout = lib, ptr, layout
+        self.width = int(lib.mcbs_feature_layout_width(ptr))
+        self.has_masks = layout.mask_columns > 0
+
+    def close(self) -> None:
+        if getattr(self, "ptr", None):
+            self.lib.mcbs_feature_layout_destroy(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+FEATURE_FIELDS = ("scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel")
 
 
 class BatchEngine:
@@ -166,6 +197,8 @@ class BatchEngine:
                          out_of_bound=torch.zeros(self.E, dtype=u8, device=dev),
                          raw_reward=torch.zeros(self.E, dtype=f32, device=dev))
         self._info_struct = InfoBuffers(**{k: v.data_ptr() for k, v in self.info.items()})
+        self._feature_rows = {k: int(np.prod(self._shapes[k][0])) for k in FEATURE_FIELDS}        # int32 values per row of each field
+        self._feature_dtypes = {torch.float32: (0, 4), torch.bfloat16: (1, 2), torch.float16: (2, 2)}  # MCBS_FEATURES_* code, item size
 
     def close(self) -> None:
         if getattr(self, "_h", None):
@@ -509,6 +542,75 @@ class BatchEngine:
             _check(self.lib, self.lib.mcbs_unpack_action_mask(self._h, bits.data_ptr(), bits.stride(0), out.data_ptr(), out.stride(0),
                                                               bits.shape[0], self._stream()), "mcbs_unpack_action_mask")
         return out
+
+    # -- feature encoder (include/mcbs.h): observation rows -> the one-hot float rows a policy's first layer takes --
+    def feature_layout(self, layout) -> FeatureLayoutHandle:
+        """Hand a `features.FeatureLayout` (built for this engine's topology and bounds) to the library; the handle is what
+        encode_features takes.  Descriptors are checked and uploaded once."""
+        d = np.ascontiguousarray(layout.descriptors, dtype=np.uint32)
+        r = np.ascontiguousarray(layout.mask_ranges, dtype=np.uint32).reshape(-1, 3)
+        h = C.c_void_p()
+        rc = self.lib.mcbs_feature_layout_create(self._h, d.ctypes.data if d.size else None, d.size, r.ctypes.data if r.size else None,
+                                                 r.shape[0], C.byref(h))
+        _check(self.lib, rc, "mcbs_feature_layout_create")
+        handle = FeatureLayoutHandle(self.lib, h, layout)
+        if handle.width != layout.width:
+            raise McbsError(f"feature layout: the library counts {handle.width} columns, the layout {layout.width}")
+        return handle
+
+    def encode_features(self, handle: FeatureLayoutHandle, obs: dict, bits=None, out=None, dtype=None, out_of_range=None):
+        """Feature rows [n, F] of n observation rows, one launch (mcbs_encode_features).  obs: the int32 fields `scalars`,
+        `leaked_credentials`, `credential_cache_matrix`, `discovered_nodes_properties`, `nodes_privilegelevel` as contiguous device
+        tensors with a leading row axis n — the live observation (n = E) or rows gathered from a rollout buffer (any n); a field the
+        layout does not read may be missing.  bits: packed masks int32 [n, >= W] (pack_action_mask's format), needed when the layout has
+        mask columns.  out: device float32 / bfloat16 / float16 [n, >= F] with contiguous rows (columns from F on are not touched), or
+        None for a new tensor of `dtype` (default float32) whose rows are padded to whole 128-byte lines; returns the [n, F] view.
+        Every column below F is written.  out_of_range: optional device int32 [1]; the number of elements whose value lay outside its
+        class count is ADDED to it (such an element's columns are all zero)."""
+        t = self.torch
+        F = handle.width
+        ptrs, n = {}, None
+        for k, per_row in self._feature_rows.items():
+            v = obs.get(k)
+            if v is None:
+                continue
+            if v.dtype != t.int32 or v.device != self.device or not v.is_contiguous() or v.dim() < 1 or v.numel() != v.shape[0] * per_row:
+                raise ValueError(f"obs[{k!r}] must be a contiguous device int32 tensor of {per_row} values per row")
+            if n is None:
+                n = v.shape[0]
+            elif v.shape[0] != n:
+                raise ValueError(f"obs[{k!r}] has {v.shape[0]} rows, other fields {n}")
+            ptrs[k] = v.data_ptr()
+        if n is None:
+            raise ValueError("obs holds none of the observation's int32 fields")
+        if handle.has_masks:
+            if bits is None:
+                raise ValueError("the layout has mask columns: bits (packed action masks [n, >= W]) is required")
+            self._packed_rows(bits, "bits")
+            if bits.shape[0] != n:
+                raise ValueError(f"bits has {bits.shape[0]} rows, the observation {n}")
+        if out is None:
+            dtype = dtype or t.float32
+            if dtype not in self._feature_dtypes:
+                raise ValueError("features dtype must be float32, bfloat16 or float16")
+            out = t.empty((n, handle.layout.padded_width(self._feature_dtypes[dtype][1])), dtype=dtype, device=self.device)
+        if out.dtype not in self._feature_dtypes:
+            raise ValueError("out must be float32, bfloat16 or float16")
+        code = self._feature_dtypes[out.dtype][0]
+        if dtype is not None and out.dtype != dtype:
+            raise ValueError(f"out is {out.dtype}, dtype asks for {dtype}")
+        # the C side sees only the row stride: a view narrower than F would have its rows written past their end
+        if out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1 or out.device != self.device or out.shape[1] < F:
+            raise ValueError(f"out must be a device tensor [{n}, >= {F}] with contiguous rows")
+        if out_of_range is not None and (out_of_range.dtype != t.int32 or out_of_range.numel() != 1 or out_of_range.device != self.device):
+            raise ValueError("out_of_range must be a device int32 tensor of one element")
+        if n:
+            stride = out.stride(0) if n > 1 else max(out.stride(0), out.shape[1])
+            _check(self.lib, self.lib.mcbs_encode_features(self._h, handle.ptr, C.byref(ObsBuffers(**ptrs)), bits.data_ptr() if handle.has_masks else None,
+                                                           (bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1])) if handle.has_masks else 0, out.data_ptr(), code, stride, n,
+                                                           out_of_range.data_ptr() if out_of_range is not None else None, self._stream()),
+                   "mcbs_encode_features")
+        return out[:, :F]
 
     # -- learned defender (batches created with defender=("external",)) --
     def alloc_defender_obs(self) -> dict:

@@ -1,0 +1,164 @@
+"""The policy's input features: the layout of the float row that Stable-Baselines3's "MultiInputPolicy" builds from the attacker
+wrapper's Dict observation (preprocess_obs + CombinedExtractor; marlon/baseline_models/ppo/train.py:79, ppo_multi/train_marl_multi.py:275).
+
+Every key of the observation becomes a run of columns — a `Discrete(n)` a one-hot of n, every element of a `MultiDiscrete(nvec)` a
+one-hot of its own width, a `MultiBinary` its values as 0.0 / 1.0 — and the runs are concatenated in key order into one `[n, F]` row.
+`FeatureLayout` describes that row for a topology and its observation bounds; `mcbs_encode_features` (marlon_amd/csrc/mcbs_features.hip)
+writes it on the device in one launch from the descriptors this class builds, `encode_host` is the same encoding in NumPy.
+
+Pure Python / NumPy: importable without a GPU and without the native library.
+"""
+from __future__ import annotations
+
+from typing import Dict, Iterable, List, Optional, Tuple
+
+import numpy as np
+
+from ._abi import EnvSpec
+from .flatten import FlatTopology
+
+SCALAR_KEYS = ["newly_discovered_nodes_count", "lateral_move", "customer_data_found", "probe_result", "escalation",
+               "credential_cache_length", "discovered_node_count"]
+ARRAY_KEYS = ["leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel"]
+MASK_KEYS = ["connect", "local_vulnerability", "remote_vulnerability"]     # MaskedDiscreteAttackerWrapper's order (the packed bits')
+# the int32 fields of mcbs_obs_buffers in the struct's order: a row's source values are these, flattened, one after the other
+OBS_FIELDS = ["scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel"]
+
+MAX_SOURCE, MAX_CLASSES = 1 << 15, 1 << 16        # what a 32-bit column descriptor holds (class 16 bits, source index 15, first flag 1)
+FIRST = 1 << 31
+
+
+class FeatureLayout:
+    """Feature row of the attacker observation of `topo` under `spec`'s bounds.
+
+    keys: the observation keys in the order of their column runs; default: every key sorted by name — how a `gymnasium.spaces.Dict`
+        built from a plain dict orders its keys (gymnasium is not a dependency here, so this is stated, not checked: pass `keys` to
+        impose another order or to leave keys out).
+    include_masks: also the three action masks `connect`, `local_vulnerability`, `remote_vulnerability` (observation keys in the
+        reference's spaces), copied as 0 / 1 from the bit-packed Discrete mask (`mcbs_pack_action_mask`'s format).
+    reference_counts: the reference declares `credential_cache_length` as `Discrete(maximum_total_credentials)` and
+        `discovered_node_count` as `Discrete(maximum_node_count)` (cyberbattle_env.py:307-309) although both counts REACH their bound
+        (Chain-10 has 12 nodes at maximum_node_count = 12), where `one_hot` raises.  By default the two therefore get one class more
+        than declared; `reference_counts=True` gives the reference's widths exactly, and a full count then encodes as an all-zero
+        group and is counted as out of range.
+
+    Class counts (N = maximum_node_count, C = maximum_total_credentials, K = maximum_discoverable_credentials_per_action, P = ports,
+    NP = properties; cyberbattle_env.py:262-320, attack_wrapper.py:164-204): newly_discovered_nodes_count N+1; lateral_move,
+    customer_data_found 2; probe_result 3; escalation 4; credential_cache_length C+1 (C); discovered_node_count N+1 (N);
+    leaked_credentials K x (2, C, N, P); credential_cache_matrix C x (N, P); discovered_nodes_properties N*NP x 3;
+    nodes_privilegelevel N x 4; the masks N*N*P*C, N*L and N*N*R single columns.
+
+    A value outside [0, classes) leaves its group all zero (and never touches a neighbour); `encode_host(..., return_out_of_range=True)`
+    and the device encoder's `out_of_range` count such elements.
+
+    width: F.  segments: key -> (first column, columns).  groups: one (key, source index, classes) per one-hot element in row order.
+    descriptors / mask_ranges: what `mcbs_feature_layout_create` takes (include/mcbs.h)."""
+
+    def __init__(self, topo: FlatTopology, spec: EnvSpec, keys: Optional[Iterable[str]] = None, include_masks: bool = False,
+                 reference_counts: bool = False):
+        N, C, K = spec.maximum_node_count, spec.maximum_total_credentials, spec.maximum_discoverable_credentials_per_action
+        L, R, P, NP = len(topo.local_vulnerabilities), len(topo.remote_vulnerabilities), len(topo.ports), len(topo.properties)
+        self.N, self.C, self.K, self.L, self.R, self.P, self.NP = N, C, K, L, R, P, NP
+        self.include_masks, self.reference_counts = bool(include_masks), bool(reference_counts)
+        self.field_len = [7, K * 4, C * 2, N * NP, N]
+        self.field_off = [int(x) for x in np.concatenate([[0], np.cumsum(self.field_len)[:-1]])]
+        self.values_per_row = int(sum(self.field_len))
+        scalar_classes = [N + 1, 2, 2, 3, 4, C if reference_counts else C + 1, N if reference_counts else N + 1]
+        o = self.field_off
+        # key -> [(source index, classes)] in element order
+        elements: Dict[str, List[Tuple[int, int]]] = {k: [(i, scalar_classes[i])] for i, k in enumerate(SCALAR_KEYS)}
+        elements["leaked_credentials"] = [(o[1] + 4 * k + j, n) for k in range(K) for j, n in enumerate((2, C, N, P))]
+        elements["credential_cache_matrix"] = [(o[2] + 2 * c + j, n) for c in range(C) for j, n in enumerate((N, P))]
+        elements["discovered_nodes_properties"] = [(o[3] + i, 3) for i in range(N * NP)]
+        elements["nodes_privilegelevel"] = [(o[4] + i, 4) for i in range(N)]
+        M, ML, MR = N * N * P * C, N * L, N * N * R
+        self.discrete_n = M + ML + MR
+        mask_bits = {"connect": (0, M), "local_vulnerability": (M, ML), "remote_vulnerability": (M + ML, MR)}
+        known = list(elements) + (MASK_KEYS if include_masks else [])
+        self.keys = sorted(known) if keys is None else list(keys)
+        if len(set(self.keys)) != len(self.keys):
+            raise ValueError("a key is listed twice")
+        for k in self.keys:
+            if k not in known:
+                raise ValueError(f"unknown observation key {k!r}" + (" (the action masks need include_masks=True)" if k in MASK_KEYS else ""))
+        self.segments: Dict[str, Tuple[int, int]] = {}
+        self.groups: List[Tuple[str, int, int]] = []
+        desc: List[int] = []
+        ranges: List[Tuple[int, int, int]] = []
+        col = 0
+        for k in self.keys:
+            if k in mask_bits:
+                b0, n = mask_bits[k]
+                if n:
+                    ranges.append((col, n, b0))
+                self.segments[k] = (col, n)
+                col += n
+                continue
+            first = col
+            for src, n in elements[k]:
+                if n < 1 or n > MAX_CLASSES or src >= MAX_SOURCE:
+                    raise ValueError(f"{k}: {n} classes / source value {src} do not fit a column descriptor "
+                                     f"(at most {MAX_CLASSES} classes, {MAX_SOURCE} int32 values per observation row)")
+                self.groups.append((k, src, n))
+                desc.extend((FIRST if c == 0 else 0) | (src << 16) | c for c in range(n))
+                col += n
+            self.segments[k] = (first, col - first)
+        self.width = col
+        self.n_elements = len(self.groups)
+        self.descriptors = np.asarray(desc, dtype=np.uint32)
+        self.mask_ranges = np.asarray(ranges, dtype=np.uint32).reshape(-1, 3)
+        self.mask_columns = int(self.mask_ranges[:, 1].sum()) if len(ranges) else 0
+        self.mask_words = (self.discrete_n + 31) // 32         # words of a packed mask row (mcbs_pack_action_mask)
+
+    def padded_width(self, itemsize: int) -> int:
+        """F rounded up so that a row is a whole number of 128-byte lines: the row stride the wrappers allocate."""
+        per_line = 128 // itemsize
+        return (self.width + per_line - 1) // per_line * per_line
+
+    # -- host encoding --
+    def _values(self, obs: dict) -> np.ndarray:
+        """[n, values_per_row] int64: the row's source values from a dict holding either the engine's fields (`scalars` [n, 7], ...) or
+        the wrapper's public keys (the seven named counts [n] instead of `scalars`)."""
+        if "scalars" in obs:
+            sc = np.asarray(obs["scalars"]).reshape(-1, 7)
+        else:                                         # a named count the layout leaves out may be absent: it reads as zero
+            present = [k for k in SCALAR_KEYS + ARRAY_KEYS if k in obs]
+            if not present:
+                raise KeyError("observation holds none of the layout's keys")
+            n = np.asarray(obs[present[0]]).shape[0]
+            absent = [k for k in SCALAR_KEYS if k not in obs and k in self.segments]
+            if absent:
+                raise KeyError(f"observation lacks {absent}")
+            sc = np.stack([np.asarray(obs[k]).reshape(n) if k in obs else np.zeros(n, np.int64) for k in SCALAR_KEYS], axis=1)
+        n = sc.shape[0]
+        parts = [sc.astype(np.int64)]
+        for k, ln in zip(ARRAY_KEYS, self.field_len[1:]):
+            if k in obs:
+                parts.append(np.asarray(obs[k]).reshape(n, ln).astype(np.int64))
+            elif k in self.segments:
+                raise KeyError(f"observation lacks {k!r}")
+            else:
+                parts.append(np.zeros((n, ln), np.int64))
+        return np.concatenate(parts, axis=1)
+
+    def encode_host(self, obs: dict, dtype=np.float32, return_out_of_range: bool = False):
+        """The feature rows [n, F] of a dict of host arrays with a leading row axis (the engine's fields or the wrapper's public
+        observation keys; with mask columns also `connect` / `local_vulnerability` / `remote_vulnerability`, any shape after the row
+        axis, non-zero = allowed).  With return_out_of_range: (rows, number of elements whose value lay outside [0, classes))."""
+        vals = self._values(obs)
+        n = vals.shape[0]
+        out = np.zeros((n, self.width), dtype=dtype)
+        rows = np.arange(n)
+        bad = 0
+        col = {k: c0 for k, (c0, _) in self.segments.items()}
+        for k, src, ncls in self.groups:
+            v = vals[:, src]
+            ok = (v >= 0) & (v < ncls)
+            out[rows[ok], col[k] + v[ok]] = 1
+            bad += int((~ok).sum())
+            col[k] += ncls
+        for k in self.keys:
+            if k in MASK_KEYS:
+                c0, w = self.segments[k]
+                out[:, c0:c0 + w] = (np.asarray(obs[k]).reshape(n, w) != 0)
+        return (out, bad) if return_out_of_range else out

@@ -112,6 +112,7 @@ class AttackerVecEnv:
         self._act_in = t.zeros((n_envs,) if self.discrete else (n_envs, 10), dtype=t.int64, device=dev)
         self._executed = t.zeros(n_envs, dtype=t.bool, device=dev)
         self._graph_out = self._terminated_out = None
+        self._feature_handles, self._feature_bits = {}, None       # features(): layout handles per option set, the packed-mask scratch
         self.reset()
 
     # -- observation plumbing --
@@ -171,6 +172,68 @@ class AttackerVecEnv:
     def unpack_action_mask(self, bits, out=None):
         """Packed masks [n, >= W] -> bool [n, A] (what action_masks() returns for the same step)."""
         return self.engine.unpack_action_mask(bits, out)
+
+    # -- the policy's input features (marlon_amd/features.py, mcbs_encode_features) --
+    def _feature_handle(self, include_masks: bool, reference_counts: bool, keys=None):
+        key = (bool(include_masks), bool(reference_counts), None if keys is None else tuple(keys))
+        h = self._feature_handles.get(key)
+        if h is None:
+            from .features import FeatureLayout
+            h = self._feature_handles[key] = self.engine.feature_layout(FeatureLayout(self.topo, self.spec, keys=keys, include_masks=include_masks,
+                                                                                      reference_counts=reference_counts))
+        return h
+
+    def feature_layout(self, include_masks: bool = False, reference_counts: bool = False, keys=None):
+        """The `features.FeatureLayout` behind features() / encode_features() for these options: `width` sizes a policy's first layer,
+        `segments` (key -> (first column, columns)) slices the row."""
+        return self._feature_handle(include_masks, reference_counts, keys).layout
+
+    def _pack_bits_from_mask(self, mask):
+        """bool [n, A] -> packed int32 [n, row_words] with torch expressions: for batches whose packed mask cannot be rebuilt from the
+        observation digest (ExternalRandomEvents).  About exactness, not speed."""
+        t = self.torch
+        W, row_words = self.engine.packed_mask_words()
+        n = mask.shape[0]
+        m = t.zeros((n, row_words * 32), dtype=t.int64, device=mask.device)
+        m[:, :self.discrete_n] = mask
+        words = (m.view(n, row_words, 32) << t.arange(32, dtype=t.int64, device=mask.device)).sum(dim=2)
+        return words.to(t.int32)                         # (values up to 2^32 - 1 wrap to the same 32 bits)
+
+    def features(self, out=None, dtype=None, include_masks: bool = False, reference_counts: bool = False, out_of_range=None):
+        """The observation this env last returned as the float rows Stable-Baselines3's MultiInputPolicy would build from it
+        (every Discrete / MultiDiscrete element one-hot, concatenated in sorted key order; features.FeatureLayout), one launch:
+        [n_envs, F] float32 / bfloat16 / float16.  out=: write into a preallocated [n_envs, >= F] tensor, e.g. buffer[t] of a rollout
+        buffer; without it a new tensor with rows padded to whole 128-byte lines is allocated and its [:, :F] view returned.
+        include_masks: also the three action masks as 0 / 1 columns; the mask is packed first (action_masks_packed), whether or not
+        the masks are materialised — under ExternalRandomEvents, where the digest cannot give the mask, the materialised mask is packed
+        instead (materialize_masks=False then raises).  reference_counts / out_of_range: see FeatureLayout / engine.encode_features."""
+        bits = None
+        if include_masks:
+            from ._abi import DEFENDER_RANDOM_EVENTS
+            if self.engine._cfg.defender_kind == DEFENDER_RANDOM_EVENTS:
+                if not self.materialize_masks:
+                    raise RuntimeError("features(include_masks=True) under ExternalRandomEvents needs the materialised masks "
+                                       "(the mask cannot be rebuilt from the observation digest there): create the env with materialize_masks=True")
+                bits = self._pack_bits_from_mask(self.action_masks())
+            else:
+                if self._feature_bits is None:
+                    self._feature_bits = self.torch.zeros((self.num_envs, self.engine.packed_mask_words()[1]), dtype=self.torch.int32,
+                                                          device=self.engine.device)
+                bits = self.action_masks_packed(out=self._feature_bits)
+        return self.engine.encode_features(self._feature_handle(include_masks, reference_counts), self._obs, bits=bits, out=out, dtype=dtype,
+                                           out_of_range=out_of_range)
+
+    def encode_features(self, obs, bits=None, out=None, dtype=None, reference_counts: bool = False, out_of_range=None):
+        """features() for any n stored observation rows (a shuffled minibatch gathered from a rollout buffer): obs holds the int32
+        fields `scalars` [n, 7] (or the seven named counts [n]), `leaked_credentials`, `credential_cache_matrix`,
+        `discovered_nodes_properties`, `nodes_privilegelevel` with a leading row axis; bits = the rows' packed masks [n, >= W]
+        (action_masks_packed) adds the mask columns."""
+        t = self.torch
+        if "scalars" not in obs:
+            obs = dict(obs, scalars=t.stack([obs[k] for k in SCALAR_KEYS], dim=1).to(t.int32))
+        fields = {k: obs[k].contiguous() for k in FLAT_FIELDS[:5] if k in obs}
+        return self.engine.encode_features(self._feature_handle(bits is not None, reference_counts), fields, bits=bits, out=out, dtype=dtype,
+                                           out_of_range=out_of_range)
 
     # -- VecEnv surface --
     def reset(self):
