@@ -356,7 +356,10 @@ int  mcbs_sample_actions(mcbs_batch*, int32_t valid, uint64_t seed, uint64_t ste
  *   discrete:      int64 [E]    = MaskedDiscreteAttackerWrapper's Discrete index (action_masking.py:112-142):
  *                  connect block ((src*N+tgt)*P+port)*C+cred, then local src*L+vuln, then remote (src*N+tgt)*R+vuln
  * Exactly one of the two is non-NULL.  An action whose source / target index is not below the env's discovered-node
- * count is turned into a skip row and flagged in invalid[E] (attack_wrapper.py:236-253,286-308). */
+ * count is turned into a skip row and flagged in invalid[E] (attack_wrapper.py:236-253,286-308).  So is everything outside the
+ * action space: a Discrete index below 0 or not below mcbs_discrete_action_count, a MultiDiscrete kind other than 0, 1, 2, a negative
+ * MultiDiscrete component of the chosen kind (the reference raises on these before it steps: action_masking.py:109-110,
+ * attack_wrapper.py:262) — the env is not stepped.  The same holds for the decoders inside mcbs_attacker_wrapper_step. */
 int  mcbs_decode_attacker_actions(mcbs_batch*, const int64_t* multidiscrete, const int64_t* discrete,
                                   int32_t* actions_out, uint8_t* invalid_out, void* stream);
 

@@ -92,9 +92,12 @@ __device__ __forceinline__ void decode_body(const DevState& S, const StepCfg& C,
         c = is_c ? qr : (is_l ? 0 : x0);
         d = is_c ? x0 : 0;
     }
-    bool ok;                                               // _action_in_discovered_range
-    if (kind == 0) ok = a < nd;
-    else if (kind == 1 || kind == 2) ok = a < nd && b < nd;
+    // _action_in_discovered_range; a negative index or component is no action of the space (the reference raises before it steps:
+    // action_masking.py:109-110), and every quotient chain of a negative index leaves a negative coordinate: one sign test, no branch
+    const bool nonneg = (a | b | c | d) >= 0;
+    bool ok;
+    if (kind == 0) ok = nonneg && a < nd;
+    else if (kind == 1 || kind == 2) ok = nonneg && a < nd && b < nd;
     else ok = false;
     int32_t* o = out + (size_t)e * 5;
     o[0] = ok ? (int32_t)kind : MCBS_ACTION_SKIP;

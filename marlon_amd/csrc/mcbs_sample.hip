@@ -8,6 +8,12 @@
 // reference draws from PCG64 streams; only the distribution is reproduced here — this is harness, not part of the step's
 // parity.)  Philox keyed by (seed, global env id), counter (env id, step, draw block): the same (seed, step) gives the same action
 // whether it is sampled by the stand-alone kernel or inside a rollout.
+//
+// Two readings where the reference's text leaves room (tests/sampler_law.py models the same ones, tests/test_sampler_law.py holds that
+// model to histograms of the reference itself): the owned sources are enumerated along the discovery list from the LIVE privilege
+// levels (the reference walks every node of the network, actions.py:317-319, and caches the list between steps — equal whenever
+// every node with privilege is discovered and the cache is fresh); and an env without any owned node, where the reference would
+// raise, gets a row inside the action-space bounds after the 64 attempts (the same row on every call with the same key).
 #pragma once
 #include "mcbs_device.h"
 

@@ -180,7 +180,8 @@ struct FusedHook {
             c = is_c ? qr : (is_l ? 0 : x0);
             d = is_c ? x0 : 0;
         }
-        const bool ok = kind == 0 ? a < nd : ((kind == 1 || kind == 2) ? (a < nd && b < nd) : false);    // _action_in_discovered_range
+        const bool nonneg = (a | b | c | d) >= 0;          // a negative index or component is intercepted too (decode_body)
+        const bool ok = nonneg && (kind == 0 ? a < nd : ((kind == 1 || kind == 2) ? (a < nd && b < nd) : false));    // _action_in_discovered_range
         row[0] = ok ? (int32_t)kind : MCBS_ACTION_SKIP;
         row[1] = (int32_t)a; row[2] = (int32_t)b; row[3] = (int32_t)c; row[4] = (int32_t)d;
         invalid = !ok;
