@@ -349,10 +349,12 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     S.off_rows = (uint32_t)align_up((size_t)S.off_cred + (2u * (h->n_triples + 1u) > 32u ? 2u * (h->n_triples + 1u) : 32u), 16);
     const bool external = cfg->defender_kind == MCBS_DEFENDER_EXTERNAL;
     // small topologies (Chain-10, ToyCtf): the eight sets of an env as 16-bit fields of one 16-byte word and 4-byte node rows,
-    // so that the header and the WHOLE body are level-1 loads (mcbs_device.h); lists stay u8 / u16 with < 16 entries each
+    // so that the header and the WHOLE body are level-1 loads (mcbs_device.h); node and triple ids fit a nibble, so both lists
+    // (at most 16 nodes, fewer than 16 triples) are one more 16-byte word behind the sets, and the body is rows only
     S.tiny_p = h->n_props; S.tiny_v = h->max_slots;
     S.packed = (N <= 16u && h->n_cred_strings <= 16u && h->n_triples < 16u && S.tiny_p + 4u + 2u * S.tiny_v <= 32u &&
                 !getenv("MCBS_NO_PACKED_SETS")) ? 1u : 0u;
+    if (S.packed) S.off_disc = S.off_cred = S.off_rows = 0u;
     const size_t row_bytes = S.packed ? 4u : sizeof(Row);
     S.off_fw = external ? (uint32_t)align_up((size_t)S.off_rows + row_bytes * N, 16) : 0u;
     size_t body_end = external ? (size_t)S.off_fw + 2u * h->n_fw_lists : (size_t)S.off_rows + row_bytes * N;
@@ -399,7 +401,7 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     if (const char* ov = getenv("MCBS_COOP_MAX_ENVS")) coop_max_envs = (uint32_t)strtoul(ov, nullptr, 10);   // experiments
     b->coop = !S.packed && S.WT >= 2u && N > 64u && !S.wide && !b->lds_topo && !getenv("MCBS_NO_COOP") && E <= coop_max_envs &&
               (cfg->defender_kind == MCBS_DEFENDER_NONE || cfg->defender_kind == MCBS_DEFENDER_SCAN_AND_REIMAGE);
-    const size_t o_masks = take(S.packed ? 16ull * E : 8ull * M_COUNT * S.WT * E);
+    const size_t o_masks = take(S.packed ? 32ull * E : 8ull * M_COUNT * S.WT * E);   // packed: the sets column, then the lists-word column
     const size_t o_cach = S.wide ? take(8ull * S.TW * E) : 0;
     const bool has_def = cfg->defender_kind != MCBS_DEFENDER_NONE;   // in-env or external: both re-image nodes
     const size_t o_ring = has_def ? take(8ull * 16 * S.WT * E) : 0;
@@ -435,7 +437,7 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
         r.props_tags = (owned0 ? ns[n].props : 0ull) | ((uint64_t)(ns[n].tags0 & 0xFu) << 60);
         S.row_put(init.data(), n, r);
     }
-    memcpy(init.data() + S.off_disc, topo->host.data() + h->off_init_order, h->n_init_owned);
+    if (!S.packed) memcpy(init.data() + S.off_disc, topo->host.data() + h->off_init_order, h->n_init_owned);
     if (external) memcpy(init.data() + S.off_fw, topo->host.data() + h->off_fw_list0, 2u * h->n_fw_lists);
     if (random_events) {
         const uint8_t* tb = topo->host.data();
@@ -510,6 +512,9 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
         }
         f[M_RUN] = (uint16_t)((1u << N) - 1u);
         for (int q = 0; q < 4; ++q) C.init_packed[q] = (uint32_t)f[2 * q] | ((uint32_t)f[2 * q + 1] << 16);
+        uint64_t dl = 0;                                           // the lists word of a fresh env (reset_header builds the same one)
+        for (uint32_t i = 0; i < h->n_init_owned && i < 16u; ++i) dl |= (uint64_t)(order0[i] & 0xFu) << (4u * i);
+        C.init_lists[0] = (uint32_t)dl; C.init_lists[1] = (uint32_t)(dl >> 32); C.init_lists[2] = C.init_lists[3] = 0u;
     }
 
     e = hipMalloc(&b->C_dev, sizeof(StepCfg));
@@ -1604,10 +1609,9 @@ extern "C" int mcbs_get_state(mcbs_batch* b, void* host_buf, size_t nbytes) {
             }
         }
         uint16_t* order = reinterpret_cast<uint16_t*>(p + sizeof(mcbs_state_header) + sizeof(mcbs_state_node) * S.N);
-        for (uint32_t k = 0; k < S.N; ++k) order[k] = k < sh->n_discovered ? eb[S.off_disc + k] : 0xFFFF;
+        for (uint32_t k = 0; k < S.N; ++k) order[k] = k < sh->n_discovered ? (uint16_t)S.disc_get(mk, eb, e, k) : 0xFFFF;
         uint16_t* cc = order + S.N;
-        const uint16_t* cl = reinterpret_cast<const uint16_t*>(eb + S.off_cred);
-        for (uint32_t k = 0; k < b->cfg.maximum_total_credentials; ++k) cc[k] = k < sh->n_creds ? cl[k] : 0xFFFF;
+        for (uint32_t k = 0; k < b->cfg.maximum_total_credentials; ++k) cc[k] = k < sh->n_creds ? (uint16_t)S.cred_get(mk, eb, e, k) : 0xFFFF;
     }
     return MCBS_OK;
 }
@@ -1671,14 +1675,14 @@ extern "C" int mcbs_set_state(mcbs_batch* b, const void* host_buf, size_t nbytes
             r.ever = sn[n].attacked_ever; r.since = sn[n].attacked_since;
             S.row_put(eb, n, r);
         }
+        if (S.packed) static_cast<uint4*>(mk)[(size_t)S.E + e] = make_uint4(0u, 0u, 0u, 0u);   // the lists word: zero at and past the counts
         for (uint32_t i = 0; i < sh->n_discovered; ++i) {
             if (order[i] >= S.N) return fail(MCBS_EINVAL, "env %u: discovery order entry out of range", e);
-            eb[S.off_disc + i] = (uint8_t)order[i];
+            S.disc_put(mk, eb, e, i, order[i]);
         }
-        uint16_t* cl = reinterpret_cast<uint16_t*>(eb + S.off_cred);
         for (uint32_t i = 0; i < sh->n_creds; ++i) {
             if (cc[i] >= th->n_triples) return fail(MCBS_EINVAL, "env %u: credential cache entry out of range", e);
-            cl[i] = cc[i];
+            S.cred_put(mk, eb, e, i, cc[i]);
             add(M_CACH, cc[i], e);
             const uint32_t c = tr[cc[i]].cred;                     // a cached triple implies its credential string is gathered
             add(M_GATH, c, e);

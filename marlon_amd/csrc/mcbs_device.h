@@ -9,10 +9,15 @@
 //   * one "body" record per env (array-of-structures, stride body_stride): the discovery order (u8 node
 //     ids) and the credential cache (u16 triple ids) first — their first 16 entries each are fetched with
 //     the header, before the action is decoded — then 16-byte node rows {discovered-property mask + privilege_k
-//     tags, attacked-ever and attacked-since-reimage slot masks} (packed batches: 4 bytes per row; privilege levels, the
-//     running flags and the re-imaging countdown live in the set columns and the re-imaging ring).  Rows are
-//     gathered by node id, which differs per env, so they sit next to each other per env rather than
-//     along the env axis.
+//     tags, attacked-ever and attacked-since-reimage slot masks} (privilege levels, the running flags and the
+//     re-imaging countdown live in the set columns and the re-imaging ring).  Rows are gathered by node id,
+//     which differs per env, so they sit next to each other per env rather than along the env axis.
+//   * packed batches (<= 16 nodes, < 16 credential triples: Chain-10, ToyCtf): the body holds 4-byte rows only
+//     (off_rows == 0), and BOTH lists are nibbles of one 16-byte "lists word" per env in an env-fastest column
+//     directly behind the packed sets: .x/.y the discovery order, .z/.w the credential cache, entry i at bits
+//     4i..4i+3 of its half.  Entries at or past the count are ZERO, always (reset, mcbs_set_state and the step
+//     kernel's appends keep it so): an append is an OR at 4 * count, and "did the word change" is a compare
+//     with the word the step loaded.  disc_at / cred_at below hide the two list layouts.
 //   * the topology blob (include/mcbs.h "MCBT") is shared by every env and read-only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,7 +77,8 @@ struct DevState {
     uint64_t* masks;    // [M_COUNT][WT][E]: discovered / agent installed / ever owned / running / privilege bit 0 / bit 1 /
                         // gathered credential strings / cached credential triples; every set padded to WT words.
                         // `packed` batches (<= 16 nodes, credential strings and triples: Chain-10, ToyCtf): [E][M_COUNT] u16
-                        // instead, i.e. ONE 16-byte word per env holds all eight sets (a quarter of the bytes the step moves)
+                        // instead, i.e. ONE 16-byte word per env holds all eight sets (a quarter of the bytes the step moves),
+                        // followed by the lists-word column [E] uint4 (header comment): reinterpret_cast<uint4*>(masks)[E + e]
     // word w of set k of env e, whichever layout the batch uses (kernels off the hot path; the step kernel is specialised)
     __host__ __device__ __forceinline__ uint64_t set_word(const void* base, int k, uint32_t w, uint32_t e) const {
         return packed ? (uint64_t)static_cast<const uint16_t*>(base)[(size_t)e * M_COUNT + (uint32_t)k]
@@ -100,7 +106,7 @@ struct DevState {
     uint32_t wide;
     uint32_t packed;    // 1: the sets of an env are 16-bit fields of one uint4 (see masks) and its node rows are 4 bytes each:
     uint32_t tiny_p, tiny_v;   // properties (tiny_p bits) | tags (4) | attacked-ever (tiny_v bits) | attacked-since (tiny_v bits) <= 32 bits,
-                        // so that the whole body (discovery order 16 B, credential cache 32 B, <= 16 rows 64 B) is fetched with the header
+                        // so that the lists word (16 B) and the whole body (<= 16 rows, 64 B) are fetched with the header
                         // and the step has no load that depends on the action (Chain-10: 14 + 4 + 7 + 7 = 32 bits)
     __host__ __device__ __forceinline__ uint32_t tiny_pack(uint64_t props, uint32_t tags, uint32_t ever, uint32_t since) const {
         return (uint32_t)props | (tags << tiny_p) | (ever << (tiny_p + 4u)) | (tiny_v ? since << (tiny_p + 4u + tiny_v) : 0u);
@@ -121,7 +127,47 @@ struct DevState {
             tiny_pack(r.props_tags & ((1ull << tiny_p) - 1ull), (uint32_t)(r.props_tags >> 60), r.ever & ((1u << tiny_v) - 1u),
                       r.since & ((1u << tiny_v) - 1u));
     }
-    uint32_t body_stride, off_disc, off_cred, off_rows, Cmax;
+    uint32_t body_stride, off_disc, off_cred, off_rows, Cmax;   // (packed batches: off_disc / off_cred unused, off_rows == 0)
+    // entry i of the discovery order / of the credential cache of env e, whichever layout the batch uses: body_e = the env's body,
+    // mbase = the masks allocation (S.masks on the device, its host copy in mcbs_get_state / mcbs_set_state).  i < 16 for packed batches.
+    // entry i (< 16) of one half {lo, hi} of a lists word: the ONE definition of the packed format every reader uses
+    static __host__ __device__ __forceinline__ uint32_t list_nibble(uint32_t lo, uint32_t hi, uint32_t i) {
+        return (((i & 8u) ? hi : lo) >> ((i & 7u) * 4u)) & 0xFu;
+    }
+    // (ONE load from a selected address, not a load in each arm of a branch: the observation kernels issue these with their level-1
+    // loads, and a load under control flow waits for the branch's operands first)
+    __host__ __device__ __forceinline__ uint32_t disc_get(const void* mbase, const uint8_t* body_e, uint32_t e, uint32_t i) const {
+        const bool pk = packed != 0u;
+        const uint32_t at = off_disc + i;
+        const uint32_t* p = pk ? static_cast<const uint32_t*>(mbase) + ((size_t)E + e) * 4u + ((i >> 3) & 1u)
+                               : reinterpret_cast<const uint32_t*>(body_e + (at & ~3u));
+        return (*p >> (pk ? (i & 7u) * 4u : (at & 3u) * 8u)) & (pk ? 0xFu : 0xFFu);
+    }
+    __host__ __device__ __forceinline__ uint32_t cred_get(const void* mbase, const uint8_t* body_e, uint32_t e, uint32_t i) const {
+        const bool pk = packed != 0u;
+        const uint32_t at = off_cred + 2u * i;
+        const uint32_t* p = pk ? static_cast<const uint32_t*>(mbase) + ((size_t)E + e) * 4u + 2u + ((i >> 3) & 1u)
+                               : reinterpret_cast<const uint32_t*>(body_e + (at & ~3u));
+        return (*p >> (pk ? (i & 7u) * 4u : (at & 2u) * 8u)) & (pk ? 0xFu : 0xFFFFu);
+    }
+    // ... := v.  Packed batches: the slot must hold zero (an append at the count, or a lists word cleared first)
+    __host__ __device__ __forceinline__ void disc_put(void* mbase, uint8_t* body_e, uint32_t e, uint32_t i, uint32_t v) const {
+        if (!packed) { body_e[off_disc + i] = (uint8_t)v; return; }
+        static_cast<uint32_t*>(mbase)[((size_t)E + e) * 4u + ((i >> 3) & 1u)] |= (v & 0xFu) << ((i & 7u) * 4u);
+    }
+    __host__ __device__ __forceinline__ void cred_put(void* mbase, uint8_t* body_e, uint32_t e, uint32_t i, uint32_t v) const {
+        if (!packed) { reinterpret_cast<uint16_t*>(body_e + off_cred)[i] = (uint16_t)v; return; }
+        static_cast<uint32_t*>(mbase)[((size_t)E + e) * 4u + 2u + ((i >> 3) & 1u)] |= (v & 0xFu) << ((i & 7u) * 4u);
+    }
+    __device__ __forceinline__ uint32_t disc_at(const uint8_t* body_e, uint32_t e, uint32_t i) const { return disc_get(masks, body_e, e, i); }
+    // ... for callers that know the layout at compile time (LAYOUT 1 packed, 0 general; anything else: decided at run time)
+    template <int LAYOUT>
+    __device__ __forceinline__ uint32_t disc_at_as(const uint8_t* body_e, uint32_t e, uint32_t i) const {
+        if (LAYOUT == 0) return body_e[off_disc + i];
+        if (LAYOUT == 1) { const uint2 d = reinterpret_cast<const uint2*>(masks)[((size_t)E + e) * 2u]; return list_nibble(d.x, d.y, i); }
+        return disc_at(body_e, e, i);
+    }
+    __device__ __forceinline__ uint32_t cred_at(const uint8_t* body_e, uint32_t e, uint32_t i) const { return cred_get(masks, body_e, e, i); }
     uint32_t off_fw;    // body offset of uint16 fw[n_fw_lists]: per-env state of the six manageable rule names in every firewall
                         // rule list (bit r: a rule named r exists, bit 6+r: the first one is ALLOW); MCBS_DEFENDER_EXTERNAL only
 };
@@ -163,8 +209,8 @@ struct StepCfg {        // the parts of mcbs_batch_cfg the kernels read
     double   avail_term0;
     uint32_t avail_uniform, pad_u;
     // packed batches: everything an env's re-initialisation writes, as constants the step kernel reads through the scalar cache — the
-    // reset image of the body (<= 256 bytes: discovery order 16, credential cache 32, <= 16 four-byte rows, the learned defender's rule-list words), the eight sets as the one
-    // uint4, and the number of initially owned nodes — so that the auto-reset of an env that just ended is a handful of STORES by its own
+    // reset image of the body (<= 256 bytes: <= 16 four-byte rows, the learned defender's rule-list words), the eight sets as the one
+    // uint4, the lists word (init_lists: the initial discovery order as nibbles; the credential half is zero), and the number of initially owned nodes — so that the auto-reset of an env that just ended is a handful of STORES by its own
     // lane: no load behind the step's stores, no wave-level copy, no fence (bench.py `headline_with_resets`)
     uint32_t init_image[64];
     uint32_t init_packed[4];
@@ -174,6 +220,7 @@ struct StepCfg {        // the parts of mcbs_batch_cfg the kernels read
                                  // of dividing doubles per env and step
     uint32_t init_image_ok;  // 0: the body does not fit init_image (learned-defender / random-events state behind the rows): wave-level copy instead
     uint32_t pad_v[1];
+    uint32_t init_lists[4];
 };
 
 // mcbs_rollout_random: the looping step kernel samples each step's action itself; passed as a kernel argument of that variant only
@@ -261,7 +308,10 @@ __device__ __forceinline__ double to_double53(uint32_t a, uint32_t b) {
 
 // Header + mask columns of a freshly reset env (cyberbattle_env.py:375-394, actions.py:149-152): the nodes with
 // agent_installed are owned at max(initial privilege, LocalUser), discovered in network order, every node Running,
-// no credential gathered, availability 1.0.  The body (rows, discovery order) is copied from init_body by the caller.
+// no credential gathered, availability 1.0.  The body (rows; general layout: the discovery order too) is copied from init_body by the
+// caller; the lists word of a packed batch is written here.
+// LISTS = false: the caller knows at compile time that the batch is not packed (the general-layout step kernels keep the code they had).
+template <bool LISTS = true>
 __device__ __forceinline__ void reset_header(const DevState& S, const Topo& T, uint32_t e, uint32_t episode) {
     const mcbs_topo_header& H = T.H();
     const uint8_t* order = T.base + H.off_init_order;
@@ -286,6 +336,11 @@ __device__ __forceinline__ void reset_header(const DevState& S, const Topo& T, u
     if (S.wide) for (uint32_t w = 0; w < S.TW; ++w) S.cach[(size_t)w * S.E + e] = 0ull;
     for (uint32_t w = S.NW; w < S.WT; ++w)
         for (int k = 0; k < M_GATH; ++k) S.put(k, w, e, 0ull);
+    if (LISTS && S.packed) {          // the lists word: the initial discovery order as nibbles, zeros past it and in the credential half
+        uint64_t dl = 0;
+        for (uint32_t i = 0; i < n_init && i < 16u; ++i) dl |= (uint64_t)(order[i] & 0xFu) << (4u * i);
+        reinterpret_cast<uint4*>(S.masks)[S.E + e] = make_uint4((uint32_t)dl, (uint32_t)(dl >> 32), 0u, 0u);
+    }
     S.h0[e] = make_uint4(0u, 0u, n_init, n_init);
     S.h1[e] = make_double2(0.0, 1.0);
     S.episode[e] = episode;

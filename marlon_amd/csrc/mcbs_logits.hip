@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void mask_logits_kernel(DevState S, Topo T, co
             if (!(own(i) && i < n_disc)) return false;
             const uint8_t* body = S.body + (size_t)e * S.body_stride;
             const mcbs_node_static* NS = reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node);
-            return (NS[body[S.off_disc + i]].local_mask >> l) & 1u;
+            return (NS[S.disc_at(body, e, i)].local_mask >> l) & 1u;
         }
         return a < G.A && pair_on(fdiv(a - remote0, G.dR));   // remote[s][t][r] = on(s, t)
     };

@@ -89,8 +89,8 @@ __device__ __forceinline__ void obs_env(const DevState& S, const Topo& T, const 
     const uint8_t* body_l1 = S.body + (size_t)e * S.body_stride;
     const uint32_t n_trip_cap = T.H().n_triples;                       // the credential list holds up to n_triples entries (+ one slack slot)
     const uint4 h0 = S.h0[e];
-    const uint32_t dl_head = body_l1[S.off_disc + (lane < S.N ? lane : S.N - 1u)];
-    const uint32_t cl_head = reinterpret_cast<const uint16_t*>(body_l1 + S.off_cred)[lane < n_trip_cap ? lane : n_trip_cap];
+    const uint32_t dl_head = S.disc_at(body_l1, e, lane < S.N ? lane : S.N - 1u);
+    const uint32_t cl_head = S.cred_at(body_l1, e, lane < n_trip_cap ? lane : n_trip_cap);
     const bool one_word = S.NW == 1u;
     uint64_t w_inst = 0, w_plo = 0, w_phi = 0;
     if (one_word) { w_inst = S.get(M_INST, 0, e); w_plo = S.get(M_PLO, 0, e); w_phi = S.get(M_PHI, 0, e); }
@@ -100,8 +100,6 @@ __device__ __forceinline__ void obs_env(const DevState& S, const Topo& T, const 
     const uint32_t kind = (flags >> F_KIND_SHIFT) & 0xFu, level = (flags >> F_LEVEL_SHIFT) & 3u;
     const uint32_t new_nodes = (flags >> F_NEWNODES_SHIFT) & 0x3FFu, new_creds = (flags >> F_NEWCREDS_SHIFT) & 0x3FFu;
     const uint8_t* body = S.body + (size_t)e * S.body_stride;
-    const uint8_t* dl = body + S.off_disc;
-    const uint16_t* cl = reinterpret_cast<const uint16_t*>(body + S.off_cred);
     const mcbs_node_static* NS = reinterpret_cast<const mcbs_node_static*>(T.base + C.off_node);
     const mcbs_triple* TR = reinterpret_cast<const mcbs_triple*>(T.base + C.off_triple);
     const uint32_t Nm = O.Nmax, NP = C.n_props;
@@ -115,7 +113,7 @@ __device__ __forceinline__ void obs_env(const DevState& S, const Topo& T, const 
         if (c * 64u < n_disc) {               // wave-uniform
             bool own = false;
             if (i < n_disc) {
-                const uint32_t n = c == 0 ? dl_head : dl[i];
+                const uint32_t n = c == 0 ? dl_head : S.disc_at(body, e, i);
                 own = one_word ? (bool)((w_inst >> n) & 1ull) : S.has(M_INST, n, e);
                 st.ext_of[n] = (uint8_t)i;
                 st.props[i] = S.row_get(body, n).props_tags & ROW_PROPS_MASK;
@@ -127,7 +125,7 @@ __device__ __forceinline__ void obs_env(const DevState& S, const Topo& T, const 
         }
     }
     for (uint32_t i = lane; i < n_creds; i += 64u) {
-        const mcbs_triple t = TR[i < 64u ? cl_head : cl[i]];
+        const mcbs_triple t = TR[i < 64u ? cl_head : S.cred_at(body, e, i)];
         st.cred_node[i] = (uint8_t)t.node;
         st.cred_port[i] = (uint8_t)t.port;
     }
@@ -613,8 +611,8 @@ __device__ __forceinline__ TinyOut obs_tiny_group(const DevState& S, const Topo&
     const uint32_t n_trip_cap = T.H().n_triples;
     // level 1
     const uint4 h0 = S.h0[ec];
-    const uint32_t n = body[S.off_disc + (j < S.N ? j : S.N - 1u)];
-    const uint32_t tid = reinterpret_cast<const uint16_t*>(body + S.off_cred)[j < n_trip_cap ? j : n_trip_cap];
+    const uint32_t n = S.disc_at(body, ec, j < S.N ? j : S.N - 1u);
+    const uint32_t tid = S.cred_at(body, ec, j < n_trip_cap ? j : n_trip_cap);
     const uint64_t w_inst = S.get(M_INST, 0, ec), w_plo = S.get(M_PLO, 0, ec), w_phi = S.get(M_PHI, 0, ec);
     const uint32_t flags = h0.y, n_disc = h0.z & 0xFFFFu, n_creds = h0.z >> 16;
     const bool live = valid && !(flags & F_SKIP);             // split step, skip action: the env's previous observation stands
@@ -819,14 +817,13 @@ __global__ __launch_bounds__(256) void mask_kernel(DevState S, Topo T, const Ste
     uint32_t q = idx0 / inner, in = idx0 - q * inner;     // q = s*N + t (or s for local), in = position inside the row
     uint32_t s, t;
     if (REGION == 2) { s = q; t = 0; } else { s = q / Nm; t = q - s * Nm; }
-    const uint8_t* dl = S.body + (size_t)e * S.body_stride + S.off_disc;
     const mcbs_node_static* NS = reinterpret_cast<const mcbs_node_static*>(T.base + C.off_node);
     alignas(16) int8_t v[W];
     uint32_t lmask = 0;
     bool row_on = false;
     auto load_row = [&]() {
         row_on = s < Nm && ((d.own_ext[(s >> 6) & 3u] >> (s & 63u)) & 1ull) && (REGION == 2 || t < d.n_disc);
-        if (REGION == 2 && row_on) lmask = local_mask_of(C, NS, S.body + (size_t)e * S.body_stride, dl[s]);
+        if (REGION == 2 && row_on) lmask = local_mask_of(C, NS, S.body + (size_t)e * S.body_stride, S.disc_at(S.body + (size_t)e * S.body_stride, e, s));
     };
     load_row();
     uint32_t c = REGION == 0 ? in % Cm : 0u;              // credential index inside the (source, target, port) row

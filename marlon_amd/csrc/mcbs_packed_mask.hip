@@ -49,7 +49,7 @@ __global__ __launch_bounds__(256) void pack_mask_kernel(DevState S, Topo T, cons
     auto whole_row = [&](uint32_t q, uint32_t) -> uint64_t { return pair_on(q) ? ~0ull : 0ull; };   // connect / remote: on or off as a whole
     auto local_row = [&](uint32_t i, uint32_t k) -> uint64_t {                                     // local[i][l] = owned(i) && l applies to node i
         if (!(own(i) && i < n_disc)) return 0ull;
-        return (uint64_t)NS[body[S.off_disc + i]].local_mask >> k;
+        return (uint64_t)NS[S.disc_at(body, e, i)].local_mask >> k;
     };
     uint64_t pp = 0;                                     // credential pattern of one period, repeated to at least C + 32 bits (uniform)
     if (G.C + 32u <= 64u) {

@@ -19,6 +19,8 @@
 
 namespace mcbs {
 
+// LAYOUT: 1 packed batch / 0 general layout where the caller knows it at compile time (the step kernel's rollout), -1: decided at run time
+template <int LAYOUT = -1>
 __device__ inline void sample_action(const DevState& S, const Topo& T, const StepCfg& C, uint32_t e, int valid, uint64_t seed, uint64_t step,
                                      uint32_t Nmax, uint32_t Cmax, int32_t (&a)[5]) {
     const uint64_t gid = C.env_id_base + e;
@@ -43,15 +45,15 @@ __device__ inline void sample_action(const DevState& S, const Topo& T, const Ste
     const uint4 h0 = S.h0[e];
     const uint32_t n_disc = h0.z & 0xFFFFu, n_creds = h0.z >> 16, owned = h0.w & 0xFFFFu;
     const uint8_t* body = S.body + (size_t)e * S.body_stride;
-    const uint8_t* dl = body + S.off_disc;
     const mcbs_node_static* NS = reinterpret_cast<const mcbs_node_static*>(T.base + C.off_node);
+    auto disc = [&](uint32_t i) -> uint32_t { return S.template disc_at_as<LAYOUT>(body, e, i); };
     // one pass over the discovery order up front (independent loads), instead of set look-ups in memory inside every attempt:
     // bit i of own_ext / inst_ext = the node at external index i has privilege >= LocalUser / has the agent installed
     uint64_t plo[4] = {0, 0, 0, 0}, phi[4] = {0, 0, 0, 0}, inst[4] = {0, 0, 0, 0};
     for (uint32_t w = 0; w < S.NW && w < 4u; ++w) { plo[w] = S.get(M_PLO, w, e); phi[w] = S.get(M_PHI, w, e); inst[w] = S.get(M_INST, w, e); }
     uint64_t own_ext[4] = {0, 0, 0, 0}, inst_ext[4] = {0, 0, 0, 0};
     for (uint32_t i = 0; i < n_disc; ++i) {
-        const uint32_t n = dl[i], w = (n >> 6) & 3u, b = n & 63u;
+        const uint32_t n = disc(i), w = (n >> 6) & 3u, b = n & 63u;
         own_ext[(i >> 6) & 3u] |= (((plo[w] | phi[w]) >> b) & 1ull) << (i & 63u);
         inst_ext[(i >> 6) & 3u] |= ((inst[w] >> b) & 1ull) << (i & 63u);
     }
@@ -73,7 +75,7 @@ __device__ inline void sample_action(const DevState& S, const Topo& T, const Ste
         if (kind == 0) {
             const uint32_t v = below(C.L);
             a[0] = 0; a[1] = (int32_t)src; a[2] = (int32_t)v; a[3] = 0; a[4] = 0;
-            if (installed && ((local_mask_of(C, NS, body, dl[src]) >> v) & 1u)) break;
+            if (installed && ((local_mask_of(C, NS, body, disc(src)) >> v) & 1u)) break;
         } else if (kind == 1) {
             a[0] = 1; a[1] = (int32_t)src; a[2] = (int32_t)below(n_disc); a[3] = (int32_t)below(C.R); a[4] = 0;
             if (installed) break;

@@ -15,8 +15,11 @@
 //   level 1 (addresses depend on the env index only, issued back to back, all coalesced along the env axis):
 //           header uint4, action row, first 16 discovery-order entries, first 16 credential-cache entries,
 //           EVERY set of the env as u64 bit-mask words (discovered, agent installed, ever owned, running,
-//           privilege bit-planes, gathered credentials, cached credential triples; packed batches: one uint4 and
-//           every 4-byte node row), {cum_reward, availability}; the config words (action-space bounds, goal
+//           privilege bit-planes, gathered credentials, cached credential triples), {cum_reward, availability};
+//           packed batches: the sets are one uint4, BOTH lists are the nibbles of one more uint4 (the "lists word",
+//           mcbs_device.h: picks are one 64-bit shift and a mask, a leaked element is OR-ed in at 4 * count in
+//           registers and the word goes back once, if it changed) and every 4-byte node row comes along;
+//           the config words (action-space bounds, goal
 //           constants) are fetched through the config pointer AFTER these are in flight;
 //   level 2 (address depends on the action / header): the target node's 16-byte row, the re-imaging ring slot
 //           of this defender tick (list entries beyond the first 16 for large topologies come first), and the
@@ -115,6 +118,9 @@ __device__ __forceinline__ uint32_t half_of(const uint4& a, const uint4& b, uint
     return (uint32_t)(((i & 8u) ? wb : wa) >> ((i & 3u) * 16u)) & 0xFFFFu;
 }
 
+// entry i (< 16) of a list held as 16 nibbles (packed batches: one half of the lists word)
+__device__ __forceinline__ uint32_t nibble_of(uint64_t l, uint32_t i) { return DevState::list_nibble((uint32_t)l, (uint32_t)(l >> 32), i); }
+
 // dword i (< 16) of four 16-byte vectors, as 64-bit selects and one shift (see byte_of)
 __device__ __forceinline__ uint32_t dword_of(const uint4& r0, const uint4& r1, const uint4& r2, const uint4& r3, uint32_t i) {
 #define MCBS_P64(a, b) ((uint64_t)(a) | ((uint64_t)(b) << 32))
@@ -135,25 +141,6 @@ __device__ __forceinline__ uint32_t dword_of(const uint4& r0, const uint4& r1, c
 __device__ __forceinline__ bool differs(const uint4& a, const uint4& b) { return ((a.x ^ b.x) | (a.y ^ b.y) | (a.z ^ b.z) | (a.w ^ b.w)) != 0u; }
 __device__ __forceinline__ bool differs(const double2& a, const double2& b) {   // bit patterns, not values: -0.0 + 0.0 is a change
     return ((__double_as_longlong(a.x) ^ __double_as_longlong(b.x)) | (__double_as_longlong(a.y) ^ __double_as_longlong(b.y))) != 0;
-}
-
-// entry i (< 16) of a 16-byte vector of u8 / of two 16-byte vectors of u16 := v (64-bit mask arithmetic, see byte_of)
-__device__ __forceinline__ void put_byte(uint4& v, uint32_t i, uint32_t x) {
-    uint64_t lo = (uint64_t)v.x | ((uint64_t)v.y << 32), hi = (uint64_t)v.z | ((uint64_t)v.w << 32);
-    const uint32_t sh = (i & 7u) * 8u;
-    const uint64_t clr = ~(0xFFull << sh), val = (uint64_t)(x & 0xFFu) << sh;
-    if (i & 8u) hi = (hi & clr) | val; else lo = (lo & clr) | val;
-    v = make_uint4((uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32));
-}
-__device__ __forceinline__ void put_half(uint4& a, uint4& b, uint32_t i, uint32_t x) {
-    uint64_t w[4] = {(uint64_t)a.x | ((uint64_t)a.y << 32), (uint64_t)a.z | ((uint64_t)a.w << 32), (uint64_t)b.x | ((uint64_t)b.y << 32),
-                     (uint64_t)b.z | ((uint64_t)b.w << 32)};
-    const uint32_t sh = (i & 3u) * 16u, q = (i >> 2) & 3u;
-    const uint64_t clr = ~(0xFFFFull << sh), val = (uint64_t)(x & 0xFFFFu) << sh;
-#pragma unroll
-    for (uint32_t k = 0; k < 4u; ++k) w[k] = k == q ? ((w[k] & clr) | val) : w[k];
-    a = make_uint4((uint32_t)w[0], (uint32_t)(w[0] >> 32), (uint32_t)w[1], (uint32_t)(w[1] >> 32));
-    b = make_uint4((uint32_t)w[2], (uint32_t)(w[2] >> 32), (uint32_t)w[3], (uint32_t)(w[3] >> 32));
 }
 
 // Hook points of step_body for kernels that wrap more work around the same step in the same launch (mcbs_wrapper_fused.hip); every
@@ -194,9 +181,9 @@ struct Lane {
     uint4 prw0 = {0, 0, 0, 0}, prw1 = {0, 0, 0, 0}, prw2 = {0, 0, 0, 0}, prw3 = {0, 0, 0, 0};
     uint32_t ptgt = 0xFFFFFFFFu, pword = 0;
     const uint8_t* ere_blob = nullptr;   // the topology blob (ExternalRandomEvents reads its cold tables)
-    // fused wrapper step (mcbs_wrapper_fused.hip, act<.., REC = true>): the heads of the two lists kept up to date in registers while the
-    // leak entries are appended, so that the observation can be assembled without reading the lists back
-    uint4 rec_dh = {0, 0, 0, 0}, rec_c0 = {0, 0, 0, 0}, rec_c1 = {0, 0, 0, 0};
+    // packed batches: the two halves of the env's lists word (discovery order / credential cache as nibbles, zero at and past the counts);
+    // act() appends to them in registers, step_body stores the word back, the fused wrapper step hands it to its observation stage
+    uint64_t ldisc = 0, lcred = 0;
 
     __device__ __forceinline__ const HotNode* NS(uint32_t n) const { return reinterpret_cast<const HotNode*>(tb + C.hot_node) + n; }
     __device__ __forceinline__ Row* row(uint32_t n) const { return reinterpret_cast<Row*>(body + S.off_rows) + n; }
@@ -219,10 +206,12 @@ struct Lane {
     //   raw_nx : the raw reward when !X (0 out of bounds, -1 credential index outside the cache; env.py:736-737)
     //   kind   : 0 local, 1 remote, 2 connect; `col` = vulnerability column (exploits; 0 for connect),
     //            `port` / `triple` = connect arguments (0 for exploits).  Every index is valid for every lane.
-    // WIDE_OK = false: the batch cannot have a wide cached-triple set (packed layout); compiles its handling out.
+    // WIDE_OK = false: the batch cannot have a wide cached-triple set (packed layout); compiles its handling out, and the lists are
+    // the nibbles of ldisc / lcred instead of arrays in the body.
     // DK: the batch's defender kind; MCBS_DEFENDER_RANDOM_EVENTS consults the env's own vulnerability / service / firewall state
     // GUARD = false (the looping variant, see step_body): list appends go to the slot past the end whether or not the element is new
-    template <bool WIDE_OK, int DK, bool REC = false, bool GUARD = true>
+    // (general layout only: a packed list must stay zero past its count)
+    template <bool WIDE_OK, int DK, bool GUARD = true>
     __device__ __forceinline__ void act(bool X, double raw_nx, int kind, uint32_t src, uint32_t tgt, uint32_t col, uint32_t port, uint32_t triple) {
         const bool k2 = kind == 2;
         // ---- look-ups of both flavours (LDS) ----
@@ -339,8 +328,8 @@ struct Lane {
         auto leak = [&](const uint2 p) {                 // one LeakedCredentials / LeakedNodesId entry {node | cred << 16, triple | port << 16}
             const uint32_t pn = p.x & 0xFFFFu, pc = p.x >> 16, pt = p.y & 0xFFFFu;
             // an element is appended only if it is new (an exec-masked store; nothing reads a list at or past its count, and
-            // mcbs_get_state reports 0xFFFF there; the lists keep one slack slot for !GUARD).  The record heads (REC) take every entry:
-            // registers, read below the counts only
+            // mcbs_get_state reports 0xFFFF there; the lists keep one slack slot for !GUARD).  Packed batches: no store here — a new
+            // element is OR-ed into the slot at the count (zero until now), anything else ORs zero
             const bool new_n = !rget<WT>(m[M_DISC], pn);
             const bool new_g = creds & !rget<WT>(m[M_GATH], pc);
             bool new_c;
@@ -350,11 +339,12 @@ struct Lane {
                 new_c = creds & !(old & bit);
                 if (stage) *w = old | bit;
             } else new_c = creds & !rget<WT>(m[M_CACH], pt);
-            if (!GUARD || MCBS_CHANGED(new_n)) disc_list()[n_disc] = (uint8_t)pn;
-            if (!GUARD || MCBS_CHANGED(new_c)) cred_list()[n_creds] = (uint16_t)pt;
-            if (REC) {                                   // (packed batches: both lists have fewer than 16 entries)
-                put_byte(rec_dh, n_disc & 15u, pn);
-                put_half(rec_c0, rec_c1, n_creds & 15u, pt);
+            if (!WIDE_OK) {
+                ldisc |= (uint64_t)(new_n ? pn & 0xFu : 0u) << ((n_disc & 15u) * 4u);
+                lcred |= (uint64_t)(new_c ? pt & 0xFu : 0u) << ((n_creds & 15u) * 4u);
+            } else {
+                if (!GUARD || MCBS_CHANGED(new_n)) disc_list()[n_disc] = (uint8_t)pn;
+                if (!GUARD || MCBS_CHANGED(new_c)) cred_list()[n_creds] = (uint16_t)pt;
             }
             uint64_t b0[WT], b1[WT], b2[WT];
             rbit<WT>(b0, pn, new_n); rbit<WT>(b1, pc, new_g); rbit<WT>(b2, pt & (WT * 64u - 1u), new_c && !wide);
@@ -522,10 +512,10 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
     const uint4 h0 = S.h0[ec];
     uint4 a03 = make_uint4(0, 0, 0, 0);
     uint32_t a4 = 0;
-    uint4 dhead = make_uint4(0, 0, 0, 0), chead0 = dhead, chead1 = dhead;
+    uint4 dhead = make_uint4(0, 0, 0, 0), chead0 = dhead, chead1 = dhead, lists0 = dhead;
     if (MANY && roll.mode) {                            // on-device random agent: this step's action comes from the env's own state
         int32_t ra[5];
-        sample_action(S, T, C, ec, roll.mode == 2u, roll.seed, roll.step0 + it, roll.nmax, roll.cmax, ra);
+        sample_action<PK ? 1 : 0>(S, T, C, ec, roll.mode == 2u, roll.seed, roll.step0 + it, roll.nmax, roll.cmax, ra);
         a03 = make_uint4((uint32_t)ra[0], (uint32_t)ra[1], (uint32_t)ra[2], (uint32_t)ra[3]);
         a4 = (uint32_t)ra[4];
         if (io.actions && active) {
@@ -539,7 +529,9 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
         a03 = make_uint4(ap[0], ap[1], ap[2], ap[3]);
         a4 = ap[4];
     }
-    if (PHASE != 2) {
+    if (PK && PHASE != 2) {                              // packed batch: both lists are one word
+        lists0 = reinterpret_cast<const uint4*>(S.masks)[S.E + ec];
+    } else if (PHASE != 2) {
         dhead = *reinterpret_cast<const uint4*>(body + S.off_disc);
         chead0 = *reinterpret_cast<const uint4*>(body + S.off_cred);
         chead1 = *reinterpret_cast<const uint4*>(body + S.off_cred + 16);
@@ -631,7 +623,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
 #pragma unroll
         for (int w = 0; w < WT; ++w) ln.m[k][w] = m0[k][w];
     ln.ere_blob = T.base;
-    if (Hook::kObs) { ln.rec_dh = dhead; ln.rec_c0 = chead0; ln.rec_c1 = chead1; }
+    if (PK) { ln.ldisc = (uint64_t)lists0.x | ((uint64_t)lists0.y << 32); ln.lcred = (uint64_t)lists0.z | ((uint64_t)lists0.w << 32); }
     if (!PK && S.wide) {                                // this lane's LDS column for the wide cached-triple set, behind the hot image
         ln.wide_lds = reinterpret_cast<uint64_t*>(topo_lds + (TOPO_LDS ? C.hot_bytes / 16u : 0u)) + threadIdx.x;
         ln.wide_stride = bdim;
@@ -656,8 +648,8 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
         const bool X = live & !skip & !oob & (k0 | k1 | k2);
         // indices every lane may use: its own when the action executes, entry 0 otherwise
         const uint32_t i1 = X ? a1 : 0u, i2 = (X & !k0) ? a2 : i1, i4 = (X & k2) ? a4 : 0u;
-        uint32_t src = byte_of(dhead, i1 & 15u), tgt = byte_of(dhead, i2 & 15u);
-        uint32_t triple = half_of(chead0, chead1, i4 & 15u);
+        uint32_t src = PK ? nibble_of(ln.ldisc, i1) : byte_of(dhead, i1 & 15u), tgt = PK ? nibble_of(ln.ldisc, i2) : byte_of(dhead, i2 & 15u);
+        uint32_t triple = PK ? nibble_of(ln.lcred, i4) : half_of(chead0, chead1, i4 & 15u);
         if (!PK && (i1 | i2 | i4) >= 16u) {                     // large topologies: entries past the first 16 of a list
             const uint32_t s2 = ln.disc_list()[i1], t2 = ln.disc_list()[i2], c2 = ln.cred_list()[i4];
             src = i1 >= 16u ? s2 : src; tgt = i2 >= 16u ? t2 : tgt; triple = i4 >= 16u ? c2 : triple;
@@ -680,10 +672,13 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
         ln.props = pt & ROW_PROPS_MASK; ln.tags = (uint32_t)(pt >> 60);
         ln.ever = r0.z; ln.since = r0.w;
         STAMP(3);  // row landed
-        ln.template act<!PK, DEFK, Hook::kObs, GUARD>(X, skip ? -1.0 : 0.0, kind, src, tgt, X ? (k0 ? a2 : (k1 ? cL + a3 : 0u)) : 0u, (X & k2) ? a3 : 0u, triple);
+        ln.template act<!PK, DEFK, GUARD>(X, skip ? -1.0 : 0.0, kind, src, tgt, X ? (k0 ? a2 : (k1 ? cL + a3 : 0u)) : 0u, (X & k2) ? a3 : 0u, triple);
         // the row goes back only if the action changed it (first attack / discovery of a (node, vulnerability) pair, new properties
         // or tags); `pword` holds the row as the attacker left it either way, for reimage()
         if (PK) {
+            // the lists word goes back once, only if a leak appended to it
+            const uint4 nl = make_uint4((uint32_t)ln.ldisc, (uint32_t)(ln.ldisc >> 32), (uint32_t)ln.lcred, (uint32_t)(ln.lcred >> 32));
+            if (!GUARD || MCBS_CHANGED(differs(nl, lists0))) reinterpret_cast<uint4*>(S.masks)[S.E + e] = nl;
             const uint32_t w = S.tiny_pack(ln.props, ln.tags, ln.ever, ln.since);
             if (!GUARD || MCBS_CHANGED(w != pw0)) reinterpret_cast<uint32_t*>(body + S.off_rows)[tgt] = w;
             if (PHASE == 0) { ln.rows_in_regs = true; ln.prw0 = rw0; ln.prw1 = rw1; ln.prw2 = rw2; ln.prw3 = rw3; ln.ptgt = tgt; ln.pword = w; }
@@ -795,7 +790,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
     STAMP(5);              // all stores of the step retired
     if (PHASE != 1 && PK && C.init_image_ok) {
         // Packed batches: an env that just ended is re-initialised by its OWN lane with stores only — the body's reset image (<= 16 x 16
-        // bytes), the sets and the header come from the config through the scalar cache, the episode counter was fetched at level 1.
+        // bytes), the sets, the lists word and the header come from the config through the scalar cache, the episode counter was fetched at level 1.
         // (Round 2 let the whole wavefront copy the image from memory behind a fence, like the large layouts below: with ~1 % of the
         // envs ending per step that cost every other wavefront a write-acknowledgement round trip — 6.06 vs 5.05 us per step.)
         if (need_reset) {
@@ -805,6 +800,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
             for (uint32_t i = 0; i < 16u; ++i)
                 if (i < nv) dst[i] = make_uint4(C.init_image[4 * i], C.init_image[4 * i + 1], C.init_image[4 * i + 2], C.init_image[4 * i + 3]);
             reinterpret_cast<uint4*>(S.masks)[e] = make_uint4(C.init_packed[0], C.init_packed[1], C.init_packed[2], C.init_packed[3]);
+            reinterpret_cast<uint4*>(S.masks)[S.E + e] = make_uint4(C.init_lists[0], C.init_lists[1], C.init_lists[2], C.init_lists[3]);
             if (S.ring) for (uint32_t s = 0; s < 16u; ++s) S.ring[(size_t)s * S.E + e] = 0ull;
             S.h0[e] = make_uint4(0u, 0u, C.n_init, C.n_init);
             S.h1[e] = make_double2(0.0, 1.0);
@@ -828,7 +824,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
                 for (uint32_t off = lane * 16u; off < S.body_stride; off += 64u * 16u)
                     *reinterpret_cast<uint4*>(dst + off) = *reinterpret_cast<const uint4*>(S.init_body + off);
             }
-            if (need_reset) reset_header(S, T, e, S.episode[e] + 1u);
+            if (need_reset) reset_header<PK>(S, T, e, S.episode[e] + 1u);
         }
     }
     if constexpr (Hook::kFinish) hook.finish(S, C, T, e, active, hk_reward, hk_done, episode);

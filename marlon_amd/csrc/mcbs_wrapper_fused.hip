@@ -11,9 +11,9 @@
 //   loads   : everything the step loads (mcbs_step.hip levels 1 and 2), the policy's action, the wrapper's counters — once;
 //   compute : lane = env for the decode, the attacker's action, the defender / goals and the wrapper's bookkeeping (mcbs_step.hip's
 //             step_body with three hook points, the same code the headline kernel runs);
-//   observe : between the attacker's action and the defender's turn each lane hands what its env's observation is made of — list heads
-//             (kept up to date in registers while leaked entries are appended), node rows, three sets, flags and counts — to the
-//             workgroup through 132 bytes of LDS, straight from the registers the step holds; after the step all four wavefronts turn
+//   observe : between the attacker's action and the defender's turn each lane hands what its env's observation is made of — the lists
+//             word (both lists as nibbles, appended to in registers by the step), node rows, three sets, flags and counts — to the
+//             workgroup through 88 bytes of LDS, straight from the registers the step holds; after the step all four wavefronts turn
 //             the 64 hand-overs into records by discovery index (known properties, privilege, (node index, port) per cached credential);
 //   stores  : state, outputs, the re-initialisation of the envs that ended (their own lane, stores only), and then the observation of
 //             the wavefront's 64 envs STREAMED OUT COOPERATIVELY: the 64 envs' rows of each observation array are one contiguous
@@ -40,7 +40,7 @@ constexpr uint32_t FUSED_FIELDS = 5;          // 0 scalars [7], 1 leaked_credent
 constexpr uint32_t FUSED_FRESH_DWORDS = 1024; // LDS room for one reset observation
 constexpr uint32_t FUSED_THREADS = 256;        // one workgroup = 64 envs: the first wavefront steps them (lane = env), all four stream the observation
 constexpr uint32_t FUSED_STAGE_DWORDS = 37;   // per env; odd, so that lane-per-env accesses fall into 37 i mod 32: all banks
-constexpr uint32_t FUSED_RAW_DWORDS = 33;     // per env: what the stepping lane hands over (list heads, rows, sets); odd as well
+constexpr uint32_t FUSED_RAW_DWORDS = 23;     // per env: what the stepping lane hands over (lists word, rows, sets); odd as well
 
 struct FusedArgs {                             // kernel argument, by value (the per-step output pointers change from step to step)
     mcbs_wrapper_buffers w;
@@ -77,13 +77,13 @@ struct FusedStage {                            // view of one env's 37 dwords of
     __device__ __forceinline__ uint32_t& own() const { return p[31]; }
     __device__ __forceinline__ uint8_t* ext_of() const { return reinterpret_cast<uint8_t*>(p + 32); }
 };
-struct FusedRaw {                              // view of one env's 33 dwords of LDS: written by the stepping lane between the attacker's action and the defender's turn
+struct FusedRaw {                              // view of one env's 23 dwords of LDS: written by the stepping lane between the attacker's action and the defender's turn
     uint32_t* p;
-    // [0..3] discovery order (16 node ids), [4..11] credential cache (16 triple ids, u16), [12..27] the sixteen 4-byte node rows (target's as the
-    // attacker left it), [28] agent-installed | privilege bit 0 << 16, [29] privilege bit 1
-    __device__ __forceinline__ const uint8_t* disc() const { return reinterpret_cast<const uint8_t*>(p); }
-    __device__ __forceinline__ const uint16_t* cache() const { return reinterpret_cast<const uint16_t*>(p + 4); }
-    __device__ __forceinline__ uint32_t row(uint32_t n) const { return p[12 + n]; }
+    // [0..1] discovery order (16 node ids, a nibble each), [2..3] credential cache (16 triple ids, a nibble each), [4..19] the sixteen 4-byte
+    // node rows (target's as the attacker left it), [20] agent-installed | privilege bit 0 << 16, [21] privilege bit 1
+    __device__ __forceinline__ uint32_t disc(uint32_t j) const { return DevState::list_nibble(p[0], p[1], j); }
+    __device__ __forceinline__ uint32_t cache(uint32_t r) const { return DevState::list_nibble(p[2], p[3], r); }
+    __device__ __forceinline__ uint32_t row(uint32_t n) const { return p[4 + n]; }
 };
 constexpr uint32_t FM_LIVE = 1u << 16, FM_BLANK = 1u << 17, FM_ENDED = 1u << 18;
 
@@ -190,20 +190,18 @@ struct FusedHook {
     }
 
     // Between the attacker's action and the defender's turn: the stepping lane hands what its env's observation is made of to the workgroup
-    // — list heads, node rows, the three sets — as it holds them in registers (nine 16-byte LDS writes), plus flags and counts.
+    // — the lists word, node rows, the three sets — as it holds them in registers, plus flags and counts.
     template <class LaneT>
     __device__ __forceinline__ void stage_obs(const DevState& S, const StepCfg& C, const LaneT& ln, uint32_t flags, bool not_skipped) {
         const FusedRaw rw = raw(lane);
-        rw.p[0] = ln.rec_dh.x; rw.p[1] = ln.rec_dh.y; rw.p[2] = ln.rec_dh.z; rw.p[3] = ln.rec_dh.w;
-        rw.p[4] = ln.rec_c0.x; rw.p[5] = ln.rec_c0.y; rw.p[6] = ln.rec_c0.z; rw.p[7] = ln.rec_c0.w;
-        rw.p[8] = ln.rec_c1.x; rw.p[9] = ln.rec_c1.y; rw.p[10] = ln.rec_c1.z; rw.p[11] = ln.rec_c1.w;
-        rw.p[12] = ln.prw0.x; rw.p[13] = ln.prw0.y; rw.p[14] = ln.prw0.z; rw.p[15] = ln.prw0.w;
-        rw.p[16] = ln.prw1.x; rw.p[17] = ln.prw1.y; rw.p[18] = ln.prw1.z; rw.p[19] = ln.prw1.w;
-        rw.p[20] = ln.prw2.x; rw.p[21] = ln.prw2.y; rw.p[22] = ln.prw2.z; rw.p[23] = ln.prw2.w;
-        rw.p[24] = ln.prw3.x; rw.p[25] = ln.prw3.y; rw.p[26] = ln.prw3.z; rw.p[27] = ln.prw3.w;
-        rw.p[12 + (ln.ptgt & 15u)] = ln.pword;              // the target's row as the attacker left it (same lane, program order)
-        rw.p[28] = ((uint32_t)ln.m[M_INST][0] & 0xFFFFu) | ((uint32_t)ln.m[M_PLO][0] << 16);
-        rw.p[29] = (uint32_t)ln.m[M_PHI][0];
+        rw.p[0] = (uint32_t)ln.ldisc; rw.p[1] = (uint32_t)(ln.ldisc >> 32); rw.p[2] = (uint32_t)ln.lcred; rw.p[3] = (uint32_t)(ln.lcred >> 32);
+        rw.p[4] = ln.prw0.x; rw.p[5] = ln.prw0.y; rw.p[6] = ln.prw0.z; rw.p[7] = ln.prw0.w;
+        rw.p[8] = ln.prw1.x; rw.p[9] = ln.prw1.y; rw.p[10] = ln.prw1.z; rw.p[11] = ln.prw1.w;
+        rw.p[12] = ln.prw2.x; rw.p[13] = ln.prw2.y; rw.p[14] = ln.prw2.z; rw.p[15] = ln.prw2.w;
+        rw.p[16] = ln.prw3.x; rw.p[17] = ln.prw3.y; rw.p[18] = ln.prw3.z; rw.p[19] = ln.prw3.w;
+        rw.p[4 + (ln.ptgt & 15u)] = ln.pword;               // the target's row as the attacker left it (same lane, program order)
+        rw.p[20] = ((uint32_t)ln.m[M_INST][0] & 0xFFFFu) | ((uint32_t)ln.m[M_PLO][0] << 16);
+        rw.p[21] = (uint32_t)ln.m[M_PHI][0];
         const FusedStage st = stage(lane);
         const bool blank = (flags & F_OOB) != 0;
         st.flags() = flags;
@@ -220,9 +218,9 @@ struct FusedHook {
             const FusedRaw rw = raw(env);
             const FusedStage st = stage(env);
             const uint32_t meta = st.meta(), n_disc = meta & 0xFFu;
-            const uint32_t n = rw.disc()[j] & 15u;
+            const uint32_t n = rw.disc(j);
             const bool on = j < n_disc;
-            const uint32_t sets = rw.p[28], phi = rw.p[29];
+            const uint32_t sets = rw.p[20], phi = rw.p[21];
             st.props(j) = on ? (rw.row(n) & pmask) : 0u;
             st.privb()[j] = (on && !(meta & FM_BLANK)) ? (uint8_t)((((sets >> 16) >> n) & 1u) | (((phi >> n) & 1u) << 1)) : (uint8_t)0;
             if (on) st.ext_of()[n] = (uint8_t)j;
@@ -239,7 +237,7 @@ struct FusedHook {
             const uint32_t env = item >> 4, r = item & 15u;
             const FusedRaw rw = raw(env);
             const FusedStage st = stage(env);
-            const uint32_t t = tr[rw.cache()[r] & 15u];                          // node | port << 16 (entries beyond n_creds are never read)
+            const uint32_t t = tr[rw.cache(r)];                          // node | port << 16 (entries beyond n_creds are never read)
             st.cred()[r] = (uint16_t)((uint32_t)st.ext_of()[t & 15u] | ((t >> 16) << 8));
         }
     }
@@ -279,6 +277,7 @@ struct FusedHook {
                 for (uint32_t i = 0; i < 16u; ++i)
                     if (i < nv) dst[i] = make_uint4(C.init_image[4 * i], C.init_image[4 * i + 1], C.init_image[4 * i + 2], C.init_image[4 * i + 3]);
                 reinterpret_cast<uint4*>(S.masks)[e] = make_uint4(C.init_packed[0], C.init_packed[1], C.init_packed[2], C.init_packed[3]);
+                reinterpret_cast<uint4*>(S.masks)[S.E + e] = make_uint4(C.init_lists[0], C.init_lists[1], C.init_lists[2], C.init_lists[3]);
                 if (S.ring) for (uint32_t s = 0; s < 16u; ++s) S.ring[(size_t)s * S.E + e] = 0ull;
                 S.h0[e] = make_uint4(0u, 0u, C.n_init, C.n_init);
                 S.h1[e] = make_double2(0.0, 1.0);
