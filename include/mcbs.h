@@ -399,6 +399,67 @@ int  mcbs_apply_packed_mask(const mcbs_batch*, const uint32_t* bits, size_t bits
 int  mcbs_unpack_action_mask(const mcbs_batch*, const uint32_t* bits, size_t bits_row_words, uint8_t* out, size_t out_row_stride,
                              uint64_t n_rows, void* stream);
 
+/* ---- masked categorical head: sample, log-prob and entropy of MaskablePPO's action distribution, one launch ----
+ * What sb3_contrib's MaskableCategorical does with the policy's logits and action_masks() (train_marl_multi.py:259-293):
+ * `where(mask, logits, -1e8)`, log_softmax over the row, then sample / log_prob / entropy with the masked terms zeroed; evaluate_actions
+ * repeats it on stored masks at update time.  A masked-out action contributes exp(-1e8 - max) == 0 in float32, so the distribution is
+ * exactly the softmax over the ALLOWED actions: these calls read only the logits under set mask bits and write 16-20 bytes per row.
+ * The logits are READ-ONLY (never modified, unlike mcbs_mask_logits) and the mask is never written anywhere.
+ *
+ * mcbs_masked_categorical (live form): one row per env, n = n_envs; the mask is that of the LAST observation of every env, rebuilt from
+ *   the per-env digest exactly like mcbs_mask_logits (same preconditions: MCBS_ESTATE under MCBS_DEFENDER_RANDOM_EVENTS and while the
+ *   digests cannot be trusted).  Row e is keyed by the GLOBAL env id env_id_base + e: shards of one batch draw what the whole batch would.
+ * mcbs_masked_categorical_packed: any n_rows (e.g. a shuffled minibatch gathered from stored masks; 0 is a no-op); the mask of row i is
+ *   bits[i, 0 .. W) in the format of mcbs_pack_action_mask, bits_row_words >= W (MCBS_EINVAL otherwise).  Bits at or beyond A in word
+ *   W-1 are ignored, not trusted to be zero.  The batch only supplies the device and A: no digest is needed, every defender kind is
+ *   served.  Row i is keyed by i.
+ *
+ * Common arguments (all device pointers):
+ *   logits      float32 (MCBS_LOGITS_F32) or bfloat16 (MCBS_LOGITS_BF16) [n, row_stride], row_stride in elements, >= A (MCBS_EINVAL
+ *               otherwise); any alignment.  NULL = all-zero logits: the uniform law over the allowed actions, which is the reference's masked
+ *               random agent (uniform over np.flatnonzero(action_masks()): random_marlon_agent.py:88-95) — dtype and row_stride are ignored.
+ *   mode        MCBS_CATEGORICAL_SAMPLE / _ARGMAX / _EVALUATE
+ *   actions     int64 [n]: written in SAMPLE and ARGMAX, read in EVALUATE
+ *   log_prob    float [n]: log p of the row's action
+ *   entropy     float [n] or NULL
+ *   n_allowed   uint32 [n] or NULL: K, the number of allowed actions of the row
+ *   uniforms    float [n] or NULL (SAMPLE; see "random numbers")
+ *   seed, step  key of the row's random number when uniforms is NULL
+ *   bad_actions optional uint32_t, INCREASED by the number of EVALUATE rows whose action lies outside [0, A) (not zeroed by the call)
+ *
+ * Semantics for the allowed set S of a row, K = |S|, x_a = (float)logits[a]; float32 arithmetic throughout with expf (the one logarithm per row, of the float32
+ * Z, K or A, is the correctly rounded float32 of a double-precision log: the device's logf is up to two ulp off), no floating-point
+ * atomics, every sum in a fixed order: two calls give bit-identical outputs, and the packed form on the mask mcbs_pack_action_mask stored
+ * gives bit for bit what the live form gave.
+ *   m = max_S x,  Z = sum_S exp(x_a - m),  log p_a = (x_a - m) - log Z,  entropy = log Z - (sum_S (x_a - m) exp(x_a - m)) / Z
+ *   (order of the sums: per mask word in ascending bit order; the words of each block of 64 consecutive words by an inclusive scan in
+ *   word order; the blocks' totals one after the other.)
+ *   ARGMAX    the allowed action with the largest logit, the lowest index among equal ones.
+ *   SAMPLE    inverse CDF in ascending action order: the first allowed action whose cumulative sum (same order as Z) exceeds u * Z; if
+ *             rounding leaves none, the last allowed action.
+ *   EVALUATE  log p of actions[i]; an action inside [0, A) that is not allowed gets (-1e8f - m) - log Z (the reference's `where`); an
+ *             action outside [0, A) gets NaN and counts one bad_action.
+ *   logits == NULL: log_prob = -log K, entropy = log K, ARGMAX = the lowest allowed action, SAMPLE = the ((u24 * K) >> 24)-th allowed
+ *             action (0-based, ascending), in exact integer arithmetic.
+ *   K == 0 (blank observation — the digest's blank flag — or an all-zero packed row): MaskableCategorical degenerates to uniform over all A
+ *             actions with entropy 0: log_prob = -log A, entropy = 0, SAMPLE = (u24 * A) >> 24, ARGMAX = 0.
+ *
+ * Random numbers: u24 is a 24-bit integer, u = u24 * 2^-24.  With uniforms: u24 = min(2^24 - 1, floor(uniforms[i] * 2^24)) (for graph
+ * capture, where seed and step would be frozen, and for tests).  Otherwise u24 = word 0 >> 8 of ONE Philox4x32-10 block with
+ *   counter = (key_lo, key_hi, step_lo, step_hi),   key = (seed_lo ^ MCBS_CATEGORICAL_PHILOX_DOMAIN, seed_hi)
+ * where key = the row key (env_id_base + e, or the row index i) and _lo / _hi are the low / high 32 bits.  The domain constant differs
+ * from the random-agent sampler's (0x5A17ACED): the same (seed, step) may be used for both. */
+#define MCBS_CATEGORICAL_SAMPLE   0
+#define MCBS_CATEGORICAL_ARGMAX   1
+#define MCBS_CATEGORICAL_EVALUATE 2
+#define MCBS_CATEGORICAL_PHILOX_DOMAIN 0xCA7E6041u
+int  mcbs_masked_categorical(mcbs_batch*, const void* logits, int32_t dtype, size_t row_stride, int32_t mode, int64_t* actions, float* log_prob,
+                             float* entropy, uint32_t* n_allowed, const float* uniforms, uint64_t seed, uint64_t step, uint32_t* bad_actions,
+                             void* stream);
+int  mcbs_masked_categorical_packed(const mcbs_batch*, const uint32_t* bits, size_t bits_row_words, uint64_t n_rows, const void* logits,
+                                    int32_t dtype, size_t row_stride, int32_t mode, int64_t* actions, float* log_prob, float* entropy,
+                                    uint32_t* n_allowed, const float* uniforms, uint64_t seed, uint64_t step, uint32_t* bad_actions, void* stream);
+
 /* ---- feature encoder: observation rows -> the float rows a policy's first layer takes, one launch ----
  * What Stable-Baselines3's "MultiInputPolicy" (marlon/baseline_models/ppo/train.py:79) does first with the wrappers' Dict observation
  * (preprocess_obs + CombinedExtractor): a Discrete(n) becomes a one-hot of n, every element of a MultiDiscrete a one-hot of its own, a

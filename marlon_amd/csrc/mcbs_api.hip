@@ -18,6 +18,7 @@
 #include "mcbs_defend.hip"
 #include "mcbs_logits.hip"
 #include "mcbs_packed_mask.hip"
+#include "mcbs_categorical.hip"
 #include "mcbs_features.hip"
 #include "mcbs_wrapper_fused.hip"
 
@@ -1318,6 +1319,63 @@ extern "C" int mcbs_unpack_action_mask(const mcbs_batch* b, const uint32_t* bits
     if (n_rows == 0) return MCBS_OK;
     hipLaunchKernelGGL(unpack_mask_kernel, packed_rows_grid(n_rows, (A + 15u + 15u) / 16u), dim3(256), 0, (hipStream_t)stream, bits, bits_row_words, out, out_row_stride, n_rows, A);
     return launch_ok("unpack action mask");
+}
+
+// ------------------------------------------------------------------ masked categorical head
+// arguments common to the two forms; `who` names the entry point in messages
+static int categorical_args(const char* who, const void* logits, int32_t dtype, size_t row_stride, int32_t mode, const int64_t* actions,
+                            const float* log_prob, uint32_t A) {
+    if (logits && dtype != MCBS_LOGITS_F32 && dtype != MCBS_LOGITS_BF16) return fail(MCBS_EINVAL, "%s: logits dtype must be MCBS_LOGITS_F32 or MCBS_LOGITS_BF16", who);
+    if (mode != MCBS_CATEGORICAL_SAMPLE && mode != MCBS_CATEGORICAL_ARGMAX && mode != MCBS_CATEGORICAL_EVALUATE)
+        return fail(MCBS_EINVAL, "%s: mode must be MCBS_CATEGORICAL_SAMPLE, _ARGMAX or _EVALUATE", who);
+    if (!actions || !log_prob) return fail(MCBS_EINVAL, "%s: actions and log_prob must not be NULL", who);
+    if (logits && row_stride < A) return fail(MCBS_EINVAL, "%s: row_stride %zu is shorter than the %u Discrete actions", who, row_stride, A);
+    return MCBS_OK;
+}
+
+static void categorical_launch(const mcbs_batch* b, bool live, const LogitsGeom& G, const uint32_t* bits, size_t bits_row_words, int32_t dtype,
+                               const CatIO& io, hipStream_t st) {
+    const uint64_t blocks = (io.n_rows + 3u) / 4u;      // one wavefront per row, four per workgroup; the kernel strides over the rest
+    const dim3 grid(blocks < 65536u ? (uint32_t)blocks : 65536u), block(256);
+#define MCBS_CAT_LAUNCH(LT_, LIVE_) \
+    hipLaunchKernelGGL((masked_categorical_kernel<LT_, LIVE_>), grid, block, 0, st, b->S, b->T, b->C_dev, b->digest, G, bits, bits_row_words, io)
+    if (dtype == MCBS_LOGITS_BF16 && io.logits) { if (live) MCBS_CAT_LAUNCH(uint16_t, true); else MCBS_CAT_LAUNCH(uint16_t, false); }
+    else { if (live) MCBS_CAT_LAUNCH(float, true); else MCBS_CAT_LAUNCH(float, false); }
+#undef MCBS_CAT_LAUNCH
+}
+
+extern "C" int mcbs_masked_categorical(mcbs_batch* b, const void* logits, int32_t dtype, size_t row_stride, int32_t mode, int64_t* actions,
+                                       float* log_prob, float* entropy, uint32_t* n_allowed, const float* uniforms, uint64_t seed, uint64_t step,
+                                       uint32_t* bad_actions, void* stream) {
+    if (!b) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    int rc;
+    if ((rc = digest_usable(b, "mcbs_masked_categorical"))) return rc;
+    LogitsGeom G;
+    if ((rc = discrete_geom(b, G))) return rc;
+    if ((rc = categorical_args("mcbs_masked_categorical", logits, dtype, row_stride, mode, actions, log_prob, G.A))) return rc;
+    CatIO io{logits, row_stride, actions, log_prob, entropy, n_allowed, uniforms, bad_actions, seed, step, b->cfg.env_id_base, b->S.E, (uint32_t)mode, G.A};
+    categorical_launch(b, true, G, nullptr, 0, dtype, io, (hipStream_t)stream);
+    return launch_ok("masked categorical");
+}
+
+extern "C" int mcbs_masked_categorical_packed(const mcbs_batch* b, const uint32_t* bits, size_t bits_row_words, uint64_t n_rows, const void* logits,
+                                              int32_t dtype, size_t row_stride, int32_t mode, int64_t* actions, float* log_prob, float* entropy,
+                                              uint32_t* n_allowed, const float* uniforms, uint64_t seed, uint64_t step, uint32_t* bad_actions,
+                                              void* stream) {
+    if (!b) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    int rc;
+    LogitsGeom G;
+    if ((rc = discrete_geom(b, G))) return rc;
+    const uint32_t W = (G.A + 31u) / 32u;
+    if (n_rows == 0) return MCBS_OK;
+    if (!bits) return fail(MCBS_EINVAL, "mcbs_masked_categorical_packed: bits must not be NULL");
+    if (bits_row_words < W) return fail(MCBS_EINVAL, "bits_row_words %zu is shorter than the %u words of %u Discrete actions", bits_row_words, W, G.A);
+    if ((rc = categorical_args("mcbs_masked_categorical_packed", logits, dtype, row_stride, mode, actions, log_prob, G.A))) return rc;
+    CatIO io{logits, row_stride, actions, log_prob, entropy, n_allowed, uniforms, bad_actions, seed, step, 0ull, n_rows, (uint32_t)mode, G.A};
+    categorical_launch(b, false, G, bits, bits_row_words, dtype, io, (hipStream_t)stream);
+    return launch_ok("masked categorical (packed)");
 }
 
 // ------------------------------------------------------------------ feature encoder

@@ -14,22 +14,22 @@
 
 namespace mcbs {
 
-// One WAVEFRONT per env (four per workgroup), each lane builds whole dwords of 32 actions from the env's digest with the predicates
-// of mask_logits_kernel and stores them as dwords (one 256-byte store per wavefront instruction), words 0 .. W-1 only: words from W up
-// to the row stride are never written.  A pure write stream; far below the bandwidth its 1 772 bytes per env would allow (DESIGN.md
-// section 7 has the measurements and the SQ counters).  (Kernel trace, 65 536 Chain-10 envs, one run, us per launch: lane k building
-// dwords 4k .. 4k+3 for one 16-byte store 387, this form 131 in the same run.)
-__global__ __launch_bounds__(256) void pack_mask_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, const ObsDigest* __restrict__ digest,
-                                                        uint32_t* __restrict__ bits, size_t row_words, LogitsGeom G) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t e = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform
-    if (e >= S.E) return;
-    const ObsDigest d = digest[e];                       // uniform per wavefront: scalar loads
-    const uint32_t n_disc = d.blank ? 0u : d.n_disc, n_creds = d.n_creds;
-    const uint32_t remote0 = G.M + G.ML, W = (G.A + 31u) / 32u;
-    const uint8_t* body = S.body + (size_t)e * S.body_stride;
-    const mcbs_node_static* NS = reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node);
-    uint32_t* row = bits + (size_t)e * row_words;
+// The mask words of one env, rebuilt from its digest with the predicates of mask_logits_kernel: word w = the 32 actions
+// [32 w, 32 w + 32) of the env's Discrete mask as bits (bits from A on are zero).  Shared by pack_mask_kernel (which stores the words) and
+// masked_categorical_kernel (mcbs_categorical.hip, which only reads the logits under the set bits).  Everything but w is uniform per
+// wavefront: d = the env's digest, n_disc = 0 for a blank observation, pp = digest_cred_pattern.
+__device__ __forceinline__ uint64_t digest_cred_pattern(const LogitsGeom& G, uint32_t n_creds) {
+    uint64_t pp = 0;                                     // credential pattern of one period, repeated to at least C + 32 bits
+    if (G.C + 32u <= 64u) {
+        const uint64_t one = n_creds >= 64u ? ~0ull : ((1ull << n_creds) - 1ull);
+        for (uint32_t sh = 0; sh < 64u; sh += G.C) pp |= one << sh;
+    }
+    return pp;
+}
+
+__device__ __forceinline__ uint32_t digest_mask_word(const DevState& S, const ObsDigest& d, const LogitsGeom& G, const mcbs_node_static* NS,
+                                                     const uint8_t* body, uint32_t e, uint32_t n_disc, uint32_t n_creds, uint64_t pp, uint32_t w) {
+    const uint32_t remote0 = G.M + G.ML;
     auto own = [&](uint32_t s) -> bool { return s < G.N && ((d.own_ext[(s >> 6) & 3u] >> (s & 63u)) & 1ull); };
     auto pair_on = [&](uint32_t q) -> bool {             // row q = (source s, target t): s owned (hence discovered), t discovered
         const uint32_t s = fdiv(q, G.dN), t = q - s * G.N;
@@ -51,44 +51,56 @@ __global__ __launch_bounds__(256) void pack_mask_kernel(DevState S, Topo T, cons
         if (!(own(i) && i < n_disc)) return 0ull;
         return (uint64_t)NS[S.disc_at(body, e, i)].local_mask >> k;
     };
-    uint64_t pp = 0;                                     // credential pattern of one period, repeated to at least C + 32 bits (uniform)
-    if (G.C + 32u <= 64u) {
-        const uint64_t one = n_creds >= 64u ? ~0ull : ((1ull << n_creds) - 1ull);
-        for (uint32_t sh = 0; sh < 64u; sh += G.C) pp |= one << sh;
-    }
-    auto word_at = [&](uint32_t w) -> uint32_t {
-        const uint32_t a0 = w * 32u, a1 = a0 + 32u < G.A ? a0 + 32u : G.A;      // actions [a0, a1); bits from A on stay zero
-        uint32_t m = 0;
-        if (a0 < G.M) {
-            // connect[s][t][p][c] = on(s, t) && c < n_creds: the dword overlaps ceil(32 / RL) + 1 rows at most, and since RL = P*C and the
-            // block starts at action 0, the credential index of action a is a mod C in every row
-            const uint32_t rows = rows_in(a0, a1 < G.M ? a1 : G.M, G.RL, G.dRL, whole_row);
-            if (rows) {
-                const uint32_t c0 = a0 - fdiv(a0, G.dC) * G.C;
-                uint32_t cred = 0;
-                if (G.C + 32u <= 64u) {
-                    cred = (uint32_t)(pp >> c0);
-                } else {
-                    uint32_t c = c0;
-                    for (uint32_t i = 0; i < 32u; ++i) {
-                        cred |= (uint32_t)(c < n_creds) << i;
-                        c = c + 1u == G.C ? 0u : c + 1u;
-                    }
+    const uint32_t a0 = w * 32u, a1 = a0 + 32u < G.A ? a0 + 32u : G.A;      // actions [a0, a1); bits from A on stay zero
+    uint32_t m = 0;
+    if (a0 < G.M) {
+        // connect[s][t][p][c] = on(s, t) && c < n_creds: the dword overlaps ceil(32 / RL) + 1 rows at most, and since RL = P*C and the
+        // block starts at action 0, the credential index of action a is a mod C in every row
+        const uint32_t rows = rows_in(a0, a1 < G.M ? a1 : G.M, G.RL, G.dRL, whole_row);
+        if (rows) {
+            const uint32_t c0 = a0 - fdiv(a0, G.dC) * G.C;
+            uint32_t cred = 0;
+            if (G.C + 32u <= 64u) {
+                cred = (uint32_t)(pp >> c0);
+            } else {
+                uint32_t c = c0;
+                for (uint32_t i = 0; i < 32u; ++i) {
+                    cred |= (uint32_t)(c < n_creds) << i;
+                    c = c + 1u == G.C ? 0u : c + 1u;
                 }
-                m = rows & cred;
             }
+            m = rows & cred;
         }
-        if (a1 > G.M && a0 < remote0) {                  // local block: rows of L bits, the node's vulnerability mask
-            const uint32_t lo = a0 > G.M ? a0 : G.M, hi = a1 < remote0 ? a1 : remote0;
-            m |= rows_in(lo - G.M, hi - G.M, G.L, G.dL, local_row) << (lo - a0);
-        }
-        if (a1 > remote0) {                              // remote[s][t][r] = on(s, t)
-            const uint32_t lo = a0 > remote0 ? a0 : remote0;
-            m |= rows_in(lo - remote0, a1 - remote0, G.R, G.dR, whole_row) << (lo - a0);
-        }
-        return m;
-    };
-    for (uint32_t w = lane; w < W; w += 64u) row[w] = word_at(w);
+    }
+    if (a1 > G.M && a0 < remote0) {                  // local block: rows of L bits, the node's vulnerability mask
+        const uint32_t lo = a0 > G.M ? a0 : G.M, hi = a1 < remote0 ? a1 : remote0;
+        m |= rows_in(lo - G.M, hi - G.M, G.L, G.dL, local_row) << (lo - a0);
+    }
+    if (a1 > remote0) {                              // remote[s][t][r] = on(s, t)
+        const uint32_t lo = a0 > remote0 ? a0 : remote0;
+        m |= rows_in(lo - remote0, a1 - remote0, G.R, G.dR, whole_row) << (lo - a0);
+    }
+    return m;
+}
+
+// One WAVEFRONT per env (four per workgroup), each lane builds whole dwords of 32 actions from the env's digest with the predicates
+// of mask_logits_kernel and stores them as dwords (one 256-byte store per wavefront instruction), words 0 .. W-1 only: words from W up
+// to the row stride are never written.  A pure write stream; far below the bandwidth its 1 772 bytes per env would allow (DESIGN.md
+// section 7 has the measurements and the SQ counters).  (Kernel trace, 65 536 Chain-10 envs, one run, us per launch: lane k building
+// dwords 4k .. 4k+3 for one 16-byte store 387, this form 131 in the same run.)
+__global__ __launch_bounds__(256) void pack_mask_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, const ObsDigest* __restrict__ digest,
+                                                        uint32_t* __restrict__ bits, size_t row_words, LogitsGeom G) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t e = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform
+    if (e >= S.E) return;
+    const ObsDigest d = digest[e];                       // uniform per wavefront: scalar loads
+    const uint32_t n_disc = d.blank ? 0u : d.n_disc, n_creds = d.n_creds;
+    const uint32_t W = (G.A + 31u) / 32u;
+    const uint8_t* body = S.body + (size_t)e * S.body_stride;
+    const mcbs_node_static* NS = reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node);
+    uint32_t* row = bits + (size_t)e * row_words;
+    const uint64_t pp = digest_cred_pattern(G, n_creds);
+    for (uint32_t w = lane; w < W; w += 64u) row[w] = digest_mask_word(S, d, G, NS, body, e, n_disc, n_creds, pp, w);
 }
 
 // logits[i, a] = bit(i, a) ? logits[i, a] : fill for rows i < n_rows (a wavefront takes rows i, i + 4 * gridDim.x, ...).  The store

@@ -7,6 +7,7 @@ from here.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 from typing import Dict, Iterable, Optional
@@ -27,6 +28,7 @@ EXPORTS = [
     "mcbs_attacker_wrapper_step_launches", "mcbs_set_mask_discrete_stride", "mcbs_defender_wrapper_step",
     "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant",
     "mcbs_feature_layout_create", "mcbs_feature_layout_destroy", "mcbs_feature_layout_width", "mcbs_encode_features",
+    "mcbs_masked_categorical", "mcbs_masked_categorical_packed",
 ]
 
 _lib = None
@@ -101,6 +103,10 @@ def load_library(path: Optional[str] = None):
     lib.mcbs_feature_layout_width.argtypes = [C.c_void_p]
     lib.mcbs_encode_features.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ObsBuffers), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_size_t,
                                          C.c_uint64, C.c_void_p, C.c_void_p]
+    _cat = [C.c_void_p, C.c_int32, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+            C.c_void_p, C.c_void_p]           # logits, dtype, row_stride, mode, actions, log_prob, entropy, n_allowed, uniforms, seed, step, bad_actions, stream
+    lib.mcbs_masked_categorical.argtypes = [C.c_void_p] + _cat
+    lib.mcbs_masked_categorical_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64] + _cat
     lib.mcbs_copy_rows_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mcbs_attacker_wrapper_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -154,6 +160,11 @@ class FeatureLayoutHandle:
         except Exception:
             pass
 
+
+# what BatchEngine.masked_categorical returns: actions int64 [n], log_prob float32 [n], entropy float32 [n], n_allowed int32 [n]
+MaskedCategorical = collections.namedtuple("MaskedCategorical", ["actions", "log_prob", "entropy", "n_allowed"])
+CATEGORICAL_MODES = {"sample": 0, "argmax": 1, "evaluate": 2}      # MCBS_CATEGORICAL_*
+CATEGORICAL_PHILOX_DOMAIN = 0xCA7E6041                              # MCBS_CATEGORICAL_PHILOX_DOMAIN
 
 FEATURE_FIELDS = ("scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel")
 
@@ -542,6 +553,70 @@ class BatchEngine:
             _check(self.lib, self.lib.mcbs_unpack_action_mask(self._h, bits.data_ptr(), bits.stride(0), out.data_ptr(), out.stride(0),
                                                               bits.shape[0], self._stream()), "mcbs_unpack_action_mask")
         return out
+
+    # -- masked categorical head (include/mcbs.h): sample / log-prob / entropy of `Categorical(logits=where(mask, logits, -1e8))` --
+    def masked_categorical(self, logits=None, *, bits=None, mode: str = "sample", actions=None, seed: int = 0, step: int = 0, uniforms=None,
+                           out=None, bad_actions=None) -> MaskedCategorical:
+        """MaskablePPO's action distribution in one launch, reading only the logits under set mask bits; logits are never modified.
+        bits=None: the live form — one row per env, the mask of the LAST observation rebuilt from the digest (the preconditions of
+        mask_logits), rows keyed by the global env id.  bits = packed masks int32 [n, >= W] (pack_action_mask's format): any n rows, no
+        digest involved, rows keyed by their index.  logits: device float32 / bfloat16 [n, >= A] with contiguous rows, or None for the
+        uniform law over the allowed actions.  mode: "sample" (inverse CDF in ascending action order), "argmax" (lowest index among equal
+        logits) or "evaluate" (log-prob of the given `actions`, int64 [n]; NaN for an action outside [0, A), counted in bad_actions:
+        optional device int32 [1], increased, not zeroed).  seed / step key the row's Philox number unless `uniforms` (device float32 [n]
+        in [0, 1)) is given.  out: optional (actions, log_prob, entropy, n_allowed) of preallocated device tensors (int64, float32, float32,
+        int32, each [n]).  -> MaskedCategorical(actions, log_prob, entropy, n_allowed)."""
+        t = self.torch
+        if mode not in CATEGORICAL_MODES:
+            raise ValueError(f"mode must be one of {sorted(CATEGORICAL_MODES)}, got {mode!r}")
+        if bits is not None:
+            self._packed_rows(bits, "bits")
+            n = bits.shape[0]
+        else:
+            n = self.E
+        A = self.discrete_action_count()
+        if logits is not None:
+            if not isinstance(logits, t.Tensor) or logits.dtype not in (t.float32, t.bfloat16):
+                raise ValueError("logits must be a float32 or bfloat16 tensor (or None for the uniform law)")
+            # the C side sees only the row stride: a view narrower than A would have its rows read past their end
+            if logits.dim() != 2 or logits.shape[0] != n or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < A:
+                raise ValueError(f"logits must be a device tensor [{n}, >= {A}] with contiguous rows")
+
+        def vec(x, dtype, what):
+            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != (n,) or not x.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous device {dtype} tensor [{n}]")
+            return x
+
+        if out is not None and len(out) != 4:
+            raise ValueError("out must be (actions, log_prob, entropy, n_allowed)")
+        o_act, o_lp, o_ent, o_k = out if out is not None else (None, None, None, None)
+        if mode == "evaluate":
+            if actions is None:
+                raise ValueError('mode="evaluate" needs actions (int64 [n])')
+            o_act = vec(actions, t.int64, "actions")
+        else:
+            if actions is not None:
+                raise ValueError('actions are an input of mode="evaluate" only (preallocate outputs with out=)')
+            o_act = vec(o_act, t.int64, "out.actions") if o_act is not None else t.empty(n, dtype=t.int64, device=self.device)
+        o_lp = vec(o_lp, t.float32, "out.log_prob") if o_lp is not None else t.empty(n, dtype=t.float32, device=self.device)
+        o_ent = vec(o_ent, t.float32, "out.entropy") if o_ent is not None else t.empty(n, dtype=t.float32, device=self.device)
+        o_k = vec(o_k, t.int32, "out.n_allowed") if o_k is not None else t.empty(n, dtype=t.int32, device=self.device)
+        if uniforms is not None:
+            vec(uniforms, t.float32, "uniforms")
+        if bad_actions is not None and (not isinstance(bad_actions, t.Tensor) or bad_actions.dtype != t.int32 or bad_actions.numel() != 1
+                                        or bad_actions.device != self.device):
+            raise ValueError("bad_actions must be a device int32 tensor of one element")
+        common = (logits.data_ptr() if logits is not None else None, 0 if logits is None or logits.dtype == t.float32 else 1,
+                  (logits.stride(0) if n > 1 else max(logits.stride(0), logits.shape[1])) if logits is not None else 0,
+                  CATEGORICAL_MODES[mode], o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), o_k.data_ptr(),
+                  uniforms.data_ptr() if uniforms is not None else None, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                  bad_actions.data_ptr() if bad_actions is not None else None, self._stream())
+        if bits is None:
+            _check(self.lib, self.lib.mcbs_masked_categorical(self._h, *common), "mcbs_masked_categorical")
+        elif n:
+            _check(self.lib, self.lib.mcbs_masked_categorical_packed(self._h, bits.data_ptr(), bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1]),
+                                                                     n, *common), "mcbs_masked_categorical_packed")
+        return MaskedCategorical(o_act, o_lp, o_ent, o_k)
 
     # -- feature encoder (include/mcbs.h): observation rows -> the one-hot float rows a policy's first layer takes --
     def feature_layout(self, layout) -> FeatureLayoutHandle:

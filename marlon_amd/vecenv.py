@@ -324,6 +324,17 @@ class MarlonVecEnv:
         of word a >> 5): 8x smaller than action_masks(), and available when the masks are not materialised."""
         return self._out(self.venv.action_masks_packed())
 
+    # the masked categorical head (AttackerVecEnv.sample_masked / sample_masked_uniform / evaluate_masked): device tensors in, and the
+    # MaskedCategorical tuple of device tensors out whatever numpy_outputs says — these sit between a policy's logits and its loss
+    def sample_masked(self, logits, seed: int, step: int, deterministic: bool = False, uniforms=None):
+        return self.venv.sample_masked(logits, seed, step, deterministic=deterministic, uniforms=uniforms)
+
+    def sample_masked_uniform(self, seed: int, step: int):
+        return self.venv.sample_masked_uniform(seed, step)
+
+    def evaluate_masked(self, bits, logits, actions):
+        return self.venv.evaluate_masked(bits, logits, actions)
+
     def get_attr(self, attr_name: str, indices=None) -> List[Any]:
         val = getattr(self.venv, attr_name)
         idx = self._indices(indices)

@@ -173,6 +173,38 @@ class AttackerVecEnv:
         """Packed masks [n, >= W] -> bool [n, A] (what action_masks() returns for the same step)."""
         return self.engine.unpack_action_mask(bits, out)
 
+    # -- the masked categorical head (mcbs_masked_categorical): MaskableCategorical's sample / log_prob / entropy in one launch --
+    def _live_bits(self):
+        """None where the live form serves (the mask is rebuilt from the digest); under ExternalRandomEvents, where it cannot be, the
+        materialised mask packed with torch expressions, as features(include_masks=True) does (rows are then keyed by their index)."""
+        from ._abi import DEFENDER_RANDOM_EVENTS
+        if self.engine._cfg.defender_kind != DEFENDER_RANDOM_EVENTS:
+            return None
+        if not self.materialize_masks:
+            raise RuntimeError("the masked categorical head under ExternalRandomEvents needs the materialised masks (the mask cannot be "
+                               "rebuilt from the observation digest there): create the env with materialize_masks=True")
+        return self._pack_bits_from_mask(self.action_masks())
+
+    def sample_masked(self, logits, seed: int, step: int, deterministic: bool = False, uniforms=None, out=None):
+        """An action per env from `Categorical(logits=where(action_masks(), logits, -1e8))` for the observation this env last returned,
+        without the mask and without touching the logits: -> MaskedCategorical(actions, log_prob, entropy, n_allowed).
+        deterministic: the allowed action with the largest logit (lowest index among equal ones).  Rows are keyed by (seed, global env
+        id, step): pass the rollout step as `step`; uniforms (device float32 [n_envs] in [0, 1)) replaces the key, e.g. under graph
+        capture."""
+        return self.engine.masked_categorical(logits, bits=self._live_bits(), mode="argmax" if deterministic else "sample", seed=seed, step=step,
+                                              uniforms=uniforms, out=out)
+
+    def sample_masked_uniform(self, seed: int, step: int, uniforms=None, out=None):
+        """The reference's masked random agent: uniform over np.flatnonzero(action_masks()) (random_marlon_agent.py:88-95) =
+        sample_masked with no logits at all."""
+        return self.sample_masked(None, seed, step, uniforms=uniforms, out=out)
+
+    def evaluate_masked(self, bits, logits, actions, bad_actions=None, out=None):
+        """MaskablePPO's evaluate_actions for stored rows: log_prob of `actions` [n] and the entropy under logits [n, >= A] and the stored
+        packed masks bits [n, >= W] (action_masks_packed), any n.  The log_prob of an action sample_masked drew under the same mask and
+        logits comes back bit for bit."""
+        return self.engine.masked_categorical(logits, bits=bits, mode="evaluate", actions=actions, bad_actions=bad_actions, out=out)
+
     # -- the policy's input features (marlon_amd/features.py, mcbs_encode_features) --
     def _feature_handle(self, include_masks: bool, reference_counts: bool, keys=None):
         key = (bool(include_masks), bool(reference_counts), None if keys is None else tuple(keys))

@@ -6,6 +6,8 @@
     python3 tools/profile_run.py obs:<workload> [K]       K mcbs_observe launches of the whole observation (reference dtypes)
     python3 tools/profile_run.py discrete:<workload> [K]  K mcbs_observe launches of the small fields + mask_discrete (MaskablePPO path)
     python3 tools/profile_run.py logits:<workload> [K]    K mcbs_mask_logits launches (on-device mask -> logits, no mask materialised)
+    python3 tools/profile_run.py categorical:<workload> [K]  K mcbs_masked_categorical launches (live form, SAMPLE, fp32 randn * 4 logits; the logits are
+                                                          filled once before: rocprofv3 --pmc FETCH_SIZE of the kernel = its bytes read)
     python3 tools/profile_run.py wrapper:<workload> [K]   K AttackerVecEnv.step calls (Discrete actions, no mask materialised, hipGraph replay)
 workload: headline | config2 | config3 | config4 | config5  (tools/workloads.py)
 
@@ -99,6 +101,16 @@ elif what == "logits":
         eng.mask_logits(logits, fill=-1e8)
     torch.cuda.synchronize()
     out.update(bytes_per_env=4.0 * float((logits != 0).sum()) / eng.E, logits_bytes_per_env=n_act * 4)      # write-only: 4 B per masked-out action
+elif what == "categorical":
+    for t in range(40):
+        eng.step(ring[t], with_info=False)
+    eng.observe(eng.alloc_obs(W.OBS_FIELDS[:5]))
+    n_act = eng.discrete_action_count()
+    logits = torch.randn((eng.E, n_act), dtype=torch.float32, device=eng.device) * 4.0
+    for t in range(K):
+        res = eng.masked_categorical(logits, mode="sample", seed=1, step=t)
+    torch.cuda.synchronize()
+    out.update(allowed_per_env=float(res.n_allowed.double().mean()), logits_bytes_per_env=n_act * 4)
 else:
     raise SystemExit(f"unknown workload kind {what}")
 print(json.dumps(out))
