@@ -60,7 +60,10 @@ static int fail(int code, const char* fmt, ...) {
     if (_dev_guard.err != hipSuccess) return fail(MCBS_EHIP, "cannot select device %d: %s", (b)->cfg.device, hipGetErrorString(_dev_guard.err))
 
 static FastDiv fast_div_host(uint32_t d);
-struct HotLayout { uint32_t node, desc, payload, auth, auth_words, triple, avail, fwlist, bytes; };
+struct HotLayout {
+    uint32_t node, desc, payload, auth, auth_words, triple, avail, fwlist, bytes;
+    uint32_t max_leak;   // the largest payload_cnt of any descriptor: no action of this topology leaks more entries (StepCfg::max_leak)
+};
 
 struct mcbs_topology {
     std::vector<uint8_t> host;
@@ -255,6 +258,7 @@ extern "C" int mcbs_topology_create(const void* blob, size_t nbytes, int32_t dev
                     d.cost = v.cost; d.probe_mask = v.probe_mask; d.payload_off = v.payload_off; d.payload_cnt = v.payload_cnt;
                     d.precond_tt = v.precond_tt; d.kind = v.kind; d.level = v.level; d.slot = s;
                     for (uint32_t i = 0; i < 4u && i < v.payload_cnt; ++i) d.inline_payload[i] = pl[v.payload_off + i];
+                    if (v.payload_cnt > L.max_leak) L.max_leak = v.payload_cnt;
                 }
                 memcpy(hb + L.desc + sizeof(HotDesc) * ((size_t)n * W + c), &d, sizeof(d));
             }
@@ -491,6 +495,7 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     C.off_service = h->off_service; C.off_allowed = h->off_allowed; C.off_triple = h->off_triple;
     C.hot_node = topo->hot.node; C.hot_desc = topo->hot.desc; C.hot_payload = topo->hot.payload; C.hot_auth = topo->hot.auth;
     memcpy(C.rule_port, h->rule_port, 8); C.n_services = h->n_services; C.n_fw_lists = h->n_fw_lists; C.hot_fwlist = topo->hot.fwlist;
+    C.max_leak = topo->hot.max_leak;
     C.auth_words = topo->hot.auth_words; C.hot_triple = topo->hot.triple; C.hot_avail = topo->hot.avail; C.hot_bytes = topo->hot.bytes;
     C.avail_uniform = h->avail_any_order ? 1u : 0u;
     C.avail_term0 = ns[0].avail_term;

@@ -26,6 +26,7 @@ __device__ __forceinline__ void defender_turn(const DevState& S, const Topo& T, 
     uint8_t* body = S.body + (size_t)e * S.body_stride;
     Lane<WT> ln{S, C, T.hot, e, body, h0.z & 0xFFFFu, h0.z >> 16, h0.w & 0xFFFFu, h0.w >> 16, {}, 0u, 0ull, 0u, 0u, 0u, false, true, 0u, 0u,
                 0.0, MCBS_OUT_NONE, 0, 0, 0};
+    ln.A = ActCfg::of(C);
     uint64_t m0[M_COUNT][WT];
 #pragma unroll
     for (int k = 0; k < M_COUNT; ++k)

@@ -22,6 +22,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stddef.h>
 #include "mcbs.h"
 
 namespace mcbs {
@@ -179,17 +180,32 @@ struct Topo {           // device view of the MCBT blob and of the hot image bui
 };
 
 struct StepCfg {        // the parts of mcbs_batch_cfg the kernels read
-    double goal_reward, goal_low_availability, goal_own_atleast_percent;
-    double maintain_sla, winning_reward, losing_reward, scan_probability;
+    // The first 112 bytes are every word the step kernel pins behind its level-1 loads (mcbs_step.hip, step_body), next to each other
+    // and in the order it pins them, so that they arrive with a few wide scalar loads issued together: scattered over the struct they
+    // were nine loads, and the register allocator put a wait between two of them (a second scalar-memory round trip).
+    double goal_reward, goal_low_availability, maintain_sla, winning_reward, losing_reward;
+    uint32_t has_attacker_goal, goal_own_atleast, defender_goal_eviction, auto_reset, max_episode_steps;
+    uint32_t goal_own_pct_min;   // AttackerGoal.own_atleast_percent as a count: the smallest k with !(k / N < percent) in the reference's own
+                                 // fp64 division (env.py:1093-1095), found on the host (N + 1: never) — the kernels compare integers instead
+                                 // of dividing doubles per env and step
+    uint32_t L, R, P;
+    uint32_t max_leak;       // the largest leak payload of any (node, vulnerability) of the topology, from the descriptors' counts (host, at
+                             // topology creation): the step kernel skips its second prefetch batch, the rungs at or past this count and
+                             // the tail loop with one scalar test each.  Too small a bound would drop leaked entries silently.
+    uint32_t hot_node, hot_desc, hot_payload, hot_auth, auth_words;   // hot image (Topo::hot) section offsets, words per authorisation set
+    uint32_t init_image_ok;  // 0: the body does not fit init_image (learned-defender / random-events state behind the rows): wave-level copy instead
+    uint32_t pad_pin[2];
+    // ---- everything else is fetched where it is used ----
+    double goal_own_atleast_percent, scan_probability;
     double total_sla_weight, full_availability, full_sum;
     uint64_t seed, env_id_base;
-    uint32_t has_attacker_goal, goal_own_atleast, defender_goal_eviction, defender_kind;
-    uint32_t scan_capacity, scan_frequency, auto_reset, max_episode_steps, rng_kind, avail_any_order;
-    uint32_t L, R, P, V, n_props, K;
+    uint32_t defender_kind;
+    uint32_t scan_capacity, scan_frequency, rng_kind, avail_any_order;
+    uint32_t V, n_props, K;
     // section offsets into the blob, hoisted so kernels do not chase the header
     uint32_t off_node, off_slot_of, off_slot, off_payload, off_service, off_allowed, off_triple;
-    // hot image (Topo::hot) section offsets and size
-    uint32_t hot_node, hot_desc, hot_payload, hot_auth, auth_words, hot_triple, hot_avail, hot_bytes;
+    // hot image: the sections off the attacker's path, and its size
+    uint32_t hot_triple, hot_avail, hot_bytes;
     uint8_t  rule_port[8];   // identifier-port index of RDP, SSH, HTTPS, HTTP, su, sudo (0xFF: not an identifier port)
     uint32_t n_services, n_fw_lists;
     uint32_t hot_fwlist;     // uint32[N]: incoming list id | outgoing list id << 16
@@ -215,15 +231,13 @@ struct StepCfg {        // the parts of mcbs_batch_cfg the kernels read
     uint32_t init_image[64];
     uint32_t init_packed[4];
     uint32_t n_init;
-    uint32_t goal_own_pct_min;   // AttackerGoal.own_atleast_percent as a count: the smallest k with !(k / N < percent) in the reference's own
-                                 // fp64 division (env.py:1093-1095), found on the host (N + 1: never) — the kernels compare integers instead
-                                 // of dividing doubles per env and step
-    uint32_t init_image_ok;  // 0: the body does not fit init_image (learned-defender / random-events state behind the rows): wave-level copy instead
-    uint32_t pad_v[1];
+    uint32_t pad_v[3];
     uint32_t init_lists[4];
 };
 
 // mcbs_rollout_random: the looping step kernel samples each step's action itself; passed as a kernel argument of that variant only
+static_assert(offsetof(StepCfg, pad_pin) == 104, "the pinned block of StepCfg");
+
 struct RollArgs {
     uint32_t mode = 0;       // 0 off (actions are read), 1 uniform in the action space, 2 the sample_valid_action distribution
     uint32_t nmax = 0, cmax = 0, pad = 0;

@@ -19,14 +19,16 @@
 //           packed batches: the sets are one uint4, BOTH lists are the nibbles of one more uint4 (the "lists word",
 //           mcbs_device.h: picks are one 64-bit shift and a mask, a leaked element is OR-ed in at 4 * count in
 //           registers and the word goes back once, if it changed) and every 4-byte node row comes along;
-//           the config words (action-space bounds, goal
-//           constants) are fetched through the config pointer AFTER these are in flight;
+//           EVERY config word the step reads before its last store (action-space bounds, goal constants, the hot image's section
+//           offsets and table shapes, the topology's leak bound, "the reset image fits the config") is fetched through the config
+//           pointer AFTER these are in flight, in ONE pinned batch: the words are the first 112 bytes of StepCfg, so they arrive with
+//           three wide scalar loads and one wait, hidden behind the vector loads (ActCfg below hands act() its share in registers);
 //   level 2 (address depends on the action / header): the target node's 16-byte row, the re-imaging ring slot
 //           of this defender tick (list entries beyond the first 16 for large topologies come first), and the
 //           EIGHT loads from the topology's hot image — node record, source firewall word, authorisation word
 //           (indexed by triple id), the 64-byte vulnerability descriptor with the first four leak entries inline —
 //           through L1 / L2, fenced so that they go out together (leak entries 4..7: one more, wave-uniformly
-//           skipped, batch);
+//           skipped, batch, and not even tested for where the topology never leaks more than four entries: StepCfg::max_leak);
 //   ONE explicit wait for everything, in straight-line code; then pure register work and
 //   one round of stores (row, sets, list appends, header, outputs) with NO load behind any store: on gfx9 vector
 //   loads and stores retire in order on one counter, so a load behind a store waits for the write
@@ -151,6 +153,17 @@ struct NoHook {
     static constexpr bool kFinish = false;   // the hook runs after the step's stores (wrapper bookkeeping, auto-reset, streaming the observation)
 };
 
+// The config words of Lane::act(): where the hot image's sections start, the shape of its tables and the topology's largest leak
+// count.  step_body fetches them in its ONE pinned batch of scalar loads behind the level-1 vector loads and hands them over in
+// registers: read through the config pointer where act() uses them they were a scalar-memory round trip between level 1 and the
+// table loads, on every wavefront's critical path.
+struct ActCfg {
+    uint32_t hot_node, hot_desc, hot_payload, hot_auth, auth_words, LR, P, max_leak;
+    static __device__ __forceinline__ ActCfg of(const StepCfg& C) {
+        return ActCfg{C.hot_node, C.hot_desc, C.hot_payload, C.hot_auth, C.auth_words, C.L + C.R, C.P, C.max_leak};
+    }
+};
+
 // ------------------------------ per-lane working set ------------------------------
 template <int WT>
 struct Lane {
@@ -184,8 +197,9 @@ struct Lane {
     // packed batches: the two halves of the env's lists word (discovery order / credential cache as nibbles, zero at and past the counts);
     // act() appends to them in registers, step_body stores the word back, the fused wrapper step hands it to its observation stage
     uint64_t ldisc = 0, lcred = 0;
+    ActCfg A = {0u, 0u, 0u, 0u, 1u, 0u, 0u, 0xFFFFFFFFu};   // set by whoever builds the lane, before NS() / act()
 
-    __device__ __forceinline__ const HotNode* NS(uint32_t n) const { return reinterpret_cast<const HotNode*>(tb + C.hot_node) + n; }
+    __device__ __forceinline__ const HotNode* NS(uint32_t n) const { return reinterpret_cast<const HotNode*>(tb + A.hot_node) + n; }
     __device__ __forceinline__ Row* row(uint32_t n) const { return reinterpret_cast<Row*>(body + S.off_rows) + n; }
     __device__ __forceinline__ uint8_t* disc_list() const { return body + S.off_disc; }
     __device__ __forceinline__ uint16_t* cred_list() const { return reinterpret_cast<uint16_t*>(body + S.off_cred); }
@@ -220,8 +234,8 @@ struct Lane {
         const uint64_t t_props = (uint64_t)t0.x | ((uint64_t)t0.y << 32);
         const int t_value = (int)t0.z;
         const uint32_t src_fw_out = NS(src)->fw_out_allow;
-        const uint64_t auth = reinterpret_cast<const uint64_t*>(tb + C.hot_auth)[(tgt * C.P + port) * C.auth_words + (triple >> 6)];
-        const uint4* dp = reinterpret_cast<const uint4*>(tb + C.hot_desc + (tgt * (C.L + C.R) + col) * (uint32_t)sizeof(HotDesc));
+        const uint64_t auth = reinterpret_cast<const uint64_t*>(tb + A.hot_auth)[(tgt * A.P + port) * A.auth_words + (triple >> 6)];
+        const uint4* dp = reinterpret_cast<const uint4*>(tb + A.hot_desc + (tgt * A.LR + col) * (uint32_t)sizeof(HotDesc));
         const uint4 d0 = dp[0], d1 = dp[1];   // {cost lo,hi, probe lo,hi} {payload_off, cnt | tt << 16, kind | level << 8 | slot << 16, -}
         const uint4 d2 = dp[2], d3 = dp[3];   // the first four payload entries {node | cred << 16, triple | port << 16} x 2, x 2
         __builtin_amdgcn_sched_barrier(0);    // all eight table loads go out together: left alone, the scheduler sinks the descriptor's
@@ -306,7 +320,7 @@ struct Lane {
         ever |= sb; since |= sb;
         const bool creds = vk == MCBS_OUT_LEAKED_CREDENTIALS;
         const uint32_t cnt = (xb & (creds | (vk == MCBS_OUT_LEAKED_NODES))) ? (d1.y & 0xFFFFu) : 0u;
-        const uint2* pl = reinterpret_cast<const uint2*>(tb + C.hot_payload) + d1.x;
+        const uint2* pl = reinterpret_cast<const uint2*>(tb + A.hot_payload) + d1.x;
         uint32_t nn = 0, nc = 0, ncache = 0;
         const bool wide = WIDE_OK && S.wide != 0u;       // uniform: the cached-triple set lives in memory, staged in LDS for the loop
         const bool stage = wide && cnt != 0u && creds;
@@ -314,12 +328,16 @@ struct Lane {
             for (uint32_t w = 0; w < S.TW; ++w) wide_lds[w * wide_stride] = S.cach[(size_t)w * S.E + e];
         // The first four entries came with the descriptor; entries 4..7 are fetched now, before the first store (a load behind a store
         // waits for the store's write acknowledgement), wave-uniformly skipped when no lane has that many; longer lists: the tail loop.
+        // A.max_leak (the topology's largest payload count, found on the host) bounds all three with ONE scalar test each: Chain-10
+        // and ToyCtf never leak more than one entry per action, and walked four ballot tests here and one per rung below for nothing.
         constexpr uint32_t PF = 8;
         uint2 pre[PF] = {make_uint2(d2.x, d2.y), make_uint2(d2.z, d2.w), make_uint2(d3.x, d3.y), make_uint2(d3.z, d3.w),
                          make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u)};
+        if (A.max_leak > 4u) {
 #pragma unroll
-        for (uint32_t i = 4; i < PF; ++i)
-            if (__ballot(i < cnt)) pre[i] = pl[i < cnt ? i : 0u];
+            for (uint32_t i = 4; i < PF; ++i)
+                if (__ballot(i < cnt)) pre[i] = pl[i < cnt ? i : 0u];
+        }
         // Every load of the step has been issued by now and the stores start below.  Wait for ALL of them here, in straight-line code:
         // the leak entries run under divergent control flow, and a wait the compiler has to place INSIDE it (it cannot prove that an
         // entry's operands have landed) is `s_waitcnt vmcnt(0)` with the previous entry's stores in flight — a write-acknowledgement
@@ -354,10 +372,11 @@ struct Lane {
         };
 #pragma unroll
         for (uint32_t i = 0; i < PF; ++i) {
-            if (!__ballot(i < cnt)) break;
+            if (i >= A.max_leak || !__ballot(i < cnt)) break;
             if (i < cnt) leak(pre[i]);
         }
-        for (uint32_t i = PF; i < cnt; ++i) leak(pl[i]);
+        if (A.max_leak > PF)
+            for (uint32_t i = PF; i < cnt; ++i) leak(pl[i]);
         if (stage)
             for (uint32_t w = 0; w < S.TW; ++w) S.cach[(size_t)w * S.E + e] = wide_lds[w * wide_stride];
         rx += 5 * (int)nn + 3 * (int)nc;
@@ -577,12 +596,16 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
     unsigned long long g_reward = __double_as_longlong(C.goal_reward), g_low = __double_as_longlong(C.goal_low_availability),
                        g_sla = __double_as_longlong(C.maintain_sla),
                        g_win = __double_as_longlong(C.winning_reward), g_lose = __double_as_longlong(C.losing_reward);
+    // ... and the config words of act() and of the reset test behind the step's last store (ActCfg)
+    uint32_t a_node = C.hot_node, a_desc = C.hot_desc, a_payload = C.hot_payload, a_auth = C.hot_auth, a_aw = C.auth_words, a_leak = C.max_leak,
+             g_image = C.init_image_ok;
     uint32_t g_has = C.has_attacker_goal, g_own = C.goal_own_atleast, g_evict = C.defender_goal_eviction, g_auto = C.auto_reset, g_max = C.max_episode_steps,
              g_pctmin = C.goal_own_pct_min;
     if (PHASE != 1)
         asm volatile("" : "+s"(cL), "+s"(cR), "+s"(cP), "+s"(g_reward), "+s"(g_low), "+s"(g_pctmin), "+s"(g_sla), "+s"(g_win), "+s"(g_lose), "+s"(g_has),
-                          "+s"(g_own), "+s"(g_evict), "+s"(g_auto), "+s"(g_max));
-    else asm volatile("" : "+s"(cL), "+s"(cR), "+s"(cP));
+                          "+s"(g_own), "+s"(g_evict), "+s"(g_auto), "+s"(g_max), "+s"(g_image), "+s"(a_node), "+s"(a_desc), "+s"(a_payload),
+                          "+s"(a_auth), "+s"(a_aw), "+s"(a_leak));
+    else asm volatile("" : "+s"(cL), "+s"(cR), "+s"(cP), "+s"(a_node), "+s"(a_desc), "+s"(a_payload), "+s"(a_auth), "+s"(a_aw), "+s"(a_leak));
     if (!TOPO_LDS) tb = T.hot;
     if (TOPO_LDS && it == 0u) {                         // cooperative copy of the hot topology image, 16 bytes per lane
         const uint4* src = reinterpret_cast<const uint4*>(T.hot);
@@ -623,6 +646,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
 #pragma unroll
         for (int w = 0; w < WT; ++w) ln.m[k][w] = m0[k][w];
     ln.ere_blob = T.base;
+    ln.A = ActCfg{a_node, a_desc, a_payload, a_auth, a_aw, cL + cR, cP, a_leak};
     if (PK) { ln.ldisc = (uint64_t)lists0.x | ((uint64_t)lists0.y << 32); ln.lcred = (uint64_t)lists0.z | ((uint64_t)lists0.w << 32); }
     if (!PK && S.wide) {                                // this lane's LDS column for the wide cached-triple set, behind the hot image
         ln.wide_lds = reinterpret_cast<uint64_t*>(topo_lds + (TOPO_LDS ? C.hot_bytes / 16u : 0u)) + threadIdx.x;
@@ -788,7 +812,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
     }
     }
     STAMP(5);              // all stores of the step retired
-    if (PHASE != 1 && PK && C.init_image_ok) {
+    if (PHASE != 1 && PK && g_image) {
         // Packed batches: an env that just ended is re-initialised by its OWN lane with stores only — the body's reset image (<= 16 x 16
         // bytes), the sets, the lists word and the header come from the config through the scalar cache, the episode counter was fetched at level 1.
         // (Round 2 let the whole wavefront copy the image from memory behind a fence, like the large layouts below: with ~1 % of the
