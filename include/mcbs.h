@@ -460,6 +460,35 @@ int  mcbs_masked_categorical_packed(const mcbs_batch*, const uint32_t* bits, siz
                                     int32_t dtype, size_t row_stride, int32_t mode, int64_t* actions, float* log_prob, float* entropy,
                                     uint32_t* n_allowed, const float* uniforms, uint64_t seed, uint64_t step, uint32_t* bad_actions, void* stream);
 
+/* ---- masked categorical head: gradient — the backward pass of EVALUATE on stored rows, one launch ----
+ * What autograd gives for the composite `where(mask, logits, -1e8)` -> Categorical -> log_prob(actions) and the entropy with the masked
+ * terms zeroed, differentiated with respect to the logits, from the allowed logits alone.  Packed form only (gradients are taken at
+ * update time, on stored rows): bits, bits_row_words, n_rows, logits, dtype, row_stride and actions are those of
+ * mcbs_masked_categorical_packed in EVALUATE mode; the batch only supplies the device and A, every defender kind is served; n_rows == 0
+ * is a no-op.
+ *   grad_log_prob  float [n] or NULL: g_lp, the incoming gradient of log_prob[i]; NULL = all zeros
+ *   grad_entropy   float [n] or NULL: g_H, the incoming gradient of entropy[i]; NULL = all zeros
+ *   grad_logits    [n, grad_row_stride] in the dtype of logits, grad_row_stride in elements, >= A; any alignment.  WRITE-ONLY: every
+ *                  element [i, 0 .. A) is written exactly once (the caller need not clear it), elements from A up to grad_row_stride are
+ *                  never written.  bfloat16 output is the float32 value rounded to nearest even.
+ * For the allowed set S of row i: K, m, Z, log Z and H = the entropy are exactly the forward's (the same sums in the same order, the same
+ * device code), c = actions[i],  p_a = exp(x_a - m) * (1 / Z),  log p_a = (x_a - m) - log Z.
+ *   a in S:       grad_logits[i, a] = p_a * (-g_lp - g_H * (log p_a + H)) + (a == c ? g_lp : 0); the product term is exactly 0 where
+ *                 exp(x_a - m) underflows to 0 (the forward's rule: (-inf) * 0 is no term)
+ *   a not in S:   exactly +0.0, also when a == c: the composite's `where` passes no gradient to a masked logit (a chosen action that is
+ *                 not allowed still contributes -g_lp * p_a to the allowed ones)
+ *   K == 0 (all-zero packed row) or c outside [0, A): the whole row is +0.0 (the forward has returned NaN for such a c and counted it; the
+ *                 gradient call counts nothing)
+ * float32 arithmetic throughout in a fixed order, no floating-point atomics: two calls give bit-identical output, and it does not depend on
+ * the alignment or the strides of the rows.  logits is READ-ONLY; the value of a logit under a clear mask bit never reaches any output
+ * (whole 16-byte groups of logits may be loaded).
+ * MCBS_EINVAL: bits, logits, actions or grad_logits NULL (the uniform law has no gradient); a dtype other than MCBS_LOGITS_F32 / _BF16;
+ * bits_row_words < W; row_stride < A or grad_row_stride < A; the grad_logits rows overlap the logits rows (rows of equal stride interleaved
+ * in one buffer are accepted; with different strides the two extents may not intersect at all). */
+int  mcbs_masked_categorical_grad(const mcbs_batch*, const uint32_t* bits, size_t bits_row_words, uint64_t n_rows, const void* logits,
+                                  int32_t dtype, size_t row_stride, const int64_t* actions, const float* grad_log_prob,
+                                  const float* grad_entropy, void* grad_logits, size_t grad_row_stride, void* stream);
+
 /* ---- feature encoder: observation rows -> the float rows a policy's first layer takes, one launch ----
  * What Stable-Baselines3's "MultiInputPolicy" (marlon/baseline_models/ppo/train.py:79) does first with the wrappers' Dict observation
  * (preprocess_obs + CombinedExtractor): a Discrete(n) becomes a one-hot of n, every element of a MultiDiscrete a one-hot of its own, a

@@ -19,6 +19,7 @@
 #include "mcbs_logits.hip"
 #include "mcbs_packed_mask.hip"
 #include "mcbs_categorical.hip"
+#include "mcbs_categorical_grad.hip"
 #include "mcbs_features.hip"
 #include "mcbs_wrapper_fused.hip"
 
@@ -1381,6 +1382,58 @@ extern "C" int mcbs_masked_categorical_packed(const mcbs_batch* b, const uint32_
     CatIO io{logits, row_stride, actions, log_prob, entropy, n_allowed, uniforms, bad_actions, seed, step, 0ull, n_rows, (uint32_t)mode, G.A};
     categorical_launch(b, false, G, bits, bits_row_words, dtype, io, (hipStream_t)stream);
     return launch_ok("masked categorical (packed)");
+}
+
+// do rows [p, p + k * stride + A) and [q, q + k * qstride + A) (k < n, bytes) share a byte?  Exact for equal strides (rows interleaved in one
+// buffer are fine), conservative otherwise: then any intersection of the two extents counts
+static bool rows_overlap(uintptr_t p, size_t stride, uintptr_t q, size_t qstride, uint64_t n, size_t row_bytes) {
+    const uintptr_t pe = p + (uintptr_t)((n - 1u) * stride + row_bytes), qe = q + (uintptr_t)((n - 1u) * qstride + row_bytes);
+    if (pe <= q || qe <= p) return false;
+    if (stride != qstride || n == 1u) return true;
+    const size_t r = (size_t)((q >= p ? q - p : stride - (p - q) % stride) % stride);       // q's rows lie r bytes behind p's, modulo the stride
+    return r < row_bytes || stride - r < row_bytes;
+}
+
+extern "C" int mcbs_masked_categorical_grad(const mcbs_batch* b, const uint32_t* bits, size_t bits_row_words, uint64_t n_rows, const void* logits,
+                                            int32_t dtype, size_t row_stride, const int64_t* actions, const float* grad_log_prob,
+                                            const float* grad_entropy, void* grad_logits, size_t grad_row_stride, void* stream) {
+    if (!b) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    int rc;
+    LogitsGeom G;
+    if ((rc = discrete_geom(b, G))) return rc;
+    const uint32_t A = G.A, W = (A + 31u) / 32u;
+    if (n_rows == 0) return MCBS_OK;
+    if (!bits || !logits || !actions || !grad_logits)
+        return fail(MCBS_EINVAL, "mcbs_masked_categorical_grad: bits, logits, actions and grad_logits must not be NULL (the uniform law has no gradient)");
+    if (dtype != MCBS_LOGITS_F32 && dtype != MCBS_LOGITS_BF16) return fail(MCBS_EINVAL, "mcbs_masked_categorical_grad: logits dtype must be MCBS_LOGITS_F32 or MCBS_LOGITS_BF16");
+    if (bits_row_words < W) return fail(MCBS_EINVAL, "bits_row_words %zu is shorter than the %u words of %u Discrete actions", bits_row_words, W, A);
+    if (row_stride < A) return fail(MCBS_EINVAL, "mcbs_masked_categorical_grad: row_stride %zu is shorter than the %u Discrete actions", row_stride, A);
+    if (grad_row_stride < A) return fail(MCBS_EINVAL, "mcbs_masked_categorical_grad: grad_row_stride %zu is shorter than the %u Discrete actions", grad_row_stride, A);
+    const size_t es = dtype == MCBS_LOGITS_F32 ? 4u : 2u;
+    const uintptr_t lp = reinterpret_cast<uintptr_t>(logits), gp = reinterpret_cast<uintptr_t>(grad_logits);
+    if (rows_overlap(lp, row_stride * es, gp, grad_row_stride * es, n_rows, (size_t)A * es))
+        return fail(MCBS_EINVAL, "mcbs_masked_categorical_grad: the grad_logits rows overlap the logits rows");
+    const uint64_t blocks = (n_rows + 3u) / 4u;         // one wavefront per row, four per workgroup; the kernel strides over the rest
+    const dim3 grid(blocks < 65536u ? (uint32_t)blocks : 65536u), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    CatGradIO io{logits, row_stride, actions, grad_log_prob, grad_entropy, grad_logits, grad_row_stride, n_rows, A, 0u};
+    auto aligned = [&](uintptr_t p, size_t stride, size_t gb) { return p % gb == 0 && (stride * es) % gb == 0; };
+#define MCBS_CAT_GRAD_LAUNCH(LT_, GW_, VEC_)                                                                                 \
+    do {                                                                                                                     \
+        io.logits_vec = VEC_ && aligned(lp, row_stride, GW_ * sizeof(LT_));                                                  \
+        hipLaunchKernelGGL((masked_categorical_grad_kernel<LT_, GW_, VEC_>), grid, block, 0, st, bits, bits_row_words, io); \
+    } while (0)
+    if (dtype == MCBS_LOGITS_F32) {
+        if (aligned(gp, grad_row_stride, 16)) MCBS_CAT_GRAD_LAUNCH(float, 4u, true);
+        else MCBS_CAT_GRAD_LAUNCH(float, 4u, false);
+    } else {
+        if (aligned(gp, grad_row_stride, 16)) MCBS_CAT_GRAD_LAUNCH(uint16_t, 8u, true);
+        else if (aligned(gp, grad_row_stride, 8)) MCBS_CAT_GRAD_LAUNCH(uint16_t, 4u, true);     // rows only 8-byte aligned (Chain-10: 14 172 actions)
+        else MCBS_CAT_GRAD_LAUNCH(uint16_t, 4u, false);
+    }
+#undef MCBS_CAT_GRAD_LAUNCH
+    return launch_ok("masked categorical gradient");
 }
 
 // ------------------------------------------------------------------ feature encoder

@@ -69,46 +69,49 @@ __device__ __forceinline__ V cat_wave_scan(V v, uint32_t lane) {            // i
     return v;
 }
 
-template <typename LT, bool LIVE>
-__global__ __launch_bounds__(256) void masked_categorical_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, const ObsDigest* __restrict__ digest,
-                                                                 LogitsGeom G, const uint32_t* __restrict__ bits, size_t bits_row_words, CatIO io) {
-    __shared__ uint32_t c_word[4][CAT_CACHE];
-    __shared__ float c_sum[4][CAT_CACHE];
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t A = io.A, W = (A + 31u) / 32u;
-    const uint32_t tail = (A & 31u) ? (1u << (A & 31u)) - 1u : ~0u;        // word W-1: bits from A on are ignored, not trusted to be zero
-    const LT* L = static_cast<const LT*>(io.logits);
-    uint32_t* cw = c_word[wv];
-    float* cs = c_sum[wv];
-    for (uint64_t i = (uint64_t)blockIdx.x * 4u + wv; i < io.n_rows; i += (uint64_t)gridDim.x * 4u) {     // wave-uniform
-        const LT* row = L ? L + i * io.row_stride : nullptr;
-        // the mask's source: the env's digest (uniform per wavefront: scalar loads) or the row's stored words
-        const ObsDigest d = LIVE ? digest[i] : ObsDigest{};
-        const uint32_t n_disc = d.blank ? 0u : d.n_disc, n_creds = d.n_creds;
-        const uint8_t* body = LIVE ? S.body + (size_t)i * S.body_stride : nullptr;
-        const mcbs_node_static* NS = LIVE ? reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node) : nullptr;
-        const uint64_t pp = LIVE ? digest_cred_pattern(G, n_creds) : 0ull;
-        const uint32_t* brow = LIVE ? nullptr : bits + i * bits_row_words;
-        auto fetch = [&](uint32_t w) -> uint32_t {       // word w of the row's mask (0 beyond W)
-            if (w >= W) return 0u;
-            uint32_t m;
-            if constexpr (LIVE) m = digest_mask_word(S, d, G, NS, body, (uint32_t)i, n_disc, n_creds, pp, w); else m = brow[w];
-            return w == W - 1u ? m & tail : m;
-        };
-        auto word_of = [&](uint32_t w) -> uint32_t { return w < CAT_CACHE ? cw[w] : fetch(w); };          // sweeps 2 and 3 (w = block + lane: the branch is wave-uniform)
-        // per-word sums of sweep 2, bits in ascending order
-        auto word_sums = [&](uint32_t w, uint32_t word, float m, float& s, float& t) {
-            s = 0.f; t = 0.f;
-            for (uint32_t rest = word; rest; rest &= rest - 1u) {
-                const float d = cat_logit(row, w * 32u + (uint32_t)__builtin_ctz(rest)) - m;
-                const float ex = expf(d);
-                s += ex;
-                t += ex > 0.f ? d * ex : 0.f;            // (-inf) * 0 is no term of the entropy
-            }
-        };
+// The live form's source of a row's mask words: the env's digest (digest_mask_word, the words pack_mask_kernel stores; everything but w
+// is uniform per wavefront: scalar loads).  References to the kernel's own locals: nothing is copied.
+struct CatLive {
+    const DevState& S;
+    const ObsDigest& d;
+    const LogitsGeom& G;
+    const mcbs_node_static* NS;
+    const uint8_t* body;
+    uint32_t e, n_disc, n_creds;
+    uint64_t pp;
+};
 
-        // ---- sweep 1: K, the largest allowed logit and its lowest index, the last allowed action
+// One row as its wavefront sees it, and sweeps 1 and 2 over it: shared by masked_categorical_kernel and masked_categorical_grad_kernel
+// (mcbs_categorical_grad.hip), so that K, m, Z and the entropy sum of the backward pass are the forward's, bit for bit.
+template <typename LT, bool LIVE>
+struct CatRow {
+    const CatLive* lv;         // LIVE: the env's digest;  else
+    const uint32_t* brow;      // the row's stored packed words
+    const LT* row;             // the row's logits, or NULL (all-zero logits)
+    uint32_t W, tail, lane;    // tail: word W-1: bits from A on are ignored, not trusted to be zero
+    uint32_t* cw;              // the wavefront's LDS cache: the first CAT_CACHE mask words of the row ...
+    float* cs;                 // ... and their sums s_w
+
+    __device__ __forceinline__ uint32_t fetch(uint32_t w) const {       // word w of the row's mask (0 beyond W)
+        if (w >= W) return 0u;
+        uint32_t m;
+        if constexpr (LIVE) m = digest_mask_word(lv->S, lv->d, lv->G, lv->NS, lv->body, lv->e, lv->n_disc, lv->n_creds, lv->pp, w); else m = brow[w];
+        return w == W - 1u ? m & tail : m;
+    }
+    __device__ __forceinline__ uint32_t word_of(uint32_t w) const { return w < CAT_CACHE ? cw[w] : fetch(w); }     // after sweep 1
+    // per-word sums of sweep 2, bits in ascending order
+    __device__ __forceinline__ void word_sums(uint32_t w, uint32_t word, float m, float& s, float& t) const {
+        s = 0.f; t = 0.f;
+        for (uint32_t rest = word; rest; rest &= rest - 1u) {
+            const float d = cat_logit(row, w * 32u + (uint32_t)__builtin_ctz(rest)) - m;
+            const float ex = expf(d);
+            s += ex;
+            t += ex > 0.f ? d * ex : 0.f;            // (-inf) * 0 is no term of the entropy
+        }
+    }
+
+    // ---- sweep 1: K, the largest allowed logit and its lowest index, the last allowed action; fills the word cache
+    __device__ __forceinline__ void sweep1(float& m_out, uint32_t& arg_out, uint32_t& last_out, uint32_t& K) const {
         float m = 0.f;
         uint32_t arg = ~0u, last = 0u, cnt = 0u;
         for (uint32_t wb = 0; wb < W; wb += 64u) {
@@ -136,7 +139,53 @@ __global__ __launch_bounds__(256) void masked_categorical_kernel(DevState S, Top
             const uint32_t ol = (uint32_t)__shfl_xor((int)last, o);
             last = ol > last ? ol : last;
         }
-        const uint32_t K = cat_wave_sum(cnt);
+        m_out = m; arg_out = arg; last_out = last;
+        K = cat_wave_sum(cnt);
+    }
+
+    // ---- sweep 2 (row != NULL): Z and the entropy sum; fills the sum cache
+    __device__ __forceinline__ void sweep2(float m, float& Z_out, float& T_out) const {
+        float Z = 0.f, Tt = 0.f;
+        for (uint32_t wb = 0; wb < W; wb += 64u) {
+            const uint32_t w = wb + lane, word = word_of(w);
+            if (!__ballot(word != 0u)) continue;
+            float s, t;
+            word_sums(w, word, m, s, t);
+            if (wb < CAT_CACHE) cs[w] = s;
+            Z += __shfl(cat_wave_scan(s, lane), 63);
+            Tt += cat_wave_sum(t);
+        }
+        Z_out = Z; T_out = Tt;
+    }
+};
+
+template <typename LT, bool LIVE>
+__global__ __launch_bounds__(256) void masked_categorical_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, const ObsDigest* __restrict__ digest,
+                                                                 LogitsGeom G, const uint32_t* __restrict__ bits, size_t bits_row_words, CatIO io) {
+    __shared__ uint32_t c_word[4][CAT_CACHE];
+    __shared__ float c_sum[4][CAT_CACHE];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t A = io.A, W = (A + 31u) / 32u;
+    const uint32_t tail = (A & 31u) ? (1u << (A & 31u)) - 1u : ~0u;
+    const LT* L = static_cast<const LT*>(io.logits);
+    uint32_t* cw = c_word[wv];
+    float* cs = c_sum[wv];
+    for (uint64_t i = (uint64_t)blockIdx.x * 4u + wv; i < io.n_rows; i += (uint64_t)gridDim.x * 4u) {     // wave-uniform
+        const LT* row = L ? L + i * io.row_stride : nullptr;
+        // the mask's source: the env's digest (uniform per wavefront: scalar loads) or the row's stored words
+        const ObsDigest d = LIVE ? digest[i] : ObsDigest{};
+        const CatLive lv{S, d, G, LIVE ? reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node) : nullptr,
+                         LIVE ? S.body + (size_t)i * S.body_stride : nullptr, (uint32_t)i, d.blank ? 0u : d.n_disc, d.n_creds,
+                         LIVE ? digest_cred_pattern(G, d.n_creds) : 0ull};
+        const CatRow<LT, LIVE> R{&lv, LIVE ? nullptr : bits + i * bits_row_words, row, W, tail, lane, cw, cs};
+        auto fetch = [&](uint32_t w) { return R.fetch(w); };
+        auto word_of = [&](uint32_t w) { return R.word_of(w); };          // sweep 3 (w = block + lane: the branch is wave-uniform)
+        auto word_sums = [&](uint32_t w, uint32_t word, float m, float& s, float& t) { R.word_sums(w, word, m, s, t); };
+
+        float m;
+        uint32_t arg, last, K;
+        R.sweep1(m, arg, last, K);
 
         // the row's uniform number (SAMPLE)
         uint32_t u24 = 0u;
@@ -171,15 +220,7 @@ __global__ __launch_bounds__(256) void masked_categorical_kernel(DevState S, Top
             if (!row) {
                 Z = (float)K;
             } else {
-                for (uint32_t wb = 0; wb < W; wb += 64u) {
-                    const uint32_t w = wb + lane, word = word_of(w);
-                    if (!__ballot(word != 0u)) continue;
-                    float s, t;
-                    word_sums(w, word, m, s, t);
-                    if (wb < CAT_CACHE) cs[w] = s;
-                    Z += __shfl(cat_wave_scan(s, lane), 63);
-                    Tt += cat_wave_sum(t);
-                }
+                R.sweep2(m, Z, Tt);
             }
             const float logZ = cat_log(Z);
             ent = logZ - Tt / Z;

@@ -1,0 +1,152 @@
+// mcbs_categorical_grad.hip — the backward pass of the masked categorical head (include/mcbs.h "masked categorical head: gradient").
+//
+// MaskablePPO's update differentiates log_prob(actions) and the masked entropy of `Categorical(logits=where(mask, logits, -1e8))` with
+// respect to the logits.  With p the softmax over the ALLOWED actions S, H the entropy, c the chosen action and g_lp, g_H the incoming
+// gradients of the row:
+//   a in S:      grad[a] = p_a * (-g_lp - g_H * (log p_a + H)) + (a == c ? g_lp : 0)
+//   a not in S:  grad[a] = +0.0     (the composite's `where` passes nothing to a masked logit, chosen or not)
+// so the kernel reads the packed mask and the logits under set bits, as the forward does, and writes n * A * sizeof(dtype) bytes: a write
+// stream with the store pattern of apply_packed_kernel.
+//
+// One WAVEFRONT per row (four per workgroup, grid-striding over the rows).
+//   Phase A  sweeps 1 and 2 of masked_categorical_kernel (CatRow: the same code, so K, m, Z, log Z and H are the forward's bit for bit); the
+//            row's mask words stay in the wavefront's LDS cache.
+//   Phase B  the row in groups of GW elements = one vector store, spans of 64 groups starting on 128-byte lines of memory.  Every element
+//            below A is written exactly once: an all-masked group is one vector store of zeros, a group with allowed actions is built in
+//            registers (the logits found in L2; a whole 16-byte load where the logits rows are aligned like the gradient's, else one load
+//            per set bit) and stored whole.  The row's last, partial group and rows whose base or stride is not aligned to the group
+//            (VEC = false) are stored element by element.  A logit under a clear bit may be loaded but is dropped by a select before any
+//            arithmetic reaches an output.
+// fp32 throughout, no atomics, nothing depends on the launch geometry: two calls give bit-identical output, whatever the alignment.
+#pragma once
+#include "mcbs_categorical.hip"
+
+namespace mcbs {
+
+struct CatGradIO {
+    const void* logits;        // [n, row_stride]
+    size_t row_stride;
+    const int64_t* actions;
+    const float* g_lp;         // nullable: all zeros
+    const float* g_ent;        // nullable: all zeros
+    void* grad;                // [n, grad_stride], the dtype of logits
+    size_t grad_stride;
+    uint64_t n_rows;
+    uint32_t A;
+    uint32_t logits_vec;       // the logits rows are aligned to the gradient's groups: whole-group loads
+};
+
+__device__ __forceinline__ uint32_t cat_grad_bits(float v, const float*) { return __float_as_uint(v); }
+__device__ __forceinline__ uint32_t cat_grad_bits(float v, const uint16_t*) {      // float -> bfloat16, round to nearest even
+    const uint32_t u = __float_as_uint(v);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;                // NaN stays NaN
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+template <typename LT, uint32_t GW, bool VEC>
+__global__ __launch_bounds__(256) void masked_categorical_grad_kernel(const uint32_t* __restrict__ bits, size_t bits_row_words, CatGradIO io) {
+    constexpr uint32_t NWORD = GW * (uint32_t)sizeof(LT) / 4u;      // dwords per group: 4 or 2
+    static_assert(NWORD == 4u || NWORD == 2u, "group = 16 or 8 bytes");
+    static_assert(32u % GW == 0u, "a group's bits lie in one word");
+    constexpr uint32_t ALL = (1u << GW) - 1u;
+    constexpr uint32_t GB = GW * (uint32_t)sizeof(LT);
+    __shared__ uint32_t c_word[4][CAT_CACHE];
+    __shared__ float c_sum[4][CAT_CACHE];
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t A = io.A, W = (A + 31u) / 32u;
+    const uint32_t tail = (A & 31u) ? (1u << (A & 31u)) - 1u : ~0u;
+    const LT* L = static_cast<const LT*>(io.logits);
+    LT* Gr = static_cast<LT*>(io.grad);
+    for (uint64_t i = (uint64_t)blockIdx.x * 4u + wv; i < io.n_rows; i += (uint64_t)gridDim.x * 4u) {     // wave-uniform
+        const LT* row = L + i * io.row_stride;
+        LT* out = Gr + i * io.grad_stride;
+        const CatRow<LT, false> R{nullptr, bits + i * bits_row_words, row, W, tail, lane, c_word[wv], c_sum[wv]};
+        __builtin_amdgcn_wave_barrier();                 // (the previous row's cached words may still be in use by other lanes)
+
+        // ---- phase A: the forward's K, m, Z, log Z and H
+        float m;
+        uint32_t arg, last, K;
+        R.sweep1(m, arg, last, K);
+        const int64_t act = io.actions[i];
+        const bool live = K != 0u && act >= 0 && act < (int64_t)A;      // else the whole row is +0.0
+        const uint32_t c = (uint32_t)act;
+        const float g_lp = io.g_lp ? io.g_lp[i] : 0.f, g_H = io.g_ent ? io.g_ent[i] : 0.f;
+        float rZ = 0.f, logZ = 0.f, H = 0.f;
+        if (live) {
+            float Z, Tt;
+            R.sweep2(m, Z, Tt);
+            logZ = cat_log(Z);
+            H = logZ - Tt / Z;
+            rZ = 1.0f / Z;
+        }
+        // the words cached by sweep 1 are read by other lanes below
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+
+        // gradient of allowed action a with logit x
+        auto value = [&](uint32_t a, float x) -> float {
+            const float d = x - m;
+            const float ex = expf(d);
+            const float lq = d - logZ;
+            const float prod = ex > 0.f ? (ex * rZ) * (-g_lp - g_H * (lq + H)) : 0.f;      // (-inf) * 0 is no term
+            return (a == c ? g_lp : 0.f) + prod;
+        };
+
+        // ---- phase B
+        const uint32_t sh = VEC ? (uint32_t)((reinterpret_cast<uintptr_t>(out) / GB) % (128u / GB)) : 0u;
+        const uint32_t nspan = ((A + GW - 1u) / GW + sh + 63u) / 64u;
+        for (uint32_t j = 0; j < nspan; ++j) {
+            const uint32_t g = j * 64u + lane;           // the span: groups [64 j - sh, 64 j + 64 - sh) of the row, clipped to [0, A)
+            const uint32_t a0 = (g - sh) * GW;
+            if (g < sh || a0 >= A) continue;             // the first span's head, the last span's tail
+            const uint32_t word = live ? R.word_of(a0 >> 5) : 0u;
+            const uint32_t in_row = a0 + GW <= A ? ALL : (1u << (A - a0)) - 1u;
+            const uint32_t on = (word >> (a0 & 31u)) & in_row;                          // bit k: action a0 + k is allowed
+            if (VEC && in_row == ALL) {
+                uint32_t v[NWORD];
+#pragma unroll
+                for (uint32_t k = 0; k < NWORD; ++k) v[k] = 0u;
+                if (on) {
+                    if (io.logits_vec) {
+                        uint32_t x[NWORD];
+                        if constexpr (NWORD == 4u) {
+                            const uint4 q = *reinterpret_cast<const uint4*>(row + a0);
+                            x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+                        } else {
+                            const uint2 q = *reinterpret_cast<const uint2*>(row + a0);
+                            x[0] = q.x; x[1] = q.y;
+                        }
+#pragma unroll
+                        for (uint32_t k = 0; k < GW; ++k) {
+                            float xf;
+                            if constexpr (sizeof(LT) == 4) xf = __uint_as_float(x[k]);
+                            else xf = __uint_as_float(((x[k >> 1] >> ((k & 1u) * 16u)) & 0xFFFFu) << 16);
+                            const uint32_t r = ((on >> k) & 1u) ? cat_grad_bits(value(a0 + k, xf), (const LT*)nullptr) : 0u;
+                            if constexpr (sizeof(LT) == 4) v[k] = r; else v[k >> 1] |= r << ((k & 1u) * 16u);
+                        }
+                    } else {
+#pragma unroll
+                        for (uint32_t k = 0; k < GW; ++k) {
+                            if (!((on >> k) & 1u)) continue;
+                            const uint32_t r = cat_grad_bits(value(a0 + k, cat_logit(row, a0 + k)), (const LT*)nullptr);
+                            if constexpr (sizeof(LT) == 4) v[k] = r; else v[k >> 1] |= r << ((k & 1u) * 16u);
+                        }
+                    }
+                }
+                if constexpr (NWORD == 4u) *reinterpret_cast<uint4*>(out + a0) = make_uint4(v[0], v[1], v[2], v[3]);
+                else *reinterpret_cast<uint2*>(out + a0) = make_uint2(v[0], v[1]);
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < GW; ++k) {
+                    if (!((in_row >> k) & 1u)) continue;
+                    const uint32_t r = ((on >> k) & 1u) ? cat_grad_bits(value(a0 + k, cat_logit(row, a0 + k)), (const LT*)nullptr) : 0u;
+                    if constexpr (sizeof(LT) == 4) out[a0 + k] = __uint_as_float(r); else out[a0 + k] = (uint16_t)r;
+                }
+            }
+        }
+    }
+}
+
+} // namespace mcbs

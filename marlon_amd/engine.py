@@ -28,7 +28,7 @@ EXPORTS = [
     "mcbs_attacker_wrapper_step_launches", "mcbs_set_mask_discrete_stride", "mcbs_defender_wrapper_step",
     "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant",
     "mcbs_feature_layout_create", "mcbs_feature_layout_destroy", "mcbs_feature_layout_width", "mcbs_encode_features",
-    "mcbs_masked_categorical", "mcbs_masked_categorical_packed",
+    "mcbs_masked_categorical", "mcbs_masked_categorical_packed", "mcbs_masked_categorical_grad",
 ]
 
 _lib = None
@@ -107,6 +107,9 @@ def load_library(path: Optional[str] = None):
             C.c_void_p, C.c_void_p]           # logits, dtype, row_stride, mode, actions, log_prob, entropy, n_allowed, uniforms, seed, step, bad_actions, stream
     lib.mcbs_masked_categorical.argtypes = [C.c_void_p] + _cat
     lib.mcbs_masked_categorical_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64] + _cat
+    # bits, bits_row_words, n_rows, logits, dtype, row_stride, actions, grad_log_prob, grad_entropy, grad_logits, grad_row_stride, stream
+    lib.mcbs_masked_categorical_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcbs_copy_rows_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mcbs_attacker_wrapper_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -165,6 +168,39 @@ class FeatureLayoutHandle:
 MaskedCategorical = collections.namedtuple("MaskedCategorical", ["actions", "log_prob", "entropy", "n_allowed"])
 CATEGORICAL_MODES = {"sample": 0, "argmax": 1, "evaluate": 2}      # MCBS_CATEGORICAL_*
 CATEGORICAL_PHILOX_DOMAIN = 0xCA7E6041                              # MCBS_CATEGORICAL_PHILOX_DOMAIN
+
+_MASKED_EVALUATE = None
+
+
+def _masked_evaluate_function(torch):
+    """The torch.autograd.Function behind BatchEngine.masked_evaluate (made on first use: this module does not import torch at load)."""
+    global _MASKED_EVALUATE
+    if _MASKED_EVALUATE is not None:
+        return _MASKED_EVALUATE
+
+    class MaskedEvaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, logits, eng, bits, actions, bad_actions):
+            r = eng.masked_categorical(logits, bits=bits, mode="evaluate", actions=actions, bad_actions=bad_actions)
+            ctx.eng = eng
+            ctx.save_for_backward(logits, bits, actions)
+            ctx.mark_non_differentiable(r.n_allowed)
+            ctx.set_materialize_grads(False)             # an output the loss does not use arrives as None, not as zeros
+            return r.log_prob, r.entropy, r.n_allowed
+
+        @staticmethod
+        def backward(ctx, g_lp, g_ent, _g_k):
+            logits, bits, actions = ctx.saved_tensors
+            if not ctx.needs_input_grad[0]:
+                return None, None, None, None, None
+            grad = ctx.eng.masked_categorical_grad(logits, bits, actions,
+                                                   None if g_lp is None else g_lp.float().contiguous(),
+                                                   None if g_ent is None else g_ent.float().contiguous())
+            return grad, None, None, None, None
+
+    _MASKED_EVALUATE = MaskedEvaluate
+    return MaskedEvaluate
+
 
 FEATURE_FIELDS = ("scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel")
 
@@ -617,6 +653,54 @@ class BatchEngine:
             _check(self.lib, self.lib.mcbs_masked_categorical_packed(self._h, bits.data_ptr(), bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1]),
                                                                      n, *common), "mcbs_masked_categorical_packed")
         return MaskedCategorical(o_act, o_lp, o_ent, o_k)
+
+    def masked_categorical_grad(self, logits, bits, actions, grad_log_prob=None, grad_entropy=None, out=None):
+        """The backward pass of masked_categorical(bits=..., mode="evaluate") in one launch: the gradient with respect to `logits` of
+        log_prob(actions) and the entropy, given their incoming gradients grad_log_prob / grad_entropy (device float32 [n]; None = zeros).
+        logits float32 / bfloat16 [n, >= A], bits int32 [n, >= W], actions int64 [n] as in the forward.  out: a device tensor of the
+        logits' dtype [n, >= A] with contiguous rows that does not overlap logits, or None for a new [n, A] one; columns [0, A) are
+        written entirely (masked actions, all-zero rows and rows whose action lies outside [0, A): +0.0), columns from A on never.
+        -> grad_logits."""
+        t = self.torch
+        if not isinstance(bits, t.Tensor):
+            raise ValueError("bits must be a device int32 tensor [n, >= W] (the gradient exists in the packed form only)")
+        self._packed_rows(bits, "bits")
+        n = bits.shape[0]
+        A = self.discrete_action_count()
+        if not isinstance(logits, t.Tensor) or logits.dtype not in (t.float32, t.bfloat16):
+            raise ValueError("logits must be a float32 or bfloat16 tensor (the uniform law has no gradient)")
+        if logits.dim() != 2 or logits.shape[0] != n or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < A:
+            raise ValueError(f"logits must be a device tensor [{n}, >= {A}] with contiguous rows")
+
+        def vec(x, dtype, what):
+            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != (n,) or not x.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous device {dtype} tensor [{n}]")
+            return x
+
+        vec(actions, t.int64, "actions")
+        if grad_log_prob is not None:
+            vec(grad_log_prob, t.float32, "grad_log_prob")
+        if grad_entropy is not None:
+            vec(grad_entropy, t.float32, "grad_entropy")
+        if out is None:
+            out = t.empty((n, A), dtype=logits.dtype, device=self.device)
+        elif (not isinstance(out, t.Tensor) or out.dtype != logits.dtype or out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1
+              or out.device != self.device or out.shape[1] < A):
+            raise ValueError(f"out must be a device {logits.dtype} tensor [{n}, >= {A}] with contiguous rows")
+        if n:
+            stride = lambda x: x.stride(0) if n > 1 else max(x.stride(0), x.shape[1])
+            _check(self.lib, self.lib.mcbs_masked_categorical_grad(
+                self._h, bits.data_ptr(), stride(bits), n, logits.data_ptr(), 0 if logits.dtype == t.float32 else 1, stride(logits),
+                actions.data_ptr(), grad_log_prob.data_ptr() if grad_log_prob is not None else None,
+                grad_entropy.data_ptr() if grad_entropy is not None else None, out.data_ptr(), stride(out), self._stream()),
+                "mcbs_masked_categorical_grad")
+        return out
+
+    def masked_evaluate(self, logits, bits, actions, bad_actions=None) -> MaskedCategorical:
+        """masked_categorical(bits=..., mode="evaluate") as a node of torch's autograd graph: log_prob and entropy carry a graph into
+        `logits`, whose backward is masked_categorical_grad (one launch each way); actions and n_allowed are not differentiable."""
+        lp, ent, k = _masked_evaluate_function(self.torch).apply(logits, self, bits, actions, bad_actions)
+        return MaskedCategorical(actions, lp, ent, k)
 
     # -- feature encoder (include/mcbs.h): observation rows -> the one-hot float rows a policy's first layer takes --
     def feature_layout(self, layout) -> FeatureLayoutHandle:

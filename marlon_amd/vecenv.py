@@ -332,8 +332,8 @@ class MarlonVecEnv:
     def sample_masked_uniform(self, seed: int, step: int):
         return self.venv.sample_masked_uniform(seed, step)
 
-    def evaluate_masked(self, bits, logits, actions):
-        return self.venv.evaluate_masked(bits, logits, actions)
+    def evaluate_masked(self, bits, logits, actions, differentiable: bool = False):
+        return self.venv.evaluate_masked(bits, logits, actions, differentiable=differentiable)
 
     def get_attr(self, attr_name: str, indices=None) -> List[Any]:
         val = getattr(self.venv, attr_name)

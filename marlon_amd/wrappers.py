@@ -199,10 +199,16 @@ class AttackerVecEnv:
         sample_masked with no logits at all."""
         return self.sample_masked(None, seed, step, uniforms=uniforms, out=out)
 
-    def evaluate_masked(self, bits, logits, actions, bad_actions=None, out=None):
+    def evaluate_masked(self, bits, logits, actions, bad_actions=None, out=None, differentiable: bool = False):
         """MaskablePPO's evaluate_actions for stored rows: log_prob of `actions` [n] and the entropy under logits [n, >= A] and the stored
         packed masks bits [n, >= W] (action_masks_packed), any n.  The log_prob of an action sample_masked drew under the same mask and
-        logits comes back bit for bit."""
+        logits comes back bit for bit.  differentiable=True: the same numbers, and log_prob and entropy carry an autograd graph into
+        `logits` (engine.masked_evaluate: the backward pass is one launch of mcbs_masked_categorical_grad); out= cannot be combined
+        with it."""
+        if differentiable:
+            if out is not None:
+                raise ValueError("evaluate_masked(differentiable=True) allocates its outputs: out= is not supported")
+            return self.engine.masked_evaluate(logits, bits, actions, bad_actions=bad_actions)
         return self.engine.masked_categorical(logits, bits=bits, mode="evaluate", actions=actions, bad_actions=bad_actions, out=out)
 
     # -- the policy's input features (marlon_amd/features.py, mcbs_encode_features) --
