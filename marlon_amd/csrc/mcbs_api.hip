@@ -7,6 +7,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <string>
+#include <type_traits>
 #include <vector>
 
 #include "mcbs.h"
@@ -1211,20 +1213,65 @@ static int digest_usable(const mcbs_batch* b, const char* who) {
     return MCBS_OK;
 }
 
-static int discrete_geom(const mcbs_batch* b, LogitsGeom& G) {
+// A Discrete actions and W mask words per row, as every row-shaped entry point sees the batch (one launch indexes actions in 32 bits)
+static int discrete_dims(const mcbs_batch* b, uint32_t& A, uint32_t& W) {
     const uint64_t A64 = mcbs_discrete_action_count(b);
     if (A64 >= (1ull << 31)) return fail(MCBS_ELIMIT, "Discrete action space too large for one launch");
+    A = (uint32_t)A64; W = (A + 31u) / 32u;
+    return MCBS_OK;
+}
+
+// The caller's rows hold the batch's Discrete space: `words` dwords per row of packed bits, `stride` elements per row of logits-shaped
+// values, each named as the entry point's messages name it; a NULL name skips that check
+static int rows_hold(uint32_t A, const char* words_name, size_t words, const char* stride_name, size_t stride) {
+    const uint32_t W = (A + 31u) / 32u;
+    if (words_name && words < W) return fail(MCBS_EINVAL, "%s %zu is shorter than the %u words of %u Discrete actions", words_name, words, W, A);
+    if (stride_name && stride < A) return fail(MCBS_EINVAL, "%s %zu is shorter than the %u Discrete actions", stride_name, stride, A);
+    return MCBS_OK;
+}
+
+static int discrete_geom(const mcbs_batch* b, LogitsGeom& G) {
+    uint32_t W;
+    int rc;
+    if ((rc = discrete_dims(b, G.A, W))) return rc;
     G.N = b->cfg.maximum_node_count; G.C = b->cfg.maximum_total_credentials; G.L = b->C.L; G.R = b->C.R; G.RL = b->C.P * G.C;
-    G.M = G.N * G.N * G.RL; G.ML = G.N * G.L; G.A = (uint32_t)A64;
+    G.M = G.N * G.N * G.RL; G.ML = G.N * G.L;
     G.dRL = fast_div_host(G.RL); G.dC = fast_div_host(G.C); G.dN = fast_div_host(G.N); G.dL = fast_div_host(G.L); G.dR = fast_div_host(G.R);
     return MCBS_OK;
 }
 
-static uint16_t bf16_fill(float fill) {                  // float -> bfloat16, round to nearest even
-    uint32_t bits;
-    memcpy(&bits, &fill, 4);
-    return (bits & 0x7FFFFFFFu) > 0x7F800000u ? (uint16_t)((bits >> 16) | 0x40u) : (uint16_t)((bits + 0x7FFFu + ((bits >> 16) & 1u)) >> 16);
+// One wavefront per row, four per workgroup along grid.x, at most `cap` workgroups: the kernels loop over rows beyond 4 * grid.x
+// (gridDim.x * blockDim.x must stay below 2^32), so n_rows is not limited by the launch.  Very long rows split their `chunks` of 64
+// pieces over grid.y.
+static dim3 rows_grid(uint64_t n_rows, uint32_t cap, uint32_t chunks = 1u) {
+    const uint64_t blocks = (n_rows + 3u) / 4u;
+    return dim3(blocks < cap ? (uint32_t)blocks : cap, chunks < 64u ? chunks : 64u);
 }
+
+template <uint32_t N> using GroupWidth = std::integral_constant<uint32_t, N>;
+
+// The store group of a row-writing kernel (mcbs_rowstore.h) from what the rows allow: the widest of 16, 8 and 4 bytes that both the
+// base pointer and the row stride are multiples of and that holds at least MIN_GW elements, as one vector store; else groups of
+// MIN_GW elements stored one by one.  launch(ES, GW, VEC) gets the element size, the group width and the vector flag as
+// std::integral_constant, so each caller instantiates exactly the kernels this ladder can pick.
+template <uint32_t ES, uint32_t MIN_GW, typename Launch>
+static void rows_dispatch_sized(const void* base, size_t row_stride, Launch&& launch) {
+    const uintptr_t p0 = reinterpret_cast<uintptr_t>(base);
+    const size_t rb = row_stride * ES;
+    constexpr std::integral_constant<uint32_t, ES> es{};
+    if (rb % 16 == 0 && p0 % 16 == 0) return launch(es, GroupWidth<16u / ES>{}, std::true_type{});
+    if constexpr (8u / ES >= MIN_GW) if (rb % 8 == 0 && p0 % 8 == 0) return launch(es, GroupWidth<8u / ES>{}, std::true_type{});      // rows only 8-byte aligned (Chain-10: 14 172 bf16 actions)
+    if constexpr (4u / ES >= MIN_GW && MIN_GW > 1u) if (rb % 4 == 0 && p0 % 4 == 0) return launch(es, GroupWidth<4u / ES>{}, std::true_type{});
+    launch(es, GroupWidth<MIN_GW>{}, std::bool_constant<MIN_GW == 1u>{});       // (a group of one element is its own vector store)
+}
+// elem_size 4 or 2 bytes; MIN_GW32 / MIN_GW16: the narrowest group of the caller's kernels for either
+template <uint32_t MIN_GW32, uint32_t MIN_GW16, typename Launch>
+static void rows_dispatch(size_t elem_size, const void* base, size_t row_stride, Launch&& launch) {
+    if (elem_size == 4u) rows_dispatch_sized<4u, MIN_GW32>(base, row_stride, launch);
+    else rows_dispatch_sized<2u, MIN_GW16>(base, row_stride, launch);
+}
+template <uint32_t ES> using LogitsElem = std::conditional_t<ES == 4u, float, uint16_t>;       // logits rows: fp32, or bf16 patterns
+template <uint32_t ES> static LogitsElem<ES> logits_fill(float fill) { if constexpr (ES == 4u) return fill; else return (uint16_t)bf16_bits(fill); }
 
 extern "C" int mcbs_mask_logits(mcbs_batch* b, void* logits, int32_t dtype, size_t row_stride, float fill, void* stream) {
     if (!b || !logits) return fail(MCBS_EINVAL, "null argument");
@@ -1234,26 +1281,16 @@ extern "C" int mcbs_mask_logits(mcbs_batch* b, void* logits, int32_t dtype, size
     if ((rc = digest_usable(b, "mcbs_mask_logits"))) return rc;
     LogitsGeom G;
     if ((rc = discrete_geom(b, G))) return rc;
-    if (row_stride < G.A) return fail(MCBS_EINVAL, "row_stride %zu is shorter than the %u Discrete actions", row_stride, G.A);
+    if ((rc = rows_hold(G.A, nullptr, 0, "row_stride", row_stride))) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const uintptr_t p0 = reinterpret_cast<uintptr_t>(logits);
     // one wavefront per env, four per workgroup; very large action spaces split their chunks of 64 spans over grid.x
     auto grid_for = [&](uint32_t gw) { const uint32_t chunks = (((G.A + gw - 1u) / gw + 15u + 63u) / 64u + 63u) / 64u;   /* spans are shifted by up to 15 groups */ return dim3(chunks < 64u ? chunks : 64u, (b->S.E + 3u) / 4u); };
-    const dim3 block(256);
-#define MCBS_LOGITS_LAUNCH(LT_, GW_, VEC_, PTR_, FILL_) \
-    hipLaunchKernelGGL((mask_logits_kernel<LT_, GW_, VEC_>), grid_for(GW_), block, 0, st, b->S, b->T, b->C_dev, b->digest, PTR_, row_stride, FILL_, G)
-    if (dtype == MCBS_LOGITS_F32) {
-        float* lp = static_cast<float*>(logits);
-        if ((row_stride * 4) % 16 == 0 && p0 % 16 == 0) MCBS_LOGITS_LAUNCH(float, 4u, true, lp, fill);
-        else MCBS_LOGITS_LAUNCH(float, 4u, false, lp, fill);
-    } else {
-        const uint16_t f16 = bf16_fill(fill);
-        uint16_t* lp = static_cast<uint16_t*>(logits);
-        if ((row_stride * 2) % 16 == 0 && p0 % 16 == 0) MCBS_LOGITS_LAUNCH(uint16_t, 8u, true, lp, f16);
-        else if ((row_stride * 2) % 8 == 0 && p0 % 8 == 0) MCBS_LOGITS_LAUNCH(uint16_t, 4u, true, lp, f16);     // rows only 8-byte aligned (Chain-10: 14 172 actions)
-        else MCBS_LOGITS_LAUNCH(uint16_t, 4u, false, lp, f16);
-    }
-#undef MCBS_LOGITS_LAUNCH
+    rows_dispatch<4u, 4u>(dtype == MCBS_LOGITS_F32 ? 4u : 2u, logits, row_stride, [&](auto es, auto gw, auto vec) {
+        using LT = LogitsElem<decltype(es)::value>;
+        constexpr uint32_t GW = decltype(gw)::value;
+        hipLaunchKernelGGL((mask_logits_kernel<LT, GW, decltype(vec)::value>), grid_for(GW), dim3(256), 0, st, b->S, b->T, b->C_dev, b->digest,
+                           static_cast<LT*>(logits), row_stride, logits_fill<decltype(es)::value>(fill), G);
+    });
     return launch_ok("mask logits");
 }
 
@@ -1265,18 +1302,9 @@ extern "C" int mcbs_pack_action_mask(mcbs_batch* b, uint32_t* bits, size_t row_w
     if ((rc = digest_usable(b, "mcbs_pack_action_mask"))) return rc;
     LogitsGeom G;
     if ((rc = discrete_geom(b, G))) return rc;
-    const uint32_t W = (G.A + 31u) / 32u;
-    if (row_words < W) return fail(MCBS_EINVAL, "row_words %zu is shorter than the %u words of %u Discrete actions", row_words, W, G.A);
+    if ((rc = rows_hold(G.A, "row_words", row_words, nullptr, 0))) return rc;
     hipLaunchKernelGGL(pack_mask_kernel, dim3((b->S.E + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, b->S, b->T, b->C_dev, b->digest, bits, row_words, G);
     return launch_ok("pack action mask");
-}
-
-// rows of the two caller-side kernels: one wavefront per row, four per workgroup along grid.x; the kernels loop over rows beyond
-// 4 * grid.x (gridDim.x * blockDim.x must stay below 2^32), so n_rows is not limited by the launch
-static dim3 packed_rows_grid(uint64_t n_rows, uint32_t pieces) {
-    const uint64_t blocks = (n_rows + 3u) / 4u;
-    const uint32_t chunks = (pieces + 63u) / 64u;       // very long rows split their pieces over grid.y
-    return dim3(blocks < 65536u ? (uint32_t)blocks : 65536u, chunks < 64u ? chunks : 64u);
 }
 
 extern "C" int mcbs_apply_packed_mask(const mcbs_batch* b, const uint32_t* bits, size_t bits_row_words, void* logits, int32_t dtype,
@@ -1284,32 +1312,19 @@ extern "C" int mcbs_apply_packed_mask(const mcbs_batch* b, const uint32_t* bits,
     if (!b || !bits || !logits) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
     if (dtype != MCBS_LOGITS_F32 && dtype != MCBS_LOGITS_BF16) return fail(MCBS_EINVAL, "logits dtype must be MCBS_LOGITS_F32 or MCBS_LOGITS_BF16");
-    const uint64_t A64 = mcbs_discrete_action_count(b);
-    if (A64 >= (1ull << 31)) return fail(MCBS_ELIMIT, "Discrete action space too large for one launch");
-    const uint32_t A = (uint32_t)A64, W = (A + 31u) / 32u;
-    if (bits_row_words < W) return fail(MCBS_EINVAL, "bits_row_words %zu is shorter than the %u words of %u Discrete actions", bits_row_words, W, A);
-    if (logits_row_stride < A) return fail(MCBS_EINVAL, "logits_row_stride %zu is shorter than the %u Discrete actions", logits_row_stride, A);
+    uint32_t A, W;
+    int rc;
+    if ((rc = discrete_dims(b, A, W))) return rc;
+    if ((rc = rows_hold(A, "bits_row_words", bits_row_words, "logits_row_stride", logits_row_stride))) return rc;
     if (n_rows == 0) return MCBS_OK;
     hipStream_t st = (hipStream_t)stream;
-    const uintptr_t p0 = reinterpret_cast<uintptr_t>(logits);
-    const dim3 block(256);
-#define MCBS_APPLY_LAUNCH(LT_, GW_, VEC_, PTR_, FILL_)                                                                               \
-    do {                                                                                                                             \
-        const dim3 grid = packed_rows_grid(n_rows, ((A + GW_ - 1u) / GW_ + 31u + 63u) / 64u);   /* spans shifted by < 32 groups */      \
-        hipLaunchKernelGGL((apply_packed_kernel<LT_, GW_, VEC_>), grid, block, 0, st, bits, bits_row_words, PTR_, logits_row_stride, n_rows, FILL_, A); \
-    } while (0)
-    if (dtype == MCBS_LOGITS_F32) {
-        float* lp = static_cast<float*>(logits);
-        if ((logits_row_stride * 4) % 16 == 0 && p0 % 16 == 0) MCBS_APPLY_LAUNCH(float, 4u, true, lp, fill);
-        else MCBS_APPLY_LAUNCH(float, 4u, false, lp, fill);
-    } else {
-        const uint16_t f16 = bf16_fill(fill);
-        uint16_t* lp = static_cast<uint16_t*>(logits);
-        if ((logits_row_stride * 2) % 16 == 0 && p0 % 16 == 0) MCBS_APPLY_LAUNCH(uint16_t, 8u, true, lp, f16);
-        else if ((logits_row_stride * 2) % 8 == 0 && p0 % 8 == 0) MCBS_APPLY_LAUNCH(uint16_t, 4u, true, lp, f16);
-        else MCBS_APPLY_LAUNCH(uint16_t, 4u, false, lp, f16);
-    }
-#undef MCBS_APPLY_LAUNCH
+    rows_dispatch<4u, 4u>(dtype == MCBS_LOGITS_F32 ? 4u : 2u, logits, logits_row_stride, [&](auto es, auto gw, auto vec) {
+        using LT = LogitsElem<decltype(es)::value>;
+        constexpr uint32_t GW = decltype(gw)::value;
+        const dim3 grid = rows_grid(n_rows, 65536u, (((A + GW - 1u) / GW + 31u + 63u) / 64u + 63u) / 64u);   /* spans shifted by < 32 groups */
+        hipLaunchKernelGGL((apply_packed_kernel<LT, GW, decltype(vec)::value>), grid, dim3(256), 0, st, bits, bits_row_words, static_cast<LT*>(logits),
+                           logits_row_stride, n_rows, logits_fill<decltype(es)::value>(fill), A);
+    });
     return launch_ok("apply packed mask");
 }
 
@@ -1317,13 +1332,12 @@ extern "C" int mcbs_unpack_action_mask(const mcbs_batch* b, const uint32_t* bits
                                        uint64_t n_rows, void* stream) {
     if (!b || !bits || !out) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
-    const uint64_t A64 = mcbs_discrete_action_count(b);
-    if (A64 >= (1ull << 31)) return fail(MCBS_ELIMIT, "Discrete action space too large for one launch");
-    const uint32_t A = (uint32_t)A64, W = (A + 31u) / 32u;
-    if (bits_row_words < W) return fail(MCBS_EINVAL, "bits_row_words %zu is shorter than the %u words of %u Discrete actions", bits_row_words, W, A);
-    if (out_row_stride < A) return fail(MCBS_EINVAL, "out_row_stride %zu is shorter than the %u Discrete actions", out_row_stride, A);
+    uint32_t A, W;
+    int rc;
+    if ((rc = discrete_dims(b, A, W))) return rc;
+    if ((rc = rows_hold(A, "bits_row_words", bits_row_words, "out_row_stride", out_row_stride))) return rc;
     if (n_rows == 0) return MCBS_OK;
-    hipLaunchKernelGGL(unpack_mask_kernel, packed_rows_grid(n_rows, (A + 15u + 15u) / 16u), dim3(256), 0, (hipStream_t)stream, bits, bits_row_words, out, out_row_stride, n_rows, A);
+    hipLaunchKernelGGL(unpack_mask_kernel, rows_grid(n_rows, 65536u, ((A + 15u + 15u) / 16u + 63u) / 64u), dim3(256), 0, (hipStream_t)stream, bits, bits_row_words, out, out_row_stride, n_rows, A);
     return launch_ok("unpack action mask");
 }
 
@@ -1335,14 +1349,12 @@ static int categorical_args(const char* who, const void* logits, int32_t dtype, 
     if (mode != MCBS_CATEGORICAL_SAMPLE && mode != MCBS_CATEGORICAL_ARGMAX && mode != MCBS_CATEGORICAL_EVALUATE)
         return fail(MCBS_EINVAL, "%s: mode must be MCBS_CATEGORICAL_SAMPLE, _ARGMAX or _EVALUATE", who);
     if (!actions || !log_prob) return fail(MCBS_EINVAL, "%s: actions and log_prob must not be NULL", who);
-    if (logits && row_stride < A) return fail(MCBS_EINVAL, "%s: row_stride %zu is shorter than the %u Discrete actions", who, row_stride, A);
-    return MCBS_OK;
+    return logits ? rows_hold(A, nullptr, 0, (std::string(who) + ": row_stride").c_str(), row_stride) : MCBS_OK;
 }
 
 static void categorical_launch(const mcbs_batch* b, bool live, const LogitsGeom& G, const uint32_t* bits, size_t bits_row_words, int32_t dtype,
                                const CatIO& io, hipStream_t st) {
-    const uint64_t blocks = (io.n_rows + 3u) / 4u;      // one wavefront per row, four per workgroup; the kernel strides over the rest
-    const dim3 grid(blocks < 65536u ? (uint32_t)blocks : 65536u), block(256);
+    const dim3 grid = rows_grid(io.n_rows, 65536u), block(256);
 #define MCBS_CAT_LAUNCH(LT_, LIVE_) \
     hipLaunchKernelGGL((masked_categorical_kernel<LT_, LIVE_>), grid, block, 0, st, b->S, b->T, b->C_dev, b->digest, G, bits, bits_row_words, io)
     if (dtype == MCBS_LOGITS_BF16 && io.logits) { if (live) MCBS_CAT_LAUNCH(uint16_t, true); else MCBS_CAT_LAUNCH(uint16_t, false); }
@@ -1374,10 +1386,9 @@ extern "C" int mcbs_masked_categorical_packed(const mcbs_batch* b, const uint32_
     int rc;
     LogitsGeom G;
     if ((rc = discrete_geom(b, G))) return rc;
-    const uint32_t W = (G.A + 31u) / 32u;
     if (n_rows == 0) return MCBS_OK;
     if (!bits) return fail(MCBS_EINVAL, "mcbs_masked_categorical_packed: bits must not be NULL");
-    if (bits_row_words < W) return fail(MCBS_EINVAL, "bits_row_words %zu is shorter than the %u words of %u Discrete actions", bits_row_words, W, G.A);
+    if ((rc = rows_hold(G.A, "bits_row_words", bits_row_words, nullptr, 0))) return rc;
     if ((rc = categorical_args("mcbs_masked_categorical_packed", logits, dtype, row_stride, mode, actions, log_prob, G.A))) return rc;
     CatIO io{logits, row_stride, actions, log_prob, entropy, n_allowed, uniforms, bad_actions, seed, step, 0ull, n_rows, (uint32_t)mode, G.A};
     categorical_launch(b, false, G, bits, bits_row_words, dtype, io, (hipStream_t)stream);
@@ -1402,37 +1413,26 @@ extern "C" int mcbs_masked_categorical_grad(const mcbs_batch* b, const uint32_t*
     int rc;
     LogitsGeom G;
     if ((rc = discrete_geom(b, G))) return rc;
-    const uint32_t A = G.A, W = (A + 31u) / 32u;
+    const uint32_t A = G.A;
     if (n_rows == 0) return MCBS_OK;
     if (!bits || !logits || !actions || !grad_logits)
         return fail(MCBS_EINVAL, "mcbs_masked_categorical_grad: bits, logits, actions and grad_logits must not be NULL (the uniform law has no gradient)");
     if (dtype != MCBS_LOGITS_F32 && dtype != MCBS_LOGITS_BF16) return fail(MCBS_EINVAL, "mcbs_masked_categorical_grad: logits dtype must be MCBS_LOGITS_F32 or MCBS_LOGITS_BF16");
-    if (bits_row_words < W) return fail(MCBS_EINVAL, "bits_row_words %zu is shorter than the %u words of %u Discrete actions", bits_row_words, W, A);
-    if (row_stride < A) return fail(MCBS_EINVAL, "mcbs_masked_categorical_grad: row_stride %zu is shorter than the %u Discrete actions", row_stride, A);
-    if (grad_row_stride < A) return fail(MCBS_EINVAL, "mcbs_masked_categorical_grad: grad_row_stride %zu is shorter than the %u Discrete actions", grad_row_stride, A);
+    if ((rc = rows_hold(A, "bits_row_words", bits_row_words, "mcbs_masked_categorical_grad: row_stride", row_stride))) return rc;
+    if ((rc = rows_hold(A, nullptr, 0, "mcbs_masked_categorical_grad: grad_row_stride", grad_row_stride))) return rc;
     const size_t es = dtype == MCBS_LOGITS_F32 ? 4u : 2u;
     const uintptr_t lp = reinterpret_cast<uintptr_t>(logits), gp = reinterpret_cast<uintptr_t>(grad_logits);
     if (rows_overlap(lp, row_stride * es, gp, grad_row_stride * es, n_rows, (size_t)A * es))
         return fail(MCBS_EINVAL, "mcbs_masked_categorical_grad: the grad_logits rows overlap the logits rows");
-    const uint64_t blocks = (n_rows + 3u) / 4u;         // one wavefront per row, four per workgroup; the kernel strides over the rest
-    const dim3 grid(blocks < 65536u ? (uint32_t)blocks : 65536u), block(256);
     hipStream_t st = (hipStream_t)stream;
     CatGradIO io{logits, row_stride, actions, grad_log_prob, grad_entropy, grad_logits, grad_row_stride, n_rows, A, 0u};
-    auto aligned = [&](uintptr_t p, size_t stride, size_t gb) { return p % gb == 0 && (stride * es) % gb == 0; };
-#define MCBS_CAT_GRAD_LAUNCH(LT_, GW_, VEC_)                                                                                 \
-    do {                                                                                                                     \
-        io.logits_vec = VEC_ && aligned(lp, row_stride, GW_ * sizeof(LT_));                                                  \
-        hipLaunchKernelGGL((masked_categorical_grad_kernel<LT_, GW_, VEC_>), grid, block, 0, st, bits, bits_row_words, io); \
-    } while (0)
-    if (dtype == MCBS_LOGITS_F32) {
-        if (aligned(gp, grad_row_stride, 16)) MCBS_CAT_GRAD_LAUNCH(float, 4u, true);
-        else MCBS_CAT_GRAD_LAUNCH(float, 4u, false);
-    } else {
-        if (aligned(gp, grad_row_stride, 16)) MCBS_CAT_GRAD_LAUNCH(uint16_t, 8u, true);
-        else if (aligned(gp, grad_row_stride, 8)) MCBS_CAT_GRAD_LAUNCH(uint16_t, 4u, true);     // rows only 8-byte aligned (Chain-10: 14 172 actions)
-        else MCBS_CAT_GRAD_LAUNCH(uint16_t, 4u, false);
-    }
-#undef MCBS_CAT_GRAD_LAUNCH
+    rows_dispatch<4u, 4u>(es, grad_logits, grad_row_stride, [&](auto esc, auto gw, auto vec) {
+        using LT = LogitsElem<decltype(esc)::value>;
+        constexpr size_t gb = decltype(gw)::value * sizeof(LT);
+        io.logits_vec = decltype(vec)::value && lp % gb == 0 && (row_stride * es) % gb == 0;     // the logits rows are aligned like the gradient's
+        hipLaunchKernelGGL((masked_categorical_grad_kernel<LT, decltype(gw)::value, decltype(vec)::value>), rows_grid(n_rows, 65536u), dim3(256), 0, st,
+                           bits, bits_row_words, io);
+    });
     return launch_ok("masked categorical gradient");
 }
 
@@ -1553,34 +1553,21 @@ extern "C" int mcbs_encode_features(const mcbs_batch* b, const mcbs_feature_layo
     hipStream_t st = (hipStream_t)stream;
     // one wavefront per row, four per workgroup, rows beyond one grid's worth in a loop: about eight workgroups per CU keep the
     // descriptor table's trip into LDS a small share of a workgroup's life
-    const uint64_t blocks = (n_rows + 3u) / 4u;
-    const dim3 grid(blocks < 2048u ? (uint32_t)blocks : 2048u), block(256);
+    const dim3 grid = rows_grid(n_rows, 2048u), block(256);
     // the per-element kernel when its LDS fits (element table + four wavefronts' one-hot rows and bit words), else column by column from memory
     const size_t item = dtype == MCBS_FEATURES_F32 ? 4u : 2u, per = 16u / item;
     const size_t lds = (((size_t)G.V + 1u) / 2u + 4u * (((size_t)G.n_desc + per - 1u) / per + ((size_t)G.W + 3u) / 4u)) * 16u;
     const bool rows_kernel = l->elems_dev && lds <= 48u * 1024u;
-    const uintptr_t p0 = reinterpret_cast<uintptr_t>(out);
-#define MCBS_FEAT_LAUNCH(T_, GW_, VEC_, ONE_)                                                                                                \
-    do {                                                                                                                                     \
-        if (rows_kernel) hipLaunchKernelGGL((encode_features_rows_kernel<T_, GW_, VEC_>), grid, block, lds, st, G, src, l->elems_dev, bits,   \
-                                            bits_row_words, static_cast<T_*>(out), out_row_stride, n_rows, (T_)(ONE_), out_of_range);         \
-        else hipLaunchKernelGGL((encode_features_kernel<T_, GW_, VEC_>), grid, block, 0, st, G, src, l->desc_dev, bits,                \
-                                bits_row_words, static_cast<T_*>(out), out_row_stride, n_rows, (T_)(ONE_), out_of_range);                     \
-    } while (0)
-    if (dtype == MCBS_FEATURES_F32) {
-        const size_t rb = out_row_stride * 4u;
-        if (rb % 16 == 0 && p0 % 16 == 0) MCBS_FEAT_LAUNCH(uint32_t, 4u, true, 0x3F800000u);
-        else if (rb % 8 == 0 && p0 % 8 == 0) MCBS_FEAT_LAUNCH(uint32_t, 2u, true, 0x3F800000u);
-        else MCBS_FEAT_LAUNCH(uint32_t, 1u, true, 0x3F800000u);
-    } else {
-        const uint32_t one = dtype == MCBS_FEATURES_BF16 ? 0x3F80u : 0x3C00u;
-        const size_t rb = out_row_stride * 2u;
-        if (rb % 16 == 0 && p0 % 16 == 0) MCBS_FEAT_LAUNCH(uint16_t, 8u, true, one);
-        else if (rb % 8 == 0 && p0 % 8 == 0) MCBS_FEAT_LAUNCH(uint16_t, 4u, true, one);
-        else if (rb % 4 == 0 && p0 % 4 == 0) MCBS_FEAT_LAUNCH(uint16_t, 2u, true, one);
-        else MCBS_FEAT_LAUNCH(uint16_t, 2u, false, one);
-    }
-#undef MCBS_FEAT_LAUNCH
+    const uint32_t one = dtype == MCBS_FEATURES_F32 ? 0x3F800000u : dtype == MCBS_FEATURES_BF16 ? 0x3F80u : 0x3C00u;      // 1.0 as the dtype's pattern
+    rows_dispatch<1u, 2u>(item, out, out_row_stride, [&](auto es, auto gw, auto vec) {
+        using T = std::conditional_t<decltype(es)::value == 4u, uint32_t, uint16_t>;
+        constexpr uint32_t GW = decltype(gw)::value;
+        constexpr bool VEC = decltype(vec)::value;
+        if (rows_kernel) hipLaunchKernelGGL((encode_features_rows_kernel<T, GW, VEC>), grid, block, lds, st, G, src, l->elems_dev, bits,
+                                            bits_row_words, static_cast<T*>(out), out_row_stride, n_rows, (T)one, out_of_range);
+        else hipLaunchKernelGGL((encode_features_kernel<T, GW, VEC>), grid, block, 0, st, G, src, l->desc_dev, bits,
+                                bits_row_words, static_cast<T*>(out), out_row_stride, n_rows, (T)one, out_of_range);
+    });
     return launch_ok("encode features");
 }
 

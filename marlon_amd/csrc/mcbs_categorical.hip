@@ -8,7 +8,7 @@
 //
 // One WAVEFRONT per row (four independent ones per workgroup, grid-striding over the rows).  Lane k owns mask words k, k + 64, ... of
 // the row: the stored packed words (one coalesced load per 64 words) or, in the live form, the words rebuilt from the env's digest
-// (digest_mask_word, the words pack_mask_kernel stores).  Three sweeps over the words, blocks of 64 words without any set bit skipped
+// (DigestMask::word, the words pack_mask_kernel stores).  Three sweeps over the words, blocks of 64 words without any set bit skipped
 // by a ballot:
 //   1  K = number of set bits, m = the largest allowed logit and its lowest index (a gather of the logits under the set bits)
 //   2  per word s_w = sum of exp(x - m) and t_w = sum of (x - m) exp(x - m), bits in ascending order; per block of 64 words an
@@ -69,23 +69,11 @@ __device__ __forceinline__ V cat_wave_scan(V v, uint32_t lane) {            // i
     return v;
 }
 
-// The live form's source of a row's mask words: the env's digest (digest_mask_word, the words pack_mask_kernel stores; everything but w
-// is uniform per wavefront: scalar loads).  References to the kernel's own locals: nothing is copied.
-struct CatLive {
-    const DevState& S;
-    const ObsDigest& d;
-    const LogitsGeom& G;
-    const mcbs_node_static* NS;
-    const uint8_t* body;
-    uint32_t e, n_disc, n_creds;
-    uint64_t pp;
-};
-
 // One row as its wavefront sees it, and sweeps 1 and 2 over it: shared by masked_categorical_kernel and masked_categorical_grad_kernel
 // (mcbs_categorical_grad.hip), so that K, m, Z and the entropy sum of the backward pass are the forward's, bit for bit.
 template <typename LT, bool LIVE>
 struct CatRow {
-    const CatLive* lv;         // LIVE: the env's digest;  else
+    const DigestMask* lv;      // LIVE: the env's digest as a mask (uniform per wavefront: scalar loads);  else
     const uint32_t* brow;      // the row's stored packed words
     const LT* row;             // the row's logits, or NULL (all-zero logits)
     uint32_t W, tail, lane;    // tail: word W-1: bits from A on are ignored, not trusted to be zero
@@ -95,7 +83,7 @@ struct CatRow {
     __device__ __forceinline__ uint32_t fetch(uint32_t w) const {       // word w of the row's mask (0 beyond W)
         if (w >= W) return 0u;
         uint32_t m;
-        if constexpr (LIVE) m = digest_mask_word(lv->S, lv->d, lv->G, lv->NS, lv->body, lv->e, lv->n_disc, lv->n_creds, lv->pp, w); else m = brow[w];
+        if constexpr (LIVE) m = lv->word(w); else m = brow[w];
         return w == W - 1u ? m & tail : m;
     }
     __device__ __forceinline__ uint32_t word_of(uint32_t w) const { return w < CAT_CACHE ? cw[w] : fetch(w); }     // after sweep 1
@@ -175,9 +163,7 @@ __global__ __launch_bounds__(256) void masked_categorical_kernel(DevState S, Top
         const LT* row = L ? L + i * io.row_stride : nullptr;
         // the mask's source: the env's digest (uniform per wavefront: scalar loads) or the row's stored words
         const ObsDigest d = LIVE ? digest[i] : ObsDigest{};
-        const CatLive lv{S, d, G, LIVE ? reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node) : nullptr,
-                         LIVE ? S.body + (size_t)i * S.body_stride : nullptr, (uint32_t)i, d.blank ? 0u : d.n_disc, d.n_creds,
-                         LIVE ? digest_cred_pattern(G, d.n_creds) : 0ull};
+        const DigestMask lv = LIVE ? DigestMask::make(S, T, Cp, d, G, (uint32_t)i, 32u) : DigestMask{S, G, d, nullptr, nullptr, 0u, 0u, 0u, 0ull};
         const CatRow<LT, LIVE> R{&lv, LIVE ? nullptr : bits + i * bits_row_words, row, W, tail, lane, cw, cs};
         auto fetch = [&](uint32_t w) { return R.fetch(w); };
         auto word_of = [&](uint32_t w) { return R.word_of(w); };          // sweep 3 (w = block + lane: the branch is wave-uniform)

@@ -6,19 +6,18 @@
 //   a in S:      grad[a] = p_a * (-g_lp - g_H * (log p_a + H)) + (a == c ? g_lp : 0)
 //   a not in S:  grad[a] = +0.0     (the composite's `where` passes nothing to a masked logit, chosen or not)
 // so the kernel reads the packed mask and the logits under set bits, as the forward does, and writes n * A * sizeof(dtype) bytes: a write
-// stream with the store pattern of apply_packed_kernel.
+// stream with the store side of mcbs_rowstore.h.
 //
 // One WAVEFRONT per row (four per workgroup, grid-striding over the rows).
 //   Phase A  sweeps 1 and 2 of masked_categorical_kernel (CatRow: the same code, so K, m, Z, log Z and H are the forward's bit for bit); the
 //            row's mask words stay in the wavefront's LDS cache.
-//   Phase B  the row in groups of GW elements = one vector store, spans of 64 groups starting on 128-byte lines of memory.  Every element
-//            below A is written exactly once: an all-masked group is one vector store of zeros, a group with allowed actions is built in
-//            registers (the logits found in L2; a whole 16-byte load where the logits rows are aligned like the gradient's, else one load
-//            per set bit) and stored whole.  The row's last, partial group and rows whose base or stride is not aligned to the group
-//            (VEC = false) are stored element by element.  A logit under a clear bit may be loaded but is dropped by a select before any
-//            arithmetic reaches an output.
+//   Phase B  the row in groups of GW elements (mcbs_rowstore.h).  Every element below A is written exactly once: a group is built in
+//            registers, zeros under clear bits (the logits found in L2; a whole 16-byte load where the logits rows are aligned like the
+//            gradient's, else one load per set bit), and stored whole, or element by element (store_group).  A logit under a clear bit
+//            may be loaded but is dropped by a select before any arithmetic reaches an output.
 // fp32 throughout, no atomics, nothing depends on the launch geometry: two calls give bit-identical output, whatever the alignment.
 #pragma once
+#include <type_traits>
 #include "mcbs_categorical.hip"
 
 namespace mcbs {
@@ -36,20 +35,16 @@ struct CatGradIO {
     uint32_t logits_vec;       // the logits rows are aligned to the gradient's groups: whole-group loads
 };
 
-__device__ __forceinline__ uint32_t cat_grad_bits(float v, const float*) { return __float_as_uint(v); }
-__device__ __forceinline__ uint32_t cat_grad_bits(float v, const uint16_t*) {      // float -> bfloat16, round to nearest even
-    const uint32_t u = __float_as_uint(v);
-    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;                // NaN stays NaN
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
-}
-
 template <typename LT, uint32_t GW, bool VEC>
 __global__ __launch_bounds__(256) void masked_categorical_grad_kernel(const uint32_t* __restrict__ bits, size_t bits_row_words, CatGradIO io) {
-    constexpr uint32_t NWORD = GW * (uint32_t)sizeof(LT) / 4u;      // dwords per group: 4 or 2
-    static_assert(NWORD == 4u || NWORD == 2u, "group = 16 or 8 bytes");
+    using RG = RowGroups<LT, GW, VEC>;
+    constexpr uint32_t NWORD = RG::NWORD, ALL = RG::ALL;
     static_assert(32u % GW == 0u, "a group's bits lie in one word");
-    constexpr uint32_t ALL = (1u << GW) - 1u;
-    constexpr uint32_t GB = GW * (uint32_t)sizeof(LT);
+    using PT = std::conditional_t<sizeof(LT) == 4, uint32_t, uint16_t>;      // an element of the gradient as its bit pattern
+    auto pattern = [](float v) -> PT {
+        if constexpr (sizeof(LT) == 4) return __float_as_uint(v);
+        else return (PT)bf16_bits(v);
+    };
     __shared__ uint32_t c_word[4][CAT_CACHE];
     __shared__ float c_sum[4][CAT_CACHE];
     const uint32_t lane = threadIdx.x & 63u;
@@ -95,56 +90,40 @@ __global__ __launch_bounds__(256) void masked_categorical_grad_kernel(const uint
         };
 
         // ---- phase B
-        const uint32_t sh = VEC ? (uint32_t)((reinterpret_cast<uintptr_t>(out) / GB) % (128u / GB)) : 0u;
-        const uint32_t nspan = ((A + GW - 1u) / GW + sh + 63u) / 64u;
+        const uint32_t sh = RG::shift(out);
+        const uint32_t nspan = RG::nspan(A, sh);
         for (uint32_t j = 0; j < nspan; ++j) {
-            const uint32_t g = j * 64u + lane;           // the span: groups [64 j - sh, 64 j + 64 - sh) of the row, clipped to [0, A)
-            const uint32_t a0 = (g - sh) * GW;
-            if (g < sh || a0 >= A) continue;             // the first span's head, the last span's tail
+            const uint32_t g = j * 64u + lane;
+            const uint32_t a0 = RG::a0(g, sh);
+            if (RG::outside(g, sh, A)) continue;
             const uint32_t word = live ? R.word_of(a0 >> 5) : 0u;
-            const uint32_t in_row = a0 + GW <= A ? ALL : (1u << (A - a0)) - 1u;
+            const uint32_t in_row = RG::in_row(a0, A);
             const uint32_t on = (word >> (a0 & 31u)) & in_row;                          // bit k: action a0 + k is allowed
-            if (VEC && in_row == ALL) {
-                uint32_t v[NWORD];
+            PT v[GW];
 #pragma unroll
-                for (uint32_t k = 0; k < NWORD; ++k) v[k] = 0u;
-                if (on) {
-                    if (io.logits_vec) {
-                        uint32_t x[NWORD];
-                        if constexpr (NWORD == 4u) {
-                            const uint4 q = *reinterpret_cast<const uint4*>(row + a0);
-                            x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-                        } else {
-                            const uint2 q = *reinterpret_cast<const uint2*>(row + a0);
-                            x[0] = q.x; x[1] = q.y;
-                        }
-#pragma unroll
-                        for (uint32_t k = 0; k < GW; ++k) {
-                            float xf;
-                            if constexpr (sizeof(LT) == 4) xf = __uint_as_float(x[k]);
-                            else xf = __uint_as_float(((x[k >> 1] >> ((k & 1u) * 16u)) & 0xFFFFu) << 16);
-                            const uint32_t r = ((on >> k) & 1u) ? cat_grad_bits(value(a0 + k, xf), (const LT*)nullptr) : 0u;
-                            if constexpr (sizeof(LT) == 4) v[k] = r; else v[k >> 1] |= r << ((k & 1u) * 16u);
-                        }
-                    } else {
-#pragma unroll
-                        for (uint32_t k = 0; k < GW; ++k) {
-                            if (!((on >> k) & 1u)) continue;
-                            const uint32_t r = cat_grad_bits(value(a0 + k, cat_logit(row, a0 + k)), (const LT*)nullptr);
-                            if constexpr (sizeof(LT) == 4) v[k] = r; else v[k >> 1] |= r << ((k & 1u) * 16u);
-                        }
-                    }
+            for (uint32_t k = 0; k < GW; ++k) v[k] = 0u;
+            if (VEC && in_row == ALL && on && io.logits_vec) {
+                uint32_t x[NWORD];
+                if constexpr (NWORD == 4u) {
+                    const uint4 q = *reinterpret_cast<const uint4*>(row + a0);
+                    x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
+                } else {
+                    const uint2 q = *reinterpret_cast<const uint2*>(row + a0);
+                    x[0] = q.x; x[1] = q.y;
                 }
-                if constexpr (NWORD == 4u) *reinterpret_cast<uint4*>(out + a0) = make_uint4(v[0], v[1], v[2], v[3]);
-                else *reinterpret_cast<uint2*>(out + a0) = make_uint2(v[0], v[1]);
-            } else {
 #pragma unroll
                 for (uint32_t k = 0; k < GW; ++k) {
-                    if (!((in_row >> k) & 1u)) continue;
-                    const uint32_t r = ((on >> k) & 1u) ? cat_grad_bits(value(a0 + k, cat_logit(row, a0 + k)), (const LT*)nullptr) : 0u;
-                    if constexpr (sizeof(LT) == 4) out[a0 + k] = __uint_as_float(r); else out[a0 + k] = (uint16_t)r;
+                    float xf;
+                    if constexpr (sizeof(LT) == 4) xf = __uint_as_float(x[k]);
+                    else xf = __uint_as_float(((x[k >> 1] >> ((k & 1u) * 16u)) & 0xFFFFu) << 16);
+                    v[k] = ((on >> k) & 1u) ? pattern(value(a0 + k, xf)) : (PT)0u;
                 }
+            } else {
+#pragma unroll
+                for (uint32_t k = 0; k < GW; ++k)
+                    if ((on >> k) & 1u) v[k] = pattern(value(a0 + k, cat_logit(row, a0 + k)));
             }
+            store_group<PT, GW, VEC>(reinterpret_cast<PT*>(out), a0, A, v);
         }
     }
 }

@@ -10,6 +10,7 @@
 // three ranges of mask columns.  A 924-byte observation expands to 4 - 60 KB of features: DESIGN.md section 7 has the measurements.
 #pragma once
 #include "mcbs_device.h"
+#include "mcbs_rowstore.h"
 
 namespace mcbs {
 
@@ -25,6 +26,39 @@ struct FeatGeom {
     uint32_t rc0[FEAT_MAX_RANGES], rn[FEAT_MAX_RANGES], rb0[FEAT_MAX_RANGES];     // first column, columns, first bit of the packed row
 };
 struct FeatSrc { const int32_t* f[5]; };                 // dense rows of len[k] ints each; a field the layout never reads may be NULL
+
+// Does the whole group of GW columns from j0 lie inside one mask range?  Then m = its GW bits, taken from two words of the row's
+// packed mask (word_at(w), w < W: the ranges' bits lie below 32 * W).
+template <uint32_t GW, typename WordAt>
+__device__ __forceinline__ bool feat_group_bits(const FeatGeom& G, uint32_t j0, WordAt word_at, uint32_t& m) {
+    bool whole = false;
+#pragma unroll
+    for (uint32_t r = 0; r < FEAT_MAX_RANGES; ++r) {
+        if (r < G.n_ranges && j0 >= G.rc0[r] && j0 + GW <= G.rc0[r] + G.rn[r]) {
+            const uint32_t b = G.rb0[r] + (j0 - G.rc0[r]), w = b >> 5, s = b & 31u;
+            uint32_t x = word_at(w) >> s;
+            if (s + GW > 32u) x |= word_at(w + 1u) << (32u - s);
+            m = x & ((1u << GW) - 1u);
+            whole = true;
+        }
+    }
+    return whole;
+}
+
+// Column j is a mask column (true: idx = its bit of the packed row) or a one-hot column (false: idx = j less the mask columns before
+// it, its index among the one-hot columns)
+__device__ __forceinline__ bool feat_column(const FeatGeom& G, uint32_t j, uint32_t& idx) {
+    uint32_t before = 0, bit = ~0u;
+#pragma unroll
+    for (uint32_t r = 0; r < FEAT_MAX_RANGES; ++r) {
+        if (r < G.n_ranges && j >= G.rc0[r]) {
+            if (j - G.rc0[r] < G.rn[r]) bit = G.rb0[r] + (j - G.rc0[r]);
+            else before += G.rn[r];
+        }
+    }
+    idx = bit != ~0u ? bit : j - before;
+    return bit != ~0u;
+}
 
 // T: uint32_t (fp32 patterns) or uint16_t (fp16 / bf16: `one` is the caller's bit pattern of 1.0).  GW columns = one store of
 // GW * sizeof(T) bytes (16, 8 or 4); VEC = false stores element by element (16-bit rows on odd 2-byte boundaries).
@@ -45,9 +79,6 @@ template <typename T, uint32_t GW, bool VEC>
 __global__ __launch_bounds__(256) void encode_features_kernel(FeatGeom G, FeatSrc src, const uint32_t* __restrict__ desc,
                                                               const uint32_t* __restrict__ bits, size_t bits_row_words, T* __restrict__ out,
                                                               size_t out_stride, uint64_t n_rows, T one, uint32_t* __restrict__ out_of_range) {
-    constexpr uint32_t NB = GW * (uint32_t)sizeof(T);                // bytes per group
-    static_assert(NB == 16u || NB == 8u || NB == 4u || !VEC, "a group is one 16-, 8- or 4-byte store");
-    constexpr uint32_t ALL = (1u << GW) - 1u;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t* D = desc;
@@ -68,88 +99,32 @@ __global__ __launch_bounds__(256) void encode_features_kernel(FeatGeom G, FeatSr
         for (uint32_t g = lane; g < ngroup; g += 64u) {
             const uint32_t j0 = g * GW;
             uint32_t m = 0;                                          // bit k: column j0 + k is 1
-            bool whole = false;
-#pragma unroll
-            for (uint32_t r = 0; r < FEAT_MAX_RANGES; ++r) {
-                if (r < G.n_ranges && j0 >= G.rc0[r] && j0 + GW <= G.rc0[r] + G.rn[r]) {        // the whole group lies in mask range r
-                    const uint32_t b = G.rb0[r] + (j0 - G.rc0[r]), w = b >> 5, s = b & 31u;
-                    uint32_t x = word_at(w) >> s;
-                    if (s + GW > 32u) x |= word_at(w + 1u) << (32u - s);
-                    m = x & ALL;
-                    whole = true;
-                }
-            }
-            if (!whole) {
+            if (!feat_group_bits<GW>(G, j0, word_at, m)) {
 #pragma unroll
                 for (uint32_t k = 0; k < GW; ++k) {
                     const uint32_t j = j0 + k;
                     if (j >= G.F) break;
-                    uint32_t before = 0, bit = ~0u;                  // mask columns before j; j's bit if it is a mask column
-#pragma unroll
-                    for (uint32_t r = 0; r < FEAT_MAX_RANGES; ++r) {
-                        if (r < G.n_ranges && j >= G.rc0[r]) {
-                            if (j - G.rc0[r] < G.rn[r]) bit = G.rb0[r] + (j - G.rc0[r]);
-                            else before += G.rn[r];
-                        }
-                    }
-                    uint32_t on;
-                    if (bit != ~0u) {
-                        on = (word_at(bit >> 5) >> (bit & 31u)) & 1u;
+                    uint32_t idx, on;
+                    if (feat_column(G, j, idx)) {
+                        on = (word_at(idx >> 5) >> (idx & 31u)) & 1u;
                     } else {
-                        const uint32_t d = D[j - before];
+                        const uint32_t d = D[idx];
                         on = (uint32_t)(value_at((d >> 16) & (FEAT_MAX_SRC - 1u)) == (d & (FEAT_MAX_CLASS - 1u)));
                         bad += (int32_t)(d >> 31) - (int32_t)on;
                     }
                     m |= on << k;
                 }
             }
-            if (VEC && j0 + GW <= G.F) {
-                if constexpr (sizeof(T) == 4) {
-                    auto v = [&](uint32_t k) -> uint32_t { return ((m >> k) & 1u) ? (uint32_t)one : 0u; };
-                    if constexpr (GW == 4u) *reinterpret_cast<uint4*>(row + j0) = make_uint4(v(0), v(1), v(2), v(3));
-                    else if constexpr (GW == 2u) *reinterpret_cast<uint2*>(row + j0) = make_uint2(v(0), v(1));
-                    else row[j0] = (T)v(0);
-                } else {
-                    auto v = [&](uint32_t k) -> uint32_t {           // columns j0 + 2k, j0 + 2k + 1 as one dword
-                        return (((m >> (2u * k)) & 1u) ? (uint32_t)one : 0u) | (((m >> (2u * k + 1u)) & 1u) ? (uint32_t)one << 16 : 0u);
-                    };
-                    if constexpr (GW == 8u) *reinterpret_cast<uint4*>(row + j0) = make_uint4(v(0), v(1), v(2), v(3));
-                    else if constexpr (GW == 4u) *reinterpret_cast<uint2*>(row + j0) = make_uint2(v(0), v(1));
-                    else *reinterpret_cast<uint32_t*>(row + j0) = v(0);
-                }
-            } else {
+            T v[GW];
 #pragma unroll
-                for (uint32_t k = 0; k < GW; ++k)
-                    if (j0 + k < G.F) row[j0 + k] = ((m >> k) & 1u) ? one : (T)0;
-            }
+            for (uint32_t k = 0; k < GW; ++k) v[k] = ((m >> k) & 1u) ? one : (T)0;
+            store_group<T, GW, VEC>(row, j0, G.F, v);
         }
     }
     if (out_of_range) {                                              // uniform
 #pragma unroll
         for (uint32_t d = 32u; d; d >>= 1) bad += __shfl_xor(bad, (int)d);
         if (lane == 0 && bad > 0) atomicAdd(out_of_range, (uint32_t)bad);
-    }
-}
-
-// One group of GW columns, given as T patterns, to row[j0 ..]: one vector store when the group is whole, element by element at the
-// row's end (and always without VEC)
-template <typename T, uint32_t GW, bool VEC>
-__device__ __forceinline__ void store_feature_group(T* __restrict__ row, uint32_t j0, uint32_t F, const T (&v)[GW]) {
-    if (VEC && j0 + GW <= F) {
-        if constexpr (sizeof(T) == 4) {
-            if constexpr (GW == 4u) *reinterpret_cast<uint4*>(row + j0) = make_uint4(v[0], v[1], v[2], v[3]);
-            else if constexpr (GW == 2u) *reinterpret_cast<uint2*>(row + j0) = make_uint2(v[0], v[1]);
-            else row[j0] = v[0];
-        } else {
-            auto w = [&](uint32_t k) -> uint32_t { return (uint32_t)v[2u * k] | ((uint32_t)v[2u * k + 1u] << 16); };
-            if constexpr (GW == 8u) *reinterpret_cast<uint4*>(row + j0) = make_uint4(w(0), w(1), w(2), w(3));
-            else if constexpr (GW == 4u) *reinterpret_cast<uint2*>(row + j0) = make_uint2(w(0), w(1));
-            else *reinterpret_cast<uint32_t*>(row + j0) = w(0);
-        }
-    } else {
-#pragma unroll
-        for (uint32_t k = 0; k < GW; ++k)
-            if (j0 + k < F) row[j0 + k] = v[k];
     }
 }
 
@@ -171,7 +146,6 @@ __global__ __launch_bounds__(256) void encode_features_rows_kernel(FeatGeom G, F
                                                                    const uint32_t* __restrict__ bits, size_t bits_row_words, T* __restrict__ out,
                                                                    size_t out_stride, uint64_t n_rows, T one, uint32_t* __restrict__ out_of_range) {
     constexpr uint32_t PER = 16u / (uint32_t)sizeof(T);              // columns per 16 bytes
-    constexpr uint32_t ALL = (1u << GW) - 1u;
     extern __shared__ uint4 feat_rows_lds[];                         // elems [V] | per wavefront: one-hot row [n_desc] | bit words [W]
     const uint32_t ev4 = (G.V + 1u) / 2u, rv4 = (G.n_desc + PER - 1u) / PER, bv4 = (G.W + 3u) / 4u;
     const uint32_t lane = threadIdx.x & 63u;
@@ -225,38 +199,22 @@ __global__ __launch_bounds__(256) void encode_features_rows_kernel(FeatGeom G, F
             for (uint32_t g = lane; g < ngroup; g += 64u) {
                 const uint32_t j0 = g * GW;
                 T v[GW];
-                bool whole = false;
+                uint32_t m = 0;
+                if (feat_group_bits<GW>(G, j0, [&](uint32_t w) { return wbits[w]; }, m)) {
 #pragma unroll
-                for (uint32_t r = 0; r < FEAT_MAX_RANGES; ++r) {
-                    if (r < G.n_ranges && j0 >= G.rc0[r] && j0 + GW <= G.rc0[r] + G.rn[r]) {    // the whole group lies in mask range r
-                        const uint32_t b = G.rb0[r] + (j0 - G.rc0[r]), w = b >> 5, s = b & 31u;
-                        uint32_t m = wbits[w] >> s;
-                        if (s + GW > 32u) m |= wbits[w + 1u] << (32u - s);
-                        m &= ALL;
-#pragma unroll
-                        for (uint32_t k = 0; k < GW; ++k) v[k] = ((m >> k) & 1u) ? one : (T)0;
-                        whole = true;
-                    }
-                }
-                if (!whole) {
+                    for (uint32_t k = 0; k < GW; ++k) v[k] = ((m >> k) & 1u) ? one : (T)0;
+                } else {
 #pragma unroll
                     for (uint32_t k = 0; k < GW; ++k) {
                         const uint32_t j = j0 + k;
                         v[k] = (T)0;
                         if (j >= G.F) continue;
-                        uint32_t before = 0, bit = ~0u;              // mask columns before j; j's bit if it is a mask column
-#pragma unroll
-                        for (uint32_t r = 0; r < FEAT_MAX_RANGES; ++r) {
-                            if (r < G.n_ranges && j >= G.rc0[r]) {
-                                if (j - G.rc0[r] < G.rn[r]) bit = G.rb0[r] + (j - G.rc0[r]);
-                                else before += G.rn[r];
-                            }
-                        }
-                        if (bit != ~0u) v[k] = ((wbits[bit >> 5] >> (bit & 31u)) & 1u) ? one : (T)0;
-                        else v[k] = lrow[j - before];
+                        uint32_t idx;
+                        if (feat_column(G, j, idx)) v[k] = ((wbits[idx >> 5] >> (idx & 31u)) & 1u) ? one : (T)0;
+                        else v[k] = lrow[idx];
                     }
                 }
-                store_feature_group<T, GW, VEC>(row, j0, G.F, v);
+                store_group<T, GW, VEC>(row, j0, G.F, v);
             }
         }
     }

@@ -13,6 +13,7 @@
 #pragma once
 #include "mcbs_device.h"
 #include "mcbs_obs.hip"
+#include "mcbs_rowstore.h"
 
 namespace mcbs {
 
@@ -21,11 +22,103 @@ struct LogitsGeom {        // Discrete layout of the batch, set up on the host
     FastDiv dRL, dC, dN, dL, dR;
 };
 
-// LT: float, or uint16_t for 16-bit logits (bf16 patterns are only replaced).  GW: actions per group = per vector store
-// (16 bytes: 4 fp32 / 8 bf16; 8-byte groups of 4 bf16 when the rows are only 8-byte aligned, e.g. Chain-10's 14 172 actions).
+// One env's digest seen as its Discrete mask: the predicates every kernel that rebuilds the mask of the last observation uses
+// (mask_logits_kernel, pack_mask_kernel, the live form of masked_categorical_kernel).  Built once per wavefront: everything here is
+// uniform per wavefront (scalar loads); S, G and d are references to the kernel's own locals, nothing is copied.
+struct DigestMask {
+    const DevState& S;
+    const LogitsGeom& G;
+    const ObsDigest& d;        // the env's digest
+    const mcbs_node_static* NS;
+    const uint8_t* body;
+    uint32_t e, n_disc, n_creds;           // n_disc = 0 for a blank observation
+    uint64_t pp;               // credential pattern of one period, repeated to at least C + span bits; 0 when that exceeds 64
+
+    // span: the longest run of actions the caller takes from `pp` with one shift (a logits group, or a word of 32)
+    static __device__ __forceinline__ DigestMask make(const DevState& S, const Topo& T, const StepCfg* __restrict__ Cp, const ObsDigest& d,
+                                                      const LogitsGeom& G, uint32_t e, uint32_t span) {
+        uint64_t pp = 0;
+        if (G.C + span <= 64u) {
+            const uint64_t one = d.n_creds >= 64u ? ~0ull : ((1ull << d.n_creds) - 1ull);
+            for (uint32_t sh = 0; sh < 64u; sh += G.C) pp |= one << sh;
+        }
+        return DigestMask{S, G, d, reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node), S.body + (size_t)e * S.body_stride,
+                          e, d.blank ? 0u : d.n_disc, d.n_creds, pp};
+    }
+    __device__ __forceinline__ uint32_t remote0() const { return G.M + G.ML; }
+    __device__ __forceinline__ bool own(uint32_t s) const { return s < G.N && ((d.own_ext[(s >> 6) & 3u] >> (s & 63u)) & 1ull); }
+    __device__ __forceinline__ bool pair_on(uint32_t q) const {       // row q = (source s, target t): s owned (hence discovered), t discovered
+        const uint32_t s = fdiv(q, G.dN), t = q - s * G.N;
+        return own(s) && t < n_disc;
+    }
+    // node i's local vulnerabilities as bits (0: i is not an owned, discovered node)      (env.py:653-663)
+    __device__ __forceinline__ uint32_t local_bits(uint32_t i) const {
+        if (!(own(i) && i < n_disc)) return 0u;
+        return NS[S.disc_at(body, e, i)].local_mask;
+    }
+    __device__ __forceinline__ bool at(uint32_t a) const {            // one action, any region
+        if (a < G.M) {                                   // connect[s][t][p][c] = on(s, t) && c < n_creds      (env.py:664-677)
+            const uint32_t q = fdiv(a, G.dRL), r = a - q * G.RL, c = r - fdiv(r, G.dC) * G.C;
+            return c < n_creds && pair_on(q);
+        }
+        if (a < remote0()) {                             // local[i][l] = owned(i) && vulnerability l applies to node i
+            const uint32_t b = a - G.M, i = fdiv(b, G.dL), l = b - i * G.L;
+            return (local_bits(i) >> l) & 1u;
+        }
+        return a < G.A && pair_on(fdiv(a - remote0(), G.dR));   // remote[s][t][r] = on(s, t)
+    }
+    // word w = the 32 actions [32 w, 32 w + 32) as bits (bits from A on are zero): the words pack_mask_kernel stores
+    __device__ __forceinline__ uint32_t word(uint32_t w) const {
+        const uint32_t remote0 = this->remote0();
+        // bits [lo, hi) of a block of `rowlen`-long rows (hi - lo <= 32) as bits 0 .. hi-lo-1: rowbits(q, k) = the bits of row q from its
+        // k-th one on (only the low hi-lo are used)
+        auto rows_in = [&](uint32_t lo, uint32_t hi, uint32_t rowlen, const FastDiv& dRow, auto rowbits) -> uint32_t {
+            uint32_t m = 0, q = fdiv(lo, dRow), r0 = q * rowlen;
+            for (uint32_t j = lo; j < hi; ++q, r0 += rowlen) {
+                const uint32_t end = r0 + rowlen < hi ? r0 + rowlen : hi;
+                m |= (uint32_t)((rowbits(q, j - r0) & ((1ull << (end - j)) - 1ull)) << (j - lo));
+                j = end;
+            }
+            return m;
+        };
+        auto whole_row = [&](uint32_t q, uint32_t) -> uint64_t { return pair_on(q) ? ~0ull : 0ull; };   // connect / remote: on or off as a whole
+        auto local_row = [&](uint32_t i, uint32_t k) -> uint64_t { return (uint64_t)local_bits(i) >> k; };
+        const uint32_t a0 = w * 32u, a1 = a0 + 32u < G.A ? a0 + 32u : G.A;      // actions [a0, a1); bits from A on stay zero
+        uint32_t m = 0;
+        if (a0 < G.M) {
+            // connect[s][t][p][c] = on(s, t) && c < n_creds: the dword overlaps ceil(32 / RL) + 1 rows at most, and since RL = P*C and the
+            // block starts at action 0, the credential index of action a is a mod C in every row
+            const uint32_t rows = rows_in(a0, a1 < G.M ? a1 : G.M, G.RL, G.dRL, whole_row);
+            if (rows) m = rows & cred_bits<32u>(a0 - fdiv(a0, G.dC) * G.C);
+        }
+        if (a1 > G.M && a0 < remote0) {                  // local block: rows of L bits, the node's vulnerability mask
+            const uint32_t lo = a0 > G.M ? a0 : G.M, hi = a1 < remote0 ? a1 : remote0;
+            m |= rows_in(lo - G.M, hi - G.M, G.L, G.dL, local_row) << (lo - a0);
+        }
+        if (a1 > remote0) {                              // remote[s][t][r] = on(s, t)
+            const uint32_t lo = a0 > remote0 ? a0 : remote0;
+            m |= rows_in(lo - remote0, a1 - remote0, G.R, G.dR, whole_row) << (lo - a0);
+        }
+        return m;
+    }
+    // bit i: credential (c0 + i) mod C is cached, i < SPAN (the SPAN this was made with).  One credential period plus SPAN bits fits
+    // 64 bits (Chain-10: C = 12, ToyCtf: 10): `pp` = the periodic pattern "n_creds ones, C - n_creds zeros" as a bit string, so the
+    // bits are one shift; else the index just counts on modulo C
+    template <uint32_t SPAN>
+    __device__ __forceinline__ uint32_t cred_bits(uint32_t c0) const {
+        if (G.C + SPAN <= 64u) return (uint32_t)(pp >> c0);
+        uint32_t m = 0, c = c0;
+        for (uint32_t i = 0; i < SPAN; ++i) {
+            m |= (uint32_t)(c < n_creds) << i;
+            c = c + 1u == G.C ? 0u : c + 1u;
+        }
+        return m;
+    }
+};
+
+// LT: float, or uint16_t for 16-bit logits (bf16 patterns are only replaced).  GW: actions per group (mcbs_rowstore.h).
 //
-// One WAVEFRONT per env (four independent ones per workgroup: no LDS, no barrier).  A span = the 64 groups one store instruction of
-// the wavefront covers = 64 * GW consecutive actions, starting on a 128-byte line of memory.  Nearly every span holds no allowed action at all (a few dozen of Chain-10's
+// One WAVEFRONT per env (four independent ones per workgroup: no LDS, no barrier).  Nearly every span holds no allowed action at all (a few dozen of Chain-10's
 // 14 172 actions are allowed): for each chunk of 64 spans, lane k first decides whether span k is LIVE — some (source, target) row
 // overlapping it is on, or it touches the local block — and one ballot turns that into a scalar mask; a span that is not live costs
 // one scalar bit test and one store.  (Measured on the way here, 65 536 Chain-10 envs, fp32 / bf16 logits, us per launch: read-modify-write with one
@@ -36,62 +129,32 @@ struct LogitsGeom {        // Discrete layout of the batch, set up on the host
 template <typename LT, uint32_t GW, bool VEC>
 __global__ __launch_bounds__(256) void mask_logits_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, const ObsDigest* __restrict__ digest,
                                                           LT* __restrict__ logits, size_t row_stride, LT fill, LogitsGeom G) {
-    constexpr uint32_t NWORD = GW * (uint32_t)sizeof(LT) / 4u;      // dwords per group: 4 or 2
-    static_assert(NWORD == 4u || NWORD == 2u, "group = 16 or 8 bytes");
-    constexpr uint32_t ALL = (1u << GW) - 1u;
+    using RG = RowGroups<LT, GW, VEC>;
+    constexpr uint32_t ALL = RG::ALL;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t e = blockIdx.y * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform
     if (e >= S.E) return;
     const ObsDigest d = digest[e];                       // uniform per wavefront: scalar loads
-    const uint32_t n_disc = d.blank ? 0u : d.n_disc, n_creds = d.n_creds;
-    const uint32_t remote0 = G.M + G.ML;
+    const DigestMask M = DigestMask::make(S, T, Cp, d, G, e, GW);
+    const uint32_t remote0 = M.remote0();
     LT* row = logits + (size_t)e * row_stride;
-    auto own = [&](uint32_t s) -> bool { return s < G.N && ((d.own_ext[(s >> 6) & 3u] >> (s & 63u)) & 1ull); };
-    auto pair_on = [&](uint32_t q) -> bool {             // row q = (source s, target t): s owned (hence discovered), t discovered
-        const uint32_t s = fdiv(q, G.dN), t = q - s * G.N;
-        return own(s) && t < n_disc;
-    };
-    auto mask_at = [&](uint32_t a) -> bool {             // one action, any region
-        if (a < G.M) {                                   // connect[s][t][p][c] = on(s, t) && c < n_creds      (env.py:664-677)
-            const uint32_t q = fdiv(a, G.dRL), r = a - q * G.RL, c = r - fdiv(r, G.dC) * G.C;
-            return c < n_creds && pair_on(q);
-        }
-        if (a < remote0) {                               // local[i][l] = owned(i) && vulnerability l applies to node i   (env.py:653-663)
-            const uint32_t b = a - G.M, i = fdiv(b, G.dL), l = b - i * G.L;
-            if (!(own(i) && i < n_disc)) return false;
-            const uint8_t* body = S.body + (size_t)e * S.body_stride;
-            const mcbs_node_static* NS = reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node);
-            return (NS[S.disc_at(body, e, i)].local_mask >> l) & 1u;
-        }
-        return a < G.A && pair_on(fdiv(a - remote0, G.dR));   // remote[s][t][r] = on(s, t)
-    };
     // bit j: the (source, target) row that action rel + j of a block of `rowlen`-long rows belongs to is on (rowlen >= GW: two rows at most)
     auto rows_mask = [&](uint32_t rel, const FastDiv& dRow, uint32_t rowlen, uint32_t& r0) -> uint32_t {
         const uint32_t q0 = fdiv(rel, dRow);
         r0 = rel - q0 * rowlen;
         const uint32_t first = rowlen - r0 < GW ? rowlen - r0 : GW, lo = (1u << first) - 1u;
-        return (pair_on(q0) ? lo : 0u) | ((first < GW && pair_on(q0 + 1u)) ? (ALL & ~lo) : 0u);
+        return (M.pair_on(q0) ? lo : 0u) | ((first < GW && M.pair_on(q0 + 1u)) ? (ALL & ~lo) : 0u);
     };
-    uint64_t pp = 0;                                     // credential pattern of one period, repeated to at least C + GW bits (uniform)
-    if (G.C + GW <= 64u) {
-        const uint64_t one = n_creds >= 64u ? ~0ull : ((1ull << n_creds) - 1ull);
-        for (uint32_t sh = 0; sh < 64u; sh += G.C) pp |= one << sh;
-    }
-    // Spans start on 128-byte lines of MEMORY, not of the row (rows are only 16- or 8-byte aligned: Chain-10's fp32 row is 56 688 B):
-    // the env's groups are shifted down by `sh`, so that every store instruction writes whole lines and no line is shared by two
-    // instructions; the first span is short.
-    constexpr uint32_t GB = GW * (uint32_t)sizeof(LT);
-    const uint32_t sh = VEC ? (uint32_t)((reinterpret_cast<uintptr_t>(row) / GB) % (128u / GB)) : 0u;
-    const uint32_t nspan = ((G.A + GW - 1u) / GW + sh + 63u) / 64u;
+    const uint32_t sh = RG::shift(row);
+    const uint32_t nspan = RG::nspan(G.A, sh);
     for (uint32_t c0s = blockIdx.x * 64u; c0s < nspan; c0s += gridDim.x * 64u) {      // chunks of 64 spans
         bool live = false;                               // lane k: span c0s + k holds an allowed action (or might)
         {
-            const uint32_t g0 = (c0s + lane) * 64u;      // groups [g0 - sh, g0 + 64 - sh) of the row
-            const uint32_t s0 = (g0 > sh ? g0 - sh : 0u) * GW, s1 = (g0 + 64u - sh) * GW < G.A ? (g0 + 64u - sh) * GW : G.A;      // [s0, s1)
+            const uint32_t s0 = RG::span_first(c0s + lane, sh), s1 = RG::span_last(c0s + lane, sh, G.A);      // its actions [s0, s1)
             auto any_row = [&](uint32_t lo, uint32_t hi, const FastDiv& dRow) {                    // rows of actions lo .. hi (relative to their block)
                 const uint32_t qa = fdiv(lo, dRow), qb = fdiv(hi, dRow);
                 if (qb - qa > 8u) { live = true; return; }
-                for (uint32_t q = qa; q <= qb; ++q) live |= pair_on(q);
+                for (uint32_t q = qa; q <= qb; ++q) live |= M.pair_on(q);
             };
             if (s0 < s1) {
                 if (s0 < G.M) any_row(s0, (s1 < G.M ? s1 : G.M) - 1u, G.dRL);
@@ -104,54 +167,23 @@ __global__ __launch_bounds__(256) void mask_logits_kernel(DevState S, Topo T, co
 #pragma unroll 4
         for (uint32_t j = 0; j < ns; ++j) {
             const uint32_t g = (c0s + j) * 64u + lane;
-            const uint32_t a0 = (g - sh) * GW;
-            if (g < sh || a0 >= G.A) continue;           // the first span's head, the last span's tail
+            const uint32_t a0 = RG::a0(g, sh);
+            if (RG::outside(g, sh, G.A)) continue;
             uint32_t m = 0, r0;                          // bit j: action a0 + j is allowed
             if (!((live_mask >> j) & 1ull)) {            // scalar test
             } else if (a0 + GW <= G.M && G.RL >= GW) {
                 // the whole group lies in the connect block: at most two (source, target) rows, each on or off as a whole; within an
                 // on row the credential index just counts on modulo C (RL is a multiple of C)
                 const uint32_t rows = rows_mask(a0, G.dRL, G.RL, r0);
-                if (rows) {
-                    const uint32_t c0 = r0 - fdiv(r0, G.dC) * G.C;
-                    if (G.C + GW <= 64u) {
-                        // one credential period plus a group fits 64 bits (Chain-10: C = 12, ToyCtf: 10): `pp` = the periodic pattern
-                        // "n_creds ones, C - n_creds zeros" as a bit string, so the group's credential bits are one shift
-                        m = (uint32_t)(pp >> c0) & rows;
-                    } else {
-                        uint32_t c = c0;
-#pragma unroll
-                        for (uint32_t i = 0; i < GW; ++i) {
-                            m |= (uint32_t)(c < n_creds) << i;
-                            c = c + 1u == G.C ? 0u : c + 1u;
-                        }
-                        m &= rows;
-                    }
-                }
+                if (rows) m = M.cred_bits<GW>(r0 - fdiv(r0, G.dC) * G.C) & rows;
             } else if (a0 >= remote0 && a0 + GW <= G.A && G.R >= GW) {
                 m = rows_mask(a0 - remote0, G.dR, G.R, r0);     // the whole group lies in the remote block: remote[s][t][r] = on(s, t)
             } else {
 #pragma unroll
-                for (uint32_t i = 0; i < GW; ++i) m |= (uint32_t)mask_at(a0 + i) << i;
+                for (uint32_t i = 0; i < GW; ++i) m |= (uint32_t)M.at(a0 + i) << i;
             }
-            // write-only: a group whose actions are all masked out is ONE vector store of `fill`, a group that is allowed as a whole is
-            // left alone, a mixed group stores `fill` element by element — the logits are never read
-            const uint32_t in_row = a0 + GW <= G.A ? ALL : (1u << (G.A - a0)) - 1u;
-            const uint32_t off = ~m & in_row;            // bit i: action a0 + i is replaced
-            if (VEC && off == ALL) {
-                if constexpr (sizeof(LT) == 4) {
-                    const uint32_t f = __float_as_uint(fill);
-                    *reinterpret_cast<uint4*>(row + a0) = make_uint4(f, f, f, f);
-                } else {
-                    const uint32_t f = (uint32_t)fill, ff = f | (f << 16);
-                    if constexpr (NWORD == 4u) *reinterpret_cast<uint4*>(row + a0) = make_uint4(ff, ff, ff, ff);
-                    else *reinterpret_cast<uint2*>(row + a0) = make_uint2(ff, ff);
-                }
-            } else if (off) {
-#pragma unroll
-                for (uint32_t i = 0; i < GW; ++i)
-                    if ((off >> i) & 1u) row[a0 + i] = fill;
-            }
+            // write-only: allowed actions are left alone — the logits are never read
+            store_fill_group<LT, GW, VEC>(row, a0, ~m & RG::in_row(a0, G.A), fill);
         }
     }
 }
