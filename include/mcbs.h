@@ -489,6 +489,57 @@ int  mcbs_masked_categorical_grad(const mcbs_batch*, const uint32_t* bits, size_
                                   int32_t dtype, size_t row_stride, const int64_t* actions, const float* grad_log_prob,
                                   const float* grad_entropy, void* grad_logits, size_t grad_row_stride, void* stream);
 
+/* ---- generalized advantage estimation: advantages and returns of a whole [T, E] rollout, one launch ----
+ * The step between "rollout finished" and "first minibatch": what Stable-Baselines3 2.x's RolloutBuffer.compute_returns_and_advantage
+ * does with T Python iterations over [E] host vectors (the reference reaches it through on_rollout_end,
+ * marlon/baseline_models/multiagent/marl_algorithm.py:51-52).  All arrays are device memory; [T, E] arrays are rows of E elements
+ * whose starts lie `*_stride` ELEMENTS apart (>= n_envs; a [T, :E] view of a wider buffer is served), element [t, e] = base[t * stride + e].
+ *   rewards, values           float   [T, E]   inputs
+ *   episode_starts            uint8_t [T, E]   nonzero = the observation of step t was the first of an episode
+ *   bootstrap                 float   [T, E]   or NULL: the value of the terminal observation where step t was truncated, 0 elsewhere
+ *   last_values, last_dones   float / uint8_t [E]: the value of the observation after the last step, and whether that step ended an episode
+ *   advantages                float   [T, E]   output
+ *   returns                   float   [T, E]   output or NULL
+ * THE CONTRACT is this float32 recurrence, every operation rounded to float32 on its own, in exactly this order, no fused multiply-add:
+ *   g = (float)gamma;  gl = (float)(gamma * gae_lambda)        (the product taken in double)
+ *   last = 0;  nv = last_values[e];  nnt = last_dones[e] ? 0.0f : 1.0f
+ *   for t = T-1 ... 0:
+ *       r     = rewards[t, e]                                  without bootstrap: the reward itself (a -0.0 keeps its sign)
+ *       r     = rewards[t, e] + g * bootstrap[t, e]            with bootstrap
+ *       delta = (r + (g * nv) * nnt) - values[t, e]
+ *       last  = delta + (gl * nnt) * last
+ *       advantages[t, e] = last;   returns[t, e] = last + values[t, e]
+ *       nv = values[t, e];  nnt = episode_starts[t, e] ? 0.0f : 1.0f
+ * which is that loop of SB3 written out under NumPy's float32 rules (tests/gae_ref.py restates it; SB3 itself is not available to the
+ * tests, so parity with it is not pinned).  Denormals are kept.  NaN payloads are not promised.  Inputs are read-only; elements beyond
+ * column E of any row are neither read nor written; two calls give bit-identical output, whatever the strides.
+ * The batch only supplies the device: n_envs is the call's own (a defender's buffer is served by an attacker's batch).  Asynchronous on
+ * `stream`, no allocation, no synchronisation.  n_steps == 0 or n_envs == 0 is a no-op.
+ * MCBS_EINVAL (the message names the argument): batch or io NULL; a required pointer NULL; a stride below n_envs; gamma or gae_lambda not
+ * finite or outside [0, 1]; an output that overlaps an input or the other output (rows of equal byte stride interleaved in one buffer are
+ * accepted; otherwise the two extents may not intersect).  MCBS_ELIMIT: n_envs of 2^37 or more. */
+typedef struct mcbs_gae_io {
+    const float* rewards;
+    const float* values;
+    const uint8_t* episode_starts;
+    const float* bootstrap;
+    const float* last_values;
+    const uint8_t* last_dones;
+    float* advantages;
+    float* returns;
+    uint64_t n_steps;
+    uint64_t n_envs;
+    size_t rewards_stride;
+    size_t values_stride;
+    size_t episode_starts_stride;
+    size_t bootstrap_stride;
+    size_t advantages_stride;
+    size_t returns_stride;
+    double gamma;
+    double gae_lambda;
+} mcbs_gae_io;
+int  mcbs_gae(const mcbs_batch*, const mcbs_gae_io* io, void* stream);
+
 /* ---- feature encoder: observation rows -> the float rows a policy's first layer takes, one launch ----
  * What Stable-Baselines3's "MultiInputPolicy" (marlon/baseline_models/ppo/train.py:79) does first with the wrappers' Dict observation
  * (preprocess_obs + CombinedExtractor): a Discrete(n) becomes a one-hot of n, every element of a MultiDiscrete a one-hot of its own, a

@@ -66,6 +66,19 @@ class BatchVariantInfo(C.Structure):
                                           "fused_defender_obs")]
 
 
+class GaeIO(C.Structure):
+    """mcbs_gae_io (include/mcbs.h): device pointers, sizes, row strides in elements and the two coefficients of mcbs_gae"""
+    _fields_ = ([(n, C.c_void_p) for n in ("rewards", "values", "episode_starts", "bootstrap", "last_values", "last_dones", "advantages",
+                                           "returns")]
+                + [("n_steps", C.c_uint64), ("n_envs", C.c_uint64)]
+                + [(n, C.c_size_t) for n in ("rewards_stride", "values_stride", "episode_starts_stride", "bootstrap_stride",
+                                             "advantages_stride", "returns_stride")]
+                + [("gamma", C.c_double), ("gae_lambda", C.c_double)])
+
+
+assert C.sizeof(GaeIO) == 144
+
+
 class InfoBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("network_availability", "step_count", "truncated", "out_of_bound", "raw_reward")]
 

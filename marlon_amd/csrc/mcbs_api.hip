@@ -2,6 +2,7 @@
 // One translation unit: the kernels are included below.  Build: marlon_amd/csrc/Makefile (hipcc, gfx950).
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -22,6 +23,7 @@
 #include "mcbs_packed_mask.hip"
 #include "mcbs_categorical.hip"
 #include "mcbs_categorical_grad.hip"
+#include "mcbs_gae.hip"
 #include "mcbs_features.hip"
 #include "mcbs_wrapper_fused.hip"
 
@@ -1397,12 +1399,14 @@ extern "C" int mcbs_masked_categorical_packed(const mcbs_batch* b, const uint32_
 
 // do rows [p, p + k * stride + A) and [q, q + k * qstride + A) (k < n, bytes) share a byte?  Exact for equal strides (rows interleaved in one
 // buffer are fine), conservative otherwise: then any intersection of the two extents counts
-static bool rows_overlap(uintptr_t p, size_t stride, uintptr_t q, size_t qstride, uint64_t n, size_t row_bytes) {
-    const uintptr_t pe = p + (uintptr_t)((n - 1u) * stride + row_bytes), qe = q + (uintptr_t)((n - 1u) * qstride + row_bytes);
+// q_row_bytes: the width of q's rows where it differs from row_bytes, that of p's (0: the same)
+static bool rows_overlap(uintptr_t p, size_t stride, uintptr_t q, size_t qstride, uint64_t n, size_t row_bytes, size_t q_row_bytes = 0) {
+    if (!q_row_bytes) q_row_bytes = row_bytes;
+    const uintptr_t pe = p + (uintptr_t)((n - 1u) * stride + row_bytes), qe = q + (uintptr_t)((n - 1u) * qstride + q_row_bytes);
     if (pe <= q || qe <= p) return false;
     if (stride != qstride || n == 1u) return true;
     const size_t r = (size_t)((q >= p ? q - p : stride - (p - q) % stride) % stride);       // q's rows lie r bytes behind p's, modulo the stride
-    return r < row_bytes || stride - r < row_bytes;
+    return r < row_bytes || stride - r < q_row_bytes;
 }
 
 extern "C" int mcbs_masked_categorical_grad(const mcbs_batch* b, const uint32_t* bits, size_t bits_row_words, uint64_t n_rows, const void* logits,
@@ -1434,6 +1438,60 @@ extern "C" int mcbs_masked_categorical_grad(const mcbs_batch* b, const uint32_t*
                            bits, bits_row_words, io);
     });
     return launch_ok("masked categorical gradient");
+}
+
+// ------------------------------------------------------------------ generalized advantage estimation
+extern "C" int mcbs_gae(const mcbs_batch* b, const mcbs_gae_io* io, void* stream) {
+    if (!b || !io) return fail(MCBS_EINVAL, "mcbs_gae: null argument (batch or io)");
+    MCBS_ON_DEVICE(b);
+    const uint64_t T = io->n_steps, E = io->n_envs;
+    if (T == 0 || E == 0) return MCBS_OK;
+    const struct { const void* p; const char* name; } required[] = {
+        {io->rewards, "rewards"}, {io->values, "values"}, {io->episode_starts, "episode_starts"}, {io->last_values, "last_values"},
+        {io->last_dones, "last_dones"}, {io->advantages, "advantages"}};
+    for (const auto& a : required)
+        if (!a.p) return fail(MCBS_EINVAL, "mcbs_gae: %s must not be NULL", a.name);
+    if (E >= (1ull << 37)) return fail(MCBS_ELIMIT, "mcbs_gae: n_envs %llu: at most 2^37 - 1", (unsigned long long)E);
+    // every [T, E] array: base, row stride in elements, element size; inputs first
+    struct Arr { const void* p; size_t stride; size_t es; const char* name; };
+    const Arr in[] = {{io->rewards, io->rewards_stride, 4u, "rewards"}, {io->values, io->values_stride, 4u, "values"},
+                      {io->episode_starts, io->episode_starts_stride, 1u, "episode_starts"}, {io->bootstrap, io->bootstrap_stride, 4u, "bootstrap"}};
+    const Arr out[] = {{io->advantages, io->advantages_stride, 4u, "advantages"}, {io->returns, io->returns_stride, 4u, "returns"}};
+    for (const Arr& a : in)
+        if (a.p && a.stride < E) return fail(MCBS_EINVAL, "mcbs_gae: %s_stride %zu is below n_envs %llu", a.name, a.stride, (unsigned long long)E);
+    for (const Arr& a : out)
+        if (a.p && a.stride < E) return fail(MCBS_EINVAL, "mcbs_gae: %s_stride %zu is below n_envs %llu", a.name, a.stride, (unsigned long long)E);
+    if (!std::isfinite(io->gamma) || io->gamma < 0.0 || io->gamma > 1.0) return fail(MCBS_EINVAL, "mcbs_gae: gamma %g must lie in [0, 1]", io->gamma);
+    if (!std::isfinite(io->gae_lambda) || io->gae_lambda < 0.0 || io->gae_lambda > 1.0)
+        return fail(MCBS_EINVAL, "mcbs_gae: gae_lambda %g must lie in [0, 1]", io->gae_lambda);
+    auto addr = [](const void* p) { return reinterpret_cast<uintptr_t>(p); };
+    for (const Arr& o : out) {
+        if (!o.p) continue;
+        for (const Arr& a : in)
+            if (a.p && rows_overlap(addr(o.p), o.stride * 4u, addr(a.p), a.stride * a.es, T, (size_t)E * 4u, (size_t)E * a.es))
+                return fail(MCBS_EINVAL, "mcbs_gae: the %s rows overlap the %s rows", o.name, a.name);
+        // the two [E] rows: any intersection with the output's extent counts (a stride of their own, 0, never equals the output's)
+        if (rows_overlap(addr(o.p), o.stride * 4u, addr(io->last_values), 0u, T, (size_t)E * 4u))
+            return fail(MCBS_EINVAL, "mcbs_gae: the %s rows overlap last_values", o.name);
+        if (rows_overlap(addr(o.p), o.stride * 4u, addr(io->last_dones), 0u, T, (size_t)E * 4u, (size_t)E))
+            return fail(MCBS_EINVAL, "mcbs_gae: the %s rows overlap last_dones", o.name);
+    }
+    if (io->returns && rows_overlap(addr(io->advantages), io->advantages_stride * 4u, addr(io->returns), io->returns_stride * 4u, T, (size_t)E * 4u))
+        return fail(MCBS_EINVAL, "mcbs_gae: the advantages rows overlap the returns rows");
+    GaeIO k{io->rewards, io->values, io->episode_starts, io->bootstrap, io->last_values, io->last_dones, io->advantages, io->returns, T, E,
+            io->rewards_stride, io->values_stride, io->episode_starts_stride, io->bootstrap_stride, io->advantages_stride, io->returns_stride,
+            (float)io->gamma, (float)(io->gamma * io->gae_lambda)};
+    const dim3 grid((uint32_t)((E + 63u) / 64u)), block(64);
+    hipStream_t st = (hipStream_t)stream;
+    constexpr uint32_t U = MCBS_GAE_U;
+    if (io->bootstrap) {
+        if (io->returns) hipLaunchKernelGGL((gae_kernel<U, true, true>), grid, block, 0, st, k);
+        else hipLaunchKernelGGL((gae_kernel<U, true, false>), grid, block, 0, st, k);
+    } else {
+        if (io->returns) hipLaunchKernelGGL((gae_kernel<U, false, true>), grid, block, 0, st, k);
+        else hipLaunchKernelGGL((gae_kernel<U, false, false>), grid, block, 0, st, k);
+    }
+    return launch_ok("gae");
 }
 
 // ------------------------------------------------------------------ feature encoder

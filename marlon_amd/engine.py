@@ -14,7 +14,7 @@ from typing import Dict, Iterable, Optional
 
 import numpy as np
 
-from ._abi import BatchCfg, BatchVariantInfo, DefenderObs, EnvSpec, InfoBuffers, ObsBuffers, split_state, state_record_bytes
+from ._abi import BatchCfg, BatchVariantInfo, DefenderObs, EnvSpec, GaeIO, InfoBuffers, ObsBuffers, split_state, state_record_bytes
 from .flatten import FlatTopology
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -29,6 +29,7 @@ EXPORTS = [
     "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant",
     "mcbs_feature_layout_create", "mcbs_feature_layout_destroy", "mcbs_feature_layout_width", "mcbs_encode_features",
     "mcbs_masked_categorical", "mcbs_masked_categorical_packed", "mcbs_masked_categorical_grad",
+    "mcbs_gae",
 ]
 
 _lib = None
@@ -110,6 +111,7 @@ def load_library(path: Optional[str] = None):
     # bits, bits_row_words, n_rows, logits, dtype, row_stride, actions, grad_log_prob, grad_entropy, grad_logits, grad_row_stride, stream
     lib.mcbs_masked_categorical_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    lib.mcbs_gae.argtypes = [C.c_void_p, C.POINTER(GaeIO), C.c_void_p]
     lib.mcbs_copy_rows_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.mcbs_attacker_wrapper_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
                                                C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -701,6 +703,52 @@ class BatchEngine:
         `logits`, whose backward is masked_categorical_grad (one launch each way); actions and n_allowed are not differentiable."""
         lp, ent, k = _masked_evaluate_function(self.torch).apply(logits, self, bits, actions, bad_actions)
         return MaskedCategorical(actions, lp, ent, k)
+
+    # -- generalized advantage estimation (include/mcbs.h): advantages and returns of a whole [T, E] rollout in one launch --
+    def gae(self, rewards, values, episode_starts, last_values, last_dones, gamma: float, gae_lambda: float, bootstrap=None, advantages=None,
+            returns=None):
+        """Stable-Baselines3's RolloutBuffer.compute_returns_and_advantage on the device, one launch, bit for bit its float32 loop (the
+        operation order is in include/mcbs.h).  rewards, values float32 [T, E] and episode_starts uint8 [T, E] (nonzero = start) are device
+        tensors with unit inner stride: dense, or [T, :E] views of wider buffers, each with its own row stride; last_values float32 [E],
+        last_dones uint8 [E], contiguous.  bootstrap: optional float32 [T, E], the terminal observation's value where step t was truncated and
+        0 elsewhere (rewards + gamma * bootstrap replaces rewards; without it those two operations are not done at all).  advantages /
+        returns: preallocated float32 [T, E] outputs of the same kind, allocated when None; they may not overlap an input or each other
+        (McbsError).  E is the call's own: any producer's buffer is served.  -> (advantages, returns)."""
+        t = self.torch
+
+        def rows(x, dtype, what, shape=None):
+            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device:
+                raise ValueError(f"{what} must be a device {dtype} tensor on {self.device}")
+            if x.dim() != 2 or (shape is not None and tuple(x.shape) != shape):
+                raise ValueError(f"{what} must have shape [T, E]" + (f" = {list(shape)}" if shape is not None else "") + f", got {list(x.shape)}")
+            # the C side sees only the row stride: the elements of a row must be adjacent, and rows of a [T, :E] view at least E apart
+            if x.shape[1] > 1 and x.stride(1) != 1 or x.shape[0] > 1 and x.shape[1] > 0 and x.stride(0) < x.shape[1]:
+                raise ValueError(f"{what} must have unit inner stride and rows at least E elements apart (strides {x.stride()})")
+            return x
+
+        def vec(x, dtype, what, n):
+            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != (n,) or not x.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous device {dtype} tensor [{n}]")
+            return x
+
+        rows(rewards, t.float32, "rewards")
+        T, E = rewards.shape
+        shape = (T, E)
+        rows(values, t.float32, "values", shape)
+        rows(episode_starts, t.uint8, "episode_starts", shape)
+        vec(last_values, t.float32, "last_values", E)
+        vec(last_dones, t.uint8, "last_dones", E)
+        if bootstrap is not None:
+            rows(bootstrap, t.float32, "bootstrap", shape)
+        advantages = t.empty(shape, dtype=t.float32, device=self.device) if advantages is None else rows(advantages, t.float32, "advantages", shape)
+        returns = t.empty(shape, dtype=t.float32, device=self.device) if returns is None else rows(returns, t.float32, "returns", shape)
+        stride = lambda x: x.stride(0) if T > 1 else max(x.stride(0), E)
+        io = GaeIO(rewards.data_ptr(), values.data_ptr(), episode_starts.data_ptr(), bootstrap.data_ptr() if bootstrap is not None else None,
+                   last_values.data_ptr(), last_dones.data_ptr(), advantages.data_ptr(), returns.data_ptr(), T, E,
+                   stride(rewards), stride(values), stride(episode_starts), stride(bootstrap) if bootstrap is not None else 0,
+                   stride(advantages), stride(returns), float(gamma), float(gae_lambda))
+        _check(self.lib, self.lib.mcbs_gae(self._h, C.byref(io), self._stream()), "mcbs_gae")
+        return advantages, returns
 
     # -- feature encoder (include/mcbs.h): observation rows -> the one-hot float rows a policy's first layer takes --
     def feature_layout(self, layout) -> FeatureLayoutHandle:

@@ -273,6 +273,24 @@ class AttackerVecEnv:
         return self.engine.encode_features(self._feature_handle(bits is not None, reference_counts), fields, bits=bits, out=out, dtype=dtype,
                                            out_of_range=out_of_range)
 
+    # -- the rollout buffer (marlon_amd/rollout.py, mcbs_gae) --
+    @property
+    def observation_fields(self) -> Dict[str, object]:
+        """The observation this env last returned as the five int32 fields the engine writes (`scalars` [E, 7] unsplit, the others in
+        their own shapes): what encode_features() accepts and what rollout_buffer() stores; the wrapper's persistent tensors, not copies."""
+        return {k: self._obs[k] for k in FLAT_FIELDS[:5]}
+
+    def rollout_buffer(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, store_observations: bool = True):
+        """A `rollout.DeviceRolloutBuffer` of n_steps x n_envs transitions for this env: it stores the int32 observation fields
+        encode_features() accepts (not the mask fields — with discrete=True the packed masks of action_masks_packed() are stored
+        instead, `mask_bits`), actions of this wrapper's shape, and computes advantages and returns with one launch.  Its add() takes
+        `observation_fields` as obs.
+        store_observations=False: no observation storage (a trainer that keeps feature rows of its own)."""
+        from .rollout import DeviceRolloutBuffer
+        obs = self.observation_fields if store_observations else None
+        return DeviceRolloutBuffer(self.engine, n_steps, self.num_envs, obs=obs, action_shape=self._action_shape[1:],
+                                   mask_words=self.engine.packed_mask_words()[1] if self.discrete else None, gamma=gamma, gae_lambda=gae_lambda)
+
     # -- VecEnv surface --
     def reset(self):
         self.engine.reset()
