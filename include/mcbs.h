@@ -719,7 +719,7 @@ typedef struct mcbs_batch_variant_info {   /* 32 bytes */
     uint32_t words_per_set;       /* 1, 2 or 4: 64-bit words of a per-env node / credential set in the general layout */
     uint32_t wide;                /* 1: the cached-triple set lives in a column of its own (more than 256 cacheable credentials) */
     uint32_t coop;                /* 1: mcbs_step runs the G-lanes-per-env kernel (G = words_per_set) */
-    uint32_t lds_topo;            /* 1: the step kernel stages the topology's hot image in LDS (MCBS_LDS_TOPO=1 and it fits) */
+    uint32_t lds_topo;            /* always 0: the step kernel that staged the topology's hot image in LDS is gone; the field keeps the layout */
     uint32_t defender_kind;       /* MCBS_DEFENDER_* of the batch */
     uint32_t fused_wrapper;       /* 1: the batch admits the one-launch mcbs_attacker_wrapper_step */
     uint32_t fused_defender_obs;  /* 1: learned-defender turns can write the observation themselves (N <= 32, at most 256 services) */

@@ -89,15 +89,12 @@ struct mcbs_batch {
     StepCfg* C_dev = nullptr;       // device copy read by the step kernel through the scalar cache
     uint32_t* ere_lists_dev = nullptr;
     // developer switches, read ONCE at batch creation (getenv on every launch costs more than the launch itself)
-    bool lds_topo = false, no_fused_masks = false, slow_masks = false, no_row_masks = false;
-    bool no_fused_defender_obs = false;   // MCBS_NO_FUSED_DEFENDER_OBS=1: the learned defender's observation as a launch of its own
+    bool no_fused_masks = false, slow_masks = false, no_row_masks = false;
     bool no_quad_obs = false;       // MCBS_NO_QUAD_OBS=1: a wavefront per env for small topologies' observations with mask fields (rounds 1-2)
     bool force_quad_obs = false;    // MCBS_QUAD_OBS=1: obs_quad_kernel also where mask rows are whole cache lines
     bool no_block_masks = false;    // MCBS_NO_BLOCK_MASKS=1: round 2's fused mask writers (rows switched on / off per chunk)
-    bool no_fused_wrapper = false;  // MCBS_NO_FUSED_WRAPPER=1: mcbs_attacker_wrapper_step keeps its three launches (tests step both)
     size_t disc_stride = 0;         // mcbs_set_mask_discrete_stride: bytes between two envs' rows of mask_discrete (0: dense)
-    bool coop = false;              // mcbs_step runs the G-lanes-per-env kernel (mcbs_step_coop.hip): more than 64 nodes, sets of 2 or 4 words
-    uint32_t step_block_override = 0;
+    mcbs_batch_variant_info variant{};   // which kernels the batch's calls dispatch to: decided once, by batch_variant at the end of mcbs_batch_create
     uint8_t* arena = nullptr;       // every per-env column + bodies + init body, one allocation
     size_t arena_bytes = 0;
     ObsDigest* digest = nullptr;
@@ -309,6 +306,39 @@ extern "C" void mcbs_topology_destroy(mcbs_topology* t) {
 // ------------------------------------------------------------------ batch
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// reset_kernel: the envs env_mask names (NULL: all) back to step zero of a fresh episode; next_episode 1: as a new episode (mcbs_reset),
+// 0: the batch as it was created (mcbs_rewind)
+static void launch_step_zero(mcbs_batch* b, const uint8_t* env_mask, int next_episode, hipStream_t st) {
+    hipLaunchKernelGGL(reset_kernel, dim3((b->S.E + 127) / 128), dim3(128), 0, st, b->S, b->T, env_mask, next_episode);
+}
+
+// Which compiled variant the batch's calls dispatch to (mcbs_batch_variant_info, mcbs.h): everything it depends on is fixed once
+// mcbs_batch_create has laid the batch out, so it is decided there, once, and the launches read b->variant.
+static mcbs_batch_variant_info batch_variant(const mcbs_batch* b) {
+    const DevState& S = b->S;
+    const uint32_t def = b->cfg.defender_kind;
+    mcbs_batch_variant_info v{};
+    v.packed = S.packed; v.words_per_set = S.WT; v.wide = S.wide; v.defender_kind = def;
+    // large topologies: G = WT lanes per env (mcbs_step_coop.hip).  More than 64 nodes guarantees the list regions its level-1 loads
+    // cover (16 G discovery-order bytes, 32 G credential-cache bytes) lie inside the env's body; MCBS_NO_COOP=1: the one-lane kernel
+    // It pays while the one-lane kernel would leave SIMDs idle: measured on MI355X (profiles/round3_notes.md) 4.43 vs 4.96 us for
+    // 8 192 Chain-100 envs and 6.0 vs 7.4 us for 16 384 Random-256 envs, but 9.2 vs 9.0 us at 65 536 and 24.7 vs 22.9 us at 131 072 envs
+    // (the chip is full either way and the G lanes' redundant scalar work then costs issue slots): up to 512 one-lane wavefronts.
+    uint32_t coop_max_envs = 32768u;
+    if (const char* ov = getenv("MCBS_COOP_MAX_ENVS")) coop_max_envs = (uint32_t)strtoul(ov, nullptr, 10);   // experiments
+    v.coop = !S.packed && S.WT >= 2u && S.N > 64u && !S.wide && !getenv("MCBS_NO_COOP") && S.E <= coop_max_envs &&
+             (def == MCBS_DEFENDER_NONE || def == MCBS_DEFENDER_SCAN_AND_REIMAGE);
+    // mcbs_attacker_wrapper_step in ONE launch (mcbs_wrapper_fused.hip): packed batch whose reset image is held in the config, at most 16
+    // nodes / cached credentials; MCBS_NO_FUSED_WRAPPER=1 keeps the three launches (tests step both)
+    v.fused_wrapper = !(getenv("MCBS_NO_FUSED_WRAPPER") || b->no_fused_masks || !S.packed || !b->C.init_image_ok || S.N > 16u ||
+                        b->cfg.maximum_node_count > 16u || b->cfg.maximum_total_credentials > 16u || b->topo->H()->n_triples > 15u ||
+                        def == MCBS_DEFENDER_RANDOM_EVENTS);
+    // the learned defender's observation written by the turn kernel's own workgroups (one launch per turn): topologies of up to 32 nodes
+    // and 256 services; MCBS_NO_FUSED_DEFENDER_OBS=1: the separate launch
+    v.fused_defender_obs = def == MCBS_DEFENDER_EXTERNAL && S.N <= 32u && b->C.n_services <= 256u && !getenv("MCBS_NO_FUSED_DEFENDER_OBS");
+    return v;
+}
+
 extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg* cfg, mcbs_batch** out) {
     if (!topo || !cfg || !out) return fail(MCBS_EINVAL, "null argument");
     if (cfg->abi_version != MCBS_ABI_VERSION) return fail(MCBS_EINVAL, "cfg ABI version %u, library %u", cfg->abi_version, MCBS_ABI_VERSION);
@@ -340,11 +370,10 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     if (!b) return fail(MCBS_ENOMEM, "out of memory");
     b->topo = topo;
     b->cfg = *cfg;
-    b->lds_topo = getenv("MCBS_LDS_TOPO") != nullptr; b->no_fused_masks = getenv("MCBS_NO_FUSED_MASKS") != nullptr;
+    b->no_fused_masks = getenv("MCBS_NO_FUSED_MASKS") != nullptr;
     b->slow_masks = getenv("MCBS_SLOW_MASKS") != nullptr; b->no_row_masks = getenv("MCBS_NO_ROW_MASKS") != nullptr;
-    b->no_fused_wrapper = getenv("MCBS_NO_FUSED_WRAPPER") != nullptr; b->no_block_masks = getenv("MCBS_NO_BLOCK_MASKS") != nullptr;
-    b->no_quad_obs = getenv("MCBS_NO_QUAD_OBS") != nullptr; b->no_fused_defender_obs = getenv("MCBS_NO_FUSED_DEFENDER_OBS") != nullptr; b->force_quad_obs = getenv("MCBS_QUAD_OBS") != nullptr;
-    if (const char* ov = getenv("MCBS_STEP_BLOCK")) b->step_block_override = (uint32_t)atoi(ov);   // experiments only (64, 128 or 256)
+    b->no_block_masks = getenv("MCBS_NO_BLOCK_MASKS") != nullptr;
+    b->no_quad_obs = getenv("MCBS_NO_QUAD_OBS") != nullptr; b->force_quad_obs = getenv("MCBS_QUAD_OBS") != nullptr;
     const uint32_t E = cfg->n_envs, N = h->n_nodes;
     DevState& S = b->S;
     S.E = E; S.N = N; S.NW = (N + 63) / 64;
@@ -402,15 +431,6 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     S.wide = S.TW > 4u ? 1u : 0u;             // the cached-triple set does not fit 4 words: own column array (DevState::cach)
     if (!S.wide && S.TW > wt) wt = S.TW;
     S.WT = wt <= 1 ? 1 : (wt == 2 ? 2 : 4);
-    // large topologies: G = WT lanes per env (mcbs_step_coop.hip).  More than 64 nodes guarantees the list regions its level-1 loads
-    // cover (16 G discovery-order bytes, 32 G credential-cache bytes) lie inside the env's body; MCBS_NO_COOP=1: the one-lane kernel
-    // It pays while the one-lane kernel would leave SIMDs idle: measured on MI355X (profiles/round3_notes.md) 4.43 vs 4.96 us for
-    // 8 192 Chain-100 envs and 6.0 vs 7.4 us for 16 384 Random-256 envs, but 9.2 vs 9.0 us at 65 536 and 24.7 vs 22.9 us at 131 072 envs
-    // (the chip is full either way and the G lanes' redundant scalar work then costs issue slots): up to 512 one-lane wavefronts.
-    uint32_t coop_max_envs = 32768u;
-    if (const char* ov = getenv("MCBS_COOP_MAX_ENVS")) coop_max_envs = (uint32_t)strtoul(ov, nullptr, 10);   // experiments
-    b->coop = !S.packed && S.WT >= 2u && N > 64u && !S.wide && !b->lds_topo && !getenv("MCBS_NO_COOP") && E <= coop_max_envs &&
-              (cfg->defender_kind == MCBS_DEFENDER_NONE || cfg->defender_kind == MCBS_DEFENDER_SCAN_AND_REIMAGE);
     const size_t o_masks = take(S.packed ? 32ull * E : 8ull * M_COUNT * S.WT * E);   // packed: the sets column, then the lists-word column
     const size_t o_cach = S.wide ? take(8ull * S.TW * E) : 0;
     const bool has_def = cfg->defender_kind != MCBS_DEFENDER_NONE;   // in-env or external: both re-image nodes
@@ -531,9 +551,10 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     e = hipMalloc(&b->C_dev, sizeof(StepCfg));
     if (e == hipSuccess) e = hipMemcpy(b->C_dev, &b->C, sizeof(StepCfg), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(b->arena); delete b; return fail(MCBS_EHIP, "config upload failed: %s", hipGetErrorString(e)); }
-    hipLaunchKernelGGL(reset_kernel, dim3((E + 127) / 128), dim3(128), 0, 0, S, b->T, (const uint8_t*)nullptr, 0);
+    launch_step_zero(b, nullptr, 0, nullptr);
     e = hipDeviceSynchronize();
     if (e != hipSuccess) { (void)hipFree(b->arena); delete b; return fail(MCBS_EHIP, "initial reset failed: %s", hipGetErrorString(e)); }
+    b->variant = batch_variant(b);
     *out = b;
     return MCBS_OK;
 }
@@ -557,7 +578,7 @@ static int launch_ok(const char* what) {
 extern "C" int mcbs_reset(mcbs_batch* b, const uint8_t* env_mask, void* stream) {
     if (!b) return fail(MCBS_EINVAL, "null batch");
     MCBS_ON_DEVICE(b);
-    hipLaunchKernelGGL(reset_kernel, dim3((b->S.E + 127) / 128), dim3(128), 0, (hipStream_t)stream, b->S, b->T, env_mask, 1);
+    launch_step_zero(b, env_mask, 1, (hipStream_t)stream);
     if (!env_mask) b->all_fresh = true;
     b->digest_state = !env_mask ? 0 : (b->digest_state == 1 ? 2 : b->digest_state);
     return launch_ok("reset");
@@ -566,7 +587,7 @@ extern "C" int mcbs_reset(mcbs_batch* b, const uint8_t* env_mask, void* stream) 
 extern "C" int mcbs_rewind(mcbs_batch* b, void* stream) {
     if (!b) return fail(MCBS_EINVAL, "null batch");
     MCBS_ON_DEVICE(b);
-    hipLaunchKernelGGL(reset_kernel, dim3((b->S.E + 127) / 128), dim3(128), 0, (hipStream_t)stream, b->S, b->T, (const uint8_t*)nullptr, 0);
+    launch_step_zero(b, nullptr, 0, (hipStream_t)stream);
     b->all_fresh = true;
     b->digest_state = 0;
     return launch_ok("rewind");
@@ -624,80 +645,77 @@ static int timing_end(mcbs_batch* b, hipStream_t st, size_t slot) {
     return MCBS_OK;
 }
 
-// Kernel variant: words per set kept in registers (1, 2 or 4; 0 = packed batch), where the topology's hot image is read from, and
-// which defender is configured (its code and loads are compiled out otherwise).
-template <int PHASE, int WT, int DEF, bool MANY = false>
-static void launch_step_v(mcbs_batch* b, const StepIO& io, hipStream_t st, const RollArgs& roll = RollArgs{}) {
-    const uint32_t E = b->S.E, lds = b->C.hot_bytes;
-    // Where the step kernel reads the topology's hot image from.  Measured on MI355X (profiles/round2_notes.md, tools/sweep_shapes.sh):
-    // through L1 / L2 with 64-thread workgroups beats a per-workgroup LDS copy at every BASELINE shape — 5.4 vs 5.6 us at 65 536 Chain-10
-    // envs, 5.5 vs 7.4 us for the Chain-100 shard (45 KB image, 128 wavefronts), 7.8 vs 8.5 us for Random-256 — once no table read is left
-    // behind a store (leak payload prefetched, defender look-ups from scalars).  One-wavefront workgroups spread over all CUs; a copy per
-    // workgroup only pays when many wavefronts share it, and then the image is L1-resident anyway.  MCBS_LDS_TOPO=1 selects the staged
-    // variant (images up to 60 KB) for experiments.
-    if (b->lds_topo && lds <= 60000u) {
-        // workgroup size: as large as still leaves one workgroup per CU (256) — every workgroup stages its own copy of the hot
-        // image, so at 65 536 envs 64-thread workgroups re-read it 4x as often as 256-thread ones, while 512 threads would leave half
-        // of the CUs idle
-        uint32_t block = lds <= 8192u ? 64u : 256u;
-        while (block < 256u && E / (block * 2u) >= 256u) block *= 2u;
-        if (b->step_block_override) block = b->step_block_override;
-        const uint32_t shm = lds + (b->S.wide ? block * b->S.TW * 8u : 0u);
-        if constexpr (MANY) hipLaunchKernelGGL((step_many_kernel<WT, true, DEF>), dim3((E + block - 1) / block), dim3(block), shm, st, b->S, b->T, b->C_dev, io, roll);
-        else hipLaunchKernelGGL((step_kernel<PHASE, WT, true, DEF>), dim3((E + block - 1) / block), dim3(block), shm, st, b->S, b->T, b->C_dev, io);
-    } else {
-        const uint32_t block = 64u;                      // fixed (the kernel relies on it); beyond one wavefront per SIMD the shape no longer
-                                                         // matters: 22.7 (64) vs 22.2 us (256) at 131 072 Random-256 envs
-        const uint32_t shm = b->S.wide ? block * b->S.TW * 8u : 0u;
-        if constexpr (MANY) hipLaunchKernelGGL((step_many_kernel<WT, false, DEF>), dim3((E + block - 1) / block), dim3(block), shm, st, b->S, b->T, b->C_dev, io, roll);
-        else hipLaunchKernelGGL((step_kernel<PHASE, WT, false, DEF>), dim3((E + block - 1) / block), dim3(block), shm, st, b->S, b->T, b->C_dev, io);
-    }
+// Value -> template argument: calls f(std::integral_constant<int, V>{}) for the V among Vs that equals v, and for the LAST V when none
+// does (the else arm of the if / else ladders this replaces).  A call site lists exactly the values it may instantiate kernels for.
+template <int V, int... Vs, class F>
+static void pick(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>{});
+    else if (v == V) f(std::integral_constant<int, V>{});
+    else pick<Vs...>(v, f);
 }
 
-template <int PHASE, int WT, bool MANY = false>
-static void launch_step_nw(mcbs_batch* b, const StepIO& io, hipStream_t st, const RollArgs& roll) {
-    if (b->cfg.defender_kind == MCBS_DEFENDER_SCAN_AND_REIMAGE) launch_step_v<PHASE, WT, MCBS_DEFENDER_SCAN_AND_REIMAGE, MANY>(b, io, st, roll);
-    else if (b->cfg.defender_kind == MCBS_DEFENDER_RANDOM_EVENTS) launch_step_v<PHASE, WT, MCBS_DEFENDER_RANDOM_EVENTS, MANY>(b, io, st, roll);
-    else if (b->cfg.defender_kind == MCBS_DEFENDER_EXTERNAL) launch_step_v<PHASE, WT, MCBS_DEFENDER_EXTERNAL, MANY>(b, io, st, roll);
-    else launch_step_v<PHASE, WT, MCBS_DEFENDER_NONE, MANY>(b, io, st, roll);
+// The step family's variant: f(WT, DEF) with WT = words per set kept in registers (1, 2 or 4; 0 = packed batch: one word of registers
+// each) and DEF = the configured defender (its code and loads are compiled out otherwise)
+template <class F>
+static void step_variant(const mcbs_batch* b, F&& f) {
+    pick<0, 1, 2, 4>(b->S.packed ? 0 : (int)b->S.WT, [&](auto wt) {
+        pick<MCBS_DEFENDER_SCAN_AND_REIMAGE, MCBS_DEFENDER_RANDOM_EVENTS, MCBS_DEFENDER_EXTERNAL, MCBS_DEFENDER_NONE>(
+            (int)b->cfg.defender_kind, [&](auto def) { f(wt, def); });
+    });
 }
 
-template <int G>
-static void launch_step_coop(mcbs_batch* b, const StepIO& io, hipStream_t st) {
-    const uint32_t epw = 64u / G;
-    const dim3 grid((b->S.E + epw - 1u) / epw), block(64);
-    if (b->cfg.defender_kind == MCBS_DEFENDER_SCAN_AND_REIMAGE)
-        hipLaunchKernelGGL((step_coop_kernel<G, MCBS_DEFENDER_SCAN_AND_REIMAGE>), grid, block, 0, st, b->S, b->T, b->C_dev, io);
-    else hipLaunchKernelGGL((step_coop_kernel<G, MCBS_DEFENDER_NONE>), grid, block, 0, st, b->S, b->T, b->C_dev, io);
-}
+// Launch shape of every kernel built on step_body (mcbs_step.hip): one lane per env in one-wavefront workgroups — fixed, the kernels rely
+// on it; beyond one wavefront per SIMD the shape no longer matters: 22.7 (64) vs 22.2 us (256 threads) at 131 072 Random-256 envs —
+// and, as dynamic LDS, the lanes' columns of a wide cached-triple set.  The topology's hot image is read through L1 / L2: a copy in LDS
+// per workgroup measured slower at every BASELINE shape in rounds 2 and 3 (profiles/step_dispatch_refactor.md) and is gone.
+static dim3 step_grid(const mcbs_batch* b) { return dim3((b->S.E + 63u) / 64u); }
+static uint32_t step_lds(const mcbs_batch* b) { return b->S.wide ? 64u * b->S.TW * 8u : 0u; }
 
 template <int PHASE, bool MANY = false>
 static int launch_step(mcbs_batch* b, const StepIO& io, hipStream_t st, const char* what, const RollArgs& roll = RollArgs{}) {
     b->all_fresh = false;
-    if (PHASE == 0 && !MANY && b->coop) {
-        if (b->S.WT == 2) launch_step_coop<2>(b, io, st); else launch_step_coop<4>(b, io, st);
+    if (PHASE == 0 && !MANY && b->variant.coop) {           // G = WT lanes per env, G envs fewer per wavefront
+        pick<2, 4>((int)b->S.WT, [&](auto g) {
+            pick<MCBS_DEFENDER_SCAN_AND_REIMAGE, MCBS_DEFENDER_NONE>((int)b->cfg.defender_kind, [&](auto def) {
+                constexpr uint32_t epw = 64u / decltype(g)::value;
+                hipLaunchKernelGGL((step_coop_kernel<decltype(g)::value, decltype(def)::value>), dim3((b->S.E + epw - 1u) / epw), dim3(64), 0, st,
+                                   b->S, b->T, b->C_dev, io);
+            });
+        });
         return launch_ok(what);
     }
-    if (b->S.packed) launch_step_nw<PHASE, 0, MANY>(b, io, st, roll);       // WT 0: packed sets (one word of registers each)
-    else if (b->S.WT == 1) launch_step_nw<PHASE, 1, MANY>(b, io, st, roll);
-    else if (b->S.WT == 2) launch_step_nw<PHASE, 2, MANY>(b, io, st, roll);
-    else launch_step_nw<PHASE, 4, MANY>(b, io, st, roll);
+    step_variant(b, [&](auto wt, auto def) {
+        constexpr int WT = decltype(wt)::value, DEF = decltype(def)::value;
+        if constexpr (MANY) hipLaunchKernelGGL((step_many_kernel<WT, false, DEF>), step_grid(b), dim3(64), step_lds(b), st, b->S, b->T, b->C_dev, io, roll);
+        else hipLaunchKernelGGL((step_kernel<PHASE, WT, false, DEF>), step_grid(b), dim3(64), step_lds(b), st, b->S, b->T, b->C_dev, io);
+    });
     return launch_ok(what);
+}
+
+// A step launch between the two event records of mcbs_timing_enable
+template <bool MANY>
+static int launch_step_timed(mcbs_batch* b, const StepIO& io, hipStream_t st, const char* what) {
+    size_t slot;
+    int rc = timing_begin(b, st, &slot);
+    if (rc) return rc;
+    if ((rc = launch_step<0, MANY>(b, io, st, what))) return rc;
+    return timing_end(b, st, slot);
+}
+
+// The in-env defender's draws of a MCBS_RNG_TAPE batch come from the caller's tape, one step's worth: a single step needs the tape to
+// have been set; the entry point `many` (several steps per launch) cannot run from a tape at all
+static int draws_ok(const mcbs_batch* b, const char* many = nullptr) {
+    if (b->cfg.rng_kind != MCBS_RNG_TAPE || b->cfg.defender_kind == MCBS_DEFENDER_NONE) return MCBS_OK;
+    if (many) return fail(MCBS_ESTATE, "%s needs the Philox generator: a draw tape holds one step's draws", many);
+    return b->tape ? MCBS_OK : fail(MCBS_ESTATE, "rng_kind is TAPE but no draw tape was set (mcbs_set_draw_tape)");
 }
 
 extern "C" int mcbs_step(mcbs_batch* b, const int32_t* actions, float* reward, uint8_t* terminated,
                          const mcbs_info_buffers* info, void* stream) {
     if (!b || !actions || !reward || !terminated) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
-    if (b->cfg.rng_kind == MCBS_RNG_TAPE && b->cfg.defender_kind != MCBS_DEFENDER_NONE && !b->tape)
-        return fail(MCBS_ESTATE, "rng_kind is TAPE but no draw tape was set (mcbs_set_draw_tape)");
-    hipStream_t st = (hipStream_t)stream;
-    const StepIO io = make_io(b, actions, reward, terminated, info);
-    size_t slot;
-    int rc = timing_begin(b, st, &slot);
-    if (rc) return rc;
-    if ((rc = launch_step<0>(b, io, st, "step"))) return rc;
-    return timing_end(b, st, slot);
+    if (const int rc = draws_ok(b)) return rc;
+    return launch_step_timed<false>(b, make_io(b, actions, reward, terminated, info), (hipStream_t)stream, "step");
 }
 
 // n_steps consecutive steps in one launch: scripted / recorded / pre-sampled action sequences (replaying a trace, random-agent
@@ -707,16 +725,10 @@ extern "C" int mcbs_step_many(mcbs_batch* b, const int32_t* actions, float* rewa
     if (!b || !actions || !reward || !terminated) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
     if (n_steps == 0) return MCBS_OK;
-    if (b->cfg.rng_kind == MCBS_RNG_TAPE && b->cfg.defender_kind != MCBS_DEFENDER_NONE)
-        return fail(MCBS_ESTATE, "mcbs_step_many needs the Philox generator: a draw tape holds one step's draws");
-    hipStream_t st = (hipStream_t)stream;
+    if (const int rc = draws_ok(b, "mcbs_step_many")) return rc;
     StepIO io = make_io(b, actions, reward, terminated, nullptr);
     io.n_steps = n_steps;
-    size_t slot;
-    int rc = timing_begin(b, st, &slot);
-    if (rc) return rc;
-    if ((rc = launch_step<0, true>(b, io, st, "step (many)"))) return rc;
-    return timing_end(b, st, slot);
+    return launch_step_timed<true>(b, io, (hipStream_t)stream, "step (many)");
 }
 
 // Random agents entirely on the device: every step's action is drawn from the env's own state inside the step kernel
@@ -727,8 +739,7 @@ extern "C" int mcbs_rollout_random(mcbs_batch* b, int32_t valid, uint64_t seed, 
     if (!b || !reward || !terminated) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
     if (n_steps == 0) return MCBS_OK;
-    if (b->cfg.rng_kind == MCBS_RNG_TAPE && b->cfg.defender_kind != MCBS_DEFENDER_NONE)
-        return fail(MCBS_ESTATE, "mcbs_rollout_random needs the Philox generator: a draw tape holds one step's draws");
+    if (const int rc = draws_ok(b, "mcbs_rollout_random")) return rc;
     hipStream_t st = (hipStream_t)stream;
     RollArgs roll;
     roll.mode = valid ? 2u : 1u; roll.nmax = b->cfg.maximum_node_count; roll.cmax = b->cfg.maximum_total_credentials;
@@ -893,16 +904,16 @@ static int launch_region(mcbs_batch* b, int8_t* dst, size_t env_stride, size_t r
         if (gy > b->S.E) gy = b->S.E;
         if (flat) { gx = 1; gy = (uint32_t)(((uint64_t)chunks * b->S.E + 255) / 256 < 4096 ? ((uint64_t)chunks * b->S.E + 255) / 256 : 4096); }
         const dim3 fgrid(gx, gy);
-#define MCBS_LAUNCH_FAST(REG_, FLAT_) hipLaunchKernelGGL((mask_fast_kernel<REG_, FLAT_>), fgrid, dim3(256), 0, st, b->S, b->digest, dst, env_stride, \
-        region_off, (uint32_t)len, RL, Cc, Nm, b->C.R, fd(RL), fd(Cc), fd(Nm), env_mask, masks_only ? 0u : 1u, fd((uint32_t)chunks))
-        if (REGION == 0) { if (flat) MCBS_LAUNCH_FAST(0, true); else MCBS_LAUNCH_FAST(0, false); }
-        else { if (flat) MCBS_LAUNCH_FAST(1, true); else MCBS_LAUNCH_FAST(1, false); }
-#undef MCBS_LAUNCH_FAST
+        pick<1, 0>((int)flat, [&](auto fl) {
+            hipLaunchKernelGGL((mask_fast_kernel<(REGION == 0 ? 0 : 1), decltype(fl)::value != 0>), fgrid, dim3(256), 0, st, b->S, b->digest, dst, env_stride,
+                               region_off, (uint32_t)len, RL, Cc, Nm, b->C.R, fd(RL), fd(Cc), fd(Nm), env_mask, masks_only ? 0u : 1u, fd((uint32_t)chunks));
+        });
         return launch_ok("mask (fast)");
     }
-    if (W == 16) hipLaunchKernelGGL((mask_kernel<16, REGION>), grid, dim3(256), 0, st, b->S, b->T, b->C_dev, b->digest, dst, env_stride, region_off, Nm, Cm, env_mask, masks_only ? 0u : 1u);
-    else if (W == 4) hipLaunchKernelGGL((mask_kernel<4, REGION>), grid, dim3(256), 0, st, b->S, b->T, b->C_dev, b->digest, dst, env_stride, region_off, Nm, Cm, env_mask, masks_only ? 0u : 1u);
-    else hipLaunchKernelGGL((mask_kernel<1, REGION>), grid, dim3(256), 0, st, b->S, b->T, b->C_dev, b->digest, dst, env_stride, region_off, Nm, Cm, env_mask, masks_only ? 0u : 1u);
+    pick<16, 4, 1>(W, [&](auto w) {
+        hipLaunchKernelGGL((mask_kernel<decltype(w)::value, REGION>), grid, dim3(256), 0, st, b->S, b->T, b->C_dev, b->digest, dst, env_stride, region_off, Nm, Cm,
+                           env_mask, masks_only ? 0u : 1u);
+    });
     return launch_ok("mask");
 }
 
@@ -943,22 +954,28 @@ extern "C" int mcbs_step_observe(mcbs_batch* b, const int32_t* actions, float* r
                                  const mcbs_info_buffers* info, const mcbs_obs_buffers* obs, void* stream) {
     if (!b || !actions || !reward || !terminated || !obs) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
-    if (b->cfg.rng_kind == MCBS_RNG_TAPE && b->cfg.defender_kind != MCBS_DEFENDER_NONE && !b->tape)
-        return fail(MCBS_ESTATE, "rng_kind is TAPE but no draw tape was set (mcbs_set_draw_tape)");
+    int rc = draws_ok(b);
+    if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
     const StepIO io = make_io(b, actions, reward, terminated, info);
-    int rc = launch_step<1>(b, io, st, "step (attacker phase)");
+    rc = launch_step<1>(b, io, st, "step (attacker phase)");
     if (rc) return rc;
     if ((rc = launch_obs(b, obs, st))) return rc;
     return launch_step<2>(b, io, st, "step (defender phase)");
 }
 
+// every pointer member of the buffer struct *w but its last `optional` ones is set
+template <class W>
+static bool arrays_set(const W* w, size_t optional) {
+    const void* const* p = reinterpret_cast<const void* const*>(w);
+    for (size_t i = 0; i + optional < sizeof(W) / sizeof(void*); ++i) if (!p[i]) return false;
+    return true;
+}
+
 extern "C" int mcbs_attacker_wrapper_post(mcbs_batch* b, const mcbs_wrapper_buffers* w, float modifier, int32_t max_timesteps, void* stream) {
     if (!b || !w) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
-    const void* const* p = reinterpret_cast<const void* const*>(w);
-    for (size_t i = 0; i + 1 < sizeof(*w) / sizeof(void*); ++i)          // `executed` (the last member) is not written by this call
-        if (!p[i]) return fail(MCBS_EINVAL, "mcbs_wrapper_buffers: every array but `executed` is required");
+    if (!arrays_set(w, 1)) return fail(MCBS_EINVAL, "mcbs_wrapper_buffers: every array but `executed` is required");   // (the last member: not written by this call)
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(w->n_done, 0, sizeof(int32_t), st));
     hipLaunchKernelGGL(wrapper_post_kernel, dim3((b->S.E + 255) / 256), dim3(256), 0, st, b->S.E, *w, modifier, max_timesteps);
@@ -987,9 +1004,7 @@ extern "C" int mcbs_copy_rows_masked(mcbs_batch* b, const mcbs_row_copies* copie
 static int finish_args(mcbs_batch* b, const mcbs_wrapper_buffers* w, float modifier, int32_t max_timesteps, int32_t auto_reset,
                        const mcbs_row_copies* keep, const mcbs_row_copies* fresh, WrapperFinishArgs* A) {
     if (!b || !w) return fail(MCBS_EINVAL, "null argument");
-    const void* const* p = reinterpret_cast<const void* const*>(w);
-    for (size_t i = 0; i + 2 < sizeof(*w) / sizeof(void*); ++i)          // n_done and executed (the last two members) may be NULL
-        if (!p[i]) return fail(MCBS_EINVAL, "mcbs_wrapper_buffers: every array but n_done and executed is required");
+    if (!arrays_set(w, 2)) return fail(MCBS_EINVAL, "mcbs_wrapper_buffers: every array but n_done and executed is required");   // (the last two members)
     mcbs_row_copies none{};
     const mcbs_row_copies* rc[2] = {keep ? keep : &none, fresh ? fresh : &none};
     for (const mcbs_row_copies* c : rc) {
@@ -1014,54 +1029,20 @@ extern "C" int mcbs_attacker_wrapper_finish(mcbs_batch* b, const mcbs_wrapper_bu
     return launch_ok("wrapper finish");
 }
 
-template <int WT, int DEF>
-static void launch_step2_finish_v(mcbs_batch* b, const StepIO& io, const WrapperFinishArgs& A, hipStream_t st) {
-    const uint32_t shm = b->S.wide ? 64u * b->S.TW * 8u : 0u;
-    hipLaunchKernelGGL((step2_finish_kernel<WT, DEF>), dim3((b->S.E + 63u) / 64u), dim3(64), shm, st, b->S, b->T, b->C_dev, io, A);
-}
-template <int WT>
-static void launch_step2_finish_nw(mcbs_batch* b, const StepIO& io, const WrapperFinishArgs& A, hipStream_t st) {
-    if (b->cfg.defender_kind == MCBS_DEFENDER_SCAN_AND_REIMAGE) launch_step2_finish_v<WT, MCBS_DEFENDER_SCAN_AND_REIMAGE>(b, io, A, st);
-    else if (b->cfg.defender_kind == MCBS_DEFENDER_RANDOM_EVENTS) launch_step2_finish_v<WT, MCBS_DEFENDER_RANDOM_EVENTS>(b, io, A, st);
-    else if (b->cfg.defender_kind == MCBS_DEFENDER_EXTERNAL) launch_step2_finish_v<WT, MCBS_DEFENDER_EXTERNAL>(b, io, A, st);
-    else launch_step2_finish_v<WT, MCBS_DEFENDER_NONE>(b, io, A, st);
-}
-
-template <int WT, int DEF>
-static void launch_decode_step1_v(mcbs_batch* b, const StepIO& io, const int64_t* md, const int64_t* discrete, uint8_t* invalid, hipStream_t st) {
-    const uint32_t shm = b->S.wide ? 64u * b->S.TW * 8u : 0u;
-    hipLaunchKernelGGL((decode_step1_kernel<WT, DEF>), dim3((b->S.E + 63u) / 64u), dim3(64), shm, st, b->S, b->T, b->C_dev, io,
-                       b->cfg.maximum_node_count, b->cfg.maximum_total_credentials, md, discrete, invalid);
-}
-template <int WT>
-static void launch_decode_step1_nw(mcbs_batch* b, const StepIO& io, const int64_t* md, const int64_t* discrete, uint8_t* invalid, hipStream_t st) {
-    if (b->cfg.defender_kind == MCBS_DEFENDER_SCAN_AND_REIMAGE) launch_decode_step1_v<WT, MCBS_DEFENDER_SCAN_AND_REIMAGE>(b, io, md, discrete, invalid, st);
-    else if (b->cfg.defender_kind == MCBS_DEFENDER_RANDOM_EVENTS) launch_decode_step1_v<WT, MCBS_DEFENDER_RANDOM_EVENTS>(b, io, md, discrete, invalid, st);
-    else if (b->cfg.defender_kind == MCBS_DEFENDER_EXTERNAL) launch_decode_step1_v<WT, MCBS_DEFENDER_EXTERNAL>(b, io, md, discrete, invalid, st);
-    else launch_decode_step1_v<WT, MCBS_DEFENDER_NONE>(b, io, md, discrete, invalid, st);
-}
-
-static bool fused_wrapper_batch_ok(const mcbs_batch* b) {
-    return !(b->no_fused_wrapper || b->lds_topo || b->no_fused_masks || !b->S.packed || !b->C.init_image_ok || b->S.N > 16u ||
-             b->cfg.maximum_node_count > 16u || b->cfg.maximum_total_credentials > 16u || b->topo->H()->n_triples > 15u ||
-             b->cfg.defender_kind == MCBS_DEFENDER_RANDOM_EVENTS);
-}
-
 extern "C" int32_t mcbs_attacker_wrapper_step_launches(const mcbs_batch* b, int32_t with_masks) {
     if (!b) return 0;
-    return (!with_masks && fused_wrapper_batch_ok(b)) ? 1 : 3;
+    return (!with_masks && b->variant.fused_wrapper) ? 1 : 3;
 }
 
-// The whole wrapper step in ONE launch (mcbs_wrapper_fused.hip) when the batch and the request fit it: packed batch whose reset image is
-// held in the config, at most 16 nodes / cached credentials, no mask field, observation rows of whole 16-byte vectors, every requested
-// field paired with its terminal array and its reset row (auto_reset).  Returns 1 when it launched, 0 when the caller should run the
-// three launches, < 0 on error.
+// The whole wrapper step in ONE launch (mcbs_wrapper_fused.hip) when the batch (variant.fused_wrapper) and the request fit it: no mask
+// field, observation rows of whole 16-byte vectors, every requested field paired with its terminal array and its reset row
+// (auto_reset).  Returns 1 when it launched, 0 when the caller should run the three launches, < 0 on error.
 static int try_fused_wrapper_step(mcbs_batch* b, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded, const StepIO& io,
                                   const mcbs_obs_buffers* o, const mcbs_wrapper_buffers* w, float modifier, int32_t max_timesteps, int32_t auto_reset,
                                   const mcbs_row_copies* keep, const mcbs_row_copies* fresh, hipStream_t st) {
     const mcbs_topo_header* h = b->topo->H();
     const uint32_t Nm = b->cfg.maximum_node_count, Cm = b->cfg.maximum_total_credentials, K = b->cfg.maximum_discoverable_credentials_per_action;
-    if (!fused_wrapper_batch_ok(b) || o->mask_local || o->mask_remote || o->mask_connect || o->mask_discrete) return 0;
+    if (!b->variant.fused_wrapper || o->mask_local || o->mask_remote || o->mask_connect || o->mask_discrete) return 0;
     const uint32_t NP = b->C.n_props;
     FusedArgs A{};
     A.w = *w; A.modifier = modifier; A.max_timesteps = max_timesteps; A.auto_reset = auto_reset;
@@ -1099,11 +1080,9 @@ static int try_fused_wrapper_step(mcbs_batch* b, const int64_t* multidiscrete, c
     A.n_triples = h->n_triples;
     b->all_fresh = false;
     const dim3 grid((b->S.E + 63u) / 64u), block(FUSED_THREADS);
-    switch (b->cfg.defender_kind) {
-    case MCBS_DEFENDER_SCAN_AND_REIMAGE: hipLaunchKernelGGL((wrapper_fused_kernel<MCBS_DEFENDER_SCAN_AND_REIMAGE>), grid, block, 0, st, b->S, b->T, b->C_dev, io, A); break;
-    case MCBS_DEFENDER_EXTERNAL: hipLaunchKernelGGL((wrapper_fused_kernel<MCBS_DEFENDER_EXTERNAL>), grid, block, 0, st, b->S, b->T, b->C_dev, io, A); break;
-    default: hipLaunchKernelGGL((wrapper_fused_kernel<MCBS_DEFENDER_NONE>), grid, block, 0, st, b->S, b->T, b->C_dev, io, A); break;
-    }
+    pick<MCBS_DEFENDER_SCAN_AND_REIMAGE, MCBS_DEFENDER_EXTERNAL, MCBS_DEFENDER_NONE>((int)b->cfg.defender_kind, [&](auto def) {
+        hipLaunchKernelGGL((wrapper_fused_kernel<decltype(def)::value>), grid, block, 0, st, b->S, b->T, b->C_dev, io, A);
+    });
     const int rc = launch_ok("wrapper step (one launch)");
     if (rc) return rc;
     b->digest_state = 1;       // every env's digest was written (or, for an intercepted action, stands)
@@ -1119,43 +1098,32 @@ extern "C" int mcbs_attacker_wrapper_step(mcbs_batch* b, const int64_t* multidis
     WrapperFinishArgs A;
     int rc = finish_args(b, w, modifier, max_timesteps, auto_reset, keep, fresh, &A);      // (all checks before the first launch)
     if (rc) return rc;
-    if (b->cfg.rng_kind == MCBS_RNG_TAPE && b->cfg.defender_kind != MCBS_DEFENDER_NONE && !b->tape)
-        return fail(MCBS_ESTATE, "rng_kind is TAPE but no draw tape was set (mcbs_set_draw_tape)");
+    if ((rc = draws_ok(b))) return rc;
     if (!multidiscrete == !discrete) return fail(MCBS_EINVAL, "need exactly one action encoding");
     hipStream_t st = (hipStream_t)stream;
     const StepIO io = make_io(b, decoded, const_cast<float*>(w->reward), const_cast<uint8_t*>(w->terminated), info);
     uint8_t* invalid = const_cast<uint8_t*>(w->invalid);
     if ((rc = try_fused_wrapper_step(b, multidiscrete, discrete, decoded, io, obs, w, modifier, max_timesteps, auto_reset, keep, fresh, st)) != 0)
         return rc < 0 ? rc : MCBS_OK;
-    if (b->lds_topo) {                       // (developer switch: the staged variant keeps separate launches)
-        if ((rc = mcbs_decode_attacker_actions(b, multidiscrete, discrete, decoded, invalid, stream))) return rc;
-        if ((rc = launch_step<1>(b, io, st, "step (attacker phase)"))) return rc;
-    } else {
-        b->all_fresh = false;
-        if (b->S.packed) launch_decode_step1_nw<0>(b, io, multidiscrete, discrete, invalid, st);
-        else if (b->S.WT == 1) launch_decode_step1_nw<1>(b, io, multidiscrete, discrete, invalid, st);
-        else if (b->S.WT == 2) launch_decode_step1_nw<2>(b, io, multidiscrete, discrete, invalid, st);
-        else launch_decode_step1_nw<4>(b, io, multidiscrete, discrete, invalid, st);
-        if ((rc = launch_ok("decode + step (attacker phase)"))) return rc;
-    }
+    // three launches, the step split around the observation: decode + attacker phase, observation, defender phase + wrapper finish
+    // (mcbs_aux.hip), in step_kernel's launch shape
+    b->all_fresh = false;
+    step_variant(b, [&](auto wt, auto def) {
+        hipLaunchKernelGGL((decode_step1_kernel<decltype(wt)::value, decltype(def)::value>), step_grid(b), dim3(64), step_lds(b), st, b->S, b->T, b->C_dev, io,
+                           b->cfg.maximum_node_count, b->cfg.maximum_total_credentials, multidiscrete, discrete, invalid);
+    });
+    if ((rc = launch_ok("decode + step (attacker phase)"))) return rc;
     if ((rc = launch_obs(b, obs, st))) return rc;
-    if (b->lds_topo) {                       // (developer switch: the staged variant keeps the two separate launches)
-        if ((rc = launch_step<2>(b, io, st, "step (defender phase)"))) return rc;
-        hipLaunchKernelGGL(wrapper_finish_kernel, dim3((b->S.E + 255) / 256), dim3(256), 0, st, b->S, b->T, A);
-        return launch_ok("wrapper finish");
-    }
-    if (b->S.packed) launch_step2_finish_nw<0>(b, io, A, st);
-    else if (b->S.WT == 1) launch_step2_finish_nw<1>(b, io, A, st);
-    else if (b->S.WT == 2) launch_step2_finish_nw<2>(b, io, A, st);
-    else launch_step2_finish_nw<4>(b, io, A, st);
+    step_variant(b, [&](auto wt, auto def) {
+        hipLaunchKernelGGL((step2_finish_kernel<decltype(wt)::value, decltype(def)::value>), step_grid(b), dim3(64), step_lds(b), st, b->S, b->T, b->C_dev, io, A);
+    });
     return launch_ok("step (defender phase) + wrapper finish");
 }
 
 extern "C" int mcbs_defender_wrapper_post(mcbs_batch* b, const mcbs_defender_wrapper_buffers* w, const mcbs_defender_wrapper_cfg* cfg, void* stream) {
     if (!b || !w || !cfg) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
-    const void* const* p = reinterpret_cast<const void* const*>(w);
-    for (size_t i = 0; i < sizeof(*w) / sizeof(void*); ++i) if (!p[i]) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
+    if (!arrays_set(w, 0)) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
     hipLaunchKernelGGL(defender_wrapper_post_kernel, dim3((b->S.E + 255) / 256), dim3(256), 0, (hipStream_t)stream, b->S.E, *w, *cfg);
     return launch_ok("defender wrapper post");
 }
@@ -1357,11 +1325,12 @@ static int categorical_args(const char* who, const void* logits, int32_t dtype, 
 static void categorical_launch(const mcbs_batch* b, bool live, const LogitsGeom& G, const uint32_t* bits, size_t bits_row_words, int32_t dtype,
                                const CatIO& io, hipStream_t st) {
     const dim3 grid = rows_grid(io.n_rows, 65536u), block(256);
-#define MCBS_CAT_LAUNCH(LT_, LIVE_) \
-    hipLaunchKernelGGL((masked_categorical_kernel<LT_, LIVE_>), grid, block, 0, st, b->S, b->T, b->C_dev, b->digest, G, bits, bits_row_words, io)
-    if (dtype == MCBS_LOGITS_BF16 && io.logits) { if (live) MCBS_CAT_LAUNCH(uint16_t, true); else MCBS_CAT_LAUNCH(uint16_t, false); }
-    else { if (live) MCBS_CAT_LAUNCH(float, true); else MCBS_CAT_LAUNCH(float, false); }
-#undef MCBS_CAT_LAUNCH
+    pick<2, 4>(dtype == MCBS_LOGITS_BF16 && io.logits ? 2 : 4, [&](auto es) {       // element size: bf16 patterns, else fp32 (also without logits)
+        pick<1, 0>((int)live, [&](auto lv) {
+            hipLaunchKernelGGL((masked_categorical_kernel<LogitsElem<(uint32_t)decltype(es)::value>, decltype(lv)::value != 0>), grid, block, 0, st,
+                               b->S, b->T, b->C_dev, b->digest, G, bits, bits_row_words, io);
+        });
+    });
 }
 
 extern "C" int mcbs_masked_categorical(mcbs_batch* b, const void* logits, int32_t dtype, size_t row_stride, int32_t mode, int64_t* actions,
@@ -1484,13 +1453,11 @@ extern "C" int mcbs_gae(const mcbs_batch* b, const mcbs_gae_io* io, void* stream
     const dim3 grid((uint32_t)((E + 63u) / 64u)), block(64);
     hipStream_t st = (hipStream_t)stream;
     constexpr uint32_t U = MCBS_GAE_U;
-    if (io->bootstrap) {
-        if (io->returns) hipLaunchKernelGGL((gae_kernel<U, true, true>), grid, block, 0, st, k);
-        else hipLaunchKernelGGL((gae_kernel<U, true, false>), grid, block, 0, st, k);
-    } else {
-        if (io->returns) hipLaunchKernelGGL((gae_kernel<U, false, true>), grid, block, 0, st, k);
-        else hipLaunchKernelGGL((gae_kernel<U, false, false>), grid, block, 0, st, k);
-    }
+    pick<1, 0>(io->bootstrap != nullptr, [&](auto boot) {
+        pick<1, 0>(io->returns != nullptr, [&](auto ret) {
+            hipLaunchKernelGGL((gae_kernel<U, decltype(boot)::value != 0, decltype(ret)::value != 0>), grid, block, 0, st, k);
+        });
+    });
     return launch_ok("gae");
 }
 
@@ -1630,13 +1597,8 @@ extern "C" int mcbs_encode_features(const mcbs_batch* b, const mcbs_feature_layo
 }
 
 // ------------------------------------------------------------------ learned defender
-// The observation written by the turn kernel's own workgroups (one launch per turn): topologies of up to 32 nodes and 256 services,
-// output arrays on 16-byte boundaries (the 128 envs of a workgroup are one contiguous region of each array, stored as 16-byte vectors).
-// MCBS_NO_FUSED_DEFENDER_OBS=1: the separate launch.
-static bool fused_defender_obs_batch_ok(const mcbs_batch* b) {
-    return b->S.N <= 32u && b->C.n_services <= 256u && !b->no_fused_defender_obs;
-}
-
+// The observation written by the turn kernel's own workgroups (variant.fused_defender_obs): output arrays on 16-byte boundaries (the 128
+// envs of a workgroup are one contiguous region of each array, stored as 16-byte vectors)
 static DefObs fused_defender_obs(const mcbs_batch* b, const mcbs_defender_obs* o) {
     DefObs d{};
     if (!o) return d;
@@ -1646,22 +1608,13 @@ static DefObs fused_defender_obs(const mcbs_batch* b, const mcbs_defender_obs* o
     d.dN = fast_div_host(N); d.d6N = fast_div_host(6u * N); d.dS = fast_div_host(d.n_services ? d.n_services : 1u);
     auto al = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
     const bool aligned = al(d.infected) && al(d.fw_in) && al(d.fw_out) && al(d.services);
-    d.fused = (fused_defender_obs_batch_ok(b) && aligned) ? 1u : 0u;
+    d.fused = (b->variant.fused_defender_obs && aligned) ? 1u : 0u;
     return d;
 }
 
 extern "C" int mcbs_batch_variant(const mcbs_batch* b, mcbs_batch_variant_info* out) {
     if (!b || !out) return fail(MCBS_EINVAL, "null argument");
-    mcbs_batch_variant_info v{};
-    v.packed = b->S.packed;
-    v.words_per_set = b->S.WT;
-    v.wide = b->S.wide;
-    v.coop = b->coop ? 1u : 0u;
-    v.lds_topo = (b->lds_topo && b->C.hot_bytes <= 60000u) ? 1u : 0u;       // the staged step kernel's own condition
-    v.defender_kind = b->cfg.defender_kind;
-    v.fused_wrapper = fused_wrapper_batch_ok(b) ? 1u : 0u;
-    v.fused_defender_obs = (b->cfg.defender_kind == MCBS_DEFENDER_EXTERNAL && fused_defender_obs_batch_ok(b)) ? 1u : 0u;
-    *out = v;
+    *out = b->variant;
     return MCBS_OK;
 }
 
@@ -1672,46 +1625,48 @@ static int launch_defender_obs(mcbs_batch* b, const mcbs_defender_obs* o, hipStr
     return launch_ok("defender observation");
 }
 
+static int learned_defender_ok(const mcbs_batch* b) {
+    if (b->cfg.defender_kind != MCBS_DEFENDER_EXTERNAL) return fail(MCBS_ESTATE, "batch was not created with MCBS_DEFENDER_EXTERNAL");
+    return MCBS_OK;
+}
+
+// One turn of the learned defender: 128 envs per workgroup, launch(WT, grid, block, observation arguments) for the batch's words per set;
+// then the observation as a launch of its own where the turn kernel could not write it
+template <class Launch>
+static int launch_defender_turn(mcbs_batch* b, const mcbs_defender_obs* obs, hipStream_t st, const char* what, Launch&& launch) {
+    b->all_fresh = false;
+    const DefObs dob = fused_defender_obs(b, obs);
+    pick<1, 2, 4>((int)b->S.WT, [&](auto wt) { launch(wt, dim3((b->S.E + 127) / 128), dim3(128), dob); });
+    const int rc = launch_ok(what);
+    if (rc || !obs || dob.fused) return rc;
+    return launch_defender_obs(b, obs, st);
+}
+
 extern "C" int mcbs_defender_step(mcbs_batch* b, const int64_t* actions, uint8_t* valid, double* availability, uint8_t* evicted,
                                   const mcbs_defender_obs* obs, void* stream) {
     if (!b || !actions) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
-    if (b->cfg.defender_kind != MCBS_DEFENDER_EXTERNAL) return fail(MCBS_ESTATE, "batch was not created with MCBS_DEFENDER_EXTERNAL");
-    hipStream_t st = (hipStream_t)stream;
-    b->all_fresh = false;
-    const dim3 grid((b->S.E + 127) / 128), block(128);
-    const DefObs dob = fused_defender_obs(b, obs);
-    if (b->S.WT == 1) hipLaunchKernelGGL((defender_kernel<1>), grid, block, 0, st, b->S, b->T, b->C_dev, actions, valid, availability, evicted, dob);
-    else if (b->S.WT == 2) hipLaunchKernelGGL((defender_kernel<2>), grid, block, 0, st, b->S, b->T, b->C_dev, actions, valid, availability, evicted, dob);
-    else hipLaunchKernelGGL((defender_kernel<4>), grid, block, 0, st, b->S, b->T, b->C_dev, actions, valid, availability, evicted, dob);
-    int rc = launch_ok("defender step");
-    if (rc || !obs || dob.fused) return rc;
-    return launch_defender_obs(b, obs, st);
+    if (const int rc = learned_defender_ok(b)) return rc;
+    return launch_defender_turn(b, obs, (hipStream_t)stream, "defender step", [&](auto wt, dim3 grid, dim3 block, const DefObs& dob) {
+        hipLaunchKernelGGL((defender_kernel<decltype(wt)::value>), grid, block, 0, (hipStream_t)stream, b->S, b->T, b->C_dev, actions, valid, availability, evicted, dob);
+    });
 }
 
 extern "C" int mcbs_defender_wrapper_step(mcbs_batch* b, const int64_t* actions, const mcbs_defender_obs* obs, const mcbs_defender_wrapper_buffers* w,
                                           const mcbs_defender_wrapper_cfg* cfg, void* stream) {
     if (!b || !actions || !w || !cfg) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
-    if (b->cfg.defender_kind != MCBS_DEFENDER_EXTERNAL) return fail(MCBS_ESTATE, "batch was not created with MCBS_DEFENDER_EXTERNAL");
-    const void* const* p = reinterpret_cast<const void* const*>(w);
-    for (size_t i = 0; i < sizeof(*w) / sizeof(void*); ++i) if (!p[i]) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
-    hipStream_t st = (hipStream_t)stream;
-    b->all_fresh = false;
-    const dim3 grid((b->S.E + 127) / 128), block(128);
-    const DefObs dob = fused_defender_obs(b, obs);
-    if (b->S.WT == 1) hipLaunchKernelGGL((defender_turn_post_kernel<1>), grid, block, 0, st, b->S, b->T, b->C_dev, actions, *w, *cfg, dob);
-    else if (b->S.WT == 2) hipLaunchKernelGGL((defender_turn_post_kernel<2>), grid, block, 0, st, b->S, b->T, b->C_dev, actions, *w, *cfg, dob);
-    else hipLaunchKernelGGL((defender_turn_post_kernel<4>), grid, block, 0, st, b->S, b->T, b->C_dev, actions, *w, *cfg, dob);
-    int rc = launch_ok("defender turn + reward shaping");
-    if (rc || !obs || dob.fused) return rc;
-    return launch_defender_obs(b, obs, st);
+    if (const int rc = learned_defender_ok(b)) return rc;
+    if (!arrays_set(w, 0)) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
+    return launch_defender_turn(b, obs, (hipStream_t)stream, "defender turn + reward shaping", [&](auto wt, dim3 grid, dim3 block, const DefObs& dob) {
+        hipLaunchKernelGGL((defender_turn_post_kernel<decltype(wt)::value>), grid, block, 0, (hipStream_t)stream, b->S, b->T, b->C_dev, actions, *w, *cfg, dob);
+    });
 }
 
 extern "C" int mcbs_defender_observe(mcbs_batch* b, const mcbs_defender_obs* obs, void* stream) {
     if (!b || !obs) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
-    if (b->cfg.defender_kind != MCBS_DEFENDER_EXTERNAL) return fail(MCBS_ESTATE, "batch was not created with MCBS_DEFENDER_EXTERNAL");
+    if (const int rc = learned_defender_ok(b)) return rc;
     return launch_defender_obs(b, obs, (hipStream_t)stream);
 }
 

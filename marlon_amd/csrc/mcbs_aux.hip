@@ -246,12 +246,12 @@ __global__ __launch_bounds__(256) void wrapper_finish_kernel(DevState S, Topo T,
 }
 
 // The defender / goals half of a split step (step_kernel<2>) and the wrapper's finish in ONE launch: one-wavefront workgroups as
-// launch_step_v uses them (hot image through L1 / L2), lane = env in both halves; the finish reads the reward and the done flag its own
+// launch_step uses them (hot image through L1 / L2), lane = env in both halves; the finish reads the reward and the done flag its own
 // lane has just stored.  One graph node less per wrapper step.
 template <int WTP, int DEFK>
 __global__ __launch_bounds__(64) void step2_finish_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, StepIO io, WrapperFinishArgs A) {
     NoHook nh;
-    step_body<2, WTP, false, DEFK, false>(S, T, Cp, io, RollArgs{}, nh);
+    step_body<2, WTP, DEFK, false>(S, T, Cp, io, RollArgs{}, nh);
     wrapper_finish_body(S, T, A, blockIdx.x * 64u + threadIdx.x, threadIdx.x);
 }
 
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(64) void decode_step1_kernel(DevState S, Topo T, co
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");       // the row's stores stay ahead of the step's loads of it
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     NoHook nh;
-    step_body<1, WTP, false, DEFK, false>(S, T, Cp, io, RollArgs{}, nh);
+    step_body<1, WTP, DEFK, false>(S, T, Cp, io, RollArgs{}, nh);
 }
 
 } // namespace mcbs

@@ -36,8 +36,8 @@
 //   rare per wavefront (64 envs), so nothing on those paths may cost another trip to memory: a first version that
 //   tested the ever-owned / discovered / credential sets lazily in memory spent 9 of its 10 dependency levels there
 //   (profiles/round1_notes.md).  Round 1 staged the hot image in LDS per workgroup; reading it through L1 / L2
-//   with one-wavefront workgroups measured faster at every BASELINE shape (TOPO_LDS = true survives behind
-//   MCBS_LDS_TOPO=1 for the comparison).
+//   with one-wavefront workgroups measured faster at every BASELINE shape, twice (profiles/round2_notes.md,
+//   profiles/step_dispatch_refactor.md), and the staged variant is gone.
 //
 // Control flow.  The lanes of a wavefront hold different action kinds, outcomes and validity, so every `if` of the
 // reference that the compiler keeps as a branch is paid by the whole wave (compare, exec-mask save, branch, restore:
@@ -476,16 +476,16 @@ struct Lane {
 
 // PHASE 0: whole step.  PHASE 1: attacker's action only (raw reward parked in S.pending).
 // PHASE 2: defender, goals, outputs, auto-reset (after the observation kernels ran).
-// WT: words per set held in registers (1, 2 or 4; >= NW, SW, TW).  TOPO_LDS: topology tables staged in LDS.
+// WT: words per set held in registers (1, 2 or 4; >= NW, SW, TW).
 // DEFK: MCBS_DEFENDER_* (none / in-env ScanAndReimage / external learned defender).
 // MANY: the in-kernel step loop of mcbs_step_many / mcbs_rollout_random (step_many_kernel below); `roll` = the random agent of
 // mcbs_rollout_random (mode 0: actions are read from io.actions).
-template <int PHASE, int WTP, bool TOPO_LDS, int DEFK, bool MANY, class Hook>
+template <int PHASE, int WTP, int DEFK, bool MANY, class Hook>
 __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, const StepCfg* __restrict__ Cp, const StepIO& io, const RollArgs& roll, Hook& hook) {
     constexpr bool PK = WTP == 0;           // packed batch: the eight sets are 16-bit fields of one uint4 per env
     constexpr int WT = PK ? 1 : WTP;
     const StepCfg& C = *Cp;   // in device memory: fields are fetched by scalar loads where they are used, not all up front
-    extern __shared__ uint4 topo_lds[];
+    extern __shared__ uint4 dyn_lds[];
 #ifdef MCBS_DIAG
     unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #define STAMP(i) do { __builtin_amdgcn_sched_barrier(0); asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); st_[i] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -499,8 +499,8 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
     // from the config (select of two loads -> load of the selected address), i.e. one more memory round trip after level 1
     // (fetched and pinned AFTER the level-1 vector loads are issued, below: pinned here, the kernel waited for the kernel-argument
     // load, then for this load through the config pointer, before its first vector load went out — a quarter of a wavefront's life)
-    // Workgroups of the L1 / L2 variant are always one wavefront (mcbs_api.hip): the env index needs no hidden-argument load
-    const uint32_t bdim = TOPO_LDS ? blockDim.x : 64u;
+    // Workgroups are always one wavefront (mcbs_api.hip): the env index needs no hidden-argument load
+    constexpr uint32_t bdim = 64u;
     const uint32_t e = blockIdx.x * bdim + threadIdx.x;
     const bool active = e < S.E;
     const uint32_t ec = active ? e : 0u;                // clamp so inactive lanes read valid memory and take no branch
@@ -518,7 +518,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
     // stores in program order; the reset copy is by lanes of the same wavefront).  Envs never interact, so no grid-wide
     // synchronisation is involved; what goes away is the per-launch cost between dependent steps.
     const uint32_t n_it = MANY ? io.n_steps : 1u;
-    const uint8_t* tb = TOPO_LDS ? reinterpret_cast<const uint8_t*>(topo_lds) : T.hot;
+    const uint8_t* const tb = T.hot;                    // the topology's hot image, through L1 / L2
     for (uint32_t it = 0; it < n_it; ++it) {
     StepIO iok = io;
     if (MANY) {
@@ -606,27 +606,8 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
                           "+s"(g_own), "+s"(g_evict), "+s"(g_auto), "+s"(g_max), "+s"(g_image), "+s"(a_node), "+s"(a_desc), "+s"(a_payload),
                           "+s"(a_auth), "+s"(a_aw), "+s"(a_leak));
     else asm volatile("" : "+s"(cL), "+s"(cR), "+s"(cP), "+s"(a_node), "+s"(a_desc), "+s"(a_payload), "+s"(a_auth), "+s"(a_aw), "+s"(a_leak));
-    if (!TOPO_LDS) tb = T.hot;
-    if (TOPO_LDS && it == 0u) {                         // cooperative copy of the hot topology image, 16 bytes per lane
-        const uint4* src = reinterpret_cast<const uint4*>(T.hot);
-        const uint32_t nvec = C.hot_bytes / 16u, bd = bdim;
-        if (PK || nvec <= 2u * bd) {                    // small image (Chain-10: 1.1 passes): the plain loop is the fastest here; packed
-                                                        // batches (<= 16 nodes) never have a large one, and their kernel keeps exactly this code
-            for (uint32_t i = threadIdx.x; i < nvec; i += bd) topo_lds[i] = src[i];
-        } else {                                        // large image (Chain-100: 8 passes): four loads in flight per lane, not one —
-            for (uint32_t i = threadIdx.x; i < nvec; i += 4u * bd) {   // a plain loop waits for each pass before issuing the next
-                const uint32_t i1 = i + bd, i2 = i + 2u * bd, i3 = i + 3u * bd, last = nvec - 1u;
-                const uint4 v0 = src[i], v1 = src[i1 < nvec ? i1 : last], v2 = src[i2 < nvec ? i2 : last], v3 = src[i3 < nvec ? i3 : last];
-                topo_lds[i] = v0;
-                if (i1 < nvec) topo_lds[i1] = v1;
-                if (i2 < nvec) topo_lds[i2] = v2;
-                if (i3 < nvec) topo_lds[i3] = v3;
-            }
-        }
-        __syncthreads();
-    }
 
-    STAMP(2);          // level-1 loads and the LDS copy have landed
+    STAMP(2);          // level-1 loads have landed
     bool need_reset = false;
     float hk_reward = 0.0f;
     bool hk_done = false;
@@ -648,8 +629,8 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
     ln.ere_blob = T.base;
     ln.A = ActCfg{a_node, a_desc, a_payload, a_auth, a_aw, cL + cR, cP, a_leak};
     if (PK) { ln.ldisc = (uint64_t)lists0.x | ((uint64_t)lists0.y << 32); ln.lcred = (uint64_t)lists0.z | ((uint64_t)lists0.w << 32); }
-    if (!PK && S.wide) {                                // this lane's LDS column for the wide cached-triple set, behind the hot image
-        ln.wide_lds = reinterpret_cast<uint64_t*>(topo_lds + (TOPO_LDS ? C.hot_bytes / 16u : 0u)) + threadIdx.x;
+    if (!PK && S.wide) {                                // this lane's LDS column for the wide cached-triple set, at the start of dynamic LDS
+        ln.wide_lds = reinterpret_cast<uint64_t*>(dyn_lds) + threadIdx.x;
         ln.wide_stride = bdim;
     }
     // level 2 (needs the header): this defender tick's ring slot
@@ -867,16 +848,18 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
 // agent's parameters therefore travel only with the looping variant below, which is launched once per K steps.
 template <int PHASE, int WTP, bool TOPO_LDS, int DEFK>
 __global__ __launch_bounds__(256) void step_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, StepIO io) {
+    static_assert(!TOPO_LDS, "no LDS-staged hot image: the parameter keeps the kernel's name for the benchmark and the committed traces");
     NoHook nh;
-    step_body<PHASE, WTP, TOPO_LDS, DEFK, false>(S, T, Cp, io, RollArgs{}, nh);
+    step_body<PHASE, WTP, DEFK, false>(S, T, Cp, io, RollArgs{}, nh);
 }
 
 // mcbs_step_many / mcbs_rollout_random: io.n_steps consecutive steps in one launch; `roll` is a kernel ARGUMENT (nothing in device
 // memory is patched per call, so launches on different streams or inside a stream capture cannot see each other's mode).
 template <int WTP, bool TOPO_LDS, int DEFK>
 __global__ __launch_bounds__(256) void step_many_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, StepIO io, RollArgs roll) {
+    static_assert(!TOPO_LDS, "as step_kernel: kept for the kernel's name");
     NoHook nh;
-    step_body<0, WTP, TOPO_LDS, DEFK, true>(S, T, Cp, io, roll, nh);
+    step_body<0, WTP, DEFK, true>(S, T, Cp, io, roll, nh);
 }
 
 } // namespace mcbs

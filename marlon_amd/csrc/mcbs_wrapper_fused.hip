@@ -427,7 +427,7 @@ __global__ __launch_bounds__(FUSED_THREADS) void wrapper_fused_kernel(DevState S
     // The first wavefront advances the workgroup's 64 envs (lane = env: the headline kernel's code with the hooks above) and leaves their
     // observation records in LDS; the other three meanwhile put the reset observation there.  Then all four stream the observation out:
     // with one wavefront per SIMD every LDS round trip of the streaming loops was exposed (30 us per launch); four hide each other's.
-    if (tid < 64u) step_body<0, 0, false, DEFK, false>(S, T, Cp, io, RollArgs{}, hook);
+    if (tid < 64u) step_body<0, 0, DEFK, false>(S, T, Cp, io, RollArgs{}, hook);
     else hook.fill_reset_rows(tid - 64u, FUSED_THREADS - 64u);
     // LDS-only barriers: the records are complete (lgkmcnt(0)), nobody waits for the global stores in flight (vmcnt untouched)
 #define MCBS_LDS_BARRIER() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_s_waitcnt(0xC07F); \

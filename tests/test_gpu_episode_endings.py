@@ -16,7 +16,6 @@ oracle alone), and each case here replays one of them.
 | lane4 | random_net 129 | MCBS_NO_COOP=1 | words_per_set=4, coop=0 |
 | coop4 | random_net 129 | | words_per_set=4, coop=1 (G = 4) |
 | wide | ActiveDirectory-6 | | wide=1 |
-| lds | random_net 24 | MCBS_LDS_TOPO=1 | lds_topo=1 |
 
 | spec (endings.case) | what ends the episodes |
 |---|---|
@@ -29,7 +28,7 @@ oracle alone), and each case here replays one of them.
 
 | entry point | cells | test |
 |---|---|---|
-| step | all nine | test_step_ends_episodes_as_the_oracle |
+| step | all eight | test_step_ends_episodes_as_the_oracle |
 | step_many, two launches with endings and re-initialisations inside | general1, lane2, lane4, wide | test_step_many_ends_episodes_as_the_oracle |
 | step / step_observe / step_many alternating on ONE state (the cooperative kernel, the phase kernels and the looping one-lane kernel hand `owned` and the slack list entry to each other) | coop2, coop4 | test_cooperative_batch_alternates_entry_points |
 | step_observe (goals evaluated in phase 2), small observation fields | lane2, wide | test_step_observe_ends_episodes_as_the_oracle |
@@ -60,7 +59,6 @@ CELLS = {
     "lane4": ("random129", {"MCBS_NO_COOP": "1"}, dict(packed=0, words_per_set=4, wide=0, coop=0, lds_topo=0)),
     "coop4": ("random129", {}, dict(packed=0, words_per_set=4, wide=0, coop=1, lds_topo=0)),
     "wide": ("ad6", {}, dict(packed=0, wide=1, coop=0, lds_topo=0)),
-    "lds": ("random24", {"MCBS_LDS_TOPO": "1"}, dict(packed=0, words_per_set=1, wide=0, coop=0, lds_topo=1)),
 }
 
 
