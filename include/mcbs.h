@@ -725,6 +725,11 @@ typedef struct mcbs_batch_variant_info {   /* 32 bytes */
     uint32_t fused_defender_obs;  /* 1: learned-defender turns can write the observation themselves (N <= 32, at most 256 services) */
 } mcbs_batch_variant_info;
 int  mcbs_batch_variant(const mcbs_batch*, mcbs_batch_variant_info* out);
+/* 1: an mcbs_step of this batch with (with_info != 0) or without info buffers takes the lean launch — the packed, attacker-only whole
+ * step with the argument block that holds only what it reads (marlon_amd/csrc/mcbs_step.hip); 0: the full argument list, or a null
+ * batch.  Decided at batch creation except for the info buffers, which are per call.  (A query of its own: the variant record above
+ * is fixed at 32 bytes.) */
+int32_t mcbs_step_is_lean(const mcbs_batch*, int32_t with_info);
 
 /* Kernel timing hook for bench.py: HIP events recorded on `stream` around each mcbs_step launch
  * while enabled; mcbs_timing_read synchronises and returns the summed kernel milliseconds. */

@@ -95,6 +95,8 @@ struct mcbs_batch {
     bool no_block_masks = false;    // MCBS_NO_BLOCK_MASKS=1: round 2's fused mask writers (rows switched on / off per chunk)
     size_t disc_stride = 0;         // mcbs_set_mask_discrete_stride: bytes between two envs' rows of mask_discrete (0: dense)
     mcbs_batch_variant_info variant{};   // which kernels the batch's calls dispatch to: decided once, by batch_variant at the end of mcbs_batch_create
+    bool lean_step = false;         // mcbs_step without info buffers takes the lean argument block (packed, no defender, reset image in the
+                                    // config); decided once, in mcbs_batch_create
     uint8_t* arena = nullptr;       // every per-env column + bodies + init body, one allocation
     size_t arena_bytes = 0;
     ObsDigest* digest = nullptr;
@@ -555,6 +557,7 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     e = hipDeviceSynchronize();
     if (e != hipSuccess) { (void)hipFree(b->arena); delete b; return fail(MCBS_EHIP, "initial reset failed: %s", hipGetErrorString(e)); }
     b->variant = batch_variant(b);
+    b->lean_step = S.packed && cfg->defender_kind == MCBS_DEFENDER_NONE && C.init_image_ok && !S.ring;
     *out = b;
     return MCBS_OK;
 }
@@ -682,6 +685,20 @@ static int launch_step(mcbs_batch* b, const StepIO& io, hipStream_t st, const ch
                                    b->S, b->T, b->C_dev, io);
             });
         });
+        return launch_ok(what);
+    }
+    if (PHASE == 0 && !MANY && b->lean_step && !(io.availability || io.step_count || io.truncated || io.oob || io.raw_reward)) {
+        // no info buffers on a packed, attacker-only batch: the same kernel with the argument block that holds only what it reads
+        const DevState& S = b->S;
+        LeanStepArgs a{};
+        a.h0 = S.h0; a.masks = S.masks; a.body = S.body; a.h1 = S.h1; a.actions = io.actions; a.reward = io.reward; a.terminated = io.terminated;
+        a.E = S.E; a.body_stride = S.body_stride; a.hot = b->T.hot; a.N = S.N; a.tiny_p = S.tiny_p; a.tiny_v = S.tiny_v;
+        a.episode = S.episode; a.pending = S.pending;
+        static_assert(sizeof(LeanStepArgs) + sizeof(void*) + 16 <= 256, "step kernel arguments spill into a fifth cache line (make_io)");
+#ifdef MCBS_DIAG
+        a.stamps = io.stamps;
+#endif
+        hipLaunchKernelGGL((step_kernel<0, 0, false, MCBS_DEFENDER_NONE>), step_grid(b), dim3(64), 0, st, b->C_dev, a);
         return launch_ok(what);
     }
     step_variant(b, [&](auto wt, auto def) {
@@ -1610,6 +1627,10 @@ static DefObs fused_defender_obs(const mcbs_batch* b, const mcbs_defender_obs* o
     const bool aligned = al(d.infected) && al(d.fw_in) && al(d.fw_out) && al(d.services);
     d.fused = (b->variant.fused_defender_obs && aligned) ? 1u : 0u;
     return d;
+}
+
+extern "C" int32_t mcbs_step_is_lean(const mcbs_batch* b, int32_t with_info) {
+    return (b && b->lean_step && !with_info) ? 1 : 0;
 }
 
 extern "C" int mcbs_batch_variant(const mcbs_batch* b, mcbs_batch_variant_info* out) {

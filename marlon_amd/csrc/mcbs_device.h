@@ -262,6 +262,33 @@ struct StepIO {
 #endif
 };
 
+// Arguments of the lean launch of the packed, attacker-only whole step (mcbs_step.hip step_kernel(cfg, LeanStepArgs); chosen by mcbs_api.hip
+// launch_step for mcbs_step without info buffers): only what that instantiation reads.  The kernel takes the config pointer first and
+// this block behind it, so the first 64 bytes of its arguments are the config pointer and the words the level-1 addresses need — the
+// pointers to h0, masks, body, h1, the actions and the episode counters, env count and body stride — and the node count that decides
+// the fourth row vector follows directly: adjacent, so that they arrive in one batch of wide scalar loads with one wait before the
+// first vector load.  The row format, the hot image's base and the output pointers come next; `pending` is written by the reset tail
+// only.  The optional outputs, the draw tape and n_steps of StepIO are not here: a call that wants them takes the full argument list.
+struct LeanStepArgs {
+    uint4*    h0;            // DevState::h0, masks, body, h1, episode
+    uint64_t* masks;
+    uint8_t*  body;
+    double2*  h1;
+    const int32_t* actions;  // StepIO::actions
+    uint32_t* episode;
+    uint32_t  E, body_stride;   // DevState's, as N, tiny_p, tiny_v
+    // ---- byte 64 of the kernel's arguments (the config pointer is the first eight) ----
+    uint32_t  N, tiny_p, tiny_v, pad;
+    const uint8_t* hot;      // Topo::hot
+    float*    reward;        // StepIO::reward, terminated
+    uint8_t*  terminated;
+    double*   pending;       // reset tail only
+#ifdef MCBS_DIAG
+    unsigned long long* stamps;
+#endif
+};
+static_assert(offsetof(LeanStepArgs, N) == 56, "the level-1 block of LeanStepArgs");
+
 struct FastDiv { uint32_t mul, sh1, sh2; };   // n / d for 32-bit n (Granlund-Montgomery round-up form), set up on the host
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, FastDiv d) {
     const uint32_t t = __umulhi(n, d.mul);

@@ -11,7 +11,8 @@
 // once, so the launch takes as long as ONE wavefront's dependent chain of memory accesses (two thirds of a
 // wavefront's cycles are parked at s_waitcnt: profiles/round2_notes.md).  The kernel is therefore organised by
 // dependency level, not by reference function:
-//   prologue: ONE batch of kernel-argument loads, then
+//   prologue: ONE batch of kernel-argument loads (the lean launch at the end of this file — mcbs_step without info buffers on a packed,
+//           attacker-only batch, the headline — passes only what the kernel reads: no optional outputs, no tape, no ring, nothing spilled), then
 //   level 1 (addresses depend on the env index only, issued back to back, all coalesced along the env axis):
 //           header uint4, action row, first 16 discovery-order entries, first 16 credential-cache entries,
 //           EVERY set of the env as u64 bit-mask words (discovered, agent installed, ever owned, running,
@@ -64,6 +65,7 @@
 // "attacked since the node's last re-imaging"; agent_installed doubles as "currently owned"
 // (actions.py:517-522), see DESIGN.md "Logical time".
 #pragma once
+#include <type_traits>
 #include "mcbs_device.h"
 #include "mcbs_ere.hip"
 #include "mcbs_sample.hip"
@@ -74,37 +76,43 @@ namespace mcbs {
 // (word selection is written as mask arithmetic, not as a select chain: the compiler turns a chain of selects over m[0..WT)
 // into a dynamically indexed stack array, i.e. scratch memory round trips, for WT == 4)
 __device__ __forceinline__ uint64_t word_is(uint32_t n, int i) { return 0ull - (uint64_t)((n >> 6) == (uint32_t)i); }
-template <int WT>
-__device__ __forceinline__ bool rget(const uint64_t (&m)[WT], uint32_t n) {
-    uint64_t w = WT == 1 ? m[0] : 0ull;
+// W: the word a set is held in — uint64_t, or uint32_t where the kernel knows that a set has at most 16 elements (the lean packed step):
+// the same bits in half the registers, and 32-bit shifts and compares instead of 64-bit ones
+template <int WT, class W>
+__device__ __forceinline__ bool rget(const W (&m)[WT], uint32_t n) {
+    constexpr uint32_t BM = (uint32_t)sizeof(W) * 8u - 1u;
+    W w = WT == 1 ? m[0] : W(0);
     if (WT > 1) {
 #pragma unroll
-        for (int i = 0; i < WT; ++i) w |= m[i] & word_is(n, i);
+        for (int i = 0; i < WT; ++i) w |= m[i] & (W)word_is(n, i);
     }
-    return (w >> (n & 63u)) & 1ull;
+    return (w >> (n & BM)) & W(1);
 }
-template <int WT>
-__device__ __forceinline__ void rset(uint64_t (&m)[WT], uint32_t n) {
+template <int WT, class W>
+__device__ __forceinline__ void rset(W (&m)[WT], uint32_t n) {
+    constexpr uint32_t BM = (uint32_t)sizeof(W) * 8u - 1u;
 #pragma unroll
-    for (int i = 0; i < WT; ++i) m[i] |= (1ull << (n & 63u)) & (WT == 1 ? ~0ull : word_is(n, i));
+    for (int i = 0; i < WT; ++i) m[i] |= (W(1) << (n & BM)) & (WT == 1 ? ~W(0) : (W)word_is(n, i));
 }
-template <int WT>
-__device__ __forceinline__ void rclear(uint64_t (&m)[WT], uint32_t n) {
+template <int WT, class W>
+__device__ __forceinline__ void rclear(W (&m)[WT], uint32_t n) {
+    constexpr uint32_t BM = (uint32_t)sizeof(W) * 8u - 1u;
 #pragma unroll
-    for (int i = 0; i < WT; ++i) m[i] &= ~((1ull << (n & 63u)) & (WT == 1 ? ~0ull : word_is(n, i)));
+    for (int i = 0; i < WT; ++i) m[i] &= ~((W(1) << (n & BM)) & (WT == 1 ? ~W(0) : (W)word_is(n, i)));
 }
-template <int WT>   // returns the previous value of the bit
-__device__ __forceinline__ bool rtestset(uint64_t (&m)[WT], uint32_t n) {
+template <int WT, class W>   // returns the previous value of the bit
+__device__ __forceinline__ bool rtestset(W (&m)[WT], uint32_t n) {
     const bool was = rget<WT>(m, n);
     rset<WT>(m, n);
     return was;
 }
 // predicated forms for the straight-line attacker path: the bit of element n as a WT-word set, empty when !on
-template <int WT>
-__device__ __forceinline__ void rbit(uint64_t (&b)[WT], uint32_t n, bool on) {
-    const uint64_t bit = on ? (1ull << (n & 63u)) : 0ull;
+template <int WT, class W>
+__device__ __forceinline__ void rbit(W (&b)[WT], uint32_t n, bool on) {
+    constexpr uint32_t BM = (uint32_t)sizeof(W) * 8u - 1u;
+    const W bit = on ? (W(1) << (n & BM)) : W(0);
 #pragma unroll
-    for (int i = 0; i < WT; ++i) b[i] = bit & (WT == 1 ? ~0ull : word_is(n, i));
+    for (int i = 0; i < WT; ++i) b[i] = bit & (WT == 1 ? ~W(0) : (W)word_is(n, i));
 }
 
 // entry i (< 16) of a 16-byte vector of u8, and of two 16-byte vectors of u16 (entries 0..7 | 8..15); written with 64-bit
@@ -165,7 +173,7 @@ struct ActCfg {
 };
 
 // ------------------------------ per-lane working set ------------------------------
-template <int WT>
+template <int WT, class W = uint64_t>
 struct Lane {
     const DevState& S;
     const StepCfg& C;
@@ -173,7 +181,7 @@ struct Lane {
     uint32_t e;
     uint8_t* body;
     uint32_t n_disc, n_creds, owned, dclk;
-    uint64_t m[M_COUNT][WT];
+    W m[M_COUNT][WT];
     uint32_t dirty;      // defender paths: bit k = set k changed and must be written back
     // the target node's row, in registers
     uint64_t props;      // discovered properties (60 bits)
@@ -296,15 +304,15 @@ struct Lane {
         const uint32_t priv = privilege(tgt);
         const uint32_t np = priv > own_level ? priv : own_level;   // model.escalate
         const bool chg = newly & (np != priv);
-        uint64_t bn[WT], bc[WT];
+        W bn[WT], bc[WT];
         rbit<WT>(bn, tgt, newly);
         rbit<WT>(bc, tgt, chg);
 #pragma unroll
         for (int w = 0; w < WT; ++w) {
             m[M_EVER][w] |= bn[w];
             m[M_INST][w] |= bn[w];
-            m[M_PLO][w] = (m[M_PLO][w] & ~bc[w]) | ((np & 1u) ? bc[w] : 0ull);
-            m[M_PHI][w] = (m[M_PHI][w] & ~bc[w]) | ((np & 2u) ? bc[w] : 0ull);
+            m[M_PLO][w] = (m[M_PLO][w] & ~bc[w]) | ((np & 1u) ? bc[w] : W(0));
+            m[M_PHI][w] = (m[M_PHI][w] & ~bc[w]) | ((np & 2u) ? bc[w] : W(0));
         }
         owned += (chg & (priv == 0u)) ? 1u : 0u;
         props |= newly ? t_props : 0ull;                        // all (non-tag) properties become known
@@ -364,8 +372,8 @@ struct Lane {
                 if (!GUARD || MCBS_CHANGED(new_n)) disc_list()[n_disc] = (uint8_t)pn;
                 if (!GUARD || MCBS_CHANGED(new_c)) cred_list()[n_creds] = (uint16_t)pt;
             }
-            uint64_t b0[WT], b1[WT], b2[WT];
-            rbit<WT>(b0, pn, new_n); rbit<WT>(b1, pc, new_g); rbit<WT>(b2, pt & (WT * 64u - 1u), new_c && !wide);
+            W b0[WT], b1[WT], b2[WT];
+            rbit<WT>(b0, pn, new_n); rbit<WT>(b1, pc, new_g); rbit<WT>(b2, pt & (WT * (uint32_t)sizeof(W) * 8u - 1u), new_c && !wide);
 #pragma unroll
             for (int w = 0; w < WT; ++w) { m[M_DISC][w] |= b0[w]; m[M_GATH][w] |= b1[w]; m[M_CACH][w] |= b2[w]; }
             n_disc += new_n; nn += new_n; nc += new_g; n_creds += new_c; ncache += new_c;
@@ -480,10 +488,15 @@ struct Lane {
 // DEFK: MCBS_DEFENDER_* (none / in-env ScanAndReimage / external learned defender).
 // MANY: the in-kernel step loop of mcbs_step_many / mcbs_rollout_random (step_many_kernel below); `roll` = the random agent of
 // mcbs_rollout_random (mode 0: actions are read from io.actions).
-template <int PHASE, int WTP, int DEFK, bool MANY, class Hook>
+// LEAN: the caller is the lean launch of the packed, attacker-only whole step (step_kernel(cfg, LeanStepArgs) below), whose S, T and io hold
+// only what that instantiation reads; false for every other kernel, whose code does not change.
+template <int PHASE, int WTP, int DEFK, bool MANY, bool LEAN = false, class Hook = NoHook>
 __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, const StepCfg* __restrict__ Cp, const StepIO& io, const RollArgs& roll, Hook& hook) {
     constexpr bool PK = WTP == 0;           // packed batch: the eight sets are 16-bit fields of one uint4 per env
     constexpr int WT = PK ? 1 : WTP;
+    using W = std::conditional_t<LEAN, uint32_t, uint64_t>;   // the lean packed step: sets of at most 16 elements, held in 32-bit words
+    static_assert(!LEAN || (PK && PHASE == 0 && !MANY && DEFK == MCBS_DEFENDER_NONE && !Hook::kAction && !Hook::kObs && !Hook::kFinish),
+                  "the lean argument block serves the packed, attacker-only, hook-less whole step");
     const StepCfg& C = *Cp;   // in device memory: fields are fetched by scalar loads where they are used, not all up front
     extern __shared__ uint4 dyn_lds[];
 #ifdef MCBS_DIAG
@@ -561,7 +574,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
         rw0 = rp[0]; rw1 = rp[1]; rw2 = rp[2];
         if (S.N > 12u) rw3 = rp[3];
     }
-    uint64_t m0[M_COUNT][WT];        // every set is stored padded to WT words: no bounds to test, all loads independent
+    W m0[M_COUNT][WT];               // every set is stored padded to WT words: no bounds to test, all loads independent
     uint4 pk = make_uint4(0, 0, 0, 0);
     if (PK) {
         pk = reinterpret_cast<const uint4*>(S.masks)[ec];
@@ -620,7 +633,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
     const bool skip_env = PHASE == 2 ? (old_flags & F_SKIP) != 0 : (int)a03.x == MCBS_ACTION_SKIP;
     const bool live = !ended & !skip_env;
 
-    Lane<WT> ln{S, C, tb, ec, body, h0.z & 0xFFFFu, h0.z >> 16, h0.w & 0xFFFFu, h0.w >> 16, {}, 0u, 0ull, 0u, 0u, 0u, false, learned, 0u, 0u,
+    Lane<WT, W> ln{S, C, tb, ec, body, h0.z & 0xFFFFu, h0.z >> 16, h0.w & 0xFFFFu, h0.w >> 16, {}, 0u, 0ull, 0u, 0u, 0u, false, learned, 0u, 0u,
                 0.0, MCBS_OUT_NONE, 0, 0, 0};
 #pragma unroll
     for (int k = 0; k < M_COUNT; ++k)
@@ -793,7 +806,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
     }
     }
     STAMP(5);              // all stores of the step retired
-    if (PHASE != 1 && PK && g_image) {
+    if (PHASE != 1 && PK && (LEAN || g_image)) {   // (the lean launch is chosen only where the config holds the reset image: no wave-level copy to compile)
         // Packed batches: an env that just ended is re-initialised by its OWN lane with stores only — the body's reset image (<= 16 x 16
         // bytes), the sets, the lists word and the header come from the config through the scalar cache, the episode counter was fetched at level 1.
         // (Round 2 let the whole wavefront copy the image from memory behind a fence, like the large layouts below: with ~1 % of the
@@ -851,6 +864,30 @@ __global__ __launch_bounds__(256) void step_kernel(DevState S, Topo T, const Ste
     static_assert(!TOPO_LDS, "no LDS-staged hot image: the parameter keeps the kernel's name for the benchmark and the committed traces");
     NoHook nh;
     step_body<PHASE, WTP, DEFK, false>(S, T, Cp, io, RollArgs{}, nh);
+}
+
+// The lean launch of the packed, attacker-only whole step: mcbs_step without info buffers (mcbs_api.hip launch_step).  Same kernel name,
+// another argument list: the config pointer and LeanStepArgs (mcbs_device.h), which holds only what this instantiation reads.  Everything
+// else of DevState / Topo / StepIO is a constant here — the five optional outputs, the draw tape and the ring are null — so their tests,
+// the registers that held the pointers (the full list keeps 6 SGPRs spilled to lanes of a VGPR) and the wave-level reset copy are compiled
+// out; step_body is the same code.  The config pointer stays a kernel parameter of its own: only as a __restrict__ parameter does the
+// compiler keep reading the reset image through the scalar cache behind the step's stores (as a member of the block the reads became
+// vector loads, each with a wait behind the stores).
+template <int PHASE, int WTP, bool TOPO_LDS, int DEFK>
+__global__ __launch_bounds__(256) void step_kernel(const StepCfg* __restrict__ Cp, LeanStepArgs a) {
+    static_assert(PHASE == 0 && WTP == 0 && !TOPO_LDS && DEFK == MCBS_DEFENDER_NONE, "the lean argument block serves the packed, attacker-only whole step");
+    DevState S{};
+    S.h0 = a.h0; S.masks = a.masks; S.body = a.body; S.h1 = a.h1; S.episode = a.episode; S.pending = a.pending;
+    S.E = a.E; S.body_stride = a.body_stride; S.N = a.N; S.tiny_p = a.tiny_p; S.tiny_v = a.tiny_v;
+    S.NW = S.SW = S.TW = S.WT = 1u; S.packed = 1u;      // (off_disc = off_cred = off_rows = 0, no ring, no wide set: a packed batch without defender)
+    const Topo T{nullptr, a.hot};
+    StepIO io{};
+    io.actions = a.actions; io.reward = a.reward; io.terminated = a.terminated;
+#ifdef MCBS_DIAG
+    io.stamps = a.stamps;
+#endif
+    NoHook nh;
+    step_body<0, 0, MCBS_DEFENDER_NONE, false, true>(S, T, Cp, io, RollArgs{}, nh);
 }
 
 // mcbs_step_many / mcbs_rollout_random: io.n_steps consecutive steps in one launch; `roll` is a kernel ARGUMENT (nothing in device

@@ -26,7 +26,7 @@ EXPORTS = [
     "mcbs_step_many", "mcbs_rollout_random", "mcbs_attacker_wrapper_post", "mcbs_attacker_wrapper_clear", "mcbs_defender_wrapper_post", "mcbs_sample_actions", "mcbs_decode_attacker_actions", "mcbs_defender_step", "mcbs_defender_observe", "mcbs_set_draw_tape", "mcbs_state_record_bytes", "mcbs_get_state", "mcbs_set_state",
     "mcbs_timing_enable", "mcbs_timing_read", "mcbs_mask_logits", "mcbs_discrete_action_count", "mcbs_copy_rows_masked", "mcbs_attacker_wrapper_finish", "mcbs_attacker_wrapper_step",
     "mcbs_attacker_wrapper_step_launches", "mcbs_set_mask_discrete_stride", "mcbs_defender_wrapper_step",
-    "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant",
+    "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant", "mcbs_step_is_lean",
     "mcbs_feature_layout_create", "mcbs_feature_layout_destroy", "mcbs_feature_layout_width", "mcbs_encode_features",
     "mcbs_masked_categorical", "mcbs_masked_categorical_packed", "mcbs_masked_categorical_grad",
     "mcbs_gae",
@@ -120,6 +120,8 @@ def load_library(path: Optional[str] = None):
     lib.mcbs_attacker_wrapper_step_launches.argtypes = [C.c_void_p, C.c_int32]
     lib.mcbs_set_mask_discrete_stride.argtypes = [C.c_void_p, C.c_size_t]
     lib.mcbs_batch_variant.argtypes = [C.c_void_p, C.POINTER(BatchVariantInfo)]
+    lib.mcbs_step_is_lean.restype = C.c_int32
+    lib.mcbs_step_is_lean.argtypes = [C.c_void_p, C.c_int32]
     lib.mcbs_timing_enable.argtypes = [C.c_void_p, C.c_int32]
     lib.mcbs_timing_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     for name in EXPORTS:
@@ -880,6 +882,10 @@ class BatchEngine:
         v = BatchVariantInfo()
         _check(self.lib, self.lib.mcbs_batch_variant(self._h, C.byref(v)), "mcbs_batch_variant")
         return {name: int(getattr(v, name)) for name, _ in BatchVariantInfo._fields_}
+
+    def step_is_lean(self, with_info: bool) -> bool:
+        """Whether step(actions, with_info) of this batch takes the lean launch (packed, attacker-only batch, no info buffers)."""
+        return bool(self.lib.mcbs_step_is_lean(self._h, int(bool(with_info))))
 
     def timing_enable(self, on: bool = True) -> None:
         _check(self.lib, self.lib.mcbs_timing_enable(self._h, int(on)), "mcbs_timing_enable")
