@@ -42,6 +42,12 @@ extern "C" {
 #define MCBS_MAX_PROPS         60   /* property sets share a u64 with the 4 privilege tags of a node row */
 #define MCBS_MAX_SLOTS         32   /* vulnerabilities applicable to one node (library + own) */
 #define MCBS_MAX_LOCAL_VULNS   32   /* local-vulnerability mask per node is u32 */
+#define MCBS_MAX_VULN_COLUMNS 255   /* n_local + n_remote (at most 223 remote ids next to 32 local ones).  A CHOSEN cap of the format, not a
+                                       necessity of any field width: it keeps every column a byte-sized value (as the random-events key
+                                       lists store them, which exist only up to 64 columns) and is the largest count the tests step.  The
+                                       kernels index columns with 32-bit arithmetic; their own first limit is the descriptor table's
+                                       32-bit offsets (n_nodes * columns * 64 bytes, about 262 000 columns at 256 nodes), and the
+                                       observation's per-source remote blocks fall back to another writer past the LDS budget */
 #define MCBS_MAX_CRED_STRINGS 256    /* every set is held in <= 4 x u64 registers per env */
 #define MCBS_MAX_TRIPLES      1024  /* distinct (node, port, credential) triples; more than 256 are kept as a wide set in memory */
 

@@ -135,7 +135,8 @@ extern "C" int mcbs_topology_create(const void* blob, size_t nbytes, int32_t dev
     if (h->total_bytes != nbytes || h->header_bytes != sizeof(mcbs_topo_header)) return fail(MCBS_EINVAL, "topology blob: size mismatch");
     if (h->n_nodes == 0 || h->n_nodes > MCBS_MAX_NODES) return fail(MCBS_ELIMIT, "n_nodes %u outside 1..%d", h->n_nodes, MCBS_MAX_NODES);
     if (h->n_ports == 0 || h->n_ports > MCBS_MAX_PORTS || h->n_props > 60u || h->max_slots == 0 || h->max_slots > MCBS_MAX_SLOTS ||
-        h->n_local == 0 || h->n_local > MCBS_MAX_LOCAL_VULNS || h->n_remote == 0 || h->n_cred_strings > MCBS_MAX_CRED_STRINGS ||
+        h->n_local == 0 || h->n_local > MCBS_MAX_LOCAL_VULNS || h->n_remote == 0 || h->n_local + h->n_remote > MCBS_MAX_VULN_COLUMNS ||
+        h->n_cred_strings > MCBS_MAX_CRED_STRINGS ||
         h->n_triples > MCBS_MAX_TRIPLES)
         return fail(MCBS_ELIMIT, "topology exceeds an engine limit");
     int rc;

@@ -37,6 +37,7 @@ TOPO_MAGIC = 0x5442434D
 
 MAX_NODES, MAX_PORTS, MAX_PROPS, MAX_SLOTS, MAX_LOCAL = 256, 32, 60, 32, 32
 MAX_CRED_STRINGS, MAX_TRIPLES = 256, 1024
+MAX_COLUMNS = 255          # local + remote vulnerability identifiers (MCBS_MAX_VULN_COLUMNS): a column is a byte in the blob
 
 OUT_NONE, OUT_LEAKED_CREDENTIALS, OUT_LEAKED_NODES, OUT_PRIVILEGE_ESCALATION, OUT_LATERAL_MOVE, \
     OUT_CUSTOMER_DATA, OUT_PROBE_SUCCEEDED, OUT_PROBE_FAILED, OUT_EXPLOIT_FAILED, OUT_OTHER = range(10)
@@ -174,6 +175,8 @@ def flatten(environment) -> FlatTopology:
                          ("local vulnerabilities", L, MAX_LOCAL)):
         if n > cap:
             raise ValueError(f"topology has {n} {what}; the engine supports at most {cap}")
+    if L + R > MAX_COLUMNS:
+        raise ValueError(f"topology has {L + R} vulnerability identifiers ({L} local + {R} remote); the engine supports at most {MAX_COLUMNS}")
 
     prop_index: Dict[str, int] = {}
     for i, p in enumerate(props):

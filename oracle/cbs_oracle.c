@@ -704,6 +704,8 @@ void* cbo_create(const void* blob, size_t nbytes, const mcbs_batch_cfg* cfg) {
     const mcbs_topo_header* h = (const mcbs_topo_header*)blob;
     if (h->magic != MCBS_TOPO_MAGIC || h->total_bytes != nbytes || h->abi_version != MCBS_ABI_VERSION) return NULL;
     if (h->n_nodes > cfg->maximum_node_count) return NULL;
+    /* more than 64 vulnerability columns: flatten writes no ExternalRandomEvents tables and mcbs_batch_create refuses that defender */
+    if (cfg->defender_kind == MCBS_DEFENDER_RANDOM_EVENTS && !h->off_ere) return NULL;
     oracle* o = (oracle*)calloc(1, sizeof(oracle));
     o->blob = (uint8_t*)malloc(nbytes);
     memcpy(o->blob, blob, nbytes);

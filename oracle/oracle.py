@@ -91,6 +91,9 @@ class Oracle:
         self.topo, self.spec = topo, spec
         if topo.n_nodes > spec.maximum_node_count:
             raise ValueError(f"Network node count ({topo.n_nodes}) exceeds the specified limit of {spec.maximum_node_count}.")
+        if spec.defender is not None and spec.defender[0] == "random_events" and not int(topo.header()["off_ere"]):
+            # the engine's own refusal (mcbs_batch_create, MCBS_EINVAL), word for word
+            raise ValueError("the topology blob carries no ExternalRandomEvents tables (off_ere)")
         self._cfg = spec.to_cfg()
         self._blob = np.frombuffer(topo.blob, dtype=np.uint8).copy()
         self.h = self.lib.cbo_create(self._blob.ctypes.data, self._blob.size, C.byref(self._cfg))

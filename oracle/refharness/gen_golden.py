@@ -1,6 +1,7 @@
 """Generate the golden fixtures under tests/golden/ by running the UNMODIFIED reference.
 
 Run in the build container only (needs /root/reference):   python oracle/refharness/gen_golden.py
+`--only PREFIX` writes only the traces whose names start with PREFIX and leaves the other fixtures alone.
 The reference is imported through ref_loader (stand-ins for gymnasium / boolean.py / IPython, none
 of which contribute step arithmetic except boolean.py, whose restatement is pinned by the
 reference's own tests).  Output = data only: topology blobs flattened from the reference's objects,
@@ -29,9 +30,10 @@ sys.path.insert(0, HERE)
 
 import ref_loader  # noqa: E402
 from marlon_amd import flatten as F  # noqa: E402
-from marlon_amd.samples import kitchen_sink, random_net  # noqa: E402
+from marlon_amd.samples import capacity, kitchen_sink, random_net  # noqa: E402
 
 GOLDEN = os.path.join(REPO, "tests", "golden")
+ONLY = sys.argv[sys.argv.index("--only") + 1] if "--only" in sys.argv else ""
 ref = ref_loader.load()
 
 CHAIN10_SCRIPT = [  # the action list of the reference test cyberbattle_env_test.py:42-101 (data), as (kind, a, b, c, d)
@@ -165,6 +167,8 @@ def semi_valid_action(rng, env, n_disc, n_cache, L, R, P):
 
 def run_trace(name, make_env, topo, steps, policy, seed, spec, tape_dps=0, store_masks=True, script=None, tape_script=None):
     """One env, `steps` steps; on done the harness calls reset() (= the engine's auto_reset)."""
+    if not name.startswith(ONLY):
+        return
     rng = np.random.Generator(np.random.PCG64(seed))
     env = make_env()
     env.action_space.union_np_random = np.random.Generator(np.random.PCG64(seed + 1))
@@ -243,6 +247,34 @@ def run_trace(name, make_env, topo, steps, policy, seed, spec, tape_dps=0, store
           f"oob_like={(np.asarray(rec['reward']) == 0).sum():4d} size={os.path.getsize(path) / 1024:.0f} KiB")
 
 
+def oracle_script(topo, sp, steps, seed, tape_dps=0, prefix=None):
+    """(script, tape script) written by tests/endings.py's Policy from the CPU oracle's state (one env, the spec of the trace, the same
+    tape): the reference's own valid-action sampler repeats itself on the capacity topologies and never reaches their edges.  The
+    oracle only WRITES the actions here (clipped to the declared bounds); what they do is recorded from the reference."""
+    from oracle.oracle import Oracle
+    from tests import endings, parity
+    spec = parity.spec_from_json(sp)
+    orc = Oracle(topo, spec)
+    pol = endings.Policy(topo, spec, seed)
+    tape = np.random.Generator(np.random.PCG64(seed + 7)).random((steps, max(1, tape_dps)))
+    hi = np.array([3, spec.maximum_node_count, max(spec.maximum_node_count, len(topo.local_vulnerabilities)),
+                   max(len(topo.local_vulnerabilities), len(topo.remote_vulnerabilities), len(topo.ports)), spec.maximum_total_credentials]) - 1
+    script = []
+    for t in range(steps):
+        state = orc.get_state()
+        rows = pol.rows(state)
+        fixed = prefix(t, 0, state) if prefix is not None else None
+        if fixed is not None:
+            rows[0] = fixed
+        rows = np.clip(rows, 0, hi).astype(np.int32)
+        k, a = int(rows[0, 0]), rows[0]
+        a[2] = min(a[2], (len(topo.local_vulnerabilities) if k == 0 else spec.maximum_node_count) - 1)
+        a[3] = min(a[3], (len(topo.remote_vulnerabilities) if k == 1 else len(topo.ports)) - 1)
+        orc.step(rows, tape[t:t + 1] if tape_dps else None)
+        script.append(tuple(int(x) for x in a[:[3, 4, 5][k]]))
+    return script, ([list(r) for r in tape] if tape_dps else None)
+
+
 def main():
     os.makedirs(GOLDEN, exist_ok=True)
     AG = ref.env.AttackerGoal
@@ -259,6 +291,8 @@ def main():
         "random24": F.flatten(random_net.build(ref.model, 24, 7)),
     }
     for k, t in topos.items():
+        if ONLY:
+            break
         with open(os.path.join(GOLDEN, f"topology_{k}.bin"), "wb") as f:
             f.write(t.blob)
         with open(os.path.join(GOLDEN, f"topology_{k}.json"), "w") as f:
@@ -380,8 +414,9 @@ def main():
 
     # defender wins by eviction (entry node re-imagable): LOSING reward path (env.py:1165-1167)
     topo_se = F.flatten(kitchen_sink.build(ref.model, entry_reimagable=True))
-    with open(os.path.join(GOLDEN, "topology_sink_evict.bin"), "wb") as f:
-        f.write(topo_se.blob)
+    if not ONLY:
+        with open(os.path.join(GOLDEN, "topology_sink_evict.bin"), "wb") as f:
+            f.write(topo_se.blob)
     sp_se = dict(sp_s, defender=["scan_and_reimage", 0.8, 3, 2], maintain_sla=0.0, losing_reward=-100.0)
 
     def sink_evict():
@@ -420,6 +455,39 @@ def main():
                                       defender_agent=SAR(0.5, 3, 4), defender_constraint=DC(maintain_sla=0.5),
                                       maximum_node_count=24, maximum_total_credentials=40, throws_on_invalid_actions=False)
     run_trace("random24_defender_s51", rand24, topos["random24"], 300, "mix", 51, sp_r24, tape_dps=6, store_masks=False)
+
+    # ---- the capacity limits of the topology format (marlon_amd/samples/capacity.py): 32 ports, 60 properties, 32 local ids and 32
+    # vulnerability slots per node, without a defender and with ScanAndReimage; 257 credential triples (the first wide count), masks as CRC32
+    topo_l = F.flatten(capacity.row_limits(ref.model))
+    sp_l = dict(maximum_node_count=8, maximum_total_credentials=16, maximum_discoverable_credentials_per_action=5,
+                attacker_goal=goal(), winning_reward=5000.0, losing_reward=0.0, maintain_sla=0.0, defender=None)
+
+    def limits():
+        return ref.env.CyberBattleEnv(capacity.row_limits(ref.model), attacker_goal=AG(own_atleast_percent=1.0), maximum_node_count=8,
+                                      maximum_total_credentials=16, throws_on_invalid_actions=False)
+    script, _ = oracle_script(topo_l, sp_l, 300, 71)
+    run_trace("limits_script_s71", limits, topo_l, len(script), "script", 71, sp_l, script=script)
+    sp_ld = dict(sp_l, defender=["scan_and_reimage", 0.5, 2, 3], maintain_sla=0.3, losing_reward=-100.0)
+
+    def limits_def():
+        return ref.env.CyberBattleEnv(capacity.row_limits(ref.model), attacker_goal=AG(own_atleast_percent=1.0), defender_agent=SAR(0.5, 2, 3),
+                                      defender_constraint=DC(maintain_sla=0.3), losing_reward=-100.0, maximum_node_count=8,
+                                      maximum_total_credentials=16, throws_on_invalid_actions=False)
+    script, tape = oracle_script(topo_l, sp_ld, 300, 72, tape_dps=4)
+    run_trace("limits_defender_s72", limits_def, topo_l, len(script), "script", 72, sp_ld, tape_dps=4, script=script, tape_script=tape)
+    topo_c = F.flatten(capacity.credential_limits(ref.model, 257))
+    sp_c = dict(maximum_node_count=9, maximum_total_credentials=257, maximum_discoverable_credentials_per_action=topo_c.max_leak_per_action,
+                attacker_goal=goal(), winning_reward=5000.0, losing_reward=0.0, maintain_sla=0.0, defender=None)
+
+    def credlimits():
+        return ref.env.CyberBattleEnv(capacity.credential_limits(ref.model, 257), attacker_goal=AG(own_atleast_percent=1.0), maximum_node_count=9,
+                                      maximum_total_credentials=257, maximum_discoverable_credentials_per_action=topo_c.max_leak_per_action,
+                                      throws_on_invalid_actions=False)
+    from tests.capacity import credential_prefix
+    script, _ = oracle_script(topo_c, sp_c, 100, 73, prefix=credential_prefix(topo_c, None)[0])
+    run_trace("credlimits257_script_s73", credlimits, topo_c, len(script), "script", 73, sp_c, store_masks=False, script=script)
+    if ONLY:
+        return
 
     # ---- the reference's command-and-control walkthrough of ToyCtf (commandcontrol_test.py:14-71): total 389.0 ----
     m = ref.model

@@ -12,7 +12,7 @@ import numpy as np
 from marlon_amd import flatten as F
 from marlon_amd import model
 from marlon_amd._abi import RNG_TAPE, EnvSpec
-from marlon_amd.samples import (active_directory, chainpattern, generate_network, kitchen_sink, labelled_graph, random_net,
+from marlon_amd.samples import (active_directory, capacity, chainpattern, generate_network, kitchen_sink, labelled_graph, random_net,
                                 tinytoy, toy_ctf)
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -48,6 +48,10 @@ def topology_for(trace_name: str) -> F.FlatTopology:
         return F.flatten(random_net.build(model, 24, 7))
     if trace_name.startswith("random100") or trace_name.startswith("random200"):
         return F.flatten(random_net.build(model, int(trace_name[6:9]), 7))
+    if trace_name.startswith("limits"):
+        return F.flatten(capacity.row_limits(model))
+    if trace_name.startswith("credlimits"):
+        return F.flatten(capacity.credential_limits(model, int(trace_name.split("_")[0][10:])))
     raise KeyError(trace_name)
 
 
