@@ -495,6 +495,80 @@ int  mcbs_masked_categorical_grad(const mcbs_batch*, const uint32_t* bits, size_
                                   int32_t dtype, size_t row_stride, const int64_t* actions, const float* grad_log_prob,
                                   const float* grad_entropy, void* grad_logits, size_t grad_row_stride, void* stream);
 
+/* ---- MultiDiscrete head: sample, log-prob, entropy and gradient of PPO's MultiCategorical action distribution, one launch each way ----
+ * What Stable-Baselines3's MultiCategoricalDistribution does with the policy's logits for a MultiDiscrete(nvec) action — the defender's
+ * [5,N,N,6,2,N,6,2,N,3,N,3] (defend_wrapper.py:162-195) and the attacker's unmasked [3,N,L,N,N,R,N,N,P,C] (attack_wrapper.py:206-227):
+ * `split` the row by nvec, one Categorical per segment, sample / log_prob / entropy of each, summed over the segments; and what autograd
+ * gives for log_prob(actions) and the entropy differentiated with respect to the logits.  No masks: the reference has none for these heads.
+ *
+ * D = n_dims, off_d = sum of nvec[j] over j < d, A = sum of nvec.  The batch only supplies the device (as for mcbs_gae).  nvec is a HOST
+ * array of n_dims entries, copied into the kernel's argument block: no allocation, no synchronisation, asynchronous on `stream`.
+ * n_rows == 0 is a no-op.  All other pointers are device memory:
+ *   logits      float32 (MCBS_LOGITS_F32) or bfloat16 (MCBS_LOGITS_BF16) [n, row_stride], row_stride in elements, >= A; any alignment;
+ *               READ-ONLY.  mcbs_multicategorical only: NULL = the uniform law per dimension (dtype and row_stride are ignored).
+ *   mode        MCBS_CATEGORICAL_SAMPLE / _ARGMAX / _EVALUATE
+ *   actions     int64 [n, D] contiguous: written in SAMPLE and ARGMAX, read in EVALUATE and by the gradient
+ *   log_prob    float [n];  entropy  float [n] or NULL
+ *   uniforms    float [n, D] contiguous or NULL (SAMPLE; see "random numbers")
+ *   seed, step, row_key_base   key of the row's random numbers when uniforms is NULL; step < 2^48
+ *   bad_actions optional uint32_t, INCREASED by one per EVALUATE row with a component outside [0, nvec[d]) (not zeroed by the call)
+ *
+ * Semantics for dimension d of a row, x_a = (float)logits[off_d + a], 0 <= a < nvec[d]; float32 arithmetic throughout with expf, every
+ * operation rounded on its own (no fused multiply-add), no floating-point atomics:
+ *   m_d = max_a x_a,  Z_d = sum_a exp(x_a - m_d),  log p_{d,a} = (x_a - m_d) - log Z_d,
+ *   H_d = log Z_d - (sum_a (x_a - m_d) exp(x_a - m_d)) / Z_d      (a term whose exp underflows to 0 is no term)
+ *   log Z_d is the correctly rounded float32 of a double-precision log of the float32 Z_d, one per dimension.
+ *   log_prob = sum_d log p_{d,c_d},  entropy = sum_d H_d.
+ * ORDER OF THE SUMS: the indices of a dimension are taken in blocks of 32 consecutive ones ([0, 32), [32, 64), ...; the last one
+ * shorter).  Z_d and the entropy sum each add a block's terms from +0 one after the other in ascending a, then the blocks' totals from +0
+ * in ascending block order; a dimension of up to 32 choices — every one of the reference's environments — is therefore one serial chain
+ * in ascending a (a chain of 1 000 float32 terms would drift by tens of ulp).  The running sum at index a, which SAMPLE compares, is the
+ * total of the earlier blocks plus its block's partial sum up to a; at the last index it is Z_d.  log_prob and entropy start from +0 and
+ * add the dimensions' values in ascending d.  The order depends on nvec
+ * alone: not on n_rows, the strides, the alignment, the dtype's load path, the mode or the row's position.  Hence two calls give
+ * bit-identical outputs, the log_prob and entropy of SAMPLE / ARGMAX equal EVALUATE's on the returned actions bit for bit, and the
+ * gradient's m_d, Z_d, log Z_d and H_d are the forward's (the same device code).
+ *   ARGMAX    per dimension the largest logit, the lowest index among equal ones.
+ *   SAMPLE    per dimension inverse CDF in ascending index order: the first a at which the running sum that produced Z_d exceeds
+ *             u_d * Z_d; the last index if rounding leaves none.
+ *   EVALUATE  reads actions.  A row with any component outside [0, nvec[d]) gets log_prob = NaN (its entropy is still the row's) and
+ *             counts one bad_action.
+ *   logits == NULL: a_d = (u24_d * nvec[d]) >> 24 in integer arithmetic (ARGMAX: 0), log_prob = sum_d -log nvec[d], entropy =
+ *             sum_d log nvec[d] (each log the correctly rounded float32): action_space.sample() of the reference's random agents in law.
+ *   nvec[d] == 1 contributes exactly 0 to log_prob and to the entropy, action 0, and exactly zero gradient; its logit is never used.
+ *   A logit of -inf is an ordinary value as long as its dimension holds one finite logit.  A NaN logit, a +inf logit or an all -inf
+ *   dimension leave that row's log_prob, entropy and gradient unspecified; nothing is read or written out of bounds and every sampled
+ *   component stays inside [0, nvec[d]).
+ *
+ * Random numbers: u24 is a 24-bit integer, u = u24 * 2^-24.  With uniforms: u24_d = min(2^24 - 1, floor(uniforms[i, d] * 2^24)).
+ * Otherwise row i has key k = row_key_base + i and dimension d takes word (d & 3) >> 8 of the Philox4x32-10 block
+ *   counter = (k_lo, k_hi, step_lo, step_hi | ((d >> 2) << 16)),   key = (seed_lo ^ MCBS_MULTICATEGORICAL_PHILOX_DOMAIN, seed_hi)
+ * (_lo / _hi: the low / high 32 bits).  A caller that passes its env_id_base as row_key_base draws in a shard what the whole batch would
+ * draw.  The domain constant differs from the masked head's (0xCA7E6041) and the random-agent sampler's (0x5A17ACED).
+ *
+ * mcbs_multicategorical_grad: the backward pass of EVALUATE.  nvec, n_dims, n_rows, logits, dtype, row_stride and actions as above;
+ *   grad_log_prob  float [n] or NULL: g_lp, the incoming gradient of log_prob[i]; NULL = all zeros
+ *   grad_entropy   float [n] or NULL: g_H, the incoming gradient of entropy[i]; NULL = all zeros
+ *   grad_logits    [n, grad_row_stride] in the dtype of logits, grad_row_stride in elements, >= A; any alignment.  WRITE-ONLY: every
+ *                  element [i, 0 .. A) is written exactly once (the caller need not clear it), elements from A up to grad_row_stride are
+ *                  never written.  bfloat16 output is the float32 value rounded to nearest even.
+ *   grad_logits[i, off_d + a] = p_{d,a} * (-g_lp - g_H * (log p_{d,a} + H_d)) + (a == c_d ? g_lp : 0),  p_{d,a} = exp(x_a - m_d) * (1 / Z_d);
+ *   the product term is exactly 0 where the exp underflows to 0.  A row with a component outside its range is +0.0 throughout (the
+ *   forward has returned NaN for it and counted it; the gradient call counts nothing).
+ *
+ * MCBS_EINVAL (the message names the argument): batch or nvec NULL; n_dims outside [1, MCBS_MAX_ACTION_DIMS]; an nvec[d] outside
+ * [1, 65536]; a mode other than the three above; step >= 2^48; a dtype other than MCBS_LOGITS_F32 / _BF16; row_stride < A or
+ * grad_row_stride < A; with n_rows > 0 a required pointer NULL (actions, log_prob; for the gradient logits, actions, grad_logits: the
+ * uniform law has no gradient); the grad_logits rows overlap the logits rows (the rule of mcbs_masked_categorical_grad). */
+#define MCBS_MAX_ACTION_DIMS 16
+#define MCBS_MULTICATEGORICAL_PHILOX_DOMAIN 0x3C47E6A1u
+int  mcbs_multicategorical(const mcbs_batch*, const uint32_t* nvec, uint32_t n_dims, uint64_t n_rows, const void* logits, int32_t dtype,
+                           size_t row_stride, int32_t mode, int64_t* actions, float* log_prob, float* entropy, const float* uniforms,
+                           uint64_t seed, uint64_t step, uint64_t row_key_base, uint32_t* bad_actions, void* stream);
+int  mcbs_multicategorical_grad(const mcbs_batch*, const uint32_t* nvec, uint32_t n_dims, uint64_t n_rows, const void* logits, int32_t dtype,
+                                size_t row_stride, const int64_t* actions, const float* grad_log_prob, const float* grad_entropy,
+                                void* grad_logits, size_t grad_row_stride, void* stream);
+
 /* ---- generalized advantage estimation: advantages and returns of a whole [T, E] rollout, one launch ----
  * The step between "rollout finished" and "first minibatch": what Stable-Baselines3 2.x's RolloutBuffer.compute_returns_and_advantage
  * does with T Python iterations over [E] host vectors (the reference reaches it through on_rollout_end,

@@ -79,6 +79,20 @@ class GaeIO(C.Structure):
 assert C.sizeof(GaeIO) == 144
 
 
+# the MultiDiscrete head (include/mcbs.h): its two constants and the prototypes of its two entry points
+MCBS_MAX_ACTION_DIMS = 16
+MCBS_MULTICATEGORICAL_PHILOX_DOMAIN = 0x3C47E6A1
+MULTICATEGORICAL_ARGTYPES = {
+    # batch, nvec (host), n_dims, n_rows, logits, dtype, row_stride, mode, actions, log_prob, entropy, uniforms, seed, step, row_key_base,
+    # bad_actions, stream
+    "mcbs_multicategorical": [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_int32, C.c_void_p,
+                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p],
+    # batch, nvec (host), n_dims, n_rows, logits, dtype, row_stride, actions, grad_log_prob, grad_entropy, grad_logits, grad_row_stride, stream
+    "mcbs_multicategorical_grad": [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
+}
+
+
 class InfoBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("network_availability", "step_count", "truncated", "out_of_bound", "raw_reward")]
 

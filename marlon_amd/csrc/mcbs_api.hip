@@ -23,6 +23,7 @@
 #include "mcbs_packed_mask.hip"
 #include "mcbs_categorical.hip"
 #include "mcbs_categorical_grad.hip"
+#include "mcbs_multicategorical.hip"
 #include "mcbs_gae.hip"
 #include "mcbs_features.hip"
 #include "mcbs_wrapper_fused.hip"
@@ -1425,6 +1426,95 @@ extern "C" int mcbs_masked_categorical_grad(const mcbs_batch* b, const uint32_t*
                            bits, bits_row_words, io);
     });
     return launch_ok("masked categorical gradient");
+}
+
+// ------------------------------------------------------------------ MultiDiscrete head
+// nvec (host) -> the kernels' geometry; `who` names the entry point in messages
+static int multicategorical_geom(const char* who, const uint32_t* nvec, uint32_t n_dims, McGeom& G) {
+    if (!nvec) return fail(MCBS_EINVAL, "%s: nvec must not be NULL", who);
+    if (n_dims < 1u || n_dims > MCBS_MAX_ACTION_DIMS) return fail(MCBS_EINVAL, "%s: n_dims %u lies outside [1, %u]", who, n_dims, (unsigned)MCBS_MAX_ACTION_DIMS);
+    G = McGeom{};
+    uint32_t A = 0u;
+    for (uint32_t d = 0; d < n_dims; ++d) {
+        if (nvec[d] < 1u || nvec[d] > 65536u) return fail(MCBS_EINVAL, "%s: nvec[%u] = %u lies outside [1, 65536]", who, d, nvec[d]);
+        G.nvec[d] = nvec[d];
+        G.off[d] = A;
+        A += nvec[d];
+    }
+    G.D = n_dims;
+    G.A = A;
+    G.R = MC_LANES / n_dims;
+    return MCBS_OK;
+}
+
+// rows per workgroup pass of the staged path (0: the rows are too wide for it)
+static uint32_t multicategorical_staged_rows(const McGeom& G) {
+    const uint32_t fit = MC_LDS_FLOATS / G.A;
+    return fit < G.R ? fit : G.R;
+}
+
+template <class F>
+static void multicategorical_dispatch(McGeom& G, bool have_logits, int32_t dtype, uint64_t n_rows, F&& launch) {
+    const uint32_t staged = have_logits ? multicategorical_staged_rows(G) : 0u;
+    if (staged) G.R = staged;
+    const uint64_t groups = (n_rows + G.R - 1u) / G.R;
+    const dim3 grid(groups < 8192u ? (uint32_t)groups : 8192u), block(MC_LANES);
+    const size_t lds = (MC_LDS_HEAD + (staged ? (size_t)((G.R * G.A + 3u) & ~3u) : 0u)) * sizeof(float);
+    pick<2, 4>(dtype == MCBS_LOGITS_BF16 && have_logits ? 2 : 4, [&](auto es) {          // element size: bf16 patterns, else fp32 (also without logits)
+        pick<1, 0>(staged ? 1 : 0, [&](auto sg) { launch(es, sg, grid, block, lds); });
+    });
+}
+
+extern "C" int mcbs_multicategorical(const mcbs_batch* b, const uint32_t* nvec, uint32_t n_dims, uint64_t n_rows, const void* logits, int32_t dtype,
+                                     size_t row_stride, int32_t mode, int64_t* actions, float* log_prob, float* entropy, const float* uniforms,
+                                     uint64_t seed, uint64_t step, uint64_t row_key_base, uint32_t* bad_actions, void* stream) {
+    if (!b) return fail(MCBS_EINVAL, "mcbs_multicategorical: batch must not be NULL");
+    MCBS_ON_DEVICE(b);
+    int rc;
+    McGeom G;
+    if ((rc = multicategorical_geom("mcbs_multicategorical", nvec, n_dims, G))) return rc;
+    if (mode != MCBS_CATEGORICAL_SAMPLE && mode != MCBS_CATEGORICAL_ARGMAX && mode != MCBS_CATEGORICAL_EVALUATE)
+        return fail(MCBS_EINVAL, "mcbs_multicategorical: mode must be MCBS_CATEGORICAL_SAMPLE, _ARGMAX or _EVALUATE");
+    if (step >= (1ull << 48)) return fail(MCBS_EINVAL, "mcbs_multicategorical: step %llu: at most 2^48 - 1", (unsigned long long)step);
+    if (logits && dtype != MCBS_LOGITS_F32 && dtype != MCBS_LOGITS_BF16)
+        return fail(MCBS_EINVAL, "mcbs_multicategorical: logits dtype must be MCBS_LOGITS_F32 or MCBS_LOGITS_BF16");
+    if (logits && row_stride < G.A) return fail(MCBS_EINVAL, "mcbs_multicategorical: row_stride %zu is shorter than the %u logits of a row", row_stride, G.A);
+    if (n_rows == 0) return MCBS_OK;
+    if (!actions || !log_prob) return fail(MCBS_EINVAL, "mcbs_multicategorical: actions and log_prob must not be NULL");
+    McIO io{logits, row_stride, actions, log_prob, entropy, uniforms, bad_actions, seed, step, row_key_base, n_rows, (uint32_t)mode};
+    hipStream_t st = (hipStream_t)stream;
+    multicategorical_dispatch(G, logits != nullptr, dtype, n_rows, [&](auto es, auto sg, dim3 grid, dim3 block, size_t lds) {
+        hipLaunchKernelGGL((multicategorical_kernel<LogitsElem<(uint32_t)decltype(es)::value>, decltype(sg)::value != 0>), grid, block, lds, st, G, io);
+    });
+    return launch_ok("multicategorical");
+}
+
+extern "C" int mcbs_multicategorical_grad(const mcbs_batch* b, const uint32_t* nvec, uint32_t n_dims, uint64_t n_rows, const void* logits, int32_t dtype,
+                                          size_t row_stride, const int64_t* actions, const float* grad_log_prob, const float* grad_entropy,
+                                          void* grad_logits, size_t grad_row_stride, void* stream) {
+    if (!b) return fail(MCBS_EINVAL, "mcbs_multicategorical_grad: batch must not be NULL");
+    MCBS_ON_DEVICE(b);
+    int rc;
+    McGeom G;
+    if ((rc = multicategorical_geom("mcbs_multicategorical_grad", nvec, n_dims, G))) return rc;
+    if (dtype != MCBS_LOGITS_F32 && dtype != MCBS_LOGITS_BF16)
+        return fail(MCBS_EINVAL, "mcbs_multicategorical_grad: logits dtype must be MCBS_LOGITS_F32 or MCBS_LOGITS_BF16");
+    if (row_stride < G.A) return fail(MCBS_EINVAL, "mcbs_multicategorical_grad: row_stride %zu is shorter than the %u logits of a row", row_stride, G.A);
+    if (grad_row_stride < G.A)
+        return fail(MCBS_EINVAL, "mcbs_multicategorical_grad: grad_row_stride %zu is shorter than the %u logits of a row", grad_row_stride, G.A);
+    if (n_rows == 0) return MCBS_OK;
+    if (!logits || !actions || !grad_logits)
+        return fail(MCBS_EINVAL, "mcbs_multicategorical_grad: logits, actions and grad_logits must not be NULL (the uniform law has no gradient)");
+    const size_t es = dtype == MCBS_LOGITS_F32 ? 4u : 2u;
+    if (rows_overlap(reinterpret_cast<uintptr_t>(logits), row_stride * es, reinterpret_cast<uintptr_t>(grad_logits), grad_row_stride * es, n_rows,
+                     (size_t)G.A * es))
+        return fail(MCBS_EINVAL, "mcbs_multicategorical_grad: the grad_logits rows overlap the logits rows");
+    McGradIO io{logits, row_stride, actions, grad_log_prob, grad_entropy, grad_logits, grad_row_stride, n_rows};
+    hipStream_t st = (hipStream_t)stream;
+    multicategorical_dispatch(G, true, dtype, n_rows, [&](auto esc, auto sg, dim3 grid, dim3 block, size_t lds) {
+        hipLaunchKernelGGL((multicategorical_grad_kernel<LogitsElem<(uint32_t)decltype(esc)::value>, decltype(sg)::value != 0>), grid, block, lds, st, G, io);
+    });
+    return launch_ok("multicategorical gradient");
 }
 
 // ------------------------------------------------------------------ generalized advantage estimation

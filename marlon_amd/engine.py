@@ -14,7 +14,8 @@ from typing import Dict, Iterable, Optional
 
 import numpy as np
 
-from ._abi import BatchCfg, BatchVariantInfo, DefenderObs, EnvSpec, GaeIO, InfoBuffers, ObsBuffers, split_state, state_record_bytes
+from ._abi import (MULTICATEGORICAL_ARGTYPES, BatchCfg, BatchVariantInfo, DefenderObs, EnvSpec, GaeIO, InfoBuffers, ObsBuffers,
+                   split_state, state_record_bytes)
 from .flatten import FlatTopology
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -29,6 +30,7 @@ EXPORTS = [
     "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant", "mcbs_step_is_lean",
     "mcbs_feature_layout_create", "mcbs_feature_layout_destroy", "mcbs_feature_layout_width", "mcbs_encode_features",
     "mcbs_masked_categorical", "mcbs_masked_categorical_packed", "mcbs_masked_categorical_grad",
+    "mcbs_multicategorical", "mcbs_multicategorical_grad",
     "mcbs_gae",
 ]
 
@@ -127,6 +129,8 @@ def load_library(path: Optional[str] = None):
     for name in EXPORTS:
         if not hasattr(lib, name):
             raise NativeLibraryMissing(f"{p} does not export {name}")
+    for name, argtypes in MULTICATEGORICAL_ARGTYPES.items():
+        getattr(lib, name).argtypes = argtypes
     if path is None:
         _lib = lib
     return lib
@@ -206,6 +210,41 @@ def _masked_evaluate_function(torch):
     return MaskedEvaluate
 
 
+# what BatchEngine.multicategorical returns: actions int64 [n, D], log_prob float32 [n], entropy float32 [n]
+MultiCategorical = collections.namedtuple("MultiCategorical", ["actions", "log_prob", "entropy"])
+
+_MULTI_EVALUATE = None
+
+
+def _multicategorical_evaluate_function(torch):
+    """The torch.autograd.Function behind BatchEngine.multicategorical_evaluate (made on first use, like _masked_evaluate_function)."""
+    global _MULTI_EVALUATE
+    if _MULTI_EVALUATE is not None:
+        return _MULTI_EVALUATE
+
+    class MultiCategoricalEvaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, logits, eng, nvec, actions, bad_actions):
+            r = eng.multicategorical(logits, nvec, mode="evaluate", actions=actions, bad_actions=bad_actions)
+            ctx.eng, ctx.nvec = eng, nvec
+            ctx.save_for_backward(logits, actions)
+            ctx.set_materialize_grads(False)             # an output the loss does not use arrives as None, not as zeros
+            return r.log_prob, r.entropy
+
+        @staticmethod
+        def backward(ctx, g_lp, g_ent):
+            logits, actions = ctx.saved_tensors
+            if not ctx.needs_input_grad[0]:
+                return None, None, None, None, None
+            grad = ctx.eng.multicategorical_grad(logits, ctx.nvec, actions,
+                                                 None if g_lp is None else g_lp.float().contiguous(),
+                                                 None if g_ent is None else g_ent.float().contiguous())
+            return grad, None, None, None, None
+
+    _MULTI_EVALUATE = MultiCategoricalEvaluate
+    return MultiCategoricalEvaluate
+
+
 FEATURE_FIELDS = ("scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel")
 
 
@@ -249,6 +288,7 @@ class BatchEngine:
                          raw_reward=torch.zeros(self.E, dtype=f32, device=dev))
         self._info_struct = InfoBuffers(**{k: v.data_ptr() for k, v in self.info.items()})
         self._feature_rows = {k: int(np.prod(self._shapes[k][0])) for k in FEATURE_FIELDS}        # int32 values per row of each field
+        self._nvec_blocks = {}                             # multicategorical: nvec tuple -> (host uint32 array, D, A)
         self._feature_dtypes = {torch.float32: (0, 4), torch.bfloat16: (1, 2), torch.float16: (2, 2)}  # MCBS_FEATURES_* code, item size
 
     def close(self) -> None:
@@ -705,6 +745,118 @@ class BatchEngine:
         `logits`, whose backward is masked_categorical_grad (one launch each way); actions and n_allowed are not differentiable."""
         lp, ent, k = _masked_evaluate_function(self.torch).apply(logits, self, bits, actions, bad_actions)
         return MaskedCategorical(actions, lp, ent, k)
+
+    # -- MultiDiscrete head (include/mcbs.h): sample / log-prob / entropy / gradient of SB3's MultiCategoricalDistribution --
+    def _nvec_block(self, nvec):
+        """nvec -> (host uint32 array for the library, D, A), cached per tuple; what the C side refuses (D outside [1, 16], an entry
+        outside [1, 65 536]) is left to it."""
+        key = tuple(int(v) for v in np.asarray(nvec).reshape(-1))
+        hit = self._nvec_blocks.get(key)
+        if hit is None:
+            if any(v < 0 or v >= 2 ** 32 for v in key):
+                raise ValueError(f"nvec entries must be unsigned 32-bit numbers, got {list(key)}")
+            hit = self._nvec_blocks[key] = ((C.c_uint32 * max(len(key), 1))(*key), len(key), sum(key))
+        return hit
+
+    def multicategorical(self, logits, nvec, *, mode: str = "sample", actions=None, seed: int = 0, step: int = 0, uniforms=None,
+                         row_key_base: int = 0, out=None, bad_actions=None) -> MultiCategorical:
+        """PPO's action distribution over a MultiDiscrete(nvec) action in one launch: `split` by nvec, a Categorical per dimension,
+        log_prob and entropy summed over the dimensions; logits are never modified.  logits: device float32 / bfloat16 [n, >= A] with
+        contiguous rows, A = sum(nvec), any n; or None for the uniform law per dimension (n is then that of actions, uniforms or out,
+        else n_envs).  nvec: up to 16 dimension widths, each in [1, 65 536].  mode: "sample" (per dimension inverse CDF in ascending index
+        order), "argmax" (lowest index among equal logits) or "evaluate" (log-prob of the given `actions`, int64 [n, D]; NaN for a row with a
+        component outside [0, nvec[d]), counted in bad_actions: optional device int32 [1], increased, not zeroed).  Row i is keyed by
+        (seed, row_key_base + i, step), step < 2^48, unless `uniforms` (device float32 [n, D] in [0, 1)) is given.  out: optional
+        (actions, log_prob, entropy) of preallocated contiguous device tensors (int64 [n, D], float32 [n], float32 [n]).
+        -> MultiCategorical(actions, log_prob, entropy)."""
+        t = self.torch
+        if mode not in CATEGORICAL_MODES:
+            raise ValueError(f"mode must be one of {sorted(CATEGORICAL_MODES)}, got {mode!r}")
+        block, D, A = self._nvec_block(nvec)
+        if out is not None and len(out) != 3:
+            raise ValueError("out must be (actions, log_prob, entropy)")
+        o_act, o_lp, o_ent = out if out is not None else (None, None, None)
+        if logits is not None:
+            if not isinstance(logits, t.Tensor) or logits.dtype not in (t.float32, t.bfloat16):
+                raise ValueError("logits must be a float32 or bfloat16 tensor (or None for the uniform law)")
+            # the C side sees only the row stride: a view narrower than A would have its rows read past their end
+            if logits.dim() != 2 or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < A:
+                raise ValueError(f"logits must be a device tensor [n, >= {A}] with contiguous rows")
+            n = logits.shape[0]
+        else:
+            given = [x for x in (actions, uniforms, o_act, o_lp, o_ent) if isinstance(x, t.Tensor) and x.dim() >= 1]
+            n = given[0].shape[0] if given else self.E
+
+        def arr(x, dtype, shape, what):
+            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != shape or not x.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous device {dtype} tensor {list(shape)}")
+            return x
+
+        if mode == "evaluate":
+            if actions is None:
+                raise ValueError('mode="evaluate" needs actions (int64 [n, D])')
+            o_act = arr(actions, t.int64, (n, D), "actions")
+        else:
+            if actions is not None:
+                raise ValueError('actions are an input of mode="evaluate" only (preallocate outputs with out=)')
+            o_act = arr(o_act, t.int64, (n, D), "out.actions") if o_act is not None else t.empty((n, D), dtype=t.int64, device=self.device)
+        o_lp = arr(o_lp, t.float32, (n,), "out.log_prob") if o_lp is not None else t.empty(n, dtype=t.float32, device=self.device)
+        o_ent = arr(o_ent, t.float32, (n,), "out.entropy") if o_ent is not None else t.empty(n, dtype=t.float32, device=self.device)
+        if uniforms is not None:
+            arr(uniforms, t.float32, (n, D), "uniforms")
+        if bad_actions is not None and (not isinstance(bad_actions, t.Tensor) or bad_actions.dtype != t.int32 or bad_actions.numel() != 1
+                                        or bad_actions.device != self.device):
+            raise ValueError("bad_actions must be a device int32 tensor of one element")
+        _check(self.lib, self.lib.mcbs_multicategorical(
+            self._h, block, D, n, logits.data_ptr() if logits is not None else None, 0 if logits is None or logits.dtype == t.float32 else 1,
+            (logits.stride(0) if n > 1 else max(logits.stride(0), logits.shape[1])) if logits is not None else 0, CATEGORICAL_MODES[mode],
+            o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), uniforms.data_ptr() if uniforms is not None else None,
+            int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(row_key_base) & (2 ** 64 - 1),
+            bad_actions.data_ptr() if bad_actions is not None else None, self._stream()), "mcbs_multicategorical")
+        return MultiCategorical(o_act, o_lp, o_ent)
+
+    def multicategorical_grad(self, logits, nvec, actions, grad_log_prob=None, grad_entropy=None, out=None):
+        """The backward pass of multicategorical(mode="evaluate") in one launch: the gradient with respect to `logits` of log_prob(actions)
+        and the entropy, given their incoming gradients grad_log_prob / grad_entropy (device float32 [n]; None = zeros).  logits float32 /
+        bfloat16 [n, >= A], actions int64 [n, D] as in the forward.  out: a device tensor of the logits' dtype [n, >= A] with contiguous
+        rows that does not overlap logits, or None for a new [n, A] one; columns [0, A) are written entirely (a row with a component
+        outside its range: +0.0), columns from A on never.  -> grad_logits."""
+        t = self.torch
+        block, D, A = self._nvec_block(nvec)
+        if not isinstance(logits, t.Tensor) or logits.dtype not in (t.float32, t.bfloat16):
+            raise ValueError("logits must be a float32 or bfloat16 tensor (the uniform law has no gradient)")
+        if logits.dim() != 2 or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < A:
+            raise ValueError(f"logits must be a device tensor [n, >= {A}] with contiguous rows")
+        n = logits.shape[0]
+
+        def arr(x, dtype, shape, what):
+            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != shape or not x.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous device {dtype} tensor {list(shape)}")
+            return x
+
+        arr(actions, t.int64, (n, D), "actions")
+        if grad_log_prob is not None:
+            arr(grad_log_prob, t.float32, (n,), "grad_log_prob")
+        if grad_entropy is not None:
+            arr(grad_entropy, t.float32, (n,), "grad_entropy")
+        if out is None:
+            out = t.empty((n, A), dtype=logits.dtype, device=self.device)
+        elif (not isinstance(out, t.Tensor) or out.dtype != logits.dtype or out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1
+              or out.device != self.device or out.shape[1] < A):
+            raise ValueError(f"out must be a device {logits.dtype} tensor [{n}, >= {A}] with contiguous rows")
+        stride = lambda x: x.stride(0) if n > 1 else max(x.stride(0), x.shape[1])
+        _check(self.lib, self.lib.mcbs_multicategorical_grad(
+            self._h, block, D, n, logits.data_ptr(), 0 if logits.dtype == t.float32 else 1, stride(logits), actions.data_ptr(),
+            grad_log_prob.data_ptr() if grad_log_prob is not None else None, grad_entropy.data_ptr() if grad_entropy is not None else None,
+            out.data_ptr(), stride(out), self._stream()), "mcbs_multicategorical_grad")
+        return out
+
+    def multicategorical_evaluate(self, logits, nvec, actions, bad_actions=None) -> MultiCategorical:
+        """multicategorical(mode="evaluate") as a node of torch's autograd graph: log_prob and entropy carry a graph into `logits`, whose
+        backward is multicategorical_grad (one launch each way); actions are not differentiable."""
+        lp, ent = _multicategorical_evaluate_function(self.torch).apply(logits, self, tuple(int(v) for v in np.asarray(nvec).reshape(-1)),
+                                                                        actions, bad_actions)
+        return MultiCategorical(actions, lp, ent)
 
     # -- generalized advantage estimation (include/mcbs.h): advantages and returns of a whole [T, E] rollout in one launch --
     def gae(self, rewards, values, episode_starts, last_values, last_dones, gamma: float, gae_lambda: float, bootstrap=None, advantages=None,

@@ -36,7 +36,46 @@ FLAT_FIELDS = ["scalars", "leaked_credentials", "credential_cache_matrix", "disc
                "nodes_privilegelevel", "mask_discrete"]
 
 
-class AttackerVecEnv:
+class _MultiDiscreteHead:
+    """The MultiDiscrete head (mcbs_multicategorical) for a wrapper with `engine`, `num_envs` and `nvec`: SB3's
+    MultiCategoricalDistribution over the wrapper's MultiDiscrete(nvec) action, one launch each way."""
+
+    def _check_multidiscrete(self) -> None:
+        pass
+
+    def sample_actions(self, logits, seed: int, step: int, deterministic: bool = False, uniforms=None, out=None):
+        """An action row per env from the policy's logits [n_envs, >= sum(nvec)] (float32 / bfloat16, never modified): per dimension a
+        Categorical over its own segment of the row -> MultiCategorical(actions int64 [n_envs, D], log_prob, entropy), the latter two
+        summed over the dimensions.  deterministic: per dimension the largest logit (lowest index among equal ones).  Rows are keyed by
+        (seed, global env id, step): shards of one batch draw what the whole batch would; pass the rollout step as `step`.  uniforms
+        (device float32 [n_envs, D] in [0, 1)) replaces the key, e.g. under graph capture."""
+        self._check_multidiscrete()
+        if logits is not None and logits.shape[0] != self.num_envs:
+            raise ValueError(f"logits has {logits.shape[0]} rows, the wrapper {self.num_envs} envs")
+        return self.engine.multicategorical(logits, self._nvec, mode="argmax" if deterministic else "sample", seed=seed, step=step,
+                                            uniforms=uniforms, row_key_base=self.engine.spec.env_id_base, out=out)
+
+    def sample_uniform(self, seed: int, step: int, uniforms=None, out=None):
+        """action_space.sample() of the reference's random agents in law: every component uniform over its range = sample_actions with no
+        logits at all (log_prob = -sum log nvec[d])."""
+        self._check_multidiscrete()
+        return self.engine.multicategorical(None, self._nvec, mode="sample", seed=seed, step=step, uniforms=uniforms,
+                                            row_key_base=self.engine.spec.env_id_base, out=out)
+
+    def evaluate_actions(self, logits, actions, differentiable: bool = False, bad_actions=None, out=None):
+        """PPO's evaluate_actions for stored rows: log_prob of `actions` int64 [n, D] and the entropy under logits [n, >= sum(nvec)], any
+        n.  The log_prob of an action sample_actions drew from the same logits comes back bit for bit.  differentiable=True: the same
+        numbers, and log_prob and entropy carry an autograd graph into `logits` (engine.multicategorical_evaluate: the backward pass is
+        one launch of mcbs_multicategorical_grad); out= cannot be combined with it."""
+        self._check_multidiscrete()
+        if differentiable:
+            if out is not None:
+                raise ValueError("evaluate_actions(differentiable=True) allocates its outputs: out= is not supported")
+            return self.engine.multicategorical_evaluate(logits, self._nvec, actions, bad_actions=bad_actions)
+        return self.engine.multicategorical(logits, self._nvec, mode="evaluate", actions=actions, bad_actions=bad_actions, out=out)
+
+
+class AttackerVecEnv(_MultiDiscreteHead):
     def __init__(self, initial_environment, n_envs: int, maximum_total_credentials: int = 1000, maximum_node_count: int = 100,
                  maximum_discoverable_credentials_per_action: int = 5, defender_agent=None,
                  attacker_goal: Optional[AttackerGoal] = AttackerGoal(own_atleast_percent=1.0),
@@ -66,6 +105,7 @@ class AttackerVecEnv:
         N, Cm = maximum_node_count, maximum_total_credentials
         L, R, P = len(self.topo.local_vulnerabilities), len(self.topo.remote_vulnerabilities), len(self.topo.ports)
         self.nvec = np.array([3, N, L, N, N, R, N, N, P, Cm], dtype=np.int64)                      # attack_wrapper.py:206-227
+        self._nvec = tuple(int(v) for v in self.nvec)
         self.discrete_n = N * N * P * Cm + N * L + N * N * R                                         # action_masking.py:74-80
         dev = self.engine.device
         # materialize_masks=False: the three action masks (94 % of the observation's bytes) are not written at all; a policy applies them
@@ -172,6 +212,12 @@ class AttackerVecEnv:
     def unpack_action_mask(self, bits, out=None):
         """Packed masks [n, >= W] -> bool [n, A] (what action_masks() returns for the same step)."""
         return self.engine.unpack_action_mask(bits, out)
+
+    # -- the MultiDiscrete head (discrete=False: the reference's unmasked PPO attacker): sample_actions / sample_uniform / evaluate_actions --
+    def _check_multidiscrete(self) -> None:
+        if self.discrete:
+            raise RuntimeError("this AttackerVecEnv was created with discrete=True, its action is one Discrete index: use sample_masked / "
+                               "sample_masked_uniform / evaluate_masked")
 
     # -- the masked categorical head (mcbs_masked_categorical): MaskableCategorical's sample / log_prob / entropy in one launch --
     def _live_bits(self):
@@ -406,7 +452,7 @@ class AttackerVecEnv:
         self.engine.close()
 
 
-class DefenderVecEnv:
+class DefenderVecEnv(_MultiDiscreteHead):
     """`DefenderEnvWrapper` + `LearningDefender` (marlon/baseline_models/env_wrappers/defend_wrapper.py,
     marlon/defender_agents/defender.py) for the batch an `AttackerVecEnv(..., learned_defender=True)` owns: the two
     wrappers share one environment batch, as in MultiAgentUniverse.build (multiagent_universe.py:160-199).
@@ -434,6 +480,7 @@ class DefenderVecEnv:
         self.winning_reward = float(attacker.spec.winning_reward)
         N = attacker.topo.n_nodes
         self.nvec = np.array([5, N, N, 6, 2, N, 6, 2, N, 3, N, 3], dtype=np.int64)          # defend_wrapper.py:162-195
+        self._nvec = tuple(int(v) for v in self.nvec)
         self._obs = self.engine.alloc_defender_obs()
         self.timesteps = t.zeros(E, dtype=t.int32, device=dev)
         self.has_breached_sla = t.zeros(E, dtype=t.bool, device=dev)
@@ -451,6 +498,42 @@ class DefenderVecEnv:
     @property
     def observation(self) -> Dict[str, object]:
         return self._obs
+
+    # -- the policy's input features and the rollout buffer --
+    FEATURE_KEYS = ("incoming_firewall_status", "infected_nodes", "outgoing_firewall_status", "services_status")      # sorted key order
+
+    @property
+    def feature_width(self) -> int:
+        """Columns of a features() row: the four MultiBinary fields' sizes added up."""
+        return sum(int(np.prod(self._obs[k].shape[1:])) for k in self.FEATURE_KEYS)
+
+    def features(self, out=None, dtype=None):
+        """The observation this env last returned as the float rows Stable-Baselines3's MultiInputPolicy would build from it
+        (preprocess_obs + CombinedExtractor): the four int8 MultiBinary fields as 0.0 / 1.0, flattened and concatenated in sorted key
+        order (FEATURE_KEYS) -> [n_envs, feature_width] float32 (or `dtype`).  out=: write into a preallocated [n_envs, >= feature_width]
+        tensor, e.g. buffer[t] of a rollout buffer; columns beyond feature_width are left alone.  Four converting `copy_`s: about 140 bytes
+        per row of plumbing, not a kernel of its own."""
+        t = self.torch
+        E, F = self.num_envs, self.feature_width
+        if out is None:
+            out = t.empty((E, F), dtype=dtype if dtype is not None else t.float32, device=self.engine.device)
+        elif (not isinstance(out, t.Tensor) or out.dim() != 2 or out.shape[0] != E or out.shape[1] < F or not out.is_floating_point()
+              or out.device != self.engine.device or (dtype is not None and out.dtype != dtype)):
+            raise ValueError(f"out must be a floating-point device tensor [{E}, >= {F}]" + (f" of {dtype}" if dtype is not None else ""))
+        c = 0
+        for k in self.FEATURE_KEYS:
+            x = self._obs[k].reshape(E, -1)
+            out[:, c:c + x.shape[1]].copy_(x)
+            c += x.shape[1]
+        return out[:, :F]
+
+    def rollout_buffer(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, store_observations: bool = True):
+        """A `rollout.DeviceRolloutBuffer` of n_steps x n_envs transitions for the defender: it stores the four int8 observation fields,
+        actions [12] and no packed masks (a MultiDiscrete head has none), and computes advantages and returns with one launch.  Its add()
+        takes `observation` as obs.  store_observations=False: no observation storage (a trainer that keeps features() rows of its own)."""
+        from .rollout import DeviceRolloutBuffer
+        return DeviceRolloutBuffer(self.engine, n_steps, self.num_envs, obs=self._obs if store_observations else None, action_shape=(12,),
+                                   mask_words=None, gamma=gamma, gae_lambda=gae_lambda)
 
     def reset(self, env_mask=None):
         """Wrapper state of the envs in env_mask (all if None); the environment itself is reset by the attacker side."""
