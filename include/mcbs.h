@@ -466,6 +466,41 @@ int  mcbs_masked_categorical_packed(const mcbs_batch*, const uint32_t* bits, siz
                                     int32_t dtype, size_t row_stride, int32_t mode, int64_t* actions, float* log_prob, float* entropy,
                                     uint32_t* n_allowed, const float* uniforms, uint64_t seed, uint64_t step, uint32_t* bad_actions, void* stream);
 
+/* ---- masked action head from the latent: the masked categorical head without a logits tensor, one launch ----
+ * sb3_contrib's MaskableActorCriticPolicy ends in action_net = Linear(latent_dim_pi, A); the masked categorical head above reads only
+ * the logits under set mask bits of what that layer wrote.  These two calls COMPUTE only those: the logit of an allowed action is a
+ * dot product of the row's latent with that action's weight row, and no [n, A] tensor exists.  Same two forms, same preconditions
+ * (MCBS_ESTATE for the live form as mcbs_masked_categorical), same row keys, same outputs.
+ *
+ *   latent      [n, latent_row_stride], the policy's latent_pi
+ *   weight      [A, weight_row_stride], torch.nn.Linear's layout: one row per action
+ *   bias        [A] or NULL (zeros)
+ *   H           the layer's input width, 1 <= H <= MCBS_LINEAR_MAX_H; both strides are in elements and >= H; any alignment
+ *   dtype       MCBS_LOGITS_F32 or MCBS_LOGITS_BF16, of latent, weight and bias alike.  All three are READ-ONLY.
+ *   mode, actions, log_prob, entropy, n_allowed, uniforms, seed, step, bad_actions: as for mcbs_masked_categorical.
+ *
+ * The logit of an allowed action a of row i, with l_h = (float)latent[i, h], w_h = (float)weight[a, h] (bfloat16 widens exactly), in
+ * float32, in ONE fixed order:
+ *   four partial sums s_0 .. s_3 start at +0; for h = 0, 1, ..., H - 1 in ascending order  s_(h mod 4) = fmaf(l_h, w_h, s_(h mod 4))
+ *   (fused: one rounding per step);  x_a = ((s_0 + s_1) + (s_2 + s_3)) + (float)bias[a]   (bias == NULL: + 0.0f).
+ * x_a is a function of the latent row, the weight row and the bias element only: it does not depend on the row's index, the form, the
+ * mode, the launch geometry, alignment, strides, or on whether the kernel kept it in LDS between its sweeps or computed it again.
+ * Everything after x_a — m, Z, log p, entropy, ARGMAX ties, SAMPLE's inverse CDF and its order, K == 0, EVALUATE of a disallowed or
+ * out-of-range action, bad_actions, uniforms / Philox with MCBS_CATEGORICAL_PHILOX_DOMAIN — is the masked categorical head's contract:
+ * the outputs are bit for bit those of mcbs_masked_categorical[_packed] on a logits buffer holding these x_a.  (A GEMM sums in another
+ * order: against torch.nn.functional.linear the logits agree to rounding, exactly where every partial sum is exact.)
+ * No allocation, no host synchronisation, asynchronous on `stream`, capturable in a graph with `uniforms`.
+ * MCBS_EINVAL: latent or weight NULL (the uniform law is mcbs_masked_categorical's logits == NULL), H outside [1, MCBS_LINEAR_MAX_H], a
+ * stride < H, another dtype, a bad mode, actions or log_prob NULL; packed form: bits NULL, bits_row_words < W.  n_rows == 0 is a no-op. */
+#define MCBS_LINEAR_MAX_H 512
+int  mcbs_masked_linear_categorical(mcbs_batch*, const void* latent, size_t latent_row_stride, const void* weight, size_t weight_row_stride,
+                                    const void* bias, uint32_t H, int32_t dtype, int32_t mode, int64_t* actions, float* log_prob, float* entropy,
+                                    uint32_t* n_allowed, const float* uniforms, uint64_t seed, uint64_t step, uint32_t* bad_actions, void* stream);
+int  mcbs_masked_linear_categorical_packed(const mcbs_batch*, const uint32_t* bits, size_t bits_row_words, uint64_t n_rows, const void* latent,
+                                           size_t latent_row_stride, const void* weight, size_t weight_row_stride, const void* bias, uint32_t H,
+                                           int32_t dtype, int32_t mode, int64_t* actions, float* log_prob, float* entropy, uint32_t* n_allowed,
+                                           const float* uniforms, uint64_t seed, uint64_t step, uint32_t* bad_actions, void* stream);
+
 /* ---- masked categorical head: gradient — the backward pass of EVALUATE on stored rows, one launch ----
  * What autograd gives for the composite `where(mask, logits, -1e8)` -> Categorical -> log_prob(actions) and the entropy with the masked
  * terms zeroed, differentiated with respect to the logits, from the allowed logits alone.  Packed form only (gradients are taken at

@@ -93,6 +93,17 @@ MULTICATEGORICAL_ARGTYPES = {
 }
 
 
+# the masked action head from the latent (include/mcbs.h): the prototypes of its two entry points
+MCBS_LINEAR_MAX_H = 512
+# latent, latent_row_stride, weight, weight_row_stride, bias, H, dtype, mode, actions, log_prob, entropy, n_allowed, uniforms, seed, step,
+# bad_actions, stream
+_LINEAR_CATEGORICAL_TAIL = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
+LINEAR_CATEGORICAL_ARGTYPES = {
+    "mcbs_masked_linear_categorical": [C.c_void_p] + _LINEAR_CATEGORICAL_TAIL,                                          # batch
+    "mcbs_masked_linear_categorical_packed": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64] + _LINEAR_CATEGORICAL_TAIL,   # batch, bits, bits_row_words, n_rows
+}
+
 class InfoBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("network_availability", "step_count", "truncated", "out_of_bound", "raw_reward")]
 

@@ -23,6 +23,7 @@
 #include "mcbs_packed_mask.hip"
 #include "mcbs_categorical.hip"
 #include "mcbs_categorical_grad.hip"
+#include "mcbs_linear_categorical.hip"
 #include "mcbs_multicategorical.hip"
 #include "mcbs_gae.hip"
 #include "mcbs_features.hip"
@@ -1383,6 +1384,67 @@ extern "C" int mcbs_masked_categorical_packed(const mcbs_batch* b, const uint32_
     CatIO io{logits, row_stride, actions, log_prob, entropy, n_allowed, uniforms, bad_actions, seed, step, 0ull, n_rows, (uint32_t)mode, G.A};
     categorical_launch(b, false, G, bits, bits_row_words, dtype, io, (hipStream_t)stream);
     return launch_ok("masked categorical (packed)");
+}
+
+// ------------------------------------------------------------------ masked action head from the latent
+static int linear_categorical_args(const char* who, const void* latent, size_t latent_row_stride, const void* weight, size_t weight_row_stride,
+                                   uint32_t H, int32_t dtype, int32_t mode, const int64_t* actions, const float* log_prob) {
+    if (!latent || !weight) return fail(MCBS_EINVAL, "%s: latent and weight must not be NULL (the uniform law is mcbs_masked_categorical's logits == NULL)", who);
+    if (H < 1u || H > MCBS_LINEAR_MAX_H) return fail(MCBS_EINVAL, "%s: H %u: from 1 to %u", who, H, (uint32_t)MCBS_LINEAR_MAX_H);
+    if (latent_row_stride < H) return fail(MCBS_EINVAL, "%s: latent_row_stride %zu is shorter than H = %u", who, latent_row_stride, H);
+    if (weight_row_stride < H) return fail(MCBS_EINVAL, "%s: weight_row_stride %zu is shorter than H = %u", who, weight_row_stride, H);
+    if (dtype != MCBS_LOGITS_F32 && dtype != MCBS_LOGITS_BF16) return fail(MCBS_EINVAL, "%s: dtype must be MCBS_LOGITS_F32 or MCBS_LOGITS_BF16", who);
+    return categorical_args(who, nullptr, dtype, 0, mode, actions, log_prob, 0u);
+}
+
+static void linear_categorical_launch(const mcbs_batch* b, bool live, const LogitsGeom& G, const uint32_t* bits, size_t bits_row_words, int32_t dtype,
+                                      const LinIO& lin, const CatIO& io, hipStream_t st) {
+    const dim3 grid = rows_grid(io.n_rows, 65536u), block(256);
+    pick<2, 4>(dtype == MCBS_LOGITS_BF16 ? 2 : 4, [&](auto es) {
+        pick<1, 0>((int)live, [&](auto lv) {
+            hipLaunchKernelGGL((masked_linear_categorical_kernel<LogitsElem<(uint32_t)decltype(es)::value>, decltype(lv)::value != 0>), grid, block, 0, st,
+                               b->S, b->T, b->C_dev, b->digest, G, bits, bits_row_words, lin, io);
+        });
+    });
+}
+
+extern "C" int mcbs_masked_linear_categorical(mcbs_batch* b, const void* latent, size_t latent_row_stride, const void* weight, size_t weight_row_stride,
+                                              const void* bias, uint32_t H, int32_t dtype, int32_t mode, int64_t* actions, float* log_prob,
+                                              float* entropy, uint32_t* n_allowed, const float* uniforms, uint64_t seed, uint64_t step,
+                                              uint32_t* bad_actions, void* stream) {
+    if (!b) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    int rc;
+    if ((rc = digest_usable(b, "mcbs_masked_linear_categorical"))) return rc;
+    LogitsGeom G;
+    if ((rc = discrete_geom(b, G))) return rc;
+    if ((rc = linear_categorical_args("mcbs_masked_linear_categorical", latent, latent_row_stride, weight, weight_row_stride, H, dtype, mode, actions, log_prob)))
+        return rc;
+    const LinIO lin{latent, weight, bias, latent_row_stride, weight_row_stride, H};
+    CatIO io{nullptr, 0, actions, log_prob, entropy, n_allowed, uniforms, bad_actions, seed, step, b->cfg.env_id_base, b->S.E, (uint32_t)mode, G.A};
+    linear_categorical_launch(b, true, G, nullptr, 0, dtype, lin, io, (hipStream_t)stream);
+    return launch_ok("masked action head from the latent");
+}
+
+extern "C" int mcbs_masked_linear_categorical_packed(const mcbs_batch* b, const uint32_t* bits, size_t bits_row_words, uint64_t n_rows, const void* latent,
+                                                     size_t latent_row_stride, const void* weight, size_t weight_row_stride, const void* bias, uint32_t H,
+                                                     int32_t dtype, int32_t mode, int64_t* actions, float* log_prob, float* entropy, uint32_t* n_allowed,
+                                                     const float* uniforms, uint64_t seed, uint64_t step, uint32_t* bad_actions, void* stream) {
+    if (!b) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    int rc;
+    LogitsGeom G;
+    if ((rc = discrete_geom(b, G))) return rc;
+    if (n_rows == 0) return MCBS_OK;
+    if (!bits) return fail(MCBS_EINVAL, "mcbs_masked_linear_categorical_packed: bits must not be NULL");
+    if ((rc = rows_hold(G.A, "bits_row_words", bits_row_words, nullptr, 0))) return rc;
+    if ((rc = linear_categorical_args("mcbs_masked_linear_categorical_packed", latent, latent_row_stride, weight, weight_row_stride, H, dtype, mode, actions,
+                                      log_prob)))
+        return rc;
+    const LinIO lin{latent, weight, bias, latent_row_stride, weight_row_stride, H};
+    CatIO io{nullptr, 0, actions, log_prob, entropy, n_allowed, uniforms, bad_actions, seed, step, 0ull, n_rows, (uint32_t)mode, G.A};
+    linear_categorical_launch(b, false, G, bits, bits_row_words, dtype, lin, io, (hipStream_t)stream);
+    return launch_ok("masked action head from the latent (packed)");
 }
 
 // do rows [p, p + k * stride + A) and [q, q + k * qstride + A) (k < n, bytes) share a byte?  Exact for equal strides (rows interleaved in one

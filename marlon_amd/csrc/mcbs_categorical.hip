@@ -71,11 +71,14 @@ __device__ __forceinline__ V cat_wave_scan(V v, uint32_t lane) {            // i
 
 // One row as its wavefront sees it, and sweeps 1 and 2 over it: shared by masked_categorical_kernel and masked_categorical_grad_kernel
 // (mcbs_categorical_grad.hip), so that K, m, Z and the entropy sum of the backward pass are the forward's, bit for bit.
-template <typename LT, bool LIVE>
+// SRC, the row's logit source: the row pointer, or an object with cat_logit(src, a) and a conversion to bool (false: all-zero logits)
+// such as LinSrc (mcbs_linear_categorical.hip), which computes the logit from the policy's latent row.
+template <typename SRC> inline constexpr bool cat_src_fills_word_cache = false;      // true: cw[0 .. CAT_CACHE) is valid BEFORE sweep 1
+template <typename LT, bool LIVE, typename SRC = const LT*>
 struct CatRow {
     const DigestMask* lv;      // LIVE: the env's digest as a mask (uniform per wavefront: scalar loads);  else
     const uint32_t* brow;      // the row's stored packed words
-    const LT* row;             // the row's logits, or NULL (all-zero logits)
+    SRC row;                   // the row's logits, or NULL (all-zero logits)
     uint32_t W, tail, lane;    // tail: word W-1: bits from A on are ignored, not trusted to be zero
     uint32_t* cw;              // the wavefront's LDS cache: the first CAT_CACHE mask words of the row ...
     float* cs;                 // ... and their sums s_w
@@ -103,8 +106,13 @@ struct CatRow {
         float m = 0.f;
         uint32_t arg = ~0u, last = 0u, cnt = 0u;
         for (uint32_t wb = 0; wb < W; wb += 64u) {
-            const uint32_t w = wb + lane, word = fetch(w);
-            if (wb < CAT_CACHE) cw[w] = word;
+            const uint32_t w = wb + lane;
+            uint32_t word;
+            if constexpr (cat_src_fills_word_cache<SRC>) word = word_of(w);
+            else {
+                word = fetch(w);
+                if (wb < CAT_CACHE) cw[w] = word;
+            }
             if (!__ballot(word != 0u)) continue;
             if (!word) continue;
             cnt += (uint32_t)__popc(word);
@@ -147,6 +155,134 @@ struct CatRow {
     }
 };
 
+// Everything of one row after its CatRow is set up: the three sweeps, the row's random number and the 16-20 bytes of results.  Shared by
+// masked_categorical_kernel and masked_linear_categorical_kernel (mcbs_linear_categorical.hip): a logit source that returns the values
+// a logits buffer would hold gives bit for bit what that buffer gives.
+template <typename ROW>
+__device__ __forceinline__ void cat_row_finish(const ROW& R, const CatIO& io, uint64_t i) {
+    const uint32_t A = io.A, W = R.W, lane = R.lane;
+    const auto& row = R.row;
+    const float* cs = R.cs;
+    auto word_of = [&](uint32_t w) { return R.word_of(w); };          // sweep 3 (w = block + lane: the branch is wave-uniform)
+    auto word_sums = [&](uint32_t w, uint32_t word, float m, float& s, float& t) { R.word_sums(w, word, m, s, t); };
+
+    float m;
+    uint32_t arg, last, K;
+    R.sweep1(m, arg, last, K);
+
+    // the row's uniform number (SAMPLE)
+    uint32_t u24 = 0u;
+    if (io.mode == CAT_SAMPLE) {
+        if (io.uniforms) {
+            const float uf = io.uniforms[i] * 16777216.0f;
+            u24 = uf >= 16777215.0f ? 16777215u : (uf >= 0.f ? (uint32_t)uf : 0u);
+        } else {
+            const uint64_t key = io.key_base + i;
+            uint32_t r[4];
+            philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), (uint32_t)io.step, (uint32_t)(io.step >> 32),
+                          (uint32_t)io.seed ^ CAT_DOMAIN, (uint32_t)(io.seed >> 32), r);
+            u24 = r[0] >> 8;
+        }
+    }
+    int64_t act = 0;
+    bool bad = false;
+    if (io.mode == CAT_EVALUATE) {
+        act = io.actions[i];
+        bad = act < 0 || act >= (int64_t)A;
+    }
+    float lp, ent;
+    if (K == 0u) {
+        // blank observation / all-zero row: MaskableCategorical degenerates to uniform over all A actions, entropy 0
+        lp = -cat_log((float)A);
+        ent = 0.f;
+        if (io.mode == CAT_SAMPLE) act = (int64_t)(((uint64_t)u24 * A) >> 24);
+        else if (io.mode == CAT_ARGMAX) act = 0;
+    } else {
+        // ---- sweep 2: Z and the entropy sum
+        float Z = 0.f, Tt = 0.f;
+        if (!row) {
+            Z = (float)K;
+        } else {
+            R.sweep2(m, Z, Tt);
+        }
+        const float logZ = cat_log(Z);
+        ent = logZ - Tt / Z;
+        float x_act = 0.f;                          // the chosen action's logit (an action that is not allowed: -1e8, the reference's `where`)
+        if (io.mode == CAT_ARGMAX) {
+            act = (int64_t)arg;
+            x_act = m;
+        } else if (io.mode == CAT_EVALUATE) {
+            if (!bad) {
+                const uint32_t a = (uint32_t)act;
+                const bool on = (R.fetch(a >> 5) >> (a & 31u)) & 1u;
+                x_act = on ? (row ? cat_logit(row, a) : 0.f) : -1e8f;
+            }
+        } else if (!row) {
+            // uniform law: the ((u24 * K) >> 24)-th allowed action, in integers
+            const uint32_t k = (uint32_t)(((uint64_t)u24 * K) >> 24);
+            uint32_t base = 0u, sel = last;
+            for (uint32_t wb = 0; wb < W; wb += 64u) {
+                const uint32_t w = wb + lane, word = word_of(w);
+                if (!__ballot(word != 0u)) continue;
+                const uint32_t incl = cat_wave_scan((uint32_t)__popc(word), lane);
+                const uint64_t cross = __ballot(word != 0u && base + incl > k);
+                if (cross) {
+                    const int src = __builtin_ctzll(cross);
+                    uint32_t rest = word;
+                    for (uint32_t r = k - (base + incl - (uint32_t)__popc(word)); lane == (uint32_t)src && r; --r) rest &= rest - 1u;
+                    sel = (uint32_t)__shfl((int)(w * 32u + (uint32_t)__builtin_ctz(rest | 0x80000000u)), src);
+                    break;
+                }
+                base += (uint32_t)__shfl((int)incl, 63);
+            }
+            act = (int64_t)sel;
+        } else {
+            // ---- sweep 3: inverse CDF in ascending action order: the first allowed action whose cumulative sum exceeds u * Z
+            const float thr = (float)u24 * (1.0f / 16777216.0f) * Z;
+            float base = 0.f;
+            uint32_t sel = last;                    // rounding may leave no crossing: the last allowed action
+            for (uint32_t wb = 0; wb < W; wb += 64u) {
+                const uint32_t w = wb + lane, word = word_of(w);
+                if (!__ballot(word != 0u)) continue;
+                float s, t;
+                if (wb < CAT_CACHE) s = cs[w]; else word_sums(w, word, m, s, t);
+                const float incl = cat_wave_scan(s, lane);
+                float excl = __shfl_up(incl, 1u);
+                if (lane == 0u) excl = 0.f;
+                const uint64_t cross = __ballot(word != 0u && base + incl > thr);
+                if (cross) {
+                    const int src = __builtin_ctzll(cross);
+                    uint32_t pick = 0u;
+                    if (lane == (uint32_t)src) {
+                        // the word's last bit stands for the word's whole sum (base + incl, which did cross)
+                        pick = w * 32u + 31u - (uint32_t)__builtin_clz(word);
+                        float c = base + excl;
+                        for (uint32_t rest = word; rest & (rest - 1u); rest &= rest - 1u) {
+                            const uint32_t a = w * 32u + (uint32_t)__builtin_ctz(rest);
+                            c += expf(cat_logit(row, a) - m);
+                            if (c > thr) { pick = a; break; }
+                        }
+                    }
+                    sel = (uint32_t)__shfl((int)pick, src);
+                    break;
+                }
+                base += __shfl(incl, 63);
+            }
+            act = (int64_t)sel;
+            x_act = cat_logit(row, sel);
+        }
+        lp = (x_act - m) - logZ;
+    }
+    if (bad) lp = __uint_as_float(0x7FC00000u);
+    if (lane == 0u) {
+        if (io.mode != CAT_EVALUATE) io.actions[i] = act;
+        io.log_prob[i] = lp;
+        if (io.entropy) io.entropy[i] = ent;
+        if (io.n_allowed) io.n_allowed[i] = K;
+        if (bad && io.bad_actions) atomicAdd(io.bad_actions, 1u);
+    }
+}
+
 template <typename LT, bool LIVE>
 __global__ __launch_bounds__(256) void masked_categorical_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, const ObsDigest* __restrict__ digest,
                                                                  LogitsGeom G, const uint32_t* __restrict__ bits, size_t bits_row_words, CatIO io) {
@@ -165,125 +301,7 @@ __global__ __launch_bounds__(256) void masked_categorical_kernel(DevState S, Top
         const ObsDigest d = LIVE ? digest[i] : ObsDigest{};
         const DigestMask lv = LIVE ? DigestMask::make(S, T, Cp, d, G, (uint32_t)i, 32u) : DigestMask{S, G, d, nullptr, nullptr, 0u, 0u, 0u, 0ull};
         const CatRow<LT, LIVE> R{&lv, LIVE ? nullptr : bits + i * bits_row_words, row, W, tail, lane, cw, cs};
-        auto fetch = [&](uint32_t w) { return R.fetch(w); };
-        auto word_of = [&](uint32_t w) { return R.word_of(w); };          // sweep 3 (w = block + lane: the branch is wave-uniform)
-        auto word_sums = [&](uint32_t w, uint32_t word, float m, float& s, float& t) { R.word_sums(w, word, m, s, t); };
-
-        float m;
-        uint32_t arg, last, K;
-        R.sweep1(m, arg, last, K);
-
-        // the row's uniform number (SAMPLE)
-        uint32_t u24 = 0u;
-        if (io.mode == CAT_SAMPLE) {
-            if (io.uniforms) {
-                const float uf = io.uniforms[i] * 16777216.0f;
-                u24 = uf >= 16777215.0f ? 16777215u : (uf >= 0.f ? (uint32_t)uf : 0u);
-            } else {
-                const uint64_t key = io.key_base + i;
-                uint32_t r[4];
-                philox4x32_10((uint32_t)key, (uint32_t)(key >> 32), (uint32_t)io.step, (uint32_t)(io.step >> 32),
-                              (uint32_t)io.seed ^ CAT_DOMAIN, (uint32_t)(io.seed >> 32), r);
-                u24 = r[0] >> 8;
-            }
-        }
-        int64_t act = 0;
-        bool bad = false;
-        if (io.mode == CAT_EVALUATE) {
-            act = io.actions[i];
-            bad = act < 0 || act >= (int64_t)A;
-        }
-        float lp, ent;
-        if (K == 0u) {
-            // blank observation / all-zero row: MaskableCategorical degenerates to uniform over all A actions, entropy 0
-            lp = -cat_log((float)A);
-            ent = 0.f;
-            if (io.mode == CAT_SAMPLE) act = (int64_t)(((uint64_t)u24 * A) >> 24);
-            else if (io.mode == CAT_ARGMAX) act = 0;
-        } else {
-            // ---- sweep 2: Z and the entropy sum
-            float Z = 0.f, Tt = 0.f;
-            if (!row) {
-                Z = (float)K;
-            } else {
-                R.sweep2(m, Z, Tt);
-            }
-            const float logZ = cat_log(Z);
-            ent = logZ - Tt / Z;
-            float x_act = 0.f;                          // the chosen action's logit (an action that is not allowed: -1e8, the reference's `where`)
-            if (io.mode == CAT_ARGMAX) {
-                act = (int64_t)arg;
-                x_act = m;
-            } else if (io.mode == CAT_EVALUATE) {
-                if (!bad) {
-                    const uint32_t a = (uint32_t)act;
-                    const bool on = (fetch(a >> 5) >> (a & 31u)) & 1u;
-                    x_act = on ? (row ? cat_logit(row, a) : 0.f) : -1e8f;
-                }
-            } else if (!row) {
-                // uniform law: the ((u24 * K) >> 24)-th allowed action, in integers
-                const uint32_t k = (uint32_t)(((uint64_t)u24 * K) >> 24);
-                uint32_t base = 0u, sel = last;
-                for (uint32_t wb = 0; wb < W; wb += 64u) {
-                    const uint32_t w = wb + lane, word = word_of(w);
-                    if (!__ballot(word != 0u)) continue;
-                    const uint32_t incl = cat_wave_scan((uint32_t)__popc(word), lane);
-                    const uint64_t cross = __ballot(word != 0u && base + incl > k);
-                    if (cross) {
-                        const int src = __builtin_ctzll(cross);
-                        uint32_t rest = word;
-                        for (uint32_t r = k - (base + incl - (uint32_t)__popc(word)); lane == (uint32_t)src && r; --r) rest &= rest - 1u;
-                        sel = (uint32_t)__shfl((int)(w * 32u + (uint32_t)__builtin_ctz(rest | 0x80000000u)), src);
-                        break;
-                    }
-                    base += (uint32_t)__shfl((int)incl, 63);
-                }
-                act = (int64_t)sel;
-            } else {
-                // ---- sweep 3: inverse CDF in ascending action order: the first allowed action whose cumulative sum exceeds u * Z
-                const float thr = (float)u24 * (1.0f / 16777216.0f) * Z;
-                float base = 0.f;
-                uint32_t sel = last;                    // rounding may leave no crossing: the last allowed action
-                for (uint32_t wb = 0; wb < W; wb += 64u) {
-                    const uint32_t w = wb + lane, word = word_of(w);
-                    if (!__ballot(word != 0u)) continue;
-                    float s, t;
-                    if (wb < CAT_CACHE) s = cs[w]; else word_sums(w, word, m, s, t);
-                    const float incl = cat_wave_scan(s, lane);
-                    float excl = __shfl_up(incl, 1u);
-                    if (lane == 0u) excl = 0.f;
-                    const uint64_t cross = __ballot(word != 0u && base + incl > thr);
-                    if (cross) {
-                        const int src = __builtin_ctzll(cross);
-                        uint32_t pick = 0u;
-                        if (lane == (uint32_t)src) {
-                            // the word's last bit stands for the word's whole sum (base + incl, which did cross)
-                            pick = w * 32u + 31u - (uint32_t)__builtin_clz(word);
-                            float c = base + excl;
-                            for (uint32_t rest = word; rest & (rest - 1u); rest &= rest - 1u) {
-                                const uint32_t a = w * 32u + (uint32_t)__builtin_ctz(rest);
-                                c += expf(cat_logit(row, a) - m);
-                                if (c > thr) { pick = a; break; }
-                            }
-                        }
-                        sel = (uint32_t)__shfl((int)pick, src);
-                        break;
-                    }
-                    base += __shfl(incl, 63);
-                }
-                act = (int64_t)sel;
-                x_act = cat_logit(row, sel);
-            }
-            lp = (x_act - m) - logZ;
-        }
-        if (bad) lp = __uint_as_float(0x7FC00000u);
-        if (lane == 0u) {
-            if (io.mode != CAT_EVALUATE) io.actions[i] = act;
-            io.log_prob[i] = lp;
-            if (io.entropy) io.entropy[i] = ent;
-            if (io.n_allowed) io.n_allowed[i] = K;
-            if (bad && io.bad_actions) atomicAdd(io.bad_actions, 1u);
-        }
+        cat_row_finish(R, io, i);
     }
 }
 

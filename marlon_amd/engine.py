@@ -14,7 +14,7 @@ from typing import Dict, Iterable, Optional
 
 import numpy as np
 
-from ._abi import (MULTICATEGORICAL_ARGTYPES, BatchCfg, BatchVariantInfo, DefenderObs, EnvSpec, GaeIO, InfoBuffers, ObsBuffers,
+from ._abi import (LINEAR_CATEGORICAL_ARGTYPES, MCBS_LINEAR_MAX_H, MULTICATEGORICAL_ARGTYPES, BatchCfg, BatchVariantInfo, DefenderObs, EnvSpec, GaeIO, InfoBuffers, ObsBuffers,
                    split_state, state_record_bytes)
 from .flatten import FlatTopology
 
@@ -30,6 +30,7 @@ EXPORTS = [
     "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant", "mcbs_step_is_lean",
     "mcbs_feature_layout_create", "mcbs_feature_layout_destroy", "mcbs_feature_layout_width", "mcbs_encode_features",
     "mcbs_masked_categorical", "mcbs_masked_categorical_packed", "mcbs_masked_categorical_grad",
+    "mcbs_masked_linear_categorical", "mcbs_masked_linear_categorical_packed",
     "mcbs_multicategorical", "mcbs_multicategorical_grad",
     "mcbs_gae",
 ]
@@ -129,7 +130,7 @@ def load_library(path: Optional[str] = None):
     for name in EXPORTS:
         if not hasattr(lib, name):
             raise NativeLibraryMissing(f"{p} does not export {name}")
-    for name, argtypes in MULTICATEGORICAL_ARGTYPES.items():
+    for name, argtypes in {**MULTICATEGORICAL_ARGTYPES, **LINEAR_CATEGORICAL_ARGTYPES}.items():
         getattr(lib, name).argtypes = argtypes
     if path is None:
         _lib = lib
@@ -634,6 +635,38 @@ class BatchEngine:
                                                               bits.shape[0], self._stream()), "mcbs_unpack_action_mask")
         return out
 
+    def _categorical_outputs(self, n, mode, actions, uniforms, out, bad_actions):
+        """The checks and the out= handling the masked heads share: -> (actions, log_prob, entropy, n_allowed) to hand to the library."""
+        t = self.torch
+        if mode not in CATEGORICAL_MODES:
+            raise ValueError(f"mode must be one of {sorted(CATEGORICAL_MODES)}, got {mode!r}")
+
+        def vec(x, dtype, what):
+            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != (n,) or not x.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous device {dtype} tensor [{n}]")
+            return x
+
+        if out is not None and len(out) != 4:
+            raise ValueError("out must be (actions, log_prob, entropy, n_allowed)")
+        o_act, o_lp, o_ent, o_k = out if out is not None else (None, None, None, None)
+        if mode == "evaluate":
+            if actions is None:
+                raise ValueError('mode="evaluate" needs actions (int64 [n])')
+            o_act = vec(actions, t.int64, "actions")
+        else:
+            if actions is not None:
+                raise ValueError('actions are an input of mode="evaluate" only (preallocate outputs with out=)')
+            o_act = vec(o_act, t.int64, "out.actions") if o_act is not None else t.empty(n, dtype=t.int64, device=self.device)
+        o_lp = vec(o_lp, t.float32, "out.log_prob") if o_lp is not None else t.empty(n, dtype=t.float32, device=self.device)
+        o_ent = vec(o_ent, t.float32, "out.entropy") if o_ent is not None else t.empty(n, dtype=t.float32, device=self.device)
+        o_k = vec(o_k, t.int32, "out.n_allowed") if o_k is not None else t.empty(n, dtype=t.int32, device=self.device)
+        if uniforms is not None:
+            vec(uniforms, t.float32, "uniforms")
+        if bad_actions is not None and (not isinstance(bad_actions, t.Tensor) or bad_actions.dtype != t.int32 or bad_actions.numel() != 1
+                                        or bad_actions.device != self.device):
+            raise ValueError("bad_actions must be a device int32 tensor of one element")
+        return o_act, o_lp, o_ent, o_k
+
     # -- masked categorical head (include/mcbs.h): sample / log-prob / entropy of `Categorical(logits=where(mask, logits, -1e8))` --
     def masked_categorical(self, logits=None, *, bits=None, mode: str = "sample", actions=None, seed: int = 0, step: int = 0, uniforms=None,
                            out=None, bad_actions=None) -> MaskedCategorical:
@@ -661,31 +694,7 @@ class BatchEngine:
             # the C side sees only the row stride: a view narrower than A would have its rows read past their end
             if logits.dim() != 2 or logits.shape[0] != n or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < A:
                 raise ValueError(f"logits must be a device tensor [{n}, >= {A}] with contiguous rows")
-
-        def vec(x, dtype, what):
-            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != (n,) or not x.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous device {dtype} tensor [{n}]")
-            return x
-
-        if out is not None and len(out) != 4:
-            raise ValueError("out must be (actions, log_prob, entropy, n_allowed)")
-        o_act, o_lp, o_ent, o_k = out if out is not None else (None, None, None, None)
-        if mode == "evaluate":
-            if actions is None:
-                raise ValueError('mode="evaluate" needs actions (int64 [n])')
-            o_act = vec(actions, t.int64, "actions")
-        else:
-            if actions is not None:
-                raise ValueError('actions are an input of mode="evaluate" only (preallocate outputs with out=)')
-            o_act = vec(o_act, t.int64, "out.actions") if o_act is not None else t.empty(n, dtype=t.int64, device=self.device)
-        o_lp = vec(o_lp, t.float32, "out.log_prob") if o_lp is not None else t.empty(n, dtype=t.float32, device=self.device)
-        o_ent = vec(o_ent, t.float32, "out.entropy") if o_ent is not None else t.empty(n, dtype=t.float32, device=self.device)
-        o_k = vec(o_k, t.int32, "out.n_allowed") if o_k is not None else t.empty(n, dtype=t.int32, device=self.device)
-        if uniforms is not None:
-            vec(uniforms, t.float32, "uniforms")
-        if bad_actions is not None and (not isinstance(bad_actions, t.Tensor) or bad_actions.dtype != t.int32 or bad_actions.numel() != 1
-                                        or bad_actions.device != self.device):
-            raise ValueError("bad_actions must be a device int32 tensor of one element")
+        o_act, o_lp, o_ent, o_k = self._categorical_outputs(n, mode, actions, uniforms, out, bad_actions)
         common = (logits.data_ptr() if logits is not None else None, 0 if logits is None or logits.dtype == t.float32 else 1,
                   (logits.stride(0) if n > 1 else max(logits.stride(0), logits.shape[1])) if logits is not None else 0,
                   CATEGORICAL_MODES[mode], o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), o_k.data_ptr(),
@@ -696,6 +705,49 @@ class BatchEngine:
         elif n:
             _check(self.lib, self.lib.mcbs_masked_categorical_packed(self._h, bits.data_ptr(), bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1]),
                                                                      n, *common), "mcbs_masked_categorical_packed")
+        return MaskedCategorical(o_act, o_lp, o_ent, o_k)
+
+    def masked_linear_categorical(self, latent, weight, bias=None, *, bits=None, mode: str = "sample", actions=None, seed: int = 0, step: int = 0,
+                                  uniforms=None, out=None, bad_actions=None) -> MaskedCategorical:
+        """masked_categorical without a logits tensor (mcbs_masked_linear_categorical): the logit of an ALLOWED action is computed in the
+        kernel as bias[a] + latent[i] . weight[a], for a policy whose action_net is Linear(H, A).  latent: device float32 / bfloat16
+        [n, H]; weight: [A, H] (torch.nn.Linear's layout), bias: [A] or None, all three of one dtype, last dimension contiguous,
+        1 <= H <= 512.  bits, mode, actions, seed, step, uniforms, out, bad_actions and the result as for masked_categorical, whose outputs
+        on logits holding the same values these are bit for bit; torch.nn.functional.linear sums in another order, so against it the
+        logits agree to rounding.  Not differentiable."""
+        t = self.torch
+        if bits is not None:
+            self._packed_rows(bits, "bits")
+            n = bits.shape[0]
+        else:
+            n = self.E
+        A = self.discrete_action_count()
+        for x, what in ((latent, "latent"), (weight, "weight")) + (((bias, "bias"),) if bias is not None else ()):
+            if not isinstance(x, t.Tensor) or x.dtype not in (t.float32, t.bfloat16):
+                raise ValueError(f"{what} must be a float32 or bfloat16 tensor")
+            if x.device != self.device:
+                raise ValueError(f"{what} must be on {self.device}, not {x.device}")
+            if x.dtype != latent.dtype:
+                raise ValueError(f"latent, weight and bias must have one dtype: latent is {latent.dtype}, {what} is {x.dtype}")
+        if latent.dim() != 2 or latent.shape[0] != n or not 1 <= latent.shape[1] <= MCBS_LINEAR_MAX_H or latent.stride(1) != 1:
+            raise ValueError(f"latent must be [{n}, H] with 1 <= H <= {MCBS_LINEAR_MAX_H} and contiguous rows")
+        H = latent.shape[1]
+        if weight.dim() != 2 or tuple(weight.shape) != (A, H) or weight.stride(1) != 1:
+            raise ValueError(f"weight must be [{A}, {H}] (one row per Discrete action) with contiguous rows, got {tuple(weight.shape)}")
+        if bias is not None and (tuple(bias.shape) != (A,) or not bias.is_contiguous()):
+            raise ValueError(f"bias must be a contiguous [{A}] tensor")
+        o_act, o_lp, o_ent, o_k = self._categorical_outputs(n, mode, actions, uniforms, out, bad_actions)
+        common = (latent.data_ptr(), latent.stride(0) if n > 1 else max(latent.stride(0), H), weight.data_ptr(),
+                  weight.stride(0) if A > 1 else max(weight.stride(0), H), bias.data_ptr() if bias is not None else None, H,
+                  0 if latent.dtype == t.float32 else 1, CATEGORICAL_MODES[mode], o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), o_k.data_ptr(),
+                  uniforms.data_ptr() if uniforms is not None else None, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                  bad_actions.data_ptr() if bad_actions is not None else None, self._stream())
+        if bits is None:
+            _check(self.lib, self.lib.mcbs_masked_linear_categorical(self._h, *common), "mcbs_masked_linear_categorical")
+        elif n:
+            _check(self.lib, self.lib.mcbs_masked_linear_categorical_packed(
+                self._h, bits.data_ptr(), bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1]), n, *common),
+                "mcbs_masked_linear_categorical_packed")
         return MaskedCategorical(o_act, o_lp, o_ent, o_k)
 
     def masked_categorical_grad(self, logits, bits, actions, grad_log_prob=None, grad_entropy=None, out=None):

@@ -335,6 +335,13 @@ class MarlonVecEnv:
     def evaluate_masked(self, bits, logits, actions, differentiable: bool = False):
         return self.venv.evaluate_masked(bits, logits, actions, differentiable=differentiable)
 
+    # the same head from the policy's latent and its action_net (no logits tensor): AttackerVecEnv.sample_masked_from_latent / evaluate_masked_from_latent
+    def sample_masked_from_latent(self, latent, weight, bias, seed: int, step: int, deterministic: bool = False, uniforms=None):
+        return self.venv.sample_masked_from_latent(latent, weight, bias, seed, step, deterministic=deterministic, uniforms=uniforms)
+
+    def evaluate_masked_from_latent(self, bits, latent, weight, bias, actions):
+        return self.venv.evaluate_masked_from_latent(bits, latent, weight, bias, actions)
+
     def get_attr(self, attr_name: str, indices=None) -> List[Any]:
         val = getattr(self.venv, attr_name)
         idx = self._indices(indices)

@@ -257,6 +257,23 @@ class AttackerVecEnv(_MultiDiscreteHead):
             return self.engine.masked_evaluate(logits, bits, actions, bad_actions=bad_actions)
         return self.engine.masked_categorical(logits, bits=bits, mode="evaluate", actions=actions, bad_actions=bad_actions, out=out)
 
+    # -- the same head from the policy's latent (mcbs_masked_linear_categorical): action_net's logits are never materialised --
+    def sample_masked_from_latent(self, latent, weight, bias, seed: int, step: int, deterministic: bool = False, uniforms=None, out=None):
+        """sample_masked for a policy whose action_net is Linear(H, A), from what goes INTO that layer: latent [n_envs, H] (latent_pi),
+        weight [A, H] and bias [A] or None (action_net.weight / .bias), float32 or bfloat16 alike.  Only the logits of allowed actions are
+        computed, in the kernel; the result is bit for bit sample_masked's on logits holding those values (against F.linear, which sums
+        in another order, the stored log_prob agrees to rounding)."""
+        return self.engine.masked_linear_categorical(latent, weight, bias, bits=self._live_bits(), mode="argmax" if deterministic else "sample",
+                                                     seed=seed, step=step, uniforms=uniforms, out=out)
+
+    def evaluate_masked_from_latent(self, bits, latent, weight, bias, actions, bad_actions=None, out=None):
+        """evaluate_masked from the latent: log_prob of `actions` [n] and the entropy under stored packed masks bits [n, >= W], latent
+        [n, H], weight [A, H], bias [A] or None.  The log_prob of an action sample_masked_from_latent drew under the same mask, latent
+        and layer comes back bit for bit.  Not differentiable: the update's gradient goes through evaluate_masked(differentiable=True)
+        on materialised minibatch logits."""
+        return self.engine.masked_linear_categorical(latent, weight, bias, bits=bits, mode="evaluate", actions=actions, bad_actions=bad_actions,
+                                                     out=out)
+
     # -- the policy's input features (marlon_amd/features.py, mcbs_encode_features) --
     def _feature_handle(self, include_masks: bool, reference_counts: bool, keys=None):
         key = (bool(include_masks), bool(reference_counts), None if keys is None else tuple(keys))
