@@ -20,6 +20,9 @@ Parameters chosen from a pilot run are chosen from the ORACLE alone.  The trunca
 episode wins) and the reward goal R (a cumulative reward some env holds exactly on the step before it wins) come from the pilot's
 first episodes, which do not depend on the parameter, so what the pilot shows happens again in the case.  k of `percent` (an owned
 count enough envs exceed) needs no such exactness and is taken over the whole pilot.
+
+The weighted cases (WEIGHT_SPECS, further down) use the same machinery on topologies with unequal SLA weights, for
+tests/test_gpu_availability_weights.py: there the availability itself, the project's only floating point, is what is under test.
 """
 from __future__ import annotations
 
@@ -44,13 +47,24 @@ MEANT = {"mixed": ("goal", "evicted", "truncated"), "updown": ("goal", "evicted"
 RANDOM_NET_SEED = {24: 5, 100: 7, 129: 7}      # (24, seed 7) leaves the attacker on one node
 
 
+# SLA weights by node (and by service) index, cycled.  dyadic: unequal, and every sum of them exact in fp64 in any order.
+# odd: the non-dyadic weights of tests/test_gpu_defender_layouts.py::_weighted_topology (sums depend on the order).
+WEIGHT_KINDS = ("dyadic", "odd")
+NODE_WEIGHTS = {"dyadic": (1.0, 2.0, 0.5, 4.0, 0.25, 1.5, 3.0, 0.75, 8.0), "odd": (0.1, 0.3, 0.7, 1.9, 2.3, 0.6, 1.1, 3.3, 0.35)}
+SERVICE_WEIGHTS = (0.3, 0.6, 1.7, 0.9, 0.1, 2.2, 1.3)
+
+
 @functools.lru_cache(maxsize=None)
-def topology(name: str):
-    """The flattened topology with every node re-imagable (the defender can evict the attacker)."""
+def topology(name: str, weights: str = "uniform"):
+    """The flattened topology with every node re-imagable (the defender can evict the attacker).  weights: "uniform" (the samples' own SLA
+    weights), "dyadic" or "odd" (NODE_WEIGHTS cycled over the nodes; odd: SERVICE_WEIGHTS cycled over the services too; dyadic: a
+    stopped service weighs 1 + the node's running services, which makes the node's share (1 + running) / (1 + total) exactly 1/2)."""
     from marlon_amd import flatten as F, model
-    from marlon_amd.samples import active_directory, random_net, toy_ctf
+    from marlon_amd.samples import active_directory, kitchen_sink, random_net, toy_ctf
     if name == "toyctf":
         env = toy_ctf.new_environment()
+    elif name == "sink":
+        env = kitchen_sink.new_environment()
     elif name == "ad6":
         env = active_directory.new_random_environment(6)
     else:
@@ -58,7 +72,21 @@ def topology(name: str):
         env = random_net.build(model, n, RANDOM_NET_SEED[n])
     for _, info in env.nodes():
         info.reimagable = True
-    return F.flatten(env)
+    return F.flatten(reweigh(env, weights))
+
+
+def reweigh(env, weights: str):
+    """Set the SLA weights of a model environment in place (see topology); returns it."""
+    k = 0
+    for i, (_, info) in enumerate(env.nodes()):
+        if weights == "uniform":
+            break
+        info.sla_weight = NODE_WEIGHTS[weights][i % len(NODE_WEIGHTS[weights])]
+        running = sum(1.0 for s in info.services if s.running)
+        for s in info.services:
+            s.sla_weight = SERVICE_WEIGHTS[k % len(SERVICE_WEIGHTS)] if weights == "odd" else (1.0 if s.running else 1.0 + running)
+            k += 1
+    return env
 
 
 def make_spec(topo, **over):
@@ -169,6 +197,7 @@ class Case:
     had_two: np.ndarray                      # [T, E] the counter reached 2 or more at an EARLIER step of this episode
     up_down_up: np.ndarray                   # [T, E] by this step the episode saw: counter >= 2, then a re-image, then (a later step) a node owned
     params: dict = field(default_factory=dict)
+    imaging: np.ndarray = None               # [T, E, N] bool, weighted cases only: the node is being re-imaged at the step's defender tick
 
     @property
     def ended(self) -> np.ndarray:
@@ -229,8 +258,11 @@ def _same_state(a, b) -> bool:
     return True
 
 
-def run(name: str, topo, spec, n_steps: int, reset_at: int = -1, policy_seed: int = 11, stall: float = 0.0, params=None) -> Case:
-    """Write the script with the oracle and record it."""
+def run(name: str, topo, spec, n_steps: int, reset_at: int = -1, policy_seed: int = 11, stall: float = 0.0, params=None,
+        record_imaging: bool = False) -> Case:
+    """Write the script with the oracle and record it.  record_imaging: keep, per step, the nodes not running before the step and still
+    not running after it.  The availability a step reports is taken at its tick, after the nodes whose re-imaging is over came back and
+    before the step's scan re-images others: those nodes are the ones missing from the sum."""
     import dataclasses
     from oracle.oracle import Oracle
     orc = Oracle(topo, spec)
@@ -243,6 +275,7 @@ def run(name: str, topo, spec, n_steps: int, reset_at: int = -1, policy_seed: in
     over = np.zeros(n_envs, bool)
     reset_mask = np.zeros(n_envs, np.uint8)
     two, down, again = (np.zeros(n_envs, bool) for _ in range(3))
+    imaging = []
     same = True
     before = shadow.get_state()
     fresh = [x.copy() for x in before]
@@ -266,6 +299,8 @@ def run(name: str, topo, spec, n_steps: int, reset_at: int = -1, policy_seed: in
         for k in OUT_KEYS:
             out[k].append(o[k])
         lv = ~over
+        if record_imaging:
+            imaging.append((before[1]["running"][:, :topo.n_nodes] == 0) & (after[1]["running"][:, :topo.n_nodes] == 0))
         pb, pa = before[1]["privilege"] >= 1, after[1]["privilege"] >= 1
         between = ~pb & ~pa & (before[1]["running"] != 0) & (after[1]["running"] == 0)     # owned and re-imaged within the step
         up = np.where(lv, (~pb & pa).sum(axis=1) + between.sum(axis=1), 0)
@@ -294,7 +329,8 @@ def run(name: str, topo, spec, n_steps: int, reset_at: int = -1, policy_seed: in
             before = after
     same &= _same_state(orc.get_state(), before)
     return Case(name, topo, spec, acts, {k: np.stack(v) for k, v in out.items()}, reset_at=reset_at, reset_mask=reset_mask,
-                shadow_equal=bool(same), params=dict(params or {}), **{k: np.stack(v) for k, v in rec.items()})
+                shadow_equal=bool(same), params=dict(params or {}), imaging=np.stack(imaging) if record_imaging else None,
+                **{k: np.stack(v) for k, v in rec.items()})
 
 
 def first_episode(c: Case) -> np.ndarray:
@@ -390,9 +426,131 @@ STEPS = {"mixed": 160, "updown": 160, "frozen": 160, "reward": 80, "reward_def":
 assert max(STEPS.values()) <= T_MAX
 
 
+# ---- availability sums under non-uniform SLA weights (tests/test_gpu_availability_weights.py) ----
+# "<topology>-<spec>_<weight kind>": every node re-imagable, ScanAndReimage as in SCAN_AVAIL, eviction ends nothing (a re-imaged entry
+# node would end the episode before a second node is missing from the sum), a goal out of reach, truncation (weighted_settings).
+#   avail    maintain_sla = 0: no ending depends on the availability; the episodes truncate and restart inside the script
+#   sla_eq   maintain_sla = an availability v that first episodes of `avail` attain below full.  The goal is `availability < maintain_sla`:
+#            equality does not end the episode
+#   sla_up   maintain_sla = the next double above v: the same steps do end
+# v comes from the oracle alone: `avail` is the pilot, its first episodes are those of sla_eq and sla_up up to the step that ends them
+# (the threshold is read by nothing before that), so an env that meets v on its first played step at or below v, in the pilot, ends
+# there under sla_up and plays on under sla_eq.  Only steps count whose sum a kernel on another branch gets wrong (`discriminating`).
+WEIGHT_SPECS = tuple(f"{s}_{k}" for k in WEIGHT_KINDS for s in ("avail", "sla_eq", "sla_up"))
+WEIGHT_TOPOLOGIES = ("sink", "random24", "random100", "random129", "ad6")   # the packed cell: see weighted_settings
+WEIGHT_STEPS = 120
+WEIGHT_EPISODE = 40
+WEIGHT_GOAL = dict(own_atleast_percent=2.0, low_availability=2.0)
+
+
+def weighted_settings(topo_name: str) -> dict:
+    """ToyCtf's attacker rarely holds a second node (a long chain of exploits away), so hardly more than the entry node is ever missing
+    from the sum (3 different sets in 120 steps): the packed cell plays the kitchen-sink topology instead (6 nodes, a stopped service,
+    packed like ToyCtf) under a defender that detects less often, so that the attacker gets to hold several nodes before it loses them.
+    Beyond 64 nodes 3 draws every 2nd step seldom hit two owned nodes in different 64-bit words while both are down (39 steps among
+    100 nodes): there the defender scans on every step and the episodes last 60 steps."""
+    if topo_name == "sink":
+        defender, bound = ("scan_and_reimage", 0.3, 2, 2), WEIGHT_EPISODE
+    elif topology(topo_name).n_nodes > 64:
+        defender, bound = ("scan_and_reimage", 0.9, 3, 1), 60
+    else:
+        defender, bound = SCAN_AVAIL, WEIGHT_EPISODE
+    return dict(attacker_goal=dict(WEIGHT_GOAL), defender=defender, defender_goal_eviction=False, max_episode_steps=bound)
+
+
+def availability_sums(c: Case) -> dict:
+    """sums_of(c.topo, c.imaging): [T, E] restatements of a weighted case's availability."""
+    return sums_of(c.topo, c.imaging)
+
+
+def sums_of(topo, im: np.ndarray) -> dict:
+    """fp64 restatements of the availability from the avail_term column of the flattened topology and im [..., N] bool, the nodes being
+    re-imaged:
+    order    the sum over the running nodes in node order, divided by total_sla_weight (on_attacker_step_taken, actions.py:728-745)
+    sub_seq  full_sum minus the terms of the nodes being re-imaged, one by one in node order, divided likewise
+    sub_sum  full_sum minus (the sum of those terms in node order), divided likewise
+    uniform  full_sum minus (their number times the first node's term), divided likewise
+    and n, the number of nodes being re-imaged."""
+    h = topo.header()
+    term = topo.node_table()["avail_term"].astype(np.float64)
+    full, total = float(h["full_sum"]), float(h["total_sla_weight"])
+    order = np.zeros(im.shape[:-1], np.float64)
+    seq = np.full(im.shape[:-1], full, np.float64)
+    part = np.zeros(im.shape[:-1], np.float64)
+    for n in range(topo.n_nodes):
+        order = order + np.where(im[..., n], 0.0, term[n])
+        seq = seq - np.where(im[..., n], term[n], 0.0)
+        part = part + np.where(im[..., n], term[n], 0.0)
+    n_im = im.sum(axis=-1)
+    return dict(order=order / total, sub_seq=seq / total, sub_sum=(full - part) / total, uniform=(full - n_im * term[0]) / total, n=n_im)
+
+
+def compared(c: Case) -> np.ndarray:
+    """[T, E] bool: played steps that do not end their episode (the pairs the restatement is compared on)."""
+    return c.live & (c.out["oob"] == 0) & ~c.ended
+
+
+def _bits(x) -> np.ndarray:
+    return np.ascontiguousarray(x, np.float64).view(np.uint64)
+
+
+def discriminating(c: Case) -> np.ndarray:
+    """[T, E] bool: a node is being re-imaged and the kernel branches the topology must NOT take give other bits than the node-order sum:
+    the uniform shortcut, and for an order-dependent topology both ways of subtracting from full_sum."""
+    return discriminating_of(c.topo, c.imaging)
+
+
+def discriminating_of(topo, im: np.ndarray) -> np.ndarray:
+    s = sums_of(topo, im)
+    d = (s["n"] > 0) & (_bits(s["uniform"]) != _bits(s["order"]))
+    if int(topo.header()["avail_any_order"]) == 0:
+        d &= (_bits(s["sub_seq"]) != _bits(s["order"])) & (_bits(s["sub_sum"]) != _bits(s["order"]))
+    return d
+
+
+def sla_candidates(p: Case, v: float) -> np.ndarray:
+    """Envs of the pilot whose first episode meets v exactly on its first played step at or below v, on a discriminating step."""
+    play = first_episode(p) & p.live & (p.out["oob"] == 0)
+    low = play & (p.out["availability"] <= v)
+    t0 = np.argmax(low, axis=0)
+    cols = np.flatnonzero(low.any(axis=0))
+    hit = (p.out["availability"][t0[cols], cols] == v) & discriminating(p)[t0[cols], cols]
+    return cols[hit]
+
+
+@functools.lru_cache(maxsize=None)
+def _sla_value(topo_name: str, kind: str) -> float:
+    """The availability below full that the most envs of the pilot meet as sla_candidates do."""
+    p = case(f"{topo_name}-avail_{kind}")
+    play = first_episode(p) & p.live & (p.out["oob"] == 0) & discriminating(p)
+    values, counts = np.unique(p.out["availability"][play], return_counts=True)
+    best, best_n = None, 0
+    for v in values[np.argsort(-counts)][:40]:                      # (the most frequent values: a value few steps show ends few envs)
+        n = sla_candidates(p, float(v)).size
+        if n > best_n:
+            best, best_n = float(v), n
+    assert best is not None, f"{topo_name} {kind}: no first episode of the pilot shows a discriminating availability"
+    return best
+
+
+def _weighted_case(name: str, topo_name: str, spec_name: str) -> Case:
+    base, kind = spec_name.rsplit("_", 1)
+    topo = topology(topo_name, kind)
+    params = {}
+    sla = 0.0
+    if base != "avail":
+        v = _sla_value(topo_name, kind)
+        sla = v if base == "sla_eq" else float(np.nextafter(v, np.inf))
+        params["v"] = v
+    spec = make_spec(topo, maintain_sla=sla, **weighted_settings(topo_name))
+    return run(name, topo, spec, WEIGHT_STEPS, params=params, record_imaging=True)
+
+
 @functools.lru_cache(maxsize=None)
 def case(name: str) -> Case:
     topo_name, spec_name = name.split("-")
+    if spec_name in WEIGHT_SPECS:
+        return _weighted_case(name, topo_name, spec_name)
     topo = topology(topo_name)
     N = topo.n_nodes
     params, reset_at, stall = {}, -1, 0.0

@@ -17,6 +17,11 @@ Every condition is asserted, none is merely reported:
     that leaves no node owned;
   * `pct_*`: the owned count each threshold needs, from fractions.Fraction, is k, k, k + 1, and no env wins with fewer;
   * `frozen`: ended envs return reward 0, their old flags and step count until the reset by hand, and end again after it.
+
+The weighted cases (endings.WEIGHT_SPECS: unequal SLA weights, for tests/test_gpu_availability_weights.py) prove, per topology and
+weight kind, that the availability they make the kernels compute tells the three ways of summing apart
+(test_weighted_script_tells_the_sums_apart): the classification flatten.py makes, a NumPy fp64 restatement that agrees with the oracle
+on every compared step, and enough steps on which a kernel that took another branch would return other bits.
 """
 import numpy as np
 import pytest
@@ -85,6 +90,75 @@ def test_script_reaches_what_it_claims(name):
             "no wavefront neighbour kept going next to a frozen env"
         assert counts["evicted"][0] >= 1          # two short episodes per env: evictions stay rare on the large topologies
         assert int(c.reset_mask.sum()) >= 8 and ended[c.reset_at:].any(), "nothing ended again after the reset by hand"
+
+
+@pytest.mark.parametrize("kind", En.WEIGHT_KINDS)
+@pytest.mark.parametrize("topo_name", En.WEIGHT_TOPOLOGIES)
+def test_weighted_script_tells_the_sums_apart(topo_name, kind):
+    """From the oracle alone, for `avail`, `sla_eq` and `sla_up` of one topology and weight kind.  Compared pairs: (step, env) played,
+    not ending the episode.  Conditions (each a lower bound set beforehand, the counts are in the messages):
+      1  avail_any_order is 1 for dyadic, 0 for odd, and the terms are not all equal
+      2  the node-order restatement (endings.availability_sums) has the oracle's bits on every compared pair, in all three cases
+      a  >= 200 pairs with a node being re-imaged
+      u  >= 100 pairs on which the uniform shortcut full_sum - n * term[0] gives other bits
+      b  odd: >= 100 pairs on which full_sum - (terms of the nodes being re-imaged), subtracted one by one AND summed first, both give
+         other bits than the node-order sum; dyadic: no pair on which either does (the claim of flatten.py)
+      c  more than 64 nodes: >= 100 pairs whose re-imaging nodes lie in two or more 64-bit words
+      d  >= 100 pairs with three or more nodes being re-imaged
+      e  >= 8 envs end by SLA under sla_up on a step that sla_eq plays through with the same row, the availability being exactly v"""
+    c = En.case(f"{topo_name}-avail_{kind}")
+    h, term = c.topo.header(), c.topo.node_table()["avail_term"]
+    N = c.topo.n_nodes
+    assert int(h["avail_any_order"]) == (1 if kind == "dyadic" else 0)
+    assert np.unique(term).size > 1, "every node has the same availability term"
+    assert c.spec.maintain_sla == 0.0 and c.shadow_equal
+    counts = c.envs_by_reason()
+    assert counts["truncated"][0] >= 8 and not any(counts[k][1] for k in ("goal", "sla", "evicted")), f"avail: envs (endings) by reason {counts}"
+    np.testing.assert_array_equal(c.reasons(), En.derive(c))
+
+    bits = En._bits
+    s = En.availability_sums(c)
+    cmp_ = En.compared(c)
+    order = bits(s["order"])
+    agree = order == bits(c.out["availability"])
+    n_cmp = int(cmp_.sum())
+    assert n_cmp > 0 and int((agree & cmp_).sum()) == n_cmp, f"restatement agrees on {int((agree & cmp_).sum())} of {n_cmp} pairs"
+    a = cmp_ & (s["n"] > 0)
+    wrong_sub = (bits(s["sub_seq"]) != order) & (bits(s["sub_sum"]) != order)
+    any_sub = (bits(s["sub_seq"]) != order) | (bits(s["sub_sum"]) != order)
+    u = a & (bits(s["uniform"]) != order)
+    words = sum(c.imaging[:, :, w:w + 64].any(axis=2).astype(np.int64) for w in range(0, N, 64))
+    n = dict(a=int(a.sum()), u=int(u.sum()), b=int((a & wrong_sub).sum()), b_any=int((a & any_sub).sum()), c=int((a & (words >= 2)).sum()),
+             d=int((a & (s["n"] >= 3)).sum()), sets=len({r.tobytes() for r in c.imaging[a]}))
+    msg = f"{topo_name} {kind}: {n} over {n_cmp} compared pairs"
+    print(msg)
+    assert n["a"] >= 200 and n["u"] >= 100 and n["d"] >= 100, msg
+    assert n["b"] >= 100 if kind == "odd" else n["b_any"] == 0, msg
+    assert n["c"] >= 100 or N <= 64, msg
+    assert np.array_equal(En.discriminating(c), (s["n"] > 0) & (bits(s["uniform"]) != order) & (wrong_sub | (kind == "dyadic")))
+
+    eq, up = En.case(f"{topo_name}-sla_eq_{kind}"), En.case(f"{topo_name}-sla_up_{kind}")
+    v = eq.params["v"]
+    assert v < float(h["full_availability"]) and eq.spec.maintain_sla == v and up.spec.maintain_sla == float(np.nextafter(v, np.inf)) > v
+    for k in (eq, up):
+        assert k.shadow_equal
+        np.testing.assert_array_equal(k.reasons(), En.derive(k))
+        sk = En.availability_sums(k)
+        ck = En.compared(k)
+        assert np.array_equal(bits(sk["order"])[ck], bits(k.out["availability"])[ck]), f"{k.name}: restatement vs oracle"
+    cand = En.sla_candidates(c, v)
+    low = En.first_episode(c) & c.live & (c.out["oob"] == 0) & (c.out["availability"] <= v)
+    t0 = np.argmax(low, axis=0)[cand]
+    for k in (eq, up):                                            # the pilot's first episodes are the twins' up to the step in question
+        assert all(np.array_equal(k.actions[:t + 1, e], c.actions[:t + 1, e]) for t, e in zip(t0, cand))
+        assert np.all(k.out["availability"][t0, cand] == v) and np.all(En.discriminating(k)[t0, cand])
+    ends_up = up.reasons()[t0, cand] == "sla"
+    ends_eq = eq.ended[t0, cand]
+    e_msg = f"{topo_name} {kind}: v = {v!r}, {cand.size} candidate envs, sla_up ends {int(ends_up.sum())} of them there, sla_eq {int(ends_eq.sum())}; " \
+            f"envs (endings) by SLA: sla_eq {eq.envs_by_reason()['sla']}, sla_up {up.envs_by_reason()['sla']}"
+    print(e_msg)
+    assert int(ends_up.sum()) >= 8 and ends_up.all() and not ends_eq.any(), e_msg
+    assert not (eq.ended & (eq.out["availability"] == v) & (eq.reasons() == "sla")).any(), "equality ended an episode"
 
 
 def test_classifier_on_hand_made_outputs():

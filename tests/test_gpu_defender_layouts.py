@@ -19,6 +19,21 @@ loudly instead of quietly testing another cell.
 | DefenderVecEnv.step (defender_turn_post_kernel<WT>) WT 1 fused obs, WT 2 and WT 4 separate obs | test_defender_vec_env_shaping_against_numpy | oracle turn + NumPy shaping |
 | ScanAndReimage x wide | tests/test_gpu_parity.py::test_engine_matches_oracle_batched[ad6_wide_scan-*] | oracle |
 
+The three ways defender_tick sums the availability (uniform shortcut / any-order subtraction / node-order loop) x kernel.  Uniform:
+every sample topology (all terms 1.0).  `dyadic` and `odd` are the weight kinds of tests/endings.py (unequal terms with sums exact in
+any order; order-dependent sums); the cells are those of tests/test_gpu_episode_endings.py, the packed ones on the kitchen-sink topology.
+
+| kernel | uniform | any-order (`dyadic`) and node-order (`odd`) |
+|---|---|---|
+| step_kernel packed, WT 1, 2, 4, wide; step_coop_kernel G 2, 4 | tests/test_gpu_episode_endings.py and most others | tests/test_gpu_availability_weights.py::test_step_sums_availability_as_the_oracle, all eight cells (node-order on packed also: the `sink_*` traces of tests/test_gpu_parity.py) |
+| step_many_kernel | test_step_many_ends_episodes_as_the_oracle | ...::test_step_many_sums_availability_as_the_oracle: packed, general1, lane2, lane4, wide |
+| step_coop_kernel, phase kernels and step_many_kernel on one cooperative batch | test_cooperative_batch_alternates_entry_points | ...::test_cooperative_batch_sums_availability_on_every_entry_point: coop2, coop4 |
+| phase-2 kernel of step_observe | test_step_observe_ends_episodes_as_the_oracle | ...::test_step_observe_sums_availability_as_the_oracle: packed, lane2, wide |
+| rollout kernel (mcbs_rollout_random) | tests/test_gpu_random_agents.py | ...::test_rollout_random_sums_availability_as_the_oracle: general1, coop4 (one-lane kernel) |
+| wrapper_fused_kernel, step2_finish_kernel (AttackerVecEnv + ScanAndReimage) | tests/test_gpu_vecenv.py | ...::test_attacker_vec_env_sums_availability_as_the_oracle: packed in 1 and 3 launches, general1 |
+| defender_kernel<WT> (learned defender) | tests/test_gpu_facades.py::test_defender_step_batch_against_oracle[*] | the same test, [*-dyadic] and [*-odd]: packed, WT 1, 2, 4, wide |
+| defender_turn_post_kernel<WT> (DefenderVecEnv.step) | test_defender_vec_env_shaping_against_numpy[*] | the same test, [*-dyadic] and [*-odd]: WT 1, 2, 4 |
+
 mcbs_get_state does not carry the random-events overlay (vulnerability keys, service flags, firewall lists), so the tests make the
 channels it drives sensitive: non-dyadic node and service SLA weights (availability fingerprints each env's service flags), mask_local
 (the env's own keys), connect outcomes and rewards.
@@ -411,15 +426,35 @@ def _shape(s, valid, avail, won, has_cyber, last_cyber, c):
     return reward, term, trunc, breached, branch
 
 
-@pytest.mark.parametrize("n_nodes,want", [(24, dict(words_per_set=1, fused_defender_obs=1)), (70, dict(words_per_set=2, fused_defender_obs=0)),
-                                          (129, dict(words_per_set=4, fused_defender_obs=0))])
-def test_defender_vec_env_shaping_against_numpy(n_nodes, want):
+def _shaping_sla(topo, n_nodes, weights):
+    """maintain_sla of the shaping test.  Uniform weights: 0.9, 0.95, 0.97, i.e. k = 2.4, 3.5, 3.87 re-imaged nodes of N below 1.  Unequal
+    weights: the same k times the median node's share of the total weight below the full availability, so that one heavy node or a
+    few light ones breach it and the breach ends when they return."""
+    uniform = {24: 0.9, 70: 0.95, 129: 0.97}[n_nodes]
+    if weights == "uniform":
+        return uniform
+    h = topo.header()
+    k = round((1.0 - uniform) * n_nodes, 2)
+    return float(h["full_availability"]) - k * float(np.median(topo.node_table()["avail_term"])) / float(h["total_sla_weight"])
+
+
+SHAPING = [(24, dict(words_per_set=1, fused_defender_obs=1)), (70, dict(words_per_set=2, fused_defender_obs=0)),
+           (129, dict(words_per_set=4, fused_defender_obs=0))]
+
+
+# (the uniform cases keep the ids they had before the weight kinds were added)
+@pytest.mark.parametrize("n_nodes,want,weights", [pytest.param(n, want, w, id=f"{n}-want{i}" + ("" if w == "uniform" else f"-{w}"))
+                                                  for w in ("uniform", "dyadic", "odd") for i, (n, want) in enumerate(SHAPING)])
+def test_defender_vec_env_shaping_against_numpy(n_nodes, want, weights):
     """DefenderVecEnv.step (mcbs_defender_wrapper_step: defender_turn_post_kernel<WT>, the turn and the reward shaping in one launch, the
     observation fused into it or a launch of its own) next to AttackerVecEnv(learned_defender=True) beyond ToyCtf, with random defender
     actions (kinds -1 and -2 included, some aimed at the attacker's nodes) against the oracle's turn and a float64 NumPy restatement of
     the shaping fed by the oracle's defender_step and the attacker's last environment reward: reward bits, terminated, truncated,
     sla_breached, defender_won, the valid / invalid counts and the four observation arrays.  SLA, loss_reward and worsening scale make
-    every branch fire: a first breach, a worsening penalty while breached, recovery, eviction and truncation."""
+    every branch fire: a first breach, a worsening penalty while breached, recovery, eviction and truncation.  weights: the samples'
+    own SLA weights (every term 1.0: defender_tick's uniform shortcut), `dyadic` (its any-order subtraction) and `odd` (its node-order
+    loop) of tests/endings.py, the threshold derived per topology (_shaping_sla)."""
+    from tests import endings as En
     from marlon_amd import cyberbattle_env as ce, flatten as F, model
     from marlon_amd.samples import random_net
     from marlon_amd.wrappers import AttackerVecEnv, DefenderVecEnv
@@ -427,9 +462,11 @@ def test_defender_vec_env_shaping_against_numpy(n_nodes, want):
     env_m = random_net.build(model, n_nodes, 5)
     for _, info in env_m.nodes():
         info.reimagable = True                        # the entry node too: the defender can evict the attacker
-    topo = F.flatten(env_m)
+    topo = F.flatten(En.reweigh(env_m, weights))
+    assert weights == "uniform" or (int(topo.header()["avail_any_order"]) == (1 if weights == "dyadic" else 0)
+                                    and np.unique(topo.node_table()["avail_term"]).size > 1)
     E, T, MAXT_A, MAXT_D = 133, 60, 23, 17
-    sla = {24: 0.9, 70: 0.95, 129: 0.97}[n_nodes]
+    sla = _shaping_sla(topo, n_nodes, weights)
     att = AttackerVecEnv(topo, E, maximum_node_count=n_nodes, maximum_total_credentials=max(1, len(topo.triples)),
                          maximum_discoverable_credentials_per_action=8, attacker_goal=ce.AttackerGoal(own_atleast_percent=1.0),
                          defender_constraint=ce.DefenderConstraint(sla), losing_reward=0.0, max_timesteps=MAXT_A, seed=29,

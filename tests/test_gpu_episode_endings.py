@@ -67,10 +67,11 @@ def _engine():
     return engine
 
 
-def _create(cell, spec_name, monkeypatch):
-    """The case's script and a batch on the cell's layout (variant asserted: a moved threshold fails loudly)."""
-    topo_name, switches, want = CELLS[cell]
-    c = En.case(f"{topo_name}-{spec_name}")
+def _create(cell, spec_name, monkeypatch, topo_name=None):
+    """The case's script and a batch on the cell's layout (variant asserted: a moved threshold fails loudly).  topo_name: another
+    topology than the cell's own (it must land on the same layout)."""
+    own, switches, want = CELLS[cell]
+    c = En.case(f"{topo_name or own}-{spec_name}")
     for k, v in switches.items():
         monkeypatch.setenv(k, v)
     eng = _engine().BatchEngine(c.topo, c.spec)

@@ -278,28 +278,35 @@ DEFENDER_CASES = {   # case: the variant the batch must dispatch to
 }
 
 
-@pytest.mark.parametrize("case", list(DEFENDER_CASES))
-def test_defender_step_batch_against_oracle(case, monkeypatch):
+# (the uniform cases keep the ids they had before the weight kinds were added)
+@pytest.mark.parametrize("case,weights", [pytest.param(c, w, id=c if w == "uniform" else f"{c}-{w}")
+                                          for w in ("uniform", "dyadic", "odd") for c in DEFENDER_CASES])
+def test_defender_step_batch_against_oracle(case, weights, monkeypatch):
     """Random attacker rows and random defender vectors on a batch that does not fill its last workgroup: validity, availability bits,
     eviction, the four observation fields and the attacker's rewards equal the oracle's (which keeps real rule lists) at every step.
     ToyCtf and a 24-node instance of the config-5 generator write the observation from the turn kernel itself (round 3: one launch per
     turn), MCBS_NO_FUSED_DEFENDER_OBS=1 and the 70-node instance (two words per node set) through the separate observation launch;
     the 129-node instance at four words per set (defender_kernel<4>, the attacker's step at WT 4, the separate observation beyond 32
     nodes); ActiveDirectory-6 on the wide layout (821 cacheable credentials in a column of their own);
-    buffers pre-filled with a sentinel.  defend_wrapper.py:329-412,492-534, defender.py:31-107."""
+    buffers pre-filled with a sentinel.  defend_wrapper.py:329-412,492-534, defender.py:31-107.
+    weights: the samples' own SLA weights (every availability term 1.0: the uniform shortcut of defender_tick), and the `dyadic` and
+    `odd` weights of tests/endings.py (its any-order subtraction and its node-order loop)."""
+    from tests import endings as En
     from marlon_amd import flatten as F, model
     from marlon_amd._abi import EnvSpec
-    from marlon_amd.samples import random_net
+    from marlon_amd.samples import active_directory, random_net, toy_ctf
     from oracle.oracle import Oracle
     if case.startswith("toyctf"):
-        topo, nm, cm, E, T = parity.topology_for("toyctf"), 12, 10, 2048 + 37, 120
+        env_m, nm, cm, E, T = toy_ctf.new_environment(), 12, 10, 2048 + 37, 120
     elif case == "ad6":
-        topo = parity.topology_for("ad6_mix_s70")
-        nm, cm, E, T = topo.n_nodes, len(topo.triples), 300 + 37, 60
+        env_m, nm, cm, E, T = active_directory.new_random_environment(6), None, None, 300 + 37, 60
     else:
-        n = int(case[6:])
-        topo = F.flatten(random_net.build(model, n, 5))
-        nm, cm, E, T = n, max(1, len(topo.triples)), 300 + 37, 60
+        env_m, nm, cm, E, T = random_net.build(model, int(case[6:]), 5), None, None, 300 + 37, 60
+    topo = F.flatten(En.reweigh(env_m, weights))
+    if nm is None:
+        nm, cm = topo.n_nodes, max(1, len(topo.triples))
+    if weights != "uniform":
+        assert int(topo.header()["avail_any_order"]) == (1 if weights == "dyadic" else 0) and np.unique(topo.node_table()["avail_term"]).size > 1
     spec = EnvSpec(n_envs=E, maximum_node_count=nm, maximum_total_credentials=cm,
                    maximum_discoverable_credentials_per_action=max(8, int(topo.header()["max_leak_per_action"])),
                    attacker_goal=dict(own_atleast=6, own_atleast_percent=1.0),

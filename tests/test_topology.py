@@ -139,6 +139,63 @@ def test_availability_terms_follow_reference_order():
     assert F.flatten(toy_ctf.new_environment()).header()["avail_any_order"] == 1
 
 
+def _weights_topology(weights):
+    """Nodes without services: node i's availability term is weights[i]."""
+    nodes = {f"n{i}": m.NodeInfo(services=[], sla_weight=w, agent_installed=i == 0) for i, w in enumerate(weights)}
+    env = m.Environment(network=m.create_network(nodes), vulnerability_library={},
+                        identifiers=m.Identifiers(properties=["Linux"], ports=["SSH"], local_vulnerabilities=["v"], remote_vulnerabilities=["r"]))
+    t = F.flatten(env)
+    assert t.node_table()["avail_term"].tolist() == [float(w) for w in weights]
+    return t
+
+
+def test_any_order_classification_edges():
+    """avail_any_order == 1 promises that every subset of the terms sums exactly: as multiples of the smallest power of two that makes
+    every term an integer, they add up to less than 2**53.  It does not ask for dyadic-looking terms (one 0.3 is a 52-bit integer
+    times 2**-54 and sums exactly with itself alone) and must refuse what cannot be added exactly."""
+    any_order = lambda *w: int(_weights_topology(w).header()["avail_any_order"])
+    assert any_order(0.3) == 1
+    assert any_order(0.3, 0.3) == 0                    # two 52-bit integers: the sum needs 54 bits
+    assert any_order(1.0, 2.0, 0.5, 4.0, 0.25, 1.5, 3.0, 0.75, 8.0) == 1
+    assert any_order(1.0, 2.0 ** -60) == 0 and any_order(2.0 ** 40, 2.0 ** -20) == 0        # magnitudes too far apart for one 53-bit sum
+    assert any_order(1.0, 2.0 ** -52) == 1             # (the widest pair that still fits)
+    assert any_order(1.0, -0.5, 2.0) == 0 and any_order(-1.0) == 0                          # a negative term
+    assert any_order(0.1, 0.3, 0.7, 1.9) == 0
+
+
+@pytest.mark.parametrize("weights", [(1.0, 2.0, 0.5, 4.0, 0.25, 1.5, 3.0, 0.75, 8.0) * 15, (0.3,), (1.0, 2.0 ** -52, 0.5, 2.0 ** -51),
+                                     (2.0 ** 30 + 1.0, 2.0 ** -20, 7.0, 2.0 ** 10 + 2.0 ** -22), tuple(float(k) / 1024 for k in range(1, 257))])
+def test_any_order_sums_are_exact_in_every_order(weights):
+    """What the kernels' any-order branch relies on, for topologies flatten.py classifies 1: random subsets of the terms summed in
+    random orders, subtracted one by one from full_sum, and their sum subtracted from full_sum, all give the bits of the node-order
+    sum of the remaining terms."""
+    t = _weights_topology(weights)
+    h = t.header()
+    assert int(h["avail_any_order"]) == 1
+    term = t.node_table()["avail_term"].astype(np.float64)
+    full = float(h["full_sum"])
+    rng = np.random.Generator(np.random.PCG64(5))
+    N = term.size
+    for _ in range(200):
+        out = rng.random(N) < rng.random()            # the nodes being re-imaged
+        want = 0.0
+        for n in np.flatnonzero(~out):
+            want += float(term[n])
+        gone = np.flatnonzero(out)
+        for order in (gone, rng.permutation(gone), rng.permutation(gone)):
+            seq, part = full, 0.0
+            for n in order:
+                seq -= float(term[n])
+                part += float(term[n])
+            words = [0.0] * ((N + 63) // 64)          # a partial sum per 64-bit word, then the words (the cooperative kernel)
+            for n in order:
+                words[n // 64] += float(term[n])
+            lanes = (words + [0.0] * 3)[:4]
+            tree = (lanes[0] + lanes[1]) + (lanes[2] + lanes[3]) if N <= 256 else part
+            got = np.array([seq, full - part, full - tree, float(np.sum(term[rng.permutation(np.flatnonzero(~out))]))])
+            assert np.array_equal(got.view(np.uint64), np.full(4, want).view(np.uint64)), f"{weights[:4]}...: {got!r} != {want!r}"
+
+
 def test_every_registered_active_directory_seed_fits_the_engine():
     """ActiveDirectory-v0..v9 leak up to 821 distinct credentials (DumpNTDS); the limit is 1024 (wide cached-credential set)."""
     for seed in range(10):
