@@ -530,6 +530,52 @@ int  mcbs_masked_categorical_grad(const mcbs_batch*, const uint32_t* bits, size_
                                   int32_t dtype, size_t row_stride, const int64_t* actions, const float* grad_log_prob,
                                   const float* grad_entropy, void* grad_logits, size_t grad_row_stride, void* stream);
 
+/* ---- masked action head from the latent: gradient — the backward pass of mcbs_masked_linear_categorical_packed in EVALUATE mode ----
+ * The gradients of log_prob(actions) and the entropy with respect to latent, weight and bias, without an [n, A] tensor.  Packed form only,
+ * like mcbs_masked_categorical_grad; the batch only supplies the device and A, every defender kind is served.  bits, bits_row_words, n_rows,
+ * latent, latent_row_stride, weight, weight_row_stride, bias, H, dtype and actions are those of mcbs_masked_linear_categorical_packed in
+ * EVALUATE mode (float32 or bfloat16, READ-ONLY), grad_log_prob / grad_entropy those of mcbs_masked_categorical_grad (NULL = zeros).
+ *
+ * For row i, x_a is the forward's logit (the same device code: bit for bit), K, m, Z, log Z and the entropy are the forward's, and
+ * g_{i,a} is the float32 value mcbs_masked_categorical_grad computes, before its output rounding, on a float32 logits buffer holding
+ * these x_a: the formula there for an allowed a, 0 for a masked one, a whole row of zeros when K == 0 or actions[i] lies outside [0, A)
+ * (a DEAD row).  With S_i the allowed set of row i, l = (float)latent, w = (float)weight:
+ *   grad_latent  float [n, grad_latent_row_stride]   grad_latent[i, h] = sum over a in S_i of g_{i,a} * w_{a,h}
+ *   grad_weight  float [A, grad_weight_row_stride]   grad_weight[a, h] = sum over i with a in S_i of g_{i,a} * l_{i,h}
+ *   grad_bias    float [A]                           grad_bias[a]      = sum over i with a in S_i of g_{i,a}
+ * All three are float32 whatever `dtype`, each may be NULL (all three NULL: MCBS_EINVAL), strides in elements and >= H, any alignment.
+ * WRITE-ONLY: every element [*, 0 .. H) and [0 .. A) is written exactly once (the caller need not clear them), elements from H up to the
+ * stride never.  A dead row of grad_latent, and an action no live row allows, is +0.0.  The value of a weight, bias or logit under a
+ * clear mask bit never reaches an output.
+ *
+ * The order of every sum, in float32, a function of (n_rows, the masks, H) only — not of the launch geometry, strides, alignment, dtype
+ * or what the workspace held.  No floating-point atomics; two calls give bit-identical outputs.
+ *   grad_latent[i, h]: four partial sums t_0 .. t_3 start at +0; the k-th allowed action a of the row (k = 0, 1, ... in ascending a) does
+ *     t_(k mod 4) = fmaf(g_{i,a}, w_{a,h}, t_(k mod 4));  the result is (t_0 + t_1) + (t_2 + t_3).
+ *   grad_weight[a, h]: the rows are cut into blocks of MCBS_LINEAR_GRAD_ROW_BLOCK consecutive rows (block j = rows [j B, (j+1) B)); the
+ *     partial of block j starts at +0.0 and does  s = fmaf(g_{i,a}, l_{i,h}, s)  for the block's live rows that allow a, in ascending i;
+ *     the result is the partials added in ascending j, starting FROM partial 0:  (..(p_0 + p_1) + p_2 ..).
+ *   grad_bias[a]: the same with  s = s + g_{i,a}.
+ * So a sum with a single term is that term's rounded product added to +0.0 (a product of -0.0 comes out as +0.0, every other value as
+ * itself), and a sum without a term is +0.0.
+ *
+ * workspace: device memory of at least mcbs_masked_linear_categorical_grad_workspace(batch, n_rows, H) bytes (0 for n_rows == 0 or an H
+ * outside [1, MCBS_LINEAR_MAX_H]): 32 bytes per row and (H + 1) * 4 bytes per action (A rounded up to whole mask words) and row block —
+ * 118 MB for 16 384 rows of Chain-10's 14 172 actions at H = 64, an eighth of one float32 [n, A] tensor.  Its contents on entry do not
+ * matter and are undefined on return.  Launches: ONE (the row pass) when grad_weight and grad_bias are both NULL, else THREE (row pass,
+ * action pass, the pass that adds the block partials); n_rows == 0 writes +0.0 to grad_weight / grad_bias in one launch.  No allocation,
+ * no host synchronisation, asynchronous on `stream`, capturable in a graph.
+ * MCBS_EINVAL: all three outputs NULL; bits, latent, weight or actions NULL; H outside [1, MCBS_LINEAR_MAX_H]; a stride < H;
+ * bits_row_words < W; another dtype; workspace NULL or smaller than the query's answer; an output or the workspace sharing a byte with
+ * an input, with each other (the extents from the first to the last byte of each array are compared). */
+#define MCBS_LINEAR_GRAD_ROW_BLOCK 512
+size_t mcbs_masked_linear_categorical_grad_workspace(const mcbs_batch*, uint64_t n_rows, uint32_t H);
+int  mcbs_masked_linear_categorical_grad(const mcbs_batch*, const uint32_t* bits, size_t bits_row_words, uint64_t n_rows, const void* latent,
+                                         size_t latent_row_stride, const void* weight, size_t weight_row_stride, const void* bias, uint32_t H,
+                                         int32_t dtype, const int64_t* actions, const float* grad_log_prob, const float* grad_entropy,
+                                         float* grad_latent, size_t grad_latent_row_stride, float* grad_weight, size_t grad_weight_row_stride,
+                                         float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- MultiDiscrete head: sample, log-prob, entropy and gradient of PPO's MultiCategorical action distribution, one launch each way ----
  * What Stable-Baselines3's MultiCategoricalDistribution does with the policy's logits for a MultiDiscrete(nvec) action — the defender's
  * [5,N,N,6,2,N,6,2,N,3,N,3] (defend_wrapper.py:162-195) and the attacker's unmasked [3,N,L,N,N,R,N,N,P,C] (attack_wrapper.py:206-227):

@@ -102,7 +102,16 @@ _LINEAR_CATEGORICAL_TAIL = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_
 LINEAR_CATEGORICAL_ARGTYPES = {
     "mcbs_masked_linear_categorical": [C.c_void_p] + _LINEAR_CATEGORICAL_TAIL,                                          # batch
     "mcbs_masked_linear_categorical_packed": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64] + _LINEAR_CATEGORICAL_TAIL,   # batch, bits, bits_row_words, n_rows
+    # batch, n_rows, H -> bytes
+    "mcbs_masked_linear_categorical_grad_workspace": [C.c_void_p, C.c_uint64, C.c_uint32],
+    # batch, bits, bits_row_words, n_rows, latent, latent_row_stride, weight, weight_row_stride, bias, H, dtype, actions, grad_log_prob,
+    # grad_entropy, grad_latent, grad_latent_row_stride, grad_weight, grad_weight_row_stride, grad_bias, workspace, workspace_bytes, stream
+    "mcbs_masked_linear_categorical_grad": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
+                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
 }
+LINEAR_CATEGORICAL_RESTYPES = {"mcbs_masked_linear_categorical_grad_workspace": C.c_size_t}
+MCBS_LINEAR_GRAD_ROW_BLOCK = 512
 
 class InfoBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("network_availability", "step_count", "truncated", "out_of_bound", "raw_reward")]

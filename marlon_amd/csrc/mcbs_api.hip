@@ -24,6 +24,7 @@
 #include "mcbs_categorical.hip"
 #include "mcbs_categorical_grad.hip"
 #include "mcbs_linear_categorical.hip"
+#include "mcbs_linear_categorical_grad.hip"
 #include "mcbs_multicategorical.hip"
 #include "mcbs_gae.hip"
 #include "mcbs_features.hip"
@@ -1488,6 +1489,111 @@ extern "C" int mcbs_masked_categorical_grad(const mcbs_batch* b, const uint32_t*
                            bits, bits_row_words, io);
     });
     return launch_ok("masked categorical gradient");
+}
+
+// ------------------------------------------------------------------ masked action head from the latent: gradient
+// the workspace: [n] CatGradRow, then (from a 256-byte boundary) the block partials of grad_weight [n_blocks][32 W][H] and grad_bias [n_blocks][32 W]
+struct LinGradWorkspace {
+    uint64_t n_blocks;
+    size_t part_w, part_b, bytes;      // byte offsets and the total
+};
+static LinGradWorkspace linear_grad_workspace(uint32_t A, uint64_t n_rows, uint32_t H) {
+    LinGradWorkspace ws{};
+    if (!n_rows) return ws;
+    ws.n_blocks = (n_rows + MCBS_LINEAR_GRAD_ROW_BLOCK - 1u) / MCBS_LINEAR_GRAD_ROW_BLOCK;
+    const size_t per_block = (size_t)((A + 31u) / 32u) * 32u;
+    ws.part_w = ((size_t)n_rows * sizeof(CatGradRow) + 255u) & ~(size_t)255u;
+    ws.part_b = ws.part_w + (size_t)ws.n_blocks * per_block * H * sizeof(float);
+    ws.bytes = ws.part_b + (size_t)ws.n_blocks * per_block * sizeof(float);
+    return ws;
+}
+
+extern "C" size_t mcbs_masked_linear_categorical_grad_workspace(const mcbs_batch* b, uint64_t n_rows, uint32_t H) {
+    uint32_t A, W;
+    if (!b || discrete_dims(b, A, W) || H < 1u || H > MCBS_LINEAR_MAX_H) return 0;
+    return linear_grad_workspace(A, n_rows, H).bytes;
+}
+
+extern "C" int mcbs_masked_linear_categorical_grad(const mcbs_batch* b, const uint32_t* bits, size_t bits_row_words, uint64_t n_rows, const void* latent,
+                                                   size_t latent_row_stride, const void* weight, size_t weight_row_stride, const void* bias, uint32_t H,
+                                                   int32_t dtype, const int64_t* actions, const float* grad_log_prob, const float* grad_entropy,
+                                                   float* grad_latent, size_t grad_latent_row_stride, float* grad_weight, size_t grad_weight_row_stride,
+                                                   float* grad_bias, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char* who = "mcbs_masked_linear_categorical_grad";
+    if (!b) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    int rc;
+    LogitsGeom G;
+    if ((rc = discrete_geom(b, G))) return rc;
+    const uint32_t A = G.A, W = (A + 31u) / 32u;
+    if (!grad_latent && !grad_weight && !grad_bias) return fail(MCBS_EINVAL, "%s: grad_latent, grad_weight and grad_bias are all NULL", who);
+    if (H < 1u || H > MCBS_LINEAR_MAX_H) return fail(MCBS_EINVAL, "%s: H %u: from 1 to %u", who, H, (uint32_t)MCBS_LINEAR_MAX_H);
+    if (dtype != MCBS_LOGITS_F32 && dtype != MCBS_LOGITS_BF16) return fail(MCBS_EINVAL, "%s: dtype must be MCBS_LOGITS_F32 or MCBS_LOGITS_BF16", who);
+    if (grad_latent && grad_latent_row_stride < H) return fail(MCBS_EINVAL, "%s: grad_latent_row_stride %zu is shorter than H = %u", who, grad_latent_row_stride, H);
+    if (grad_weight && grad_weight_row_stride < H) return fail(MCBS_EINVAL, "%s: grad_weight_row_stride %zu is shorter than H = %u", who, grad_weight_row_stride, H);
+    const bool action_pass = grad_weight || grad_bias;
+    hipStream_t st = (hipStream_t)stream;
+    if (n_rows) {
+        if (!bits || !latent || !weight || !actions) return fail(MCBS_EINVAL, "%s: bits, latent, weight and actions must not be NULL", who);
+        if (latent_row_stride < H) return fail(MCBS_EINVAL, "%s: latent_row_stride %zu is shorter than H = %u", who, latent_row_stride, H);
+        if (weight_row_stride < H) return fail(MCBS_EINVAL, "%s: weight_row_stride %zu is shorter than H = %u", who, weight_row_stride, H);
+        if ((rc = rows_hold(A, "bits_row_words", bits_row_words, nullptr, 0))) return rc;
+    }
+    const LinGradWorkspace ws = linear_grad_workspace(A, n_rows, H);
+    if (ws.bytes && (!workspace || workspace_bytes < ws.bytes))
+        return fail(MCBS_EINVAL, "%s: the workspace must hold %zu bytes (mcbs_masked_linear_categorical_grad_workspace), got %zu at %p", who, ws.bytes,
+                    workspace_bytes, workspace);
+
+    // no output may share a byte with an input, the workspace or another output: the extents [first byte, last byte] are compared
+    struct Extent { const char* name; uintptr_t lo, hi; bool out; };
+    const size_t es = dtype == MCBS_LOGITS_F32 ? 4u : 2u;
+    auto extent = [](const char* name, const void* p, uint64_t rows, size_t stride, size_t width, size_t elem, bool out) {
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+        return Extent{name, lo, p && rows ? lo + (uintptr_t)(((rows - 1u) * stride + width) * elem) : lo, out};
+    };
+    const Extent ext[] = {
+        extent("grad_latent", grad_latent, n_rows, grad_latent_row_stride, H, 4u, true),
+        extent("grad_weight", grad_weight, A, grad_weight_row_stride, H, 4u, true),
+        extent("grad_bias", grad_bias, 1u, 0u, A, 4u, true),
+        extent("workspace", workspace, ws.bytes ? 1u : 0u, 0u, ws.bytes, 1u, true),
+        extent("bits", bits, n_rows, bits_row_words, W, 4u, false),
+        extent("latent", latent, n_rows, latent_row_stride, H, es, false),
+        extent("weight", weight, n_rows ? A : 0u, weight_row_stride, H, es, false),
+        extent("bias", bias, n_rows ? 1u : 0u, 0u, A, es, false),
+        extent("actions", actions, n_rows ? 1u : 0u, 0u, n_rows, 8u, false),
+        extent("grad_log_prob", grad_log_prob, n_rows ? 1u : 0u, 0u, n_rows, 4u, false),
+        extent("grad_entropy", grad_entropy, n_rows ? 1u : 0u, 0u, n_rows, 4u, false),
+    };
+    constexpr size_t NE = sizeof(ext) / sizeof(ext[0]);
+    for (size_t i = 0; i < NE; ++i)
+        for (size_t k = i + 1u; k < NE; ++k)
+            if (ext[i].out && ext[i].lo < ext[i].hi && ext[k].lo < ext[k].hi && ext[i].lo < ext[k].hi && ext[k].lo < ext[i].hi)
+                return fail(MCBS_EINVAL, "%s: %s overlaps %s", who, ext[i].name, ext[k].name);
+
+    char* wsp = static_cast<char*>(workspace);
+    LinGradIO io{actions, grad_log_prob, grad_entropy, grad_latent, grad_latent_row_stride, grad_weight, grad_weight_row_stride, grad_bias,
+                 action_pass && n_rows ? reinterpret_cast<CatGradRow*>(wsp) : nullptr,
+                 n_rows ? reinterpret_cast<float*>(wsp + ws.part_w) : nullptr, n_rows ? reinterpret_cast<float*>(wsp + ws.part_b) : nullptr,
+                 n_rows, A, (uint32_t)ws.n_blocks};
+    const LinIO lin{latent, weight, bias, latent_row_stride, weight_row_stride, H};
+    if (ws.n_blocks > 0xFFFFFFFFull) return fail(MCBS_EINVAL, "%s: too many rows", who);
+    if (n_rows) {
+        pick<2, 4>((int)es, [&](auto esc) {
+            using WT = LogitsElem<(uint32_t)decltype(esc)::value>;
+            hipLaunchKernelGGL((masked_linear_categorical_grad_row_kernel<WT>), rows_grid(n_rows, 65536u), dim3(256), 0, st, bits, bits_row_words, lin, io);
+            if (!action_pass) return;
+            const dim3 grid((W + LIN_GRAD_WORDS - 1u) / LIN_GRAD_WORDS, ws.n_blocks < 65535u ? (uint32_t)ws.n_blocks : 65535u);
+            pick<1, 2, 4, 8>(H <= 64u ? 1 : H <= 128u ? 2 : H <= 256u ? 4 : 8, [&](auto nh) {
+                hipLaunchKernelGGL((masked_linear_categorical_grad_action_kernel<WT, (uint32_t)decltype(nh)::value>), grid, dim3(256), 0, st, bits,
+                                   bits_row_words, lin, io);
+            });
+        });
+    }
+    if (action_pass) {
+        const uint32_t blocks = (A + 3u) / 4u;
+        hipLaunchKernelGGL(masked_linear_categorical_grad_reduce_kernel, dim3(blocks < 65536u ? blocks : 65536u), dim3(256), 0, st, io, H);
+    }
+    return launch_ok("masked action head gradient");
 }
 
 // ------------------------------------------------------------------ MultiDiscrete head

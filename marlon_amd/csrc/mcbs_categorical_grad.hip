@@ -35,6 +35,24 @@ struct CatGradIO {
     uint32_t logits_vec;       // the logits rows are aligned to the gradient's groups: whole-group loads
 };
 
+// What a row contributes to the gradient of each of its allowed logits: the forward's m, log Z, 1 / Z and entropy, the incoming gradients
+// and the chosen action.  32 bytes: mcbs_linear_categorical_grad.hip keeps one per row in its workspace.
+struct CatGradRow {
+    float m, logZ, rZ, H, g_lp, g_H;
+    uint32_t c;                // the chosen action (meaningful where live)
+    uint32_t live;             // 0: K == 0 or the action lies outside [0, A): the whole row is +0.0
+};
+
+// The gradient with respect to the logit x of ALLOWED action a, in float32 before any output rounding.  The ONE place it is computed:
+// masked_categorical_grad_kernel and the kernels of mcbs_linear_categorical_grad.hip call this, so their g agree bit for bit.
+__device__ __forceinline__ float cat_grad_term(const CatGradRow& r, uint32_t a, float x) {
+    const float d = x - r.m;
+    const float ex = expf(d);
+    const float lq = d - r.logZ;
+    const float prod = ex > 0.f ? (ex * r.rZ) * (-r.g_lp - r.g_H * (lq + r.H)) : 0.f;      // (-inf) * 0 is no term
+    return (a == r.c ? r.g_lp : 0.f) + prod;
+}
+
 template <typename LT, uint32_t GW, bool VEC>
 __global__ __launch_bounds__(256) void masked_categorical_grad_kernel(const uint32_t* __restrict__ bits, size_t bits_row_words, CatGradIO io) {
     using RG = RowGroups<LT, GW, VEC>;
@@ -81,13 +99,8 @@ __global__ __launch_bounds__(256) void masked_categorical_grad_kernel(const uint
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 
         // gradient of allowed action a with logit x
-        auto value = [&](uint32_t a, float x) -> float {
-            const float d = x - m;
-            const float ex = expf(d);
-            const float lq = d - logZ;
-            const float prod = ex > 0.f ? (ex * rZ) * (-g_lp - g_H * (lq + H)) : 0.f;      // (-inf) * 0 is no term
-            return (a == c ? g_lp : 0.f) + prod;
-        };
+        const CatGradRow gr{m, logZ, rZ, H, g_lp, g_H, c, live ? 1u : 0u};
+        auto value = [&](uint32_t a, float x) -> float { return cat_grad_term(gr, a, x); };
 
         // ---- phase B
         const uint32_t sh = RG::shift(out);

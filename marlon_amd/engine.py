@@ -14,7 +14,7 @@ from typing import Dict, Iterable, Optional
 
 import numpy as np
 
-from ._abi import (LINEAR_CATEGORICAL_ARGTYPES, MCBS_LINEAR_MAX_H, MULTICATEGORICAL_ARGTYPES, BatchCfg, BatchVariantInfo, DefenderObs, EnvSpec, GaeIO, InfoBuffers, ObsBuffers,
+from ._abi import (LINEAR_CATEGORICAL_ARGTYPES, LINEAR_CATEGORICAL_RESTYPES, MCBS_LINEAR_GRAD_ROW_BLOCK, MCBS_LINEAR_MAX_H, MULTICATEGORICAL_ARGTYPES, BatchCfg, BatchVariantInfo, DefenderObs, EnvSpec, GaeIO, InfoBuffers, ObsBuffers,
                    split_state, state_record_bytes)
 from .flatten import FlatTopology
 
@@ -31,6 +31,7 @@ EXPORTS = [
     "mcbs_feature_layout_create", "mcbs_feature_layout_destroy", "mcbs_feature_layout_width", "mcbs_encode_features",
     "mcbs_masked_categorical", "mcbs_masked_categorical_packed", "mcbs_masked_categorical_grad",
     "mcbs_masked_linear_categorical", "mcbs_masked_linear_categorical_packed",
+    "mcbs_masked_linear_categorical_grad_workspace", "mcbs_masked_linear_categorical_grad",
     "mcbs_multicategorical", "mcbs_multicategorical_grad",
     "mcbs_gae",
 ]
@@ -132,6 +133,8 @@ def load_library(path: Optional[str] = None):
             raise NativeLibraryMissing(f"{p} does not export {name}")
     for name, argtypes in {**MULTICATEGORICAL_ARGTYPES, **LINEAR_CATEGORICAL_ARGTYPES}.items():
         getattr(lib, name).argtypes = argtypes
+    for name, restype in LINEAR_CATEGORICAL_RESTYPES.items():
+        getattr(lib, name).restype = restype
     if path is None:
         _lib = lib
     return lib
@@ -209,6 +212,45 @@ def _masked_evaluate_function(torch):
 
     _MASKED_EVALUATE = MaskedEvaluate
     return MaskedEvaluate
+
+
+# what BatchEngine.masked_linear_categorical_grad returns: float32 [n, H], [A, H], [A]; None for a gradient that was not asked for
+MaskedLinearGrad = collections.namedtuple("MaskedLinearGrad", ["grad_latent", "grad_weight", "grad_bias"])
+
+_MASKED_LINEAR_EVALUATE = None
+
+
+def _masked_linear_evaluate_function(torch):
+    """The torch.autograd.Function behind BatchEngine.masked_linear_evaluate (made on first use, like _masked_evaluate_function)."""
+    global _MASKED_LINEAR_EVALUATE
+    if _MASKED_LINEAR_EVALUATE is not None:
+        return _MASKED_LINEAR_EVALUATE
+
+    class MaskedLinearEvaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, latent, weight, bias, eng, bits, actions, bad_actions):
+            r = eng.masked_linear_categorical(latent, weight, bias, bits=bits, mode="evaluate", actions=actions, bad_actions=bad_actions)
+            ctx.eng = eng
+            ctx.has_bias = bias is not None
+            ctx.save_for_backward(*((latent, weight, bits, actions) + ((bias,) if bias is not None else ())))
+            ctx.mark_non_differentiable(r.n_allowed)
+            ctx.set_materialize_grads(False)             # an output the loss does not use arrives as None, not as zeros
+            return r.log_prob, r.entropy, r.n_allowed
+
+        @staticmethod
+        def backward(ctx, g_lp, g_ent, _g_k):
+            latent, weight, bits, actions = ctx.saved_tensors[:4]
+            bias = ctx.saved_tensors[4] if ctx.has_bias else None
+            want = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.has_bias and ctx.needs_input_grad[2])
+            if not any(want):
+                return (None,) * 7
+            g = ctx.eng.masked_linear_categorical_grad(latent, weight, bias, bits, actions,
+                                                       None if g_lp is None else g_lp.float().contiguous(),
+                                                       None if g_ent is None else g_ent.float().contiguous(), want=want)
+            return tuple(None if x is None else x.to(latent.dtype) for x in g) + (None,) * 4
+
+    _MASKED_LINEAR_EVALUATE = MaskedLinearEvaluate
+    return MaskedLinearEvaluate
 
 
 # what BatchEngine.multicategorical returns: actions int64 [n, D], log_prob float32 [n], entropy float32 [n]
@@ -714,13 +756,32 @@ class BatchEngine:
         [n, H]; weight: [A, H] (torch.nn.Linear's layout), bias: [A] or None, all three of one dtype, last dimension contiguous,
         1 <= H <= 512.  bits, mode, actions, seed, step, uniforms, out, bad_actions and the result as for masked_categorical, whose outputs
         on logits holding the same values these are bit for bit; torch.nn.functional.linear sums in another order, so against it the
-        logits agree to rounding.  Not differentiable."""
+        logits agree to rounding.  This call builds no autograd graph: masked_linear_evaluate is mode="evaluate" with one."""
         t = self.torch
         if bits is not None:
             self._packed_rows(bits, "bits")
             n = bits.shape[0]
         else:
             n = self.E
+        A = self.discrete_action_count()
+        H = self._linear_head_inputs(latent, weight, bias, n)
+        o_act, o_lp, o_ent, o_k = self._categorical_outputs(n, mode, actions, uniforms, out, bad_actions)
+        common = (latent.data_ptr(), latent.stride(0) if n > 1 else max(latent.stride(0), H), weight.data_ptr(),
+                  weight.stride(0) if A > 1 else max(weight.stride(0), H), bias.data_ptr() if bias is not None else None, H,
+                  0 if latent.dtype == t.float32 else 1, CATEGORICAL_MODES[mode], o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), o_k.data_ptr(),
+                  uniforms.data_ptr() if uniforms is not None else None, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
+                  bad_actions.data_ptr() if bad_actions is not None else None, self._stream())
+        if bits is None:
+            _check(self.lib, self.lib.mcbs_masked_linear_categorical(self._h, *common), "mcbs_masked_linear_categorical")
+        elif n:
+            _check(self.lib, self.lib.mcbs_masked_linear_categorical_packed(
+                self._h, bits.data_ptr(), bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1]), n, *common),
+                "mcbs_masked_linear_categorical_packed")
+        return MaskedCategorical(o_act, o_lp, o_ent, o_k)
+
+    def _linear_head_inputs(self, latent, weight, bias, n) -> int:
+        """The checks on (latent, weight, bias) the calls of the head from the latent share: -> H."""
+        t = self.torch
         A = self.discrete_action_count()
         for x, what in ((latent, "latent"), (weight, "weight")) + (((bias, "bias"),) if bias is not None else ()):
             if not isinstance(x, t.Tensor) or x.dtype not in (t.float32, t.bfloat16):
@@ -736,19 +797,78 @@ class BatchEngine:
             raise ValueError(f"weight must be [{A}, {H}] (one row per Discrete action) with contiguous rows, got {tuple(weight.shape)}")
         if bias is not None and (tuple(bias.shape) != (A,) or not bias.is_contiguous()):
             raise ValueError(f"bias must be a contiguous [{A}] tensor")
-        o_act, o_lp, o_ent, o_k = self._categorical_outputs(n, mode, actions, uniforms, out, bad_actions)
-        common = (latent.data_ptr(), latent.stride(0) if n > 1 else max(latent.stride(0), H), weight.data_ptr(),
-                  weight.stride(0) if A > 1 else max(weight.stride(0), H), bias.data_ptr() if bias is not None else None, H,
-                  0 if latent.dtype == t.float32 else 1, CATEGORICAL_MODES[mode], o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), o_k.data_ptr(),
-                  uniforms.data_ptr() if uniforms is not None else None, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
-                  bad_actions.data_ptr() if bad_actions is not None else None, self._stream())
-        if bits is None:
-            _check(self.lib, self.lib.mcbs_masked_linear_categorical(self._h, *common), "mcbs_masked_linear_categorical")
-        elif n:
-            _check(self.lib, self.lib.mcbs_masked_linear_categorical_packed(
-                self._h, bits.data_ptr(), bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1]), n, *common),
-                "mcbs_masked_linear_categorical_packed")
-        return MaskedCategorical(o_act, o_lp, o_ent, o_k)
+        return H
+
+    def masked_linear_categorical_grad_workspace(self, n: int, H: int) -> int:
+        """The bytes of device workspace masked_linear_categorical_grad needs for n rows and a layer of width H."""
+        return int(self.lib.mcbs_masked_linear_categorical_grad_workspace(self._h, int(n), int(H)))
+
+    def masked_linear_categorical_grad(self, latent, weight, bias, bits, actions, grad_log_prob=None, grad_entropy=None, out=None,
+                                       want=(True, True, True), workspace=None) -> MaskedLinearGrad:
+        """The backward pass of masked_linear_categorical(bits=..., mode="evaluate") (mcbs_masked_linear_categorical_grad): the gradients of
+        log_prob(actions) and the entropy with respect to latent [n, H], weight [A, H] and bias [A], given their incoming gradients
+        grad_log_prob / grad_entropy (device float32 [n]; None = zeros), without an [n, A] tensor.  Inputs as in the forward (bias may be
+        None: zeros; grad_bias is still the sum it would receive).  -> MaskedLinearGrad(grad_latent, grad_weight, grad_bias), float32
+        whatever the inputs' dtype, every element written (dead rows and actions nobody allows: +0.0), bit-identical from call to call.
+        want: which of the three to compute (None in the result for the others; without grad_weight and grad_bias the call is one launch
+        instead of three).  out: optional (grad_latent, grad_weight, grad_bias) of preallocated device float32 tensors [n, >= H],
+        [A, >= H] with contiguous rows and [A] contiguous, None entries are allocated; an entry given is computed whatever `want` says.
+        workspace: an optional device uint8 tensor of at least masked_linear_categorical_grad_workspace(n, H) bytes; otherwise torch.empty."""
+        t = self.torch
+        if not isinstance(bits, t.Tensor):
+            raise ValueError("bits must be a device int32 tensor [n, >= W] (the gradient exists in the packed form only)")
+        self._packed_rows(bits, "bits")
+        n = bits.shape[0]
+        A = self.discrete_action_count()
+        H = self._linear_head_inputs(latent, weight, bias, n)
+
+        def vec(x, dtype, what):
+            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != (n,) or not x.is_contiguous():
+                raise ValueError(f"{what} must be a contiguous device {dtype} tensor [{n}]")
+            return x
+
+        vec(actions, t.int64, "actions")
+        if grad_log_prob is not None:
+            vec(grad_log_prob, t.float32, "grad_log_prob")
+        if grad_entropy is not None:
+            vec(grad_entropy, t.float32, "grad_entropy")
+        if out is not None and len(out) != 3:
+            raise ValueError("out must be (grad_latent, grad_weight, grad_bias)")
+        if len(want) != 3:
+            raise ValueError("want must be three booleans: (grad_latent, grad_weight, grad_bias)")
+        outs = []
+        for k, (name, shape) in enumerate((("grad_latent", (n, H)), ("grad_weight", (A, H)), ("grad_bias", (A,)))):
+            o = out[k] if out is not None else None
+            if o is None:
+                o = t.empty(shape, dtype=t.float32, device=self.device) if want[k] else None
+            elif (not isinstance(o, t.Tensor) or o.dtype != t.float32 or o.device != self.device or o.dim() != len(shape) or o.shape[0] != shape[0]
+                  or o.stride(-1) != 1 or (len(shape) == 2 and o.shape[1] < H)):
+                raise ValueError(f"out.{name} must be a device float32 tensor {list(shape)} (rows may be longer) with contiguous rows")
+            outs.append(o)
+        if all(o is None for o in outs):
+            raise ValueError("no gradient asked for: want is all False and out gives none")
+        need = self.masked_linear_categorical_grad_workspace(n, H)
+        if workspace is None:
+            workspace = t.empty(need, dtype=t.uint8, device=self.device)
+        elif (not isinstance(workspace, t.Tensor) or workspace.dtype != t.uint8 or workspace.device != self.device or not workspace.is_contiguous()
+              or workspace.numel() < need):
+            raise ValueError(f"workspace must be a contiguous device uint8 tensor of at least {need} bytes")
+        stride = lambda x, rows: x.stride(0) if rows > 1 else max(x.stride(0), x.shape[1])
+        ptr = lambda x: x.data_ptr() if x is not None else None
+        g_lat, g_w, g_b = outs
+        _check(self.lib, self.lib.mcbs_masked_linear_categorical_grad(
+            self._h, bits.data_ptr(), stride(bits, n), n, latent.data_ptr(), stride(latent, n), weight.data_ptr(), stride(weight, A), ptr(bias), H,
+            0 if latent.dtype == t.float32 else 1, actions.data_ptr(), ptr(grad_log_prob), ptr(grad_entropy),
+            ptr(g_lat), stride(g_lat, n) if g_lat is not None else 0, ptr(g_w), stride(g_w, A) if g_w is not None else 0, ptr(g_b),
+            workspace.data_ptr() if need else None, workspace.numel(), self._stream()), "mcbs_masked_linear_categorical_grad")
+        return MaskedLinearGrad(g_lat, g_w, g_b)
+
+    def masked_linear_evaluate(self, latent, weight, bias, bits, actions, bad_actions=None) -> MaskedCategorical:
+        """masked_linear_categorical(bits=..., mode="evaluate") as a node of torch's autograd graph: the same numbers bit for bit, and
+        log_prob and entropy carry a graph into latent, weight and bias, whose backward is one call of masked_linear_categorical_grad for
+        the gradients autograd asks for (cast to the inputs' dtype); actions and n_allowed are not differentiable."""
+        lp, ent, k = _masked_linear_evaluate_function(self.torch).apply(latent, weight, bias, self, bits, actions, bad_actions)
+        return MaskedCategorical(actions, lp, ent, k)
 
     def masked_categorical_grad(self, logits, bits, actions, grad_log_prob=None, grad_entropy=None, out=None):
         """The backward pass of masked_categorical(bits=..., mode="evaluate") in one launch: the gradient with respect to `logits` of

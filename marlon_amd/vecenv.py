@@ -339,8 +339,8 @@ class MarlonVecEnv:
     def sample_masked_from_latent(self, latent, weight, bias, seed: int, step: int, deterministic: bool = False, uniforms=None):
         return self.venv.sample_masked_from_latent(latent, weight, bias, seed, step, deterministic=deterministic, uniforms=uniforms)
 
-    def evaluate_masked_from_latent(self, bits, latent, weight, bias, actions):
-        return self.venv.evaluate_masked_from_latent(bits, latent, weight, bias, actions)
+    def evaluate_masked_from_latent(self, bits, latent, weight, bias, actions, differentiable: bool = False):
+        return self.venv.evaluate_masked_from_latent(bits, latent, weight, bias, actions, differentiable=differentiable)
 
     def get_attr(self, attr_name: str, indices=None) -> List[Any]:
         val = getattr(self.venv, attr_name)

@@ -266,11 +266,16 @@ class AttackerVecEnv(_MultiDiscreteHead):
         return self.engine.masked_linear_categorical(latent, weight, bias, bits=self._live_bits(), mode="argmax" if deterministic else "sample",
                                                      seed=seed, step=step, uniforms=uniforms, out=out)
 
-    def evaluate_masked_from_latent(self, bits, latent, weight, bias, actions, bad_actions=None, out=None):
+    def evaluate_masked_from_latent(self, bits, latent, weight, bias, actions, bad_actions=None, out=None, differentiable: bool = False):
         """evaluate_masked from the latent: log_prob of `actions` [n] and the entropy under stored packed masks bits [n, >= W], latent
         [n, H], weight [A, H], bias [A] or None.  The log_prob of an action sample_masked_from_latent drew under the same mask, latent
-        and layer comes back bit for bit.  Not differentiable: the update's gradient goes through evaluate_masked(differentiable=True)
-        on materialised minibatch logits."""
+        and layer comes back bit for bit.  differentiable=True: the same numbers, and log_prob and entropy carry an autograd graph into
+        latent, weight and bias (engine.masked_linear_evaluate: the backward pass is one call of mcbs_masked_linear_categorical_grad,
+        no [n, A] tensor either way); out= cannot be combined with it."""
+        if differentiable:
+            if out is not None:
+                raise ValueError("evaluate_masked_from_latent(differentiable=True) allocates its outputs: out= is not supported")
+            return self.engine.masked_linear_evaluate(latent, weight, bias, bits, actions, bad_actions=bad_actions)
         return self.engine.masked_linear_categorical(latent, weight, bias, bits=bits, mode="evaluate", actions=actions, bad_actions=bad_actions,
                                                      out=out)
 
