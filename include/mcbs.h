@@ -736,6 +736,51 @@ uint64_t mcbs_feature_layout_width(const mcbs_feature_layout*);
 int  mcbs_encode_features(const mcbs_batch*, const mcbs_feature_layout*, const mcbs_obs_buffers* obs, const uint32_t* bits, size_t bits_row_words,
                           void* out, int32_t dtype, size_t out_row_stride, uint64_t n_rows, uint32_t* out_of_range, void* stream);
 
+/* ---- packed observations: the five int32 fields of a row as bit fields, stored per step, encoded to features later ----
+ * THE PACKED ROW FORMAT (marlon_amd/features.py ObservationPacking is its host mirror).  A row's source values are the V int32 values
+ * mcbs_encode_features indexes: the five int32 fields of mcbs_obs_buffers in the struct's order, flattened.
+ *   valid codes  value s has n_s valid codes 0 .. n_s - 1 (1 <= n_s <= 65 536; features.py takes the class counts of the observation
+ *                spaces, the two counts with C + 1 and N + 1 codes, so a packed row serves either feature layout).
+ *   bit width    value s occupies b_s = bit_length(n_s) bits (the position of n_s's highest set bit, counted from 1), which always
+ *                leaves a spare code: the stored code is v where 0 <= v < n_s (v read as signed int32) and n_s, the OUT-OF-RANGE
+ *                code, for every other v.
+ *   placement    the fields follow each other in source order from bit 0 of word 0 upwards; a field never straddles a 32-bit word (one
+ *                that does not fit in what is left of the current word starts at bit 0 of the next); unused bits are 0.  W_obs = the
+ *                words used (mcbs_obs_packing_words), at most 2 048.
+ *   decoding     returns the code: in-range rows round-trip exactly, any other value comes back as n_s — which every feature layout whose
+ *                class count of that value is <= n_s encodes like the original: an all-zero group, counted as out of range.
+ *   Inside the library a value is one 32-bit descriptor, the table shared by all rows: bits 0-15 n_s - 1, bits 16-31 the field's first
+ *   bit 32 * word + shift; b_s follows from n_s.
+ * mcbs_obs_packing_create: valid_codes[n_values], n_values = the batch's V (MCBS_EINVAL otherwise); a count of 0 or above 65 536, or more
+ *   than 2 048 words: MCBS_ELIMIT.  Word and shift are derived here by the rule above; the descriptors are uploaded once.
+ * mcbs_pack_observation: obs = the five fields as DENSE int32 rows, n_rows of them, all five required; out[i, 0 .. W_obs) is written for
+ *   every i < n_rows (each word whole: the buffer need not be cleared), out_row_words >= W_obs (MCBS_EINVAL otherwise), words from W_obs
+ *   on are never touched.  out_of_range (optional device uint32_t) is INCREASED by the number of values stored as their out-of-range
+ *   code.  One launch.
+ * mcbs_unpack_observation: the inverse, into dense int32 rows: out->field[i] = the codes of packed row index[i] (index NULL: row i), for
+ *   i < n_rows; a field pointer may be NULL (not written; the mask pointers are ignored).  index: optional device int64 [n_rows] into the
+ *   n_source_rows rows of `packed` (without it n_rows <= n_source_rows: MCBS_EINVAL otherwise); an index outside [0, n_source_rows)
+ *   reads nothing, and that row's values all come back as their out-of-range codes.
+ * mcbs_encode_features_packed: mcbs_encode_features with the source values taken from packed rows — the same write-only contract (every
+ *   column below F written, nothing from F on touched, the same store widths by alignment, float32 / bfloat16 / float16, out_of_range
+ *   INCREASED by the elements whose code lies outside the layout's class count).  With index (device int64 [n_rows]) output row i is
+ *   built from row index[i] of BOTH `packed` and `bits`: pass the whole [T * E, ...] storage of a rollout buffer and a minibatch's row
+ *   index, the gather happens inside the launch.  An index outside [0, n_source_rows) never reads memory: that row is written all zero
+ *   and out_of_range grows by the layout's element count.  MCBS_EINVAL where the layout gives a value more classes than the packing
+ *   has valid codes (such a value could not be told from an out-of-range one). */
+typedef struct mcbs_obs_packing mcbs_obs_packing;
+int  mcbs_obs_packing_create(const mcbs_batch*, const uint32_t* valid_codes, size_t n_values, mcbs_obs_packing** out);
+void mcbs_obs_packing_destroy(mcbs_obs_packing*);
+uint64_t mcbs_obs_packing_words(const mcbs_obs_packing*);
+int  mcbs_pack_observation(const mcbs_batch*, const mcbs_obs_packing*, const mcbs_obs_buffers* obs, uint32_t* out, size_t out_row_words,
+                           uint64_t n_rows, uint32_t* out_of_range, void* stream);
+int  mcbs_unpack_observation(const mcbs_batch*, const mcbs_obs_packing*, const uint32_t* packed, size_t row_words, const int64_t* index,
+                             uint64_t n_source_rows, uint64_t n_rows, const mcbs_obs_buffers* out, void* stream);
+int  mcbs_encode_features_packed(const mcbs_batch*, const mcbs_feature_layout*, const mcbs_obs_packing*, const uint32_t* packed,
+                                 size_t packed_row_words, const uint32_t* bits, size_t bits_row_words, const int64_t* index,
+                                 uint64_t n_source_rows, void* out, int32_t dtype, size_t out_row_stride, uint64_t n_rows,
+                                 uint32_t* out_of_range, void* stream);
+
 /* ---- learned defender: marlon/baseline_models/env_wrappers/defend_wrapper.py:197-327,329-412,492-534
  * and marlon/defender_agents/defender.py:31-107, for batches created with MCBS_DEFENDER_EXTERNAL ---- */
 typedef struct mcbs_defender_obs {   /* DefenderEnvWrapper.observe: four MultiBinary fields, int8, network node order */

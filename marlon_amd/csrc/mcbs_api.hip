@@ -28,6 +28,7 @@
 #include "mcbs_multicategorical.hip"
 #include "mcbs_gae.hip"
 #include "mcbs_features.hip"
+#include "mcbs_obs_packing.hip"
 #include "mcbs_wrapper_fused.hip"
 
 using namespace mcbs;
@@ -1745,6 +1746,8 @@ struct mcbs_feature_layout {
     uint2* elems_dev = nullptr;     // per source value: (first one-hot column, classes) of its element; NULL when two elements share a value
     uint32_t fields_used = 0;       // bit k: some descriptor reads observation field k
     uint64_t A = 0;                 // Discrete actions of the batch the layout was made for
+    uint32_t n_elements = 0;        // one-hot elements of a row
+    std::vector<uint32_t> src_classes;      // per source value: the largest class count of an element that reads it (0: none does)
 };
 
 extern "C" int mcbs_feature_layout_create(const mcbs_batch* b, const uint32_t* desc, size_t n_desc, const uint32_t* mask_ranges,
@@ -1759,8 +1762,9 @@ extern "C" int mcbs_feature_layout_create(const mcbs_batch* b, const uint32_t* d
     for (int k = 0; k < 5; ++k) { G.len[k] = (uint32_t)lens[k]; G.off[k] = (uint32_t)V; V += lens[k]; }
     uint32_t used = 0;
     std::vector<uint2> elems((size_t)V, make_uint2(0u, 0u));
+    std::vector<uint32_t> src_classes((size_t)V, 0u);
     bool elems_ok = true;
-    uint32_t cur = 0;
+    uint32_t cur = 0, n_elements = 0;
     for (size_t j = 0; j < n_desc; ++j) {
         const uint32_t d = desc[j], cls = d & (FEAT_MAX_CLASS - 1u), s = (d >> 16) & (FEAT_MAX_SRC - 1u);
         if (s >= V) return fail(MCBS_EINVAL, "feature layout: column %zu reads value %u of %llu per row", j, s, (unsigned long long)V);
@@ -1769,12 +1773,14 @@ extern "C" int mcbs_feature_layout_create(const mcbs_batch* b, const uint32_t* d
             if (elems[s].y) elems_ok = false;
             elems[s] = make_uint2((uint32_t)j, 1u);
             cur = s;
+            ++n_elements;
         } else {
             const uint32_t p = j ? desc[j - 1] : 0u;
             if (!j || ((p >> 16) & (FEAT_MAX_SRC - 1u)) != s || (p & (FEAT_MAX_CLASS - 1u)) + 1u != cls)
                 return fail(MCBS_EINVAL, "feature layout: column %zu does not continue the element before it (classes 0, 1, 2, ... of one value)", j);
             elems[cur].y += 1u;
         }
+        if (cls + 1u > src_classes[s]) src_classes[s] = cls + 1u;
         uint32_t k = 0;
         for (uint32_t q = 1; q < 5u; ++q) k += (uint32_t)(s >= G.off[q]);
         used |= 1u << k;
@@ -1801,6 +1807,7 @@ extern "C" int mcbs_feature_layout_create(const mcbs_batch* b, const uint32_t* d
     mcbs_feature_layout* l = new (std::nothrow) mcbs_feature_layout();
     if (!l) return fail(MCBS_ENOMEM, "out of memory");
     l->device = b->cfg.device; l->G = G; l->fields_used = used; l->A = A;
+    l->n_elements = n_elements; l->src_classes = std::move(src_classes);
     if (n_desc) {
         hipError_t e = hipMalloc(&l->desc_dev, n_desc * sizeof(uint32_t));
         if (e == hipSuccess) e = hipMemcpy(l->desc_dev, desc, n_desc * sizeof(uint32_t), hipMemcpyHostToDevice);
@@ -1870,6 +1877,159 @@ extern "C" int mcbs_encode_features(const mcbs_batch* b, const mcbs_feature_layo
                                 bits_row_words, static_cast<T*>(out), out_row_stride, n_rows, (T)one, out_of_range);
     });
     return launch_ok("encode features");
+}
+
+// ------------------------------------------------------------------ packed observations
+struct mcbs_obs_packing {
+    int32_t device = 0;
+    ObsPackGeom P{};
+    uint32_t* desc_dev = nullptr;
+    std::vector<uint32_t> valid;    // per source value: its valid codes
+};
+
+// ints per row of the five int32 observation fields of a batch
+static void obs_field_lens(const mcbs_batch* b, uint64_t (&lens)[5]) {
+    lens[0] = 7u;
+    lens[1] = (uint64_t)b->cfg.maximum_discoverable_credentials_per_action * 4u;
+    lens[2] = (uint64_t)b->cfg.maximum_total_credentials * 2u;
+    lens[3] = (uint64_t)b->cfg.maximum_node_count * b->topo->H()->n_props;
+    lens[4] = b->cfg.maximum_node_count;
+}
+static bool obs_packing_fits(const mcbs_batch* b, const mcbs_obs_packing* p) {
+    uint64_t lens[5];
+    obs_field_lens(b, lens);
+    bool same = p->device == b->cfg.device;
+    for (int k = 0; k < 5; ++k) same = same && p->P.len[k] == lens[k];
+    return same;
+}
+
+extern "C" int mcbs_obs_packing_create(const mcbs_batch* b, const uint32_t* valid_codes, size_t n_values, mcbs_obs_packing** out) {
+    if (!b || !valid_codes || !out) return fail(MCBS_EINVAL, "null argument");
+    ObsPackGeom P{};
+    uint64_t lens[5], V = 0;
+    obs_field_lens(b, lens);
+    for (int k = 0; k < 5; ++k) { P.len[k] = (uint32_t)lens[k]; P.off[k] = (uint32_t)V; V += lens[k]; }
+    if (n_values != V) return fail(MCBS_EINVAL, "observation packing: %zu valid-code counts for the %llu values of a row", n_values, (unsigned long long)V);
+    std::vector<uint32_t> desc(n_values);
+    uint64_t word = 0;
+    uint32_t shift = 0;                                    // the next free bit is bit `shift` of word `word`
+    for (size_t s = 0; s < n_values; ++s) {
+        const uint32_t n = valid_codes[s];
+        if (n == 0u || n > OBS_PACK_MAX_CODES) return fail(MCBS_ELIMIT, "observation packing: value %zu has %u valid codes (1 to %u)", s, n, OBS_PACK_MAX_CODES);
+        uint32_t width = 0;
+        while ((n >> width) != 0u) ++width;                // bit_length(n)
+        if (shift + width > 32u) { ++word; shift = 0; }    // a field never straddles a word
+        if (word >= OBS_PACK_MAX_WORDS) return fail(MCBS_ELIMIT, "observation packing: a row needs more than %u words", OBS_PACK_MAX_WORDS);
+        desc[s] = (n - 1u) | (((uint32_t)word * 32u + shift) << 16);
+        shift += width;
+    }
+    P.V = (uint32_t)V;
+    P.W = (uint32_t)word + (shift ? 1u : 0u);
+    DeviceGuard guard(b->cfg.device);
+    if (guard.err != hipSuccess) return fail(MCBS_EHIP, "cannot select device %d: %s", b->cfg.device, hipGetErrorString(guard.err));
+    mcbs_obs_packing* p = new (std::nothrow) mcbs_obs_packing();
+    if (!p) return fail(MCBS_ENOMEM, "out of memory");
+    p->device = b->cfg.device; p->P = P; p->valid.assign(valid_codes, valid_codes + n_values);
+    hipError_t e = hipMalloc(&p->desc_dev, n_values * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(p->desc_dev, desc.data(), n_values * sizeof(uint32_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (p->desc_dev) (void)hipFree(p->desc_dev);
+        delete p;
+        return fail(MCBS_EHIP, "observation packing: descriptor upload failed: %s", hipGetErrorString(e));
+    }
+    *out = p;
+    return MCBS_OK;
+}
+
+extern "C" void mcbs_obs_packing_destroy(mcbs_obs_packing* p) {
+    if (!p) return;
+    DeviceGuard guard(p->device);
+    if (p->desc_dev) (void)hipFree(p->desc_dev);
+    delete p;
+}
+
+extern "C" uint64_t mcbs_obs_packing_words(const mcbs_obs_packing* p) { return p ? p->P.W : 0u; }
+
+extern "C" int mcbs_pack_observation(const mcbs_batch* b, const mcbs_obs_packing* p, const mcbs_obs_buffers* obs, uint32_t* out,
+                                     size_t out_row_words, uint64_t n_rows, uint32_t* out_of_range, void* stream) {
+    if (!b || !p || !obs || !out) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    if (!obs_packing_fits(b, p)) return fail(MCBS_EINVAL, "mcbs_pack_observation: the packing was created for a batch of another device or geometry");
+    FeatSrc src{{obs->scalars, obs->leaked_credentials, obs->credential_cache_matrix, obs->discovered_nodes_properties, obs->nodes_privilegelevel}};
+    for (uint32_t k = 0; k < 5u; ++k)
+        if (!src.f[k]) return fail(MCBS_EINVAL, "mcbs_pack_observation: all five int32 fields are packed, field %u is NULL", k);
+    if (out_row_words < p->P.W) return fail(MCBS_EINVAL, "out_row_words %zu is shorter than the %u words of a packed row", out_row_words, p->P.W);
+    if (n_rows == 0) return MCBS_OK;
+    hipLaunchKernelGGL(pack_observation_kernel, rows_grid(n_rows, 2048u), dim3(256), 4u * p->P.W * sizeof(uint32_t), (hipStream_t)stream, p->P, src,
+                       p->desc_dev, out, out_row_words, n_rows, out_of_range);
+    return launch_ok("pack observation");
+}
+
+extern "C" int mcbs_unpack_observation(const mcbs_batch* b, const mcbs_obs_packing* p, const uint32_t* packed, size_t row_words,
+                                       const int64_t* index, uint64_t n_source_rows, uint64_t n_rows, const mcbs_obs_buffers* out, void* stream) {
+    if (!b || !p || !packed || !out) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    if (!obs_packing_fits(b, p)) return fail(MCBS_EINVAL, "mcbs_unpack_observation: the packing was created for a batch of another device or geometry");
+    if (row_words < p->P.W) return fail(MCBS_EINVAL, "row_words %zu is shorter than the %u words of a packed row", row_words, p->P.W);
+    if (!index && n_rows > n_source_rows) return fail(MCBS_EINVAL, "mcbs_unpack_observation: %llu rows asked of %llu stored ones and no index",
+                                                      (unsigned long long)n_rows, (unsigned long long)n_source_rows);
+    if (n_rows == 0) return MCBS_OK;
+    ObsDst dst{{out->scalars, out->leaked_credentials, out->credential_cache_matrix, out->discovered_nodes_properties, out->nodes_privilegelevel}};
+    hipLaunchKernelGGL(unpack_observation_kernel, rows_grid(n_rows, 2048u), dim3(256), 0, (hipStream_t)stream, p->P, p->desc_dev, packed, row_words,
+                       index, n_source_rows, dst, n_rows);
+    return launch_ok("unpack observation");
+}
+
+extern "C" int mcbs_encode_features_packed(const mcbs_batch* b, const mcbs_feature_layout* l, const mcbs_obs_packing* p, const uint32_t* packed,
+                                           size_t packed_row_words, const uint32_t* bits, size_t bits_row_words, const int64_t* index,
+                                           uint64_t n_source_rows, void* out, int32_t dtype, size_t out_row_stride, uint64_t n_rows,
+                                           uint32_t* out_of_range, void* stream) {
+    if (!b || !l || !p || !packed || !out) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    if (dtype != MCBS_FEATURES_F32 && dtype != MCBS_FEATURES_BF16 && dtype != MCBS_FEATURES_F16)
+        return fail(MCBS_EINVAL, "features dtype must be MCBS_FEATURES_F32, MCBS_FEATURES_BF16 or MCBS_FEATURES_F16");
+    const FeatGeom& G = l->G;
+    bool same = obs_packing_fits(b, p) && l->device == b->cfg.device && l->A == mcbs_discrete_action_count(b);
+    for (int k = 0; k < 5; ++k) same = same && G.len[k] == p->P.len[k];
+    if (!same) return fail(MCBS_EINVAL, "mcbs_encode_features_packed: the layout or the packing was created for a batch of another device or geometry");
+    for (size_t s = 0; s < p->valid.size(); ++s)
+        if (l->src_classes[s] > p->valid[s])
+            return fail(MCBS_EINVAL, "mcbs_encode_features_packed: the layout gives value %zu %u classes, the packing %u valid codes", s,
+                        l->src_classes[s], p->valid[s]);
+    if (out_row_stride < G.F) return fail(MCBS_EINVAL, "out_row_stride %zu is shorter than the %u feature columns", out_row_stride, G.F);
+    if (packed_row_words < p->P.W) return fail(MCBS_EINVAL, "packed_row_words %zu is shorter than the %u words of a packed row", packed_row_words, p->P.W);
+    if (G.W) {
+        if (!bits) return fail(MCBS_EINVAL, "mcbs_encode_features_packed: the layout has mask columns and bits is NULL");
+        if (bits_row_words < G.W) return fail(MCBS_EINVAL, "bits_row_words %zu is shorter than the %u words the layout's mask columns read", bits_row_words, G.W);
+    }
+    if (!index && n_rows > n_source_rows) return fail(MCBS_EINVAL, "mcbs_encode_features_packed: %llu rows asked of %llu stored ones and no index",
+                                                      (unsigned long long)n_rows, (unsigned long long)n_source_rows);
+    if (n_rows == 0) return MCBS_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const dim3 grid = rows_grid(n_rows, 2048u), block(256);        // (as mcbs_encode_features)
+    // the per-element kernel when its LDS fits (as mcbs_encode_features chooses), else column by column: on four wavefronts' decoded rows
+    // in LDS when those fit, else decoding where a column asks
+    const size_t item = dtype == MCBS_FEATURES_F32 ? 4u : 2u, per = 16u / item;
+    const size_t lds_rows = (((size_t)G.V + 1u) / 2u + 4u * (((size_t)G.n_desc + per - 1u) / per + ((size_t)G.W + 3u) / 4u)) * 16u;
+    const bool rows_kernel = l->elems_dev && lds_rows <= 48u * 1024u;
+    const size_t lds = 4u * (size_t)G.V * sizeof(uint32_t);
+    const bool staged = lds <= 48u * 1024u;
+    const uint32_t one = dtype == MCBS_FEATURES_F32 ? 0x3F800000u : dtype == MCBS_FEATURES_BF16 ? 0x3F80u : 0x3C00u;      // 1.0 as the dtype's pattern
+    rows_dispatch<1u, 2u>(item, out, out_row_stride, [&](auto es, auto gw, auto vec) {
+        using T = std::conditional_t<decltype(es)::value == 4u, uint32_t, uint16_t>;
+        constexpr uint32_t GW = decltype(gw)::value;
+        constexpr bool VEC = decltype(vec)::value;
+        if (rows_kernel) hipLaunchKernelGGL((encode_features_packed_rows_kernel<T, GW, VEC>), grid, block, lds_rows, st, G, l->elems_dev, l->n_elements,
+                                            p->desc_dev, packed, packed_row_words, bits, bits_row_words, index, n_source_rows, static_cast<T*>(out),
+                                            out_row_stride, n_rows, (T)one, out_of_range);
+        else if (staged) hipLaunchKernelGGL((encode_features_packed_kernel<T, GW, VEC, true>), grid, block, lds, st, G, l->desc_dev, l->n_elements, p->desc_dev,
+                                       packed, packed_row_words, bits, bits_row_words, index, n_source_rows, static_cast<T*>(out), out_row_stride,
+                                       n_rows, (T)one, out_of_range);
+        else hipLaunchKernelGGL((encode_features_packed_kernel<T, GW, VEC, false>), grid, block, 0, st, G, l->desc_dev, l->n_elements, p->desc_dev,
+                                packed, packed_row_words, bits, bits_row_words, index, n_source_rows, static_cast<T*>(out), out_row_stride,
+                                n_rows, (T)one, out_of_range);
+    });
+    return launch_ok("encode features from packed observations");
 }
 
 // ------------------------------------------------------------------ learned defender

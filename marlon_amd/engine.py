@@ -34,6 +34,8 @@ EXPORTS = [
     "mcbs_masked_linear_categorical_grad_workspace", "mcbs_masked_linear_categorical_grad",
     "mcbs_multicategorical", "mcbs_multicategorical_grad",
     "mcbs_gae",
+    "mcbs_obs_packing_create", "mcbs_obs_packing_destroy", "mcbs_obs_packing_words", "mcbs_pack_observation", "mcbs_unpack_observation",
+    "mcbs_encode_features_packed",
 ]
 
 _lib = None
@@ -108,7 +110,18 @@ def load_library(path: Optional[str] = None):
     lib.mcbs_feature_layout_width.argtypes = [C.c_void_p]
     lib.mcbs_encode_features.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ObsBuffers), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_size_t,
                                          C.c_uint64, C.c_void_p, C.c_void_p]
-    _cat = [C.c_void_p, C.c_int32, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
+    lib.mcbs_obs_packing_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
+    lib.mcbs_obs_packing_destroy.argtypes = [C.c_void_p]
+    lib.mcbs_obs_packing_destroy.restype = None
+    lib.mcbs_obs_packing_words.restype = C.c_uint64
+    lib.mcbs_obs_packing_words.argtypes = [C.c_void_p]
+    lib.mcbs_pack_observation.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ObsBuffers), C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p]
+    lib.mcbs_unpack_observation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64,
+                                            C.POINTER(ObsBuffers), C.c_void_p]
+    # layout, packing, packed, packed_row_words, bits, bits_row_words, index, n_source_rows, out, dtype, out_row_stride, n_rows, out_of_range, stream
+    lib.mcbs_encode_features_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p]
+    _cat =[C.c_void_p, C.c_int32, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
             C.c_void_p, C.c_void_p]           # logits, dtype, row_stride, mode, actions, log_prob, entropy, n_allowed, uniforms, seed, step, bad_actions, stream
     lib.mcbs_masked_categorical.argtypes = [C.c_void_p] + _cat
     lib.mcbs_masked_categorical_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64] + _cat
@@ -167,6 +180,25 @@ class FeatureLayoutHandle:
     def close(self) -> None:
         if getattr(self, "ptr", None):
             self.lib.mcbs_feature_layout_destroy(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ObservationPackingHandle:
+    """A `features.ObservationPacking` handed to the library (mcbs_obs_packing_create): descriptors uploaded once, freed with the object."""
+
+    def __init__(self, lib, ptr, packing):
+        self.lib, self.ptr, self.packing = lib, ptr, packing
+        self.words = int(lib.mcbs_obs_packing_words(ptr))
+
+    def close(self) -> None:
+        if getattr(self, "ptr", None):
+            self.lib.mcbs_obs_packing_destroy(self.ptr)
             self.ptr = None
 
     def __del__(self):
@@ -1091,6 +1123,27 @@ class BatchEngine:
             raise McbsError(f"feature layout: the library counts {handle.width} columns, the layout {layout.width}")
         return handle
 
+    def _feature_out(self, handle: FeatureLayoutHandle, n: int, out, dtype, out_of_range):
+        """The out= / dtype= / out_of_range= handling the two feature encoders share -> (out [n, >= F], MCBS_FEATURES_* code)."""
+        t = self.torch
+        F = handle.width
+        if out is None:
+            dtype = dtype or t.float32
+            if dtype not in self._feature_dtypes:
+                raise ValueError("features dtype must be float32, bfloat16 or float16")
+            out = t.empty((n, handle.layout.padded_width(self._feature_dtypes[dtype][1])), dtype=dtype, device=self.device)
+        if out.dtype not in self._feature_dtypes:
+            raise ValueError("out must be float32, bfloat16 or float16")
+        code = self._feature_dtypes[out.dtype][0]
+        if dtype is not None and out.dtype != dtype:
+            raise ValueError(f"out is {out.dtype}, dtype asks for {dtype}")
+        # the C side sees only the row stride: a view narrower than F would have its rows written past their end
+        if out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1 or out.device != self.device or out.shape[1] < F:
+            raise ValueError(f"out must be a device tensor [{n}, >= {F}] with contiguous rows")
+        if out_of_range is not None and (out_of_range.dtype != t.int32 or out_of_range.numel() != 1 or out_of_range.device != self.device):
+            raise ValueError("out_of_range must be a device int32 tensor of one element")
+        return out, code
+
     def encode_features(self, handle: FeatureLayoutHandle, obs: dict, bits=None, out=None, dtype=None, out_of_range=None):
         """Feature rows [n, F] of n observation rows, one launch (mcbs_encode_features).  obs: the int32 fields `scalars`,
         `leaked_credentials`, `credential_cache_matrix`, `discovered_nodes_properties`, `nodes_privilegelevel` as contiguous device
@@ -1122,27 +1175,121 @@ class BatchEngine:
             self._packed_rows(bits, "bits")
             if bits.shape[0] != n:
                 raise ValueError(f"bits has {bits.shape[0]} rows, the observation {n}")
-        if out is None:
-            dtype = dtype or t.float32
-            if dtype not in self._feature_dtypes:
-                raise ValueError("features dtype must be float32, bfloat16 or float16")
-            out = t.empty((n, handle.layout.padded_width(self._feature_dtypes[dtype][1])), dtype=dtype, device=self.device)
-        if out.dtype not in self._feature_dtypes:
-            raise ValueError("out must be float32, bfloat16 or float16")
-        code = self._feature_dtypes[out.dtype][0]
-        if dtype is not None and out.dtype != dtype:
-            raise ValueError(f"out is {out.dtype}, dtype asks for {dtype}")
-        # the C side sees only the row stride: a view narrower than F would have its rows written past their end
-        if out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1 or out.device != self.device or out.shape[1] < F:
-            raise ValueError(f"out must be a device tensor [{n}, >= {F}] with contiguous rows")
-        if out_of_range is not None and (out_of_range.dtype != t.int32 or out_of_range.numel() != 1 or out_of_range.device != self.device):
-            raise ValueError("out_of_range must be a device int32 tensor of one element")
+        out, code = self._feature_out(handle, n, out, dtype, out_of_range)
         if n:
             stride = out.stride(0) if n > 1 else max(out.stride(0), out.shape[1])
             _check(self.lib, self.lib.mcbs_encode_features(self._h, handle.ptr, C.byref(ObsBuffers(**ptrs)), bits.data_ptr() if handle.has_masks else None,
                                                            (bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1])) if handle.has_masks else 0, out.data_ptr(), code, stride, n,
                                                            out_of_range.data_ptr() if out_of_range is not None else None, self._stream()),
                    "mcbs_encode_features")
+        return out[:, :F]
+
+    # -- packed observations (include/mcbs.h): int32 tensors [rows, >= W_obs], every value of the five fields a bit field --
+    def observation_packing(self, packing) -> ObservationPackingHandle:
+        """Hand a `features.ObservationPacking` (built for this engine's topology and bounds) to the library; the handle is what
+        pack_observation / unpack_observation / encode_features_packed take.  The library derives word and shift itself."""
+        v = np.ascontiguousarray(packing.valid_codes, dtype=np.uint32)
+        h = C.c_void_p()
+        _check(self.lib, self.lib.mcbs_obs_packing_create(self._h, v.ctypes.data, v.size, C.byref(h)), "mcbs_obs_packing_create")
+        handle = ObservationPackingHandle(self.lib, h, packing)
+        if handle.words != packing.words:
+            raise McbsError(f"observation packing: the library counts {handle.words} words per row, the host mirror {packing.words}")
+        return handle
+
+    def _packed_obs_rows(self, x, handle: ObservationPackingHandle, what: str):
+        t = self.torch
+        if x.dtype != t.int32 or x.dim() != 2 or x.stride(1) != 1 or x.device != self.device or x.shape[1] < handle.words:
+            raise ValueError(f"{what} must be a device int32 tensor [n, >= {handle.words}] with contiguous rows")
+        return x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1])
+
+    def _row_index(self, index, n_source: int, what: str = "index"):
+        """-> (pointer or None, rows asked): index int64 [n] on the device, or None for rows 0 .. n_source - 1"""
+        t = self.torch
+        if index is None:
+            return None, n_source
+        if index.dtype != t.int64 or index.dim() != 1 or index.device != self.device or not index.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous device int64 tensor [n]")
+        return index.data_ptr(), index.shape[0]
+
+    def pack_observation(self, handle: ObservationPackingHandle, obs: dict, out=None, out_of_range=None):
+        """The five int32 fields of n observation rows (as encode_features takes them, all five required) as packed rows, one launch
+        (mcbs_pack_observation).  out: device int32 [n, >= W_obs] with contiguous rows, e.g. `buf.observations["packed"][buf.pos]` of a
+        rollout buffer (words from W_obs on are not touched, every word below is written), or None for a new [n, W_obs] tensor.
+        out_of_range: optional device int32 [1]; the number of values stored as their out-of-range code is ADDED to it."""
+        t = self.torch
+        ptrs, n = {}, None
+        for k, per_row in self._feature_rows.items():
+            v = obs.get(k)
+            if v is None:
+                raise ValueError(f"obs lacks {k!r}: all five int32 fields are packed")
+            if v.dtype != t.int32 or v.device != self.device or not v.is_contiguous() or v.dim() < 1 or v.numel() != v.shape[0] * per_row:
+                raise ValueError(f"obs[{k!r}] must be a contiguous device int32 tensor of {per_row} values per row")
+            if n is None:
+                n = v.shape[0]
+            elif v.shape[0] != n:
+                raise ValueError(f"obs[{k!r}] has {v.shape[0]} rows, other fields {n}")
+            ptrs[k] = v.data_ptr()
+        if out is None:
+            out = t.empty((n, handle.words), dtype=t.int32, device=self.device)
+        stride = self._packed_obs_rows(out, handle, "out")
+        if out.shape[0] != n:
+            raise ValueError(f"out must have {n} rows, got {out.shape[0]}")
+        if out_of_range is not None and (out_of_range.dtype != t.int32 or out_of_range.numel() != 1 or out_of_range.device != self.device):
+            raise ValueError("out_of_range must be a device int32 tensor of one element")
+        if n:
+            _check(self.lib, self.lib.mcbs_pack_observation(self._h, handle.ptr, C.byref(ObsBuffers(**ptrs)), out.data_ptr(), stride, n,
+                                                            out_of_range.data_ptr() if out_of_range is not None else None, self._stream()),
+                   "mcbs_pack_observation")
+        return out
+
+    def unpack_observation(self, handle: ObservationPackingHandle, packed, index=None, out=None):
+        """Packed rows [m, >= W_obs] -> dict of the five int32 fields in their own shapes (mcbs_unpack_observation).  index: optional
+        device int64 [n]: output row i is stored row index[i] (an index outside [0, m) reads nothing: that row's values are their
+        out-of-range codes); without it n = m.  out: dict of contiguous device int32 tensors with n rows for the fields wanted (None:
+        all five, newly allocated)."""
+        t = self.torch
+        stride = self._packed_obs_rows(packed, handle, "packed")
+        idx, n = self._row_index(index, packed.shape[0])
+        if out is None:
+            out = {k: t.empty((n,) + self._shapes[k][0], dtype=t.int32, device=self.device) for k in FEATURE_FIELDS}
+        ptrs = {}
+        for k, v in out.items():
+            per_row = self._feature_rows.get(k)
+            if per_row is None:
+                raise ValueError(f"out[{k!r}] is not one of the observation's int32 fields")
+            if v.dtype != t.int32 or v.device != self.device or not v.is_contiguous() or v.dim() < 1 or v.shape[0] != n or v.numel() != n * per_row:
+                raise ValueError(f"out[{k!r}] must be a contiguous device int32 tensor of {n} rows of {per_row} values")
+            ptrs[k] = v.data_ptr()
+        if n and ptrs:
+            _check(self.lib, self.lib.mcbs_unpack_observation(self._h, handle.ptr, packed.data_ptr(), stride, idx, packed.shape[0], n,
+                                                              C.byref(ObsBuffers(**ptrs)), self._stream()), "mcbs_unpack_observation")
+        return out
+
+    def encode_features_packed(self, feature_handle: FeatureLayoutHandle, packing_handle: ObservationPackingHandle, packed, bits=None, index=None,
+                               out=None, dtype=None, out_of_range=None):
+        """encode_features from packed rows [m, >= W_obs] (mcbs_encode_features_packed), one launch, the same outputs and the same out=
+        / dtype= / out_of_range= rules.  bits: packed masks int32 [m, >= W], row for row with `packed`, needed when the layout has mask
+        columns.  index: optional device int64 [n]: output row i is built from row index[i] of BOTH packed and bits — pass a rollout
+        buffer's whole [T * E, ...] storage and a minibatch's row index, nothing is gathered first.  An index outside [0, m) reads
+        nothing: that row is all zero and out_of_range grows by the layout's element count."""
+        F = feature_handle.width
+        pstride = self._packed_obs_rows(packed, packing_handle, "packed")
+        m = packed.shape[0]
+        idx, n = self._row_index(index, m)
+        if feature_handle.has_masks:
+            if bits is None:
+                raise ValueError("the layout has mask columns: bits (packed action masks [m, >= W]) is required")
+            self._packed_rows(bits, "bits")
+            if bits.shape[0] != m:
+                raise ValueError(f"bits has {bits.shape[0]} rows, packed {m}")
+        out, code = self._feature_out(feature_handle, n, out, dtype, out_of_range)
+        if n:
+            stride = out.stride(0) if n > 1 else max(out.stride(0), out.shape[1])
+            masks = feature_handle.has_masks
+            _check(self.lib, self.lib.mcbs_encode_features_packed(
+                self._h, feature_handle.ptr, packing_handle.ptr, packed.data_ptr(), pstride, bits.data_ptr() if masks else None,
+                (bits.stride(0) if m > 1 else max(bits.stride(0), bits.shape[1])) if masks else 0, idx, m, out.data_ptr(), code, stride, n,
+                out_of_range.data_ptr() if out_of_range is not None else None, self._stream()), "mcbs_encode_features_packed")
         return out[:, :F]
 
     # -- learned defender (batches created with defender=("external",)) --

@@ -5,6 +5,8 @@ Every key of the observation becomes a run of columns — a `Discrete(n)` a one-
 one-hot of its own width, a `MultiBinary` its values as 0.0 / 1.0 — and the runs are concatenated in key order into one `[n, F]` row.
 `FeatureLayout` describes that row for a topology and its observation bounds; `mcbs_encode_features` (marlon_amd/csrc/mcbs_features.hip)
 writes it on the device in one launch from the descriptors this class builds, `encode_host` is the same encoding in NumPy.
+`ObservationPacking` is the host mirror of the packed row format (include/mcbs.h "packed observations"): the same source values as bit
+fields, what a rollout buffer stores per step and `mcbs_encode_features_packed` reads at update time.
 
 Pure Python / NumPy: importable without a GPU and without the native library.
 """
@@ -162,3 +164,61 @@ class FeatureLayout:
                 c0, w = self.segments[k]
                 out[:, c0:c0 + w] = (np.asarray(obs[k]).reshape(n, w) != 0)
         return (out, bad) if return_out_of_range else out
+
+
+class ObservationPacking:
+    """The packed row format of the attacker observation of `topo` under `spec`'s bounds (include/mcbs.h "packed observations"): the
+    host mirror of what `mcbs_pack_observation` writes and `mcbs_unpack_observation` / `mcbs_encode_features_packed` read.
+
+    A row's source values are the V int32 values of the five fields (`OBS_FIELDS`), flattened in that order.  Value s has
+    `valid_codes[s]` = n_s valid codes 0 .. n_s - 1: the class count `FeatureLayout(topo, spec)` gives it with reference_counts=False
+    (the two counts keep C + 1 and N + 1 codes, so a packed row serves either feature layout).  It occupies `bits[s]` =
+    n_s.bit_length() bits — always one spare code at least — at bit `shift[s]` of word `word[s]`: fields follow each other in source
+    order from bit 0 of word 0, and one that does not fit in what is left of a word starts the next (no field straddles a word; unused
+    bits are 0).  The stored code is v where 0 <= v < n_s, and n_s — the out-of-range code — for anything else; unpacking returns
+    the code.  `words`: the uint32 words of a row.
+
+    valid_codes, bits, word, shift: int arrays [V].  Pure NumPy."""
+
+    def __init__(self, topo: FlatTopology, spec: EnvSpec):
+        lay = FeatureLayout(topo, spec)
+        self.field_len, self.field_off, self.values_per_row = lay.field_len, lay.field_off, lay.values_per_row
+        self.field_shape = [(7,), (lay.K, 4), (lay.C, 2), (lay.N, lay.NP), (lay.N,)]
+        codes = np.zeros(self.values_per_row, dtype=np.int64)
+        for _, src, n in lay.groups:
+            codes[src] = n
+        if (codes < 1).any() or (codes > MAX_CLASSES).any():
+            raise ValueError(f"a source value has no element or more than {MAX_CLASSES} classes")
+        self.valid_codes = codes
+        self.bits = np.array([int(n).bit_length() for n in codes], dtype=np.int64)
+        self.word = np.zeros_like(codes)
+        self.shift = np.zeros_like(codes)
+        w = s = 0
+        for i, b in enumerate(self.bits):
+            if s + b > 32:
+                w, s = w + 1, 0
+            self.word[i], self.shift[i] = w, s
+            s += int(b)
+        self.words = w + (1 if s else 0)
+
+    def _fields(self, vals: np.ndarray) -> dict:
+        n = vals.shape[0]
+        return {k: vals[:, o:o + ln].reshape((n,) + shp).astype(np.int32)
+                for k, o, ln, shp in zip(OBS_FIELDS, self.field_off, self.field_len, self.field_shape)}
+
+    def pack_host(self, obs: dict) -> np.ndarray:
+        """uint32 [n, words] of a dict of the five int32 fields with a leading row axis (`scalars` [n, 7], ... in any trailing shape)."""
+        vals = np.concatenate([np.asarray(obs[k]).reshape(len(obs["scalars"]), ln).astype(np.int64)
+                               for k, ln in zip(OBS_FIELDS, self.field_len)], axis=1)
+        code = np.where((vals >= 0) & (vals < self.valid_codes), vals, self.valid_codes).astype(np.uint64)
+        out = np.zeros((vals.shape[0], self.words), dtype=np.uint64)
+        for i in range(self.values_per_row):                     # (fields of a word do not overlap: adding is OR-ing)
+            out[:, self.word[i]] += code[:, i] << np.uint64(self.shift[i])
+        return out.astype(np.uint32)
+
+    def unpack_host(self, packed) -> dict:
+        """The five int32 fields (codes) of uint32 / int32 rows [n, >= words]."""
+        p = np.asarray(packed)
+        p = (p.view(np.uint32) if p.dtype == np.int32 else p.astype(np.uint32)).astype(np.uint64)
+        vals = (p[:, self.word] >> self.shift.astype(np.uint64)) & ((np.uint64(1) << self.bits.astype(np.uint64)) - np.uint64(1))
+        return self._fields(vals.astype(np.int64))

@@ -153,6 +153,7 @@ class AttackerVecEnv(_MultiDiscreteHead):
         self._executed = t.zeros(n_envs, dtype=t.bool, device=dev)
         self._graph_out = self._terminated_out = None
         self._feature_handles, self._feature_bits = {}, None       # features(): layout handles per option set, the packed-mask scratch
+        self._obs_packing = None                                   # observation_packed(): the packing handle, made on first use
         self.reset()
 
     # -- observation plumbing --
@@ -341,6 +342,38 @@ class AttackerVecEnv(_MultiDiscreteHead):
         return self.engine.encode_features(self._feature_handle(bits is not None, reference_counts), fields, bits=bits, out=out, dtype=dtype,
                                            out_of_range=out_of_range)
 
+    # -- packed observations (features.ObservationPacking, mcbs_pack_observation): store per step, encode features later --
+    def _packing_handle(self):
+        if self._obs_packing is None:
+            from .features import ObservationPacking
+            self._obs_packing = self.engine.observation_packing(ObservationPacking(self.topo, self.spec))
+        return self._obs_packing
+
+    def observation_packing(self):
+        """The `features.ObservationPacking` behind observation_packed(): `words` is the row width W_obs, `pack_host` / `unpack_host`
+        the same format on the host."""
+        return self._packing_handle().packing
+
+    def observation_packed(self, out=None, out_of_range=None):
+        """The observation this env last returned as bit fields: device int32 [n_envs, W_obs], one launch — 72 B instead of 924 B per
+        Chain-10 row.  out=: write straight into a preallocated [n_envs, >= W_obs] buffer, e.g.
+        `buf.observations["packed"][buf.pos]` of rollout_buffer(pack_observations=True).  A value outside its valid codes is stored as
+        its out-of-range code (and counted into out_of_range), which encodes to the same all-zero group."""
+        return self.engine.pack_observation(self._packing_handle(), self.observation_fields, out=out, out_of_range=out_of_range)
+
+    def unpack_observation(self, packed, index=None):
+        """Packed rows [m, >= W_obs] -> the five int32 fields (`observation_fields`' keys and shapes) of those rows, or of rows
+        index[i] with index (device int64 [n])."""
+        return self.engine.unpack_observation(self._packing_handle(), packed, index=index)
+
+    def encode_features_packed(self, packed, bits=None, index=None, out=None, dtype=None, reference_counts: bool = False, out_of_range=None):
+        """encode_features() straight from stored packed rows [m, >= W_obs] (bits: their packed masks [m, >= W], adds the mask
+        columns).  With index (device int64 [n]) the rows are read where they are stored, no int32 field and no mask row is gathered:
+            x = venv.encode_features_packed(buf.observations["packed"].view(T * E, -1), bits=buf.mask_bits.view(T * E, -1),
+                                            index=batch.index, dtype=torch.bfloat16)"""
+        return self.engine.encode_features_packed(self._feature_handle(bits is not None, reference_counts), self._packing_handle(), packed,
+                                                  bits=bits, index=index, out=out, dtype=dtype, out_of_range=out_of_range)
+
     # -- the rollout buffer (marlon_amd/rollout.py, mcbs_gae) --
     @property
     def observation_fields(self) -> Dict[str, object]:
@@ -348,14 +381,20 @@ class AttackerVecEnv(_MultiDiscreteHead):
         their own shapes): what encode_features() accepts and what rollout_buffer() stores; the wrapper's persistent tensors, not copies."""
         return {k: self._obs[k] for k in FLAT_FIELDS[:5]}
 
-    def rollout_buffer(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, store_observations: bool = True):
+    def rollout_buffer(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, store_observations: bool = True,
+                       pack_observations: bool = False):
         """A `rollout.DeviceRolloutBuffer` of n_steps x n_envs transitions for this env: it stores the int32 observation fields
         encode_features() accepts (not the mask fields — with discrete=True the packed masks of action_masks_packed() are stored
         instead, `mask_bits`), actions of this wrapper's shape, and computes advantages and returns with one launch.  Its add() takes
         `observation_fields` as obs.
-        store_observations=False: no observation storage (a trainer that keeps feature rows of its own)."""
+        store_observations=False: no observation storage (a trainer that keeps feature rows of its own).
+        pack_observations=True: the observation storage is ONE key, `observations["packed"]` int32 [T, E, W_obs], instead of the five
+        fields: fill row `pos` with observation_packed(out=buf.observations["packed"][buf.pos]) and pass obs=None to add(); at update
+        time encode_features_packed(..., index=batch.index) reads the storage itself."""
         from .rollout import DeviceRolloutBuffer
         obs = self.observation_fields if store_observations else None
+        if store_observations and pack_observations:
+            obs = {"packed": self.torch.zeros((self.num_envs, self._packing_handle().words), dtype=self.torch.int32, device=self.engine.device)}
         return DeviceRolloutBuffer(self.engine, n_steps, self.num_envs, obs=obs, action_shape=self._action_shape[1:],
                                    mask_words=self.engine.packed_mask_words()[1] if self.discrete else None, gamma=gamma, gae_lambda=gae_lambda)
 
