@@ -937,6 +937,25 @@ int  mcbs_batch_variant(const mcbs_batch*, mcbs_batch_variant_info* out);
  * is fixed at 32 bytes.) */
 int32_t mcbs_step_is_lean(const mcbs_batch*, int32_t with_info);
 
+/* Topology traits: what the vulnerability descriptors and the node count of a topology make possible, found on the host when the
+ * topology's tables are built and fixed for the life of every batch on it.  A bit that is CLEAR is a rule of the reference no step of
+ * this topology can trigger; the narrow lean step kernel (marlon_amd/csrc/mcbs_step.hip) compiles such rules out. */
+#define MCBS_TOPO_ESCALATION      1u   /* some vulnerability's outcome is a privilege escalation */
+#define MCBS_TOPO_LATERAL_EXPLOIT 2u   /* some vulnerability's outcome is a lateral move (connecting with a credential is not meant) */
+#define MCBS_TOPO_PRECONDITION    4u   /* some vulnerability's precondition is false for some tag set of its node (precond_tt != 0xFFFF) */
+#define MCBS_TOPO_PROBE           8u   /* some vulnerability's outcome is ProbeSucceeded */
+#define MCBS_TOPO_MULTI_LEAK      16u  /* some vulnerability leaks more than one node id / credential */
+#define MCBS_TOPO_WIDE_ROWS       32u  /* more than 12 nodes: a packed env's node rows need a fourth 16-byte vector (reported; no kernel assumes it away) */
+#define MCBS_TOPO_ANY             63u
+/* The traits of a topology blob (the one mcbs_topology_create takes), computed on the host alone: no device is touched.  MCBS_OK, or
+ * the error mcbs_topology_create would report for the blob. */
+int  mcbs_topology_traits(const void* blob, size_t nbytes, uint32_t* traits);
+/* 1: an mcbs_step of this batch with (with_info != 0) or without info buffers takes the NARROW lean kernel — the lean launch above
+ * instantiated for topologies without privilege escalation, lateral-move exploits, preconditions and multi-entry leaks; 0: any other
+ * kernel, or a null batch.  Decided at batch creation: the batch is lean and its topology has none of the traits
+ * the instantiation assumes away.  *traits (may be null) receives the topology's MCBS_TOPO_* bits. */
+int32_t mcbs_step_topo_traits(const mcbs_batch*, int32_t with_info, uint32_t* traits);
+
 /* Kernel timing hook for bench.py: HIP events recorded on `stream` around each mcbs_step launch
  * while enabled; mcbs_timing_read synchronises and returns the summed kernel milliseconds. */
 int  mcbs_timing_enable(mcbs_batch*, int32_t on);

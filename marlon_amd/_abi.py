@@ -10,6 +10,9 @@ import numpy as np
 ABI_VERSION = 1
 DEFENDER_NONE, DEFENDER_SCAN_AND_REIMAGE, DEFENDER_EXTERNAL, DEFENDER_RANDOM_EVENTS = 0, 1, 2, 3
 RNG_PHILOX, RNG_TAPE = 0, 1
+# MCBS_TOPO_* (include/mcbs.h): what a topology's descriptors and node count make possible (mcbs_topology_traits, mcbs_step_topo_traits)
+TOPO_ESCALATION, TOPO_LATERAL_EXPLOIT, TOPO_PRECONDITION, TOPO_PROBE, TOPO_MULTI_LEAK, TOPO_WIDE_ROWS = 1, 2, 4, 8, 16, 32
+TOPO_ANY = 63
 
 
 class BatchCfg(C.Structure):

@@ -72,6 +72,7 @@ static FastDiv fast_div_host(uint32_t d);
 struct HotLayout {
     uint32_t node, desc, payload, auth, auth_words, triple, avail, fwlist, bytes;
     uint32_t max_leak;   // the largest payload_cnt of any descriptor: no action of this topology leaks more entries (StepCfg::max_leak)
+    uint32_t traits;     // MCBS_TOPO_* (mcbs.h): what the descriptors and the node count make possible; the narrow lean step is chosen by them
 };
 
 struct mcbs_topology {
@@ -101,6 +102,8 @@ struct mcbs_batch {
     mcbs_batch_variant_info variant{};   // which kernels the batch's calls dispatch to: decided once, by batch_variant at the end of mcbs_batch_create
     bool lean_step = false;         // mcbs_step without info buffers takes the lean argument block (packed, no defender, reset image in the
                                     // config); decided once, in mcbs_batch_create
+    bool narrow_step = false;       // ... and the narrow instantiation of that kernel: the topology has no trait beyond kNarrowStepCan
+                                    // (mcbs_step.hip); decided once, in mcbs_batch_create
     uint8_t* arena = nullptr;       // every per-env column + bodies + init body, one allocation
     size_t arena_bytes = 0;
     ObsDigest* digest = nullptr;
@@ -130,8 +133,8 @@ static int check_section(const mcbs_topo_header* h, uint32_t off, size_t bytes, 
     return MCBS_OK;
 }
 
-extern "C" int mcbs_topology_create(const void* blob, size_t nbytes, int32_t device, mcbs_topology** out) {
-    if (!blob || !out) return fail(MCBS_EINVAL, "null argument");
+// Everything mcbs_topology_create checks about a blob before it builds anything from it (host only)
+static int check_blob(const void* blob, size_t nbytes) {
     if (nbytes < sizeof(mcbs_topo_header)) return fail(MCBS_EINVAL, "topology blob too small");
     const mcbs_topo_header* h = static_cast<const mcbs_topo_header*>(blob);
     if (h->magic != MCBS_TOPO_MAGIC) return fail(MCBS_EINVAL, "topology blob: bad magic");
@@ -224,6 +227,50 @@ extern "C" int mcbs_topology_create(const void* blob, size_t nbytes, int32_t dev
     const uint8_t* io = b + h->off_init_order;
     if (h->n_init_owned > h->n_nodes) return fail(MCBS_EINVAL, "init order");
     for (uint32_t i = 0; i < h->n_init_owned; ++i) if (io[i] >= h->n_nodes) return fail(MCBS_EINVAL, "init order");
+    return MCBS_OK;
+}
+
+// The topology's traits (MCBS_TOPO_*, mcbs.h) from a checked blob: one pass over the vulnerability slots that some column reaches — the
+// descriptors of the hot image, the only ones an action can name — and the node count
+static uint32_t topo_traits(const void* blob) {
+    const uint8_t* b = static_cast<const uint8_t*>(blob);
+    const mcbs_topo_header* h = static_cast<const mcbs_topo_header*>(blob);
+    const mcbs_vuln_slot* sl = reinterpret_cast<const mcbs_vuln_slot*>(b + h->off_slot);
+    const uint8_t* so = b + h->off_slot_of;
+    const uint32_t W = h->n_local + h->n_remote;
+    uint32_t t = h->n_nodes > 12u ? MCBS_TOPO_WIDE_ROWS : 0u;
+    for (uint32_t n = 0; n < h->n_nodes; ++n)
+        for (uint32_t c = 0; c < W; ++c) {
+            const uint8_t s = so[(size_t)n * W + c];
+            if (s == 0xFF) continue;
+            const mcbs_vuln_slot& v = sl[(size_t)n * h->max_slots + s];
+            if (v.kind == MCBS_OUT_PRIVILEGE_ESCALATION) t |= MCBS_TOPO_ESCALATION;
+            if (v.kind == MCBS_OUT_LATERAL_MOVE) t |= MCBS_TOPO_LATERAL_EXPLOIT;
+            if (v.kind == MCBS_OUT_PROBE_SUCCEEDED) t |= MCBS_TOPO_PROBE;
+            if (v.precond_tt != 0xFFFFu) t |= MCBS_TOPO_PRECONDITION;
+            if (v.payload_cnt > 1u) t |= MCBS_TOPO_MULTI_LEAK;
+        }
+    return t;
+}
+
+extern "C" int mcbs_topology_traits(const void* blob, size_t nbytes, uint32_t* traits) {
+    if (!blob || !traits) return fail(MCBS_EINVAL, "null argument");
+    if (const int rc = check_blob(blob, nbytes)) return rc;
+    *traits = topo_traits(blob);
+    return MCBS_OK;
+}
+
+extern "C" int mcbs_topology_create(const void* blob, size_t nbytes, int32_t device, mcbs_topology** out) {
+    if (!blob || !out) return fail(MCBS_EINVAL, "null argument");
+    if (const int rc = check_blob(blob, nbytes)) return rc;
+    const uint8_t* b = static_cast<const uint8_t*>(blob);
+    const mcbs_topo_header* h = static_cast<const mcbs_topo_header*>(blob);
+    const mcbs_node_static* ns = reinterpret_cast<const mcbs_node_static*>(b + h->off_node);
+    const mcbs_vuln_slot* sl = reinterpret_cast<const mcbs_vuln_slot*>(b + h->off_slot);
+    const mcbs_payload* pl = reinterpret_cast<const mcbs_payload*>(b + h->off_payload);
+    const mcbs_service* sv = reinterpret_cast<const mcbs_service*>(b + h->off_service);
+    const uint8_t* so = b + h->off_slot_of;
+    const mcbs_triple* tr = reinterpret_cast<const mcbs_triple*>(b + h->off_triple);
 
     mcbs_topology* t = new (std::nothrow) mcbs_topology();
     if (!t) return fail(MCBS_ENOMEM, "out of memory");
@@ -232,6 +279,7 @@ extern "C" int mcbs_topology_create(const void* blob, size_t nbytes, int32_t dev
     {   // hot image: 32-byte node records, flattened (node, column) descriptors, then the list sections verbatim
         const uint32_t N = h->n_nodes, W = h->n_local + h->n_remote;
         HotLayout& L = t->hot;
+        L.traits = topo_traits(blob);
         uint32_t off = 0;
         auto take = [&](size_t bytes) { uint32_t o = off; off = (uint32_t)((off + bytes + 15) / 16 * 16); return o; };
         L.node = take(sizeof(HotNode) * N);
@@ -563,6 +611,7 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     if (e != hipSuccess) { (void)hipFree(b->arena); delete b; return fail(MCBS_EHIP, "initial reset failed: %s", hipGetErrorString(e)); }
     b->variant = batch_variant(b);
     b->lean_step = S.packed && cfg->defender_kind == MCBS_DEFENDER_NONE && C.init_image_ok && !S.ring;
+    b->narrow_step = b->lean_step && !(topo->hot.traits & ~kNarrowStepCan);
     *out = b;
     return MCBS_OK;
 }
@@ -703,7 +752,9 @@ static int launch_step(mcbs_batch* b, const StepIO& io, hipStream_t st, const ch
 #ifdef MCBS_DIAG
         a.stamps = io.stamps;
 #endif
-        hipLaunchKernelGGL((step_kernel<0, 0, false, MCBS_DEFENDER_NONE>), step_grid(b), dim3(64), 0, st, b->C_dev, a);
+        // ... instantiated for what the batch's topology can do, where that is no more than the narrow kernel handles
+        if (b->narrow_step) hipLaunchKernelGGL((step_kernel<0, 0, false, MCBS_DEFENDER_NONE>), step_grid(b), dim3(64), 0, st, b->C_dev, NarrowStepArgs{a});
+        else hipLaunchKernelGGL((step_kernel<0, 0, false, MCBS_DEFENDER_NONE>), step_grid(b), dim3(64), 0, st, b->C_dev, a);
         return launch_ok(what);
     }
     step_variant(b, [&](auto wt, auto def) {
@@ -2050,6 +2101,10 @@ static DefObs fused_defender_obs(const mcbs_batch* b, const mcbs_defender_obs* o
 
 extern "C" int32_t mcbs_step_is_lean(const mcbs_batch* b, int32_t with_info) {
     return (b && b->lean_step && !with_info) ? 1 : 0;
+}
+extern "C" int32_t mcbs_step_topo_traits(const mcbs_batch* b, int32_t with_info, uint32_t* traits) {
+    if (traits) *traits = b ? b->topo->hot.traits : 0u;
+    return (b && b->narrow_step && !with_info) ? 1 : 0;
 }
 
 extern "C" int mcbs_batch_variant(const mcbs_batch* b, mcbs_batch_variant_info* out) {

@@ -143,6 +143,18 @@ __device__ __forceinline__ uint32_t dword_of(const uint4& r0, const uint4& r1, c
     return (uint32_t)((b3 ? s1 : s0) >> ((i & 1u) * 32u));
 }
 
+// What a topology can do, as a template argument of step_body and Lane::act (MCBS_TOPO_* bits, mcbs.h): a clear bit compiles the rule
+// out.  MCBS_TOPO_ANY, the default of both, is every kernel but one; the narrow lean step (step_kernel(cfg, NarrowStepArgs) at the end of
+// this file) is instantiated with kNarrowStepCan, and mcbs_api.hip launches it only for a batch whose topology has no other trait.
+// The narrow kernel assumes away escalations, lateral-move exploits, preconditions and multi-entry leaks; each was measured to pay on the
+// headline (profiles/step_topo_traits.md).  Probes stay (Chain-10 has them).  "At most 12 nodes" — three row vectors and a narrower
+// select tree — was built, measured SLOWER and left out: MCBS_TOPO_WIDE_ROWS is derived and reported, and no kernel code reads it.
+// -DMCBS_NARROW_CAN=<bits> builds the library with another set (measuring one trait at a time).
+#ifndef MCBS_NARROW_CAN
+#define MCBS_NARROW_CAN (MCBS_TOPO_PROBE | MCBS_TOPO_WIDE_ROWS)
+#endif
+constexpr uint32_t kNarrowStepCan = MCBS_NARROW_CAN;
+
 // the step stores a row, a header or a set only when its bits changed, decided against the value it loaded (registers, no re-read).
 // Such a store is written `if (MCBS_CHANGED(changed)) ...`: expecting the store to happen makes the compiler keep it as an exec-masked
 // store with no `s_cbranch_execz` around it (its branch cost model skips a block only when it expects the block's lanes to be off).
@@ -233,8 +245,11 @@ struct Lane {
     // DK: the batch's defender kind; MCBS_DEFENDER_RANDOM_EVENTS consults the env's own vulnerability / service / firewall state
     // GUARD = false (the looping variant, see step_body): list appends go to the slot past the end whether or not the element is new
     // (general layout only: a packed list must stay zero past its count)
-    template <bool WIDE_OK, int DK, bool GUARD = true>
+    // CAN: what the batch's topology can do (MCBS_TOPO_* bits); the rules behind a clear bit are compiled out, not branched around
+    template <bool WIDE_OK, int DK, bool GUARD = true, uint32_t CAN = MCBS_TOPO_ANY>
     __device__ __forceinline__ void act(bool X, double raw_nx, int kind, uint32_t src, uint32_t tgt, uint32_t col, uint32_t port, uint32_t triple) {
+        constexpr bool T_ESC = (CAN & MCBS_TOPO_ESCALATION) != 0u, T_LAT = (CAN & MCBS_TOPO_LATERAL_EXPLOIT) != 0u,
+                       T_PRE = (CAN & MCBS_TOPO_PRECONDITION) != 0u, T_MULTI = (CAN & MCBS_TOPO_MULTI_LEAK) != 0u || WIDE_OK;
         const bool k2 = kind == 2;
         // ---- look-ups of both flavours (LDS) ----
         const uint4* tp = reinterpret_cast<const uint4*>(NS(tgt));
@@ -283,12 +298,27 @@ struct Lane {
         // ---- exploit checks: MACHINE_NOT_RUNNING 0 > SUPSPICIOUSNESS -5 > LOCAL_EXPLOIT_FAILED -20 / FAILED_REMOTE_EXPLOIT -50 > REPEAT -1 ----
         const uint32_t vk = d1.z & 0xFFu, level = (d1.z >> 8) & 0xFFu;
         const bool present = (vk != 0xFFu) & (bool)((own_present >> (col & 63u)) & 1ull);       // (random events: the key may have been patched away)
-        const bool pre_ok = ((d1.y >> 16) >> tags) & 1u;                                        // precondition on (static props, tags)
-        const bool esc = !k2 & (vk == MCBS_OUT_PRIVILEGE_ESCALATION);
+        bool pre_ok, esc, lat_x;                                                                  // (the general form verbatim: its code must not move)
+        if constexpr (CAN == MCBS_TOPO_ANY) {
+            pre_ok = ((d1.y >> 16) >> tags) & 1u;                                               // precondition on (static props, tags)
+            esc = !k2 & (vk == MCBS_OUT_PRIVILEGE_ESCALATION);
+            lat_x = vk == MCBS_OUT_LATERAL_MOVE;
+        } else {
+            pre_ok = T_PRE ? (bool)(((d1.y >> 16) >> tags) & 1u) : true;
+            esc = T_ESC ? !k2 & (vk == MCBS_OUT_PRIVILEGE_ESCALATION) : false;
+            lat_x = T_LAT && vk == MCBS_OUT_LATERAL_MOVE;
+        }
         const bool repeat_esc = esc & (bool)((tags >> level) & 1u);                             // tag already on the node
         const bool x_proceed = running & present & pre_ok & !repeat_esc;
-        const double x_fail_raw = !running ? 0.0 : (!present ? -5.0 : (!pre_ok ? (kind == 0 ? -20.0 : -50.0) : -1.0));
-        const int x_fail_kind = (running & present) ? (!pre_ok ? MCBS_OUT_EXPLOIT_FAILED : MCBS_OUT_PRIVILEGE_ESCALATION) : MCBS_OUT_NONE;
+        double x_fail_raw;
+        int x_fail_kind;
+        if constexpr (T_PRE || T_ESC) {
+            x_fail_raw = !running ? 0.0 : (!present ? -5.0 : (!pre_ok ? (kind == 0 ? -20.0 : -50.0) : -1.0));
+            x_fail_kind = (running & present) ? (!pre_ok ? MCBS_OUT_EXPLOIT_FAILED : MCBS_OUT_PRIVILEGE_ESCALATION) : MCBS_OUT_NONE;
+        } else {   // neither preconditions nor escalations: an exploit on a running node that has the vulnerability proceeds
+            x_fail_raw = !running ? 0.0 : -5.0;
+            x_fail_kind = MCBS_OUT_NONE;
+        }
         const int x_lvl = (running & present & pre_ok & esc) ? (int)level : 0;
 
         const bool so = X & src_owned;                          // else INVALID_ACTION (-1), checked first
@@ -299,7 +329,7 @@ struct Lane {
 
         // ---- __mark_node_as_owned (actions.py:251-275): `already` = currently owned (agent installed); a node that is
         // owned now was owned before, so only a change of ownership consults / sets the ever-owned bit ----
-        const bool newly = go & !already & (k2 | esc | (vk == MCBS_OUT_LATERAL_MOVE));
+        const bool newly = go & !already & (k2 | esc | lat_x);
         const bool first_time = newly & !rget<WT>(m[M_EVER], tgt);
         const uint32_t priv = privilege(tgt);
         const uint32_t np = priv > own_level ? priv : own_level;   // model.escalate
@@ -311,8 +341,10 @@ struct Lane {
         for (int w = 0; w < WT; ++w) {
             m[M_EVER][w] |= bn[w];
             m[M_INST][w] |= bn[w];
-            m[M_PLO][w] = (m[M_PLO][w] & ~bc[w]) | ((np & 1u) ? bc[w] : W(0));
-            m[M_PHI][w] = (m[M_PHI][w] & ~bc[w]) | ((np & 2u) ? bc[w] : W(0));
+            if constexpr (T_ESC) {
+                m[M_PLO][w] = (m[M_PLO][w] & ~bc[w]) | ((np & 1u) ? bc[w] : W(0));
+                m[M_PHI][w] = (m[M_PHI][w] & ~bc[w]) | ((np & 2u) ? bc[w] : W(0));
+            } else m[M_PLO][w] |= bc[w];   // own_level is LocalUser: the privilege changes only from NoAccess, to bit-plane 0 alone
         }
         owned += (chg & (priv == 0u)) ? 1u : 0u;
         props |= newly ? t_props : 0ull;                        // all (non-tag) properties become known
@@ -338,6 +370,23 @@ struct Lane {
         // waits for the store's write acknowledgement), wave-uniformly skipped when no lane has that many; longer lists: the tail loop.
         // A.max_leak (the topology's largest payload count, found on the host) bounds all three with ONE scalar test each: Chain-10
         // and ToyCtf never leak more than one entry per action, and walked four ballot tests here and one per rung below for nothing.
+        if constexpr (!T_MULTI) {
+            // No action of the topology leaks more than one entry (packed batches): the entry came with the descriptor (d2), and the leak
+            // is the one predicated append below — no ladder, no prefetch array, no tail loop.  The one wait, as in the general form.
+            __builtin_amdgcn_s_waitcnt(0x0F70);
+            const bool on = cnt != 0u;
+            const uint32_t pn = d2.x & 0xFFFFu, pc = d2.x >> 16, pt = d2.y & 0xFFFFu;
+            const bool new_n = on & !rget<WT>(m[M_DISC], pn);
+            const bool new_g = on & creds & !rget<WT>(m[M_GATH], pc);
+            const bool new_c = on & creds & !rget<WT>(m[M_CACH], pt);
+            ldisc |= (uint64_t)(new_n ? pn & 0xFu : 0u) << ((n_disc & 15u) * 4u);
+            lcred |= (uint64_t)(new_c ? pt & 0xFu : 0u) << ((n_creds & 15u) * 4u);
+            W b0[WT], b1[WT], b2[WT];
+            rbit<WT>(b0, pn, new_n); rbit<WT>(b1, pc, new_g); rbit<WT>(b2, pt & (WT * (uint32_t)sizeof(W) * 8u - 1u), new_c);
+#pragma unroll
+            for (int w = 0; w < WT; ++w) { m[M_DISC][w] |= b0[w]; m[M_GATH][w] |= b1[w]; m[M_CACH][w] |= b2[w]; }
+            n_disc += new_n; nn = new_n; nc = new_g; n_creds += new_c; ncache = new_c;
+        } else {
         constexpr uint32_t PF = 8;
         uint2 pre[PF] = {make_uint2(d2.x, d2.y), make_uint2(d2.z, d2.w), make_uint2(d3.x, d3.y), make_uint2(d3.z, d3.w),
                          make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u), make_uint2(0u, 0u)};
@@ -385,6 +434,7 @@ struct Lane {
         }
         if (A.max_leak > PF)
             for (uint32_t i = PF; i < cnt; ++i) leak(pl[i]);
+        }
         if (stage)
             for (uint32_t w = 0; w < S.TW; ++w) S.cach[(size_t)w * S.E + e] = wide_lds[w * wide_stride];
         rx += 5 * (int)nn + 3 * (int)nc;
@@ -490,13 +540,15 @@ struct Lane {
 // mcbs_rollout_random (mode 0: actions are read from io.actions).
 // LEAN: the caller is the lean launch of the packed, attacker-only whole step (step_kernel(cfg, LeanStepArgs) below), whose S, T and io hold
 // only what that instantiation reads; false for every other kernel, whose code does not change.
-template <int PHASE, int WTP, int DEFK, bool MANY, bool LEAN = false, class Hook = NoHook>
+// CAN: what the batch's topology can do (MCBS_TOPO_* bits; kNarrowStepCan above); anything but MCBS_TOPO_ANY goes with LEAN.
+template <int PHASE, int WTP, int DEFK, bool MANY, bool LEAN = false, class Hook = NoHook, uint32_t CAN = MCBS_TOPO_ANY>
 __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, const StepCfg* __restrict__ Cp, const StepIO& io, const RollArgs& roll, Hook& hook) {
     constexpr bool PK = WTP == 0;           // packed batch: the eight sets are 16-bit fields of one uint4 per env
     constexpr int WT = PK ? 1 : WTP;
     using W = std::conditional_t<LEAN, uint32_t, uint64_t>;   // the lean packed step: sets of at most 16 elements, held in 32-bit words
     static_assert(!LEAN || (PK && PHASE == 0 && !MANY && DEFK == MCBS_DEFENDER_NONE && !Hook::kAction && !Hook::kObs && !Hook::kFinish),
                   "the lean argument block serves the packed, attacker-only, hook-less whole step");
+    static_assert(LEAN || CAN == MCBS_TOPO_ANY, "only the lean step is instantiated for a topology's traits");
     const StepCfg& C = *Cp;   // in device memory: fields are fetched by scalar loads where they are used, not all up front
     extern __shared__ uint4 dyn_lds[];
 #ifdef MCBS_DIAG
@@ -690,7 +742,7 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
         ln.props = pt & ROW_PROPS_MASK; ln.tags = (uint32_t)(pt >> 60);
         ln.ever = r0.z; ln.since = r0.w;
         STAMP(3);  // row landed
-        ln.template act<!PK, DEFK, GUARD>(X, skip ? -1.0 : 0.0, kind, src, tgt, X ? (k0 ? a2 : (k1 ? cL + a3 : 0u)) : 0u, (X & k2) ? a3 : 0u, triple);
+        ln.template act<!PK, DEFK, GUARD, CAN>(X, skip ? -1.0 : 0.0, kind, src, tgt, X ? (k0 ? a2 : (k1 ? cL + a3 : 0u)) : 0u, (X & k2) ? a3 : 0u, triple);
         // the row goes back only if the action changed it (first attack / discovery of a (node, vulnerability) pair, new properties
         // or tags); `pword` holds the row as the attacker left it either way, for reimage()
         if (PK) {
@@ -888,6 +940,27 @@ __global__ __launch_bounds__(256) void step_kernel(const StepCfg* __restrict__ C
 #endif
     NoHook nh;
     step_body<0, 0, MCBS_DEFENDER_NONE, false, true>(S, T, Cp, io, RollArgs{}, nh);
+}
+
+// The narrow lean launch: the kernel above instantiated for what the batch's topology can do (kNarrowStepCan).  Chosen once, in
+// mcbs_batch_create, for a lean batch whose topology has no other trait (MCBS_TOPO_*, found on the host with the hot image): Chain-10,
+// the headline.  Same name again; the argument block is a type of its own.
+template <int PHASE, int WTP, bool TOPO_LDS, int DEFK>
+__global__ __launch_bounds__(256) void step_kernel(const StepCfg* __restrict__ Cp, NarrowStepArgs na) {
+    static_assert(PHASE == 0 && WTP == 0 && !TOPO_LDS && DEFK == MCBS_DEFENDER_NONE, "the lean argument block serves the packed, attacker-only whole step");
+    const LeanStepArgs& a = na.a;
+    DevState S{};
+    S.h0 = a.h0; S.masks = a.masks; S.body = a.body; S.h1 = a.h1; S.episode = a.episode; S.pending = a.pending;
+    S.E = a.E; S.body_stride = a.body_stride; S.N = a.N; S.tiny_p = a.tiny_p; S.tiny_v = a.tiny_v;
+    S.NW = S.SW = S.TW = S.WT = 1u; S.packed = 1u;
+    const Topo T{nullptr, a.hot};
+    StepIO io{};
+    io.actions = a.actions; io.reward = a.reward; io.terminated = a.terminated;
+#ifdef MCBS_DIAG
+    io.stamps = a.stamps;
+#endif
+    NoHook nh;
+    step_body<0, 0, MCBS_DEFENDER_NONE, false, true, NoHook, kNarrowStepCan>(S, T, Cp, io, RollArgs{}, nh);
 }
 
 // mcbs_step_many / mcbs_rollout_random: io.n_steps consecutive steps in one launch; `roll` is a kernel ARGUMENT (nothing in device

@@ -28,6 +28,7 @@ EXPORTS = [
     "mcbs_timing_enable", "mcbs_timing_read", "mcbs_mask_logits", "mcbs_discrete_action_count", "mcbs_copy_rows_masked", "mcbs_attacker_wrapper_finish", "mcbs_attacker_wrapper_step",
     "mcbs_attacker_wrapper_step_launches", "mcbs_set_mask_discrete_stride", "mcbs_defender_wrapper_step",
     "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant", "mcbs_step_is_lean",
+    "mcbs_topology_traits", "mcbs_step_topo_traits",
     "mcbs_feature_layout_create", "mcbs_feature_layout_destroy", "mcbs_feature_layout_width", "mcbs_encode_features",
     "mcbs_masked_categorical", "mcbs_masked_categorical_packed", "mcbs_masked_categorical_grad",
     "mcbs_masked_linear_categorical", "mcbs_masked_linear_categorical_packed",
@@ -139,6 +140,9 @@ def load_library(path: Optional[str] = None):
     lib.mcbs_batch_variant.argtypes = [C.c_void_p, C.POINTER(BatchVariantInfo)]
     lib.mcbs_step_is_lean.restype = C.c_int32
     lib.mcbs_step_is_lean.argtypes = [C.c_void_p, C.c_int32]
+    lib.mcbs_topology_traits.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
+    lib.mcbs_step_topo_traits.restype = C.c_int32
+    lib.mcbs_step_topo_traits.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]
     lib.mcbs_timing_enable.argtypes = [C.c_void_p, C.c_int32]
     lib.mcbs_timing_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     for name in EXPORTS:
@@ -156,6 +160,15 @@ def load_library(path: Optional[str] = None):
 def _check(lib, rc: int, what: str) -> None:
     if rc != 0:
         raise McbsError(f"{what} failed ({rc}): {lib.mcbs_last_error().decode(errors='replace')}")
+
+
+def topology_traits(topo: FlatTopology) -> int:
+    """The MCBS_TOPO_* bits (_abi.TOPO_*) the native library derives from a topology's blob; computed on the host, no GPU needed."""
+    lib = load_library()
+    blob = np.frombuffer(topo.blob, dtype=np.uint8)
+    t = C.c_uint32()
+    _check(lib, lib.mcbs_topology_traits(blob.ctypes.data, blob.size, C.byref(t)), "mcbs_topology_traits")
+    return int(t.value)
 
 
 def obs_field_shapes(topo: FlatTopology, spec: EnvSpec) -> Dict[str, tuple]:
@@ -1357,6 +1370,13 @@ class BatchEngine:
     def step_is_lean(self, with_info: bool) -> bool:
         """Whether step(actions, with_info) of this batch takes the lean launch (packed, attacker-only batch, no info buffers)."""
         return bool(self.lib.mcbs_step_is_lean(self._h, int(bool(with_info))))
+
+    def step_topo_traits(self, with_info: bool):
+        """(narrow, traits): whether step(actions, with_info) of this batch takes the narrow lean kernel, and the MCBS_TOPO_* bits of the
+        batch's topology (mcbs_step_topo_traits)."""
+        t = C.c_uint32()
+        narrow = self.lib.mcbs_step_topo_traits(self._h, int(bool(with_info)), C.byref(t))
+        return bool(narrow), int(t.value)
 
     def timing_enable(self, on: bool = True) -> None:
         _check(self.lib, self.lib.mcbs_timing_enable(self._h, int(on)), "mcbs_timing_enable")

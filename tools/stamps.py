@@ -29,7 +29,9 @@ for wl in (sys.argv[1:] or ["headline"]):
     torch.cuda.synchronize()
     s = buf.cpu().numpy().astype(np.int64)
     d = np.diff(s[:, :7], axis=1)
-    print(f"{wl}: {desc}, {eng.E} envs, {waves} waves; median s_memtime ticks per segment:")
+    narrow, traits = eng.step_topo_traits(False)
+    which = "narrow lean" if narrow else ("lean" if eng.step_is_lean(False) else "full-argument")
+    print(f"{wl}: {desc}, {eng.E} envs, {waves} waves, {which} kernel (topology traits {traits:#x}); median s_memtime ticks per segment:")
     for i, n in enumerate(names):
         print(f"  {n:32s} median {np.median(d[:, i]):9.0f}  p90 {np.percentile(d[:, i], 90):9.0f}")
     tot = s[:, 6] - s[:, 0]
