@@ -405,6 +405,41 @@ int  mcbs_apply_packed_mask(const mcbs_batch*, const uint32_t* bits, size_t bits
 int  mcbs_unpack_action_mask(const mcbs_batch*, const uint32_t* bits, size_t bits_row_words, uint8_t* out, size_t out_row_stride,
                              uint64_t n_rows, void* stream);
 
+/* ---- action-mask keys: store the few words the packed mask is a function of, rebuild the bits for a minibatch at update time ----
+ * The packed mask above is rebuilt from the observation digest (owned-source bits by discovery index, discovered-node and cached-
+ * credential counts) and, for the local-vulnerability block only, from which node sits at each discovery index.  A key row carries
+ * exactly those inputs, so it expands to the packed mask of its step long after the env has moved on (Chain-10 at 12/12: 5 words = 20 B
+ * per env and step instead of 443 words = 1 772 B).
+ *
+ * Format: device uint32_t [rows, row_words], little-endian bit and byte order within a word.
+ *   Nk = min(cfg.maximum_node_count, the topology's node count), Wk = 1 + ceil(Nk / 32) + ceil(Nk / 4) words carry a key.
+ *   word 0                        bits 0-15: the discovered-node count, the EFFECTIVE one (0 for a blank observation); bits 16-31: the
+ *                                 cached-credential count
+ *   words 1 .. ceil(Nk / 32)      bit i (bit i & 31 of word 1 + (i >> 5)): the node at discovery index i has the agent installed, for i
+ *                                 below the effective count (the digest's owned-source bits, cut to Nk)
+ *   the next ceil(Nk / 4) words   byte i (byte i & 3 of word i >> 2 of these): the node id at discovery index i, for i below the effective count
+ *   Everything else is zero: bits and bytes at or beyond the effective count, and padding.  Words from Wk up to row_words are never
+ *   touched.  One env's key is a pure function of its digest and discovery list; two envs with equal masks need not have equal keys.
+ *
+ * mcbs_mask_key_words: Wk (0 for a NULL batch).
+ * mcbs_store_mask_keys: the key of the LAST observation of every env, keys[e, 0 .. Wk), each word written whole, in one launch.  The
+ *   preconditions of mcbs_pack_action_mask: MCBS_ESTATE under MCBS_DEFENDER_RANDOM_EVENTS and while the digests cannot be trusted;
+ *   MCBS_EINVAL when keys is NULL or row_words < Wk.
+ * mcbs_expand_mask_keys: bits[i, 0 .. W) = the packed mask, in the format of mcbs_pack_action_mask, that call would have written for the
+ *   env and step key row index[i] was stored at, bit for bit; index NULL: key row i, and then n_rows <= n_source_rows (MCBS_EINVAL
+ *   otherwise).  Write-only, words from W on untouched, n_rows any count (0 is a no-op), one launch.  An index outside
+ *   [0, n_source_rows) reads no memory and gives an all-zero row.  The batch supplies the device, the geometry and the topology's static
+ *   local-vulnerability table; no per-env state and no digest is read, so every defender kind is served, given keys by the caller.
+ *   MCBS_EINVAL when keys or bits is NULL, key_row_words < Wk or bits_row_words < W.
+ *   Malformed keys never read out of bounds: a count above Nk acts as Nk; owned-source bits at or beyond the (clamped) count are
+ *   ignored; a node id at or above the topology's node count contributes no local-vulnerability bits; the credential count is used
+ *   as it stands (at or above maximum_total_credentials: every credential).  marlon_amd/mask_keys.py is the host mirror of the format
+ *   and of this rule. */
+uint64_t mcbs_mask_key_words(const mcbs_batch*);
+int  mcbs_store_mask_keys(mcbs_batch*, uint32_t* keys, size_t row_words, void* stream);
+int  mcbs_expand_mask_keys(const mcbs_batch*, const uint32_t* keys, size_t key_row_words, const int64_t* index, uint64_t n_source_rows,
+                           uint32_t* bits, size_t bits_row_words, uint64_t n_rows, void* stream);
+
 /* ---- masked categorical head: sample, log-prob and entropy of MaskablePPO's action distribution, one launch ----
  * What sb3_contrib's MaskableCategorical does with the policy's logits and action_masks() (train_marl_multi.py:259-293):
  * `where(mask, logits, -1e8)`, log_softmax over the row, then sample / log_prob / entropy with the masked terms zeroed; evaluate_actions

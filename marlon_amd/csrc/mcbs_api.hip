@@ -30,6 +30,7 @@
 #include "mcbs_features.hip"
 #include "mcbs_obs_packing.hip"
 #include "mcbs_wrapper_fused.hip"
+#include "mcbs_mask_keys.hip"
 
 using namespace mcbs;
 
@@ -1382,6 +1383,51 @@ extern "C" int mcbs_unpack_action_mask(const mcbs_batch* b, const uint32_t* bits
     if (n_rows == 0) return MCBS_OK;
     hipLaunchKernelGGL(unpack_mask_kernel, rows_grid(n_rows, 65536u, ((A + 15u + 15u) / 16u + 63u) / 64u), dim3(256), 0, (hipStream_t)stream, bits, bits_row_words, out, out_row_stride, n_rows, A);
     return launch_ok("unpack action mask");
+}
+
+// ------------------------------------------------------------------ action-mask keys
+static MaskKeyGeom mask_key_geom(const mcbs_batch* b) {
+    MaskKeyGeom K;
+    const uint32_t n = b->topo->H()->n_nodes;
+    K.Nk = b->cfg.maximum_node_count < n ? b->cfg.maximum_node_count : n;
+    K.own_words = (K.Nk + 31u) / 32u; K.node_words = (K.Nk + 3u) / 4u; K.Wk = 1u + K.own_words + K.node_words;
+    K.dWk = fast_div_host(K.Wk);
+    return K;
+}
+
+extern "C" uint64_t mcbs_mask_key_words(const mcbs_batch* b) { return b ? mask_key_geom(b).Wk : 0; }
+
+extern "C" int mcbs_store_mask_keys(mcbs_batch* b, uint32_t* keys, size_t row_words, void* stream) {
+    if (!b || !keys) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    int rc;
+    if ((rc = digest_usable(b, "mcbs_store_mask_keys"))) return rc;
+    const MaskKeyGeom K = mask_key_geom(b);
+    if (row_words < K.Wk) return fail(MCBS_EINVAL, "row_words %zu is shorter than the %u words of a mask key", row_words, K.Wk);
+    const uint64_t total = (uint64_t)b->S.E * K.Wk;                  // one thread per key word
+    if (total >= (1ull << 31)) return fail(MCBS_ELIMIT, "too many envs for one launch of mcbs_store_mask_keys");
+    hipLaunchKernelGGL(store_mask_keys_kernel, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream, b->S, b->digest, keys,
+                       row_words, K, (uint32_t)total);
+    return launch_ok("store mask keys");
+}
+
+extern "C" int mcbs_expand_mask_keys(const mcbs_batch* b, const uint32_t* keys, size_t key_row_words, const int64_t* index, uint64_t n_source_rows,
+                                     uint32_t* bits, size_t bits_row_words, uint64_t n_rows, void* stream) {
+    if (!b || !keys || !bits) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    LogitsGeom G;
+    int rc;
+    if ((rc = discrete_geom(b, G))) return rc;
+    if ((rc = rows_hold(G.A, "bits_row_words", bits_row_words, nullptr, 0))) return rc;
+    const MaskKeyGeom K = mask_key_geom(b);
+    if (key_row_words < K.Wk) return fail(MCBS_EINVAL, "key_row_words %zu is shorter than the %u words of a mask key", key_row_words, K.Wk);
+    if (!index && n_rows > n_source_rows) return fail(MCBS_EINVAL, "mcbs_expand_mask_keys: %llu rows asked of %llu stored ones and no index",
+                                                      (unsigned long long)n_rows, (unsigned long long)n_source_rows);
+    if (n_rows == 0) return MCBS_OK;
+    hipLaunchKernelGGL(expand_mask_keys_kernel, rows_grid(n_rows, 65536u), dim3(256), 0, (hipStream_t)stream,
+                       reinterpret_cast<const mcbs_node_static*>(b->T.base + b->C.off_node), b->topo->H()->n_nodes, K, G, keys, key_row_words, index,
+                       n_source_rows, bits, bits_row_words, n_rows);
+    return launch_ok("expand mask keys");
 }
 
 // ------------------------------------------------------------------ masked categorical head

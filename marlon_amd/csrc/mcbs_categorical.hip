@@ -299,7 +299,7 @@ __global__ __launch_bounds__(256) void masked_categorical_kernel(DevState S, Top
         const LT* row = L ? L + i * io.row_stride : nullptr;
         // the mask's source: the env's digest (uniform per wavefront: scalar loads) or the row's stored words
         const ObsDigest d = LIVE ? digest[i] : ObsDigest{};
-        const DigestMask lv = LIVE ? DigestMask::make(S, T, Cp, d, G, (uint32_t)i, 32u) : DigestMask{S, G, d, nullptr, nullptr, 0u, 0u, 0u, 0ull};
+        const DigestMask lv = LIVE ? DigestMask::make(S, T, Cp, d, G, (uint32_t)i, 32u) : DigestMask{G, d, LiveDiscovery{S, nullptr, nullptr, 0u}, 0u, 0u, 0ull};
         const CatRow<LT, LIVE> R{&lv, LIVE ? nullptr : bits + i * bits_row_words, row, W, tail, lane, cw, cs};
         cat_row_finish(R, io, i);
     }

@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void masked_linear_categorical_kernel(DevState
                          c_lat[wv], c_word[wv], c_before[wv], c_stash[wv]};
     for (uint64_t i = (uint64_t)blockIdx.x * 4u + wv; i < io.n_rows; i += (uint64_t)gridDim.x * 4u) {     // wave-uniform
         const ObsDigest d = LIVE ? digest[i] : ObsDigest{};
-        const DigestMask lv = LIVE ? DigestMask::make(S, T, Cp, d, G, (uint32_t)i, 32u) : DigestMask{S, G, d, nullptr, nullptr, 0u, 0u, 0u, 0ull};
+        const DigestMask lv = LIVE ? DigestMask::make(S, T, Cp, d, G, (uint32_t)i, 32u) : DigestMask{G, d, LiveDiscovery{S, nullptr, nullptr, 0u}, 0u, 0u, 0ull};
         const CatRow<float, LIVE, LinSrc<WT>> R{&lv, LIVE ? nullptr : bits + i * bits_row_words, src, W, tail, lane, c_word[wv], c_sum[wv]};
         lin_prepare(R, src, latent + i * lin.latent_stride, c_lat[wv], c_before[wv], c_stash[wv]);
         cat_row_finish(R, io, i);

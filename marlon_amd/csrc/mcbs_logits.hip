@@ -22,28 +22,43 @@ struct LogitsGeom {        // Discrete layout of the batch, set up on the host
     FastDiv dRL, dC, dN, dL, dR;
 };
 
-// One env's digest seen as its Discrete mask: the predicates every kernel that rebuilds the mask of the last observation uses
-// (mask_logits_kernel, pack_mask_kernel, the live form of masked_categorical_kernel).  Built once per wavefront: everything here is
-// uniform per wavefront (scalar loads); S, G and d are references to the kernel's own locals, nothing is copied.
-struct DigestMask {
+// Where DigestMask finds "the node at discovery index i".  Only the local-vulnerability block asks: its bits are that node's static
+// local_mask.  LiveDiscovery is the env's live discovery list (the state), which agrees with the digest only until the env moves on;
+// mcbs_mask_keys.hip has the other source, a stored key row that carries the discovery order itself.
+struct LiveDiscovery {
     const DevState& S;
+    const mcbs_node_static* NS;
+    const uint8_t* body;       // the env's body
+    uint32_t e;
+    __device__ __forceinline__ uint32_t local_mask(uint32_t i) const { return NS[S.disc_at(body, e, i)].local_mask; }
+};
+
+// One env's digest seen as its Discrete mask: the predicates every kernel that rebuilds the mask of the last observation uses
+// (mask_logits_kernel, pack_mask_kernel, the live form of masked_categorical_kernel, expand_mask_keys_kernel).  Built once per
+// wavefront: everything here is uniform per wavefront (scalar loads); G and d are references to the kernel's own locals, nothing is
+// copied.  Disc: the source of the node at a discovery index (above); the default is the live list.
+template <typename Disc = LiveDiscovery>
+struct DigestMaskOf {
     const LogitsGeom& G;
     const ObsDigest& d;        // the env's digest
-    const mcbs_node_static* NS;
-    const uint8_t* body;
-    uint32_t e, n_disc, n_creds;           // n_disc = 0 for a blank observation
+    Disc disc;
+    uint32_t n_disc, n_creds;              // n_disc = 0 for a blank observation
     uint64_t pp;               // credential pattern of one period, repeated to at least C + span bits; 0 when that exceeds 64
 
     // span: the longest run of actions the caller takes from `pp` with one shift (a logits group, or a word of 32)
-    static __device__ __forceinline__ DigestMask make(const DevState& S, const Topo& T, const StepCfg* __restrict__ Cp, const ObsDigest& d,
-                                                      const LogitsGeom& G, uint32_t e, uint32_t span) {
+    static __device__ __forceinline__ DigestMaskOf from(const LogitsGeom& G, const ObsDigest& d, const Disc& disc, uint32_t span) {
         uint64_t pp = 0;
         if (G.C + span <= 64u) {
             const uint64_t one = d.n_creds >= 64u ? ~0ull : ((1ull << d.n_creds) - 1ull);
             for (uint32_t sh = 0; sh < 64u; sh += G.C) pp |= one << sh;
         }
-        return DigestMask{S, G, d, reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node), S.body + (size_t)e * S.body_stride,
-                          e, d.blank ? 0u : d.n_disc, d.n_creds, pp};
+        return DigestMaskOf{G, d, disc, d.blank ? 0u : d.n_disc, d.n_creds, pp};
+    }
+    // ... through the live list of env e
+    static __device__ __forceinline__ DigestMaskOf make(const DevState& S, const Topo& T, const StepCfg* __restrict__ Cp, const ObsDigest& d,
+                                                        const LogitsGeom& G, uint32_t e, uint32_t span) {
+        return from(G, d, LiveDiscovery{S, reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node), S.body + (size_t)e * S.body_stride, e},
+                    span);
     }
     __device__ __forceinline__ uint32_t remote0() const { return G.M + G.ML; }
     __device__ __forceinline__ bool own(uint32_t s) const { return s < G.N && ((d.own_ext[(s >> 6) & 3u] >> (s & 63u)) & 1ull); }
@@ -54,7 +69,7 @@ struct DigestMask {
     // node i's local vulnerabilities as bits (0: i is not an owned, discovered node)      (env.py:653-663)
     __device__ __forceinline__ uint32_t local_bits(uint32_t i) const {
         if (!(own(i) && i < n_disc)) return 0u;
-        return NS[S.disc_at(body, e, i)].local_mask;
+        return disc.local_mask(i);
     }
     __device__ __forceinline__ bool at(uint32_t a) const {            // one action, any region
         if (a < G.M) {                                   // connect[s][t][p][c] = on(s, t) && c < n_creds      (env.py:664-677)
@@ -115,6 +130,7 @@ struct DigestMask {
         return m;
     }
 };
+using DigestMask = DigestMaskOf<>;
 
 // LT: float, or uint16_t for 16-bit logits (bf16 patterns are only replaced).  GW: actions per group (mcbs_rowstore.h).
 //

@@ -37,6 +37,7 @@ EXPORTS = [
     "mcbs_gae",
     "mcbs_obs_packing_create", "mcbs_obs_packing_destroy", "mcbs_obs_packing_words", "mcbs_pack_observation", "mcbs_unpack_observation",
     "mcbs_encode_features_packed",
+    "mcbs_mask_key_words", "mcbs_store_mask_keys", "mcbs_expand_mask_keys",
 ]
 
 _lib = None
@@ -104,6 +105,11 @@ def load_library(path: Optional[str] = None):
     lib.mcbs_pack_action_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     lib.mcbs_apply_packed_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_size_t, C.c_uint64, C.c_float, C.c_void_p]
     lib.mcbs_unpack_action_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]
+    lib.mcbs_mask_key_words.restype = C.c_uint64
+    lib.mcbs_mask_key_words.argtypes = [C.c_void_p]
+    lib.mcbs_store_mask_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    # batch, keys, key_row_words, index, n_source_rows, bits, bits_row_words, n_rows, stream
+    lib.mcbs_expand_mask_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]
     lib.mcbs_feature_layout_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
     lib.mcbs_feature_layout_destroy.argtypes = [C.c_void_p]
     lib.mcbs_feature_layout_destroy.restype = None
@@ -720,6 +726,54 @@ class BatchEngine:
         if bits.shape[0]:
             _check(self.lib, self.lib.mcbs_unpack_action_mask(self._h, bits.data_ptr(), bits.stride(0), out.data_ptr(), out.stride(0),
                                                               bits.shape[0], self._stream()), "mcbs_unpack_action_mask")
+        return out
+
+    # -- action-mask keys (include/mcbs.h): int32 tensors [rows, >= Wk]; a key row expands to the packed mask of the step it was stored at --
+    def mask_key_words(self) -> int:
+        """Wk = 1 + ceil(Nk / 32) + ceil(Nk / 4): the words of one key row (mask_keys.key_words on the host)."""
+        return int(self.lib.mcbs_mask_key_words(self._h))
+
+    def _key_rows(self, keys, what: str):
+        t = self.torch
+        if keys.dtype != t.int32 or keys.dim() != 2 or keys.stride(1) != 1 or keys.device != self.device:
+            raise ValueError(f"{what} must be a device int32 tensor [n, >= Wk] with contiguous rows")
+        if keys.shape[1] < self.mask_key_words():
+            raise ValueError(f"{what} rows hold {keys.shape[1]} words, a mask key needs {self.mask_key_words()}")
+        return keys
+
+    def store_mask_keys(self, out=None):
+        """The key of the Discrete action mask of the LAST observation call: the digest's counts and owned-source bits plus the
+        discovery order, Wk words per env (the preconditions of pack_action_mask).  out: device int32 [E, >= Wk] with contiguous rows
+        (e.g. buffer[t] of a [T, E, Wk] rollout buffer), or None for a new zeroed [E, Wk] tensor.  Words from Wk on are not written."""
+        t = self.torch
+        if out is None:
+            out = t.zeros((self.E, self.mask_key_words()), dtype=t.int32, device=self.device)
+        self._key_rows(out, "out")
+        if out.shape[0] != self.E:
+            raise ValueError(f"out must have {self.E} rows, got {out.shape[0]}")
+        _check(self.lib, self.lib.mcbs_store_mask_keys(self._h, out.data_ptr(), out.stride(0), self._stream()), "mcbs_store_mask_keys")
+        return out
+
+    def expand_mask_keys(self, keys, index=None, out=None):
+        """Stored keys [n_source, >= Wk] -> the packed masks pack_action_mask would have written when they were stored, bit for bit:
+        row i of the result is the mask of key row index[i] (index: device int64 [n]; an entry outside [0, n_source) gives a zero
+        row) or, without an index, of key row i.  out: device int32 [n, >= W] with contiguous rows, or None for a new zeroed
+        [n, row_words] tensor; words from W on are not written.  Reads no env state: works long after the envs have moved on, and
+        under every defender kind."""
+        t = self.torch
+        self._key_rows(keys, "keys")
+        if index is not None and (index.dtype != t.int64 or index.dim() != 1 or not index.is_contiguous() or index.device != self.device):
+            raise ValueError("index must be a contiguous device int64 tensor [n]")
+        n = keys.shape[0] if index is None else index.shape[0]
+        if out is None:
+            out = t.zeros((n, self.packed_mask_words()[1]), dtype=t.int32, device=self.device)
+        self._packed_rows(out, "out")
+        if out.shape[0] != n:
+            raise ValueError(f"out must have {n} rows, got {out.shape[0]}")
+        if n:
+            _check(self.lib, self.lib.mcbs_expand_mask_keys(self._h, keys.data_ptr(), keys.stride(0), None if index is None else index.data_ptr(),
+                                                            keys.shape[0], out.data_ptr(), out.stride(0), n, self._stream()),
+                   "mcbs_expand_mask_keys")
         return out
 
     def _categorical_outputs(self, n, mode, actions, uniforms, out, bad_actions):

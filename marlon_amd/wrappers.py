@@ -206,6 +206,19 @@ class AttackerVecEnv(_MultiDiscreteHead):
         rollout buffer, for apply_packed_mask at update time."""
         return self.engine.pack_action_mask(out)
 
+    def action_mask_keys(self, out=None):
+        """action_masks_packed() as a KEY: device int32 [n_envs, Wk] (engine.store_mask_keys; Chain-10 at 12/12: 5 words instead of
+        443), the few words the mask of the observation this env last returned is a function of.  expand_mask_keys turns stored keys
+        back into exactly the packed masks, at any later time.  out=: write straight into a preallocated buffer, e.g. buffer[t] of a
+        [T, n_envs, Wk] rollout buffer.  Not under ExternalRandomEvents (the mask is no function of the key there)."""
+        return self.engine.store_mask_keys(out)
+
+    def expand_mask_keys(self, keys, index=None, out=None):
+        """Stored keys [n_source, >= Wk] -> packed masks [n, row_words], row i from key row index[i] (int64 [n]; without an index:
+        row i): what action_masks_packed() returned at the step each key was stored, for apply_packed_mask / evaluate_masked /
+        evaluate_masked_from_latent / encode_features_packed.  out=: a preallocated int32 [n, >= W] tensor."""
+        return self.engine.expand_mask_keys(keys, index, out)
+
     def apply_packed_mask(self, bits, logits, fill: float = -1e8):
         """`where(mask, logits, fill)` in place for stored packed masks bits [n, >= W] and logits [n, >= A], any n."""
         return self.engine.apply_packed_mask(bits, logits, fill)
@@ -382,11 +395,14 @@ class AttackerVecEnv(_MultiDiscreteHead):
         return {k: self._obs[k] for k in FLAT_FIELDS[:5]}
 
     def rollout_buffer(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, store_observations: bool = True,
-                       pack_observations: bool = False):
+                       pack_observations: bool = False, mask_storage: str = "bits"):
         """A `rollout.DeviceRolloutBuffer` of n_steps x n_envs transitions for this env: it stores the int32 observation fields
         encode_features() accepts (not the mask fields — with discrete=True the packed masks of action_masks_packed() are stored
         instead, `mask_bits`), actions of this wrapper's shape, and computes advantages and returns with one launch.  Its add() takes
         `observation_fields` as obs.
+        mask_storage="keys" (discrete=True): the buffer holds `mask_keys` [T, E, Wk] instead of `mask_bits` — fill row `pos` with
+        action_mask_keys(out=buf.mask_keys[buf.pos]) or pass keys= to add() — and get() expands each minibatch's `mask_bits` from them
+        (Chain-10 at 12/12: 20 B instead of 1 772 B per transition).
         store_observations=False: no observation storage (a trainer that keeps feature rows of its own).
         pack_observations=True: the observation storage is ONE key, `observations["packed"]` int32 [T, E, W_obs], instead of the five
         fields: fill row `pos` with observation_packed(out=buf.observations["packed"][buf.pos]) and pass obs=None to add(); at update
@@ -395,8 +411,12 @@ class AttackerVecEnv(_MultiDiscreteHead):
         obs = self.observation_fields if store_observations else None
         if store_observations and pack_observations:
             obs = {"packed": self.torch.zeros((self.num_envs, self._packing_handle().words), dtype=self.torch.int32, device=self.engine.device)}
+        if mask_storage not in ("bits", "keys"):
+            raise ValueError(f"mask_storage must be 'bits' or 'keys', got {mask_storage!r}")
+        keys = self.discrete and mask_storage == "keys"
         return DeviceRolloutBuffer(self.engine, n_steps, self.num_envs, obs=obs, action_shape=self._action_shape[1:],
-                                   mask_words=self.engine.packed_mask_words()[1] if self.discrete else None, gamma=gamma, gae_lambda=gae_lambda)
+                                   mask_words=self.engine.packed_mask_words()[1] if self.discrete else None, gamma=gamma, gae_lambda=gae_lambda,
+                                   mask_key_words=self.engine.mask_key_words() if keys else None)
 
     # -- VecEnv surface --
     def reset(self):
