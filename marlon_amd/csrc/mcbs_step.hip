@@ -909,6 +909,248 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
 #endif
 }
 
+// ------------------------------ the narrow lean step: predicates as bit masks ------------------------------
+// The narrow lean kernel (kNarrowStepCan: no escalation, no lateral-move exploit, no precondition, single-entry leaks; packed,
+// attacker-only, no info buffers) has a formulation of the step of its own.  It computes what step_body<0, 0, NONE, false, true, NoHook,
+// kNarrowStepCan> computes, bit for bit; the loads, their order, the one wait and the guarded stores are the same.  What differs is
+// how the booleans are held.  One wavefront per SIMD pays for every instruction it issues, and in step_body a predicate costs three:
+// a v_cmp that turns a bit into a lane mask, a scalar and / or that combines lane masks, a v_cndmask that applies the result.  Here
+// a predicate is a full-width mask in a VGPR (0 / ~0, one v_bfe_i32 from the word that holds the bit), predicates combine with integer
+// and / or (v_bitop3, v_bfi, v_and_or), and a choice between values is (a & m) | (b & ~m):
+//   * the eight sets stay the four dwords they were loaded as: a membership test is a bit extract at n + 16 * (k & 1) of dword k >> 1,
+//     the step's new bits are OR-ed into four `add` dwords, and the word goes back as old | add where (add & ~old) != 0 (this kernel's
+//     attacker only ever sets bits); the target's 4-byte row is updated the same way, in its packed form;
+//   * the raw reward is not materialised: the kernel has no raw-reward output, so all that reaches memory is max(0, raw), and every
+//     failure arm of the reference (0, -1, -5, -10, -20, -50) is <= 0.  What can be positive is an integer (the node's value the first
+//     time it is owned; probe, first-exploit and leak bonuses) minus the vulnerability's cost, formed only for an action that took effect;
+//   * the kernel arguments past the level-1 block are pinned with the config words, and what the level-1 data alone decide (step + 1,
+//     the truncation test, the old flags, the masks of source and target) is written ahead of the wait for the tables.
+// Built, measured and left out (profiles/step_narrow_predicates.md): 24-bit multiplies for the table offsets (no gain), and forming the
+// seven store addresses behind a second scheduling fence while the table loads are in flight (slower in every run).
+// MCBS_NARROW_PRED=0 builds the narrow kernel on step_body again.
+#ifndef MCBS_NARROW_PRED
+#define MCBS_NARROW_PRED 1
+#endif
+
+// A value the compiler must take as it is (no instruction): without it, mask arithmetic on a sign-extended bit is recognised as a
+// select and becomes a compare, a lane mask and a v_cndmask again.
+__device__ __forceinline__ uint32_t opaque(uint32_t v) { asm("" : "+v"(v)); return v; }
+// bit n (low five bits of n count) of x as a mask, 0 or ~0: v_bfe_i32
+__device__ __forceinline__ uint32_t bit_mask(uint32_t x, uint32_t n) { return opaque((uint32_t)__builtin_amdgcn_sbfe((int)x, n, 1u)); }
+// a boolean the decode left as a lane mask, as such a mask: v_cndmask 0, -1
+__device__ __forceinline__ uint32_t lanes_mask(bool p) { return opaque(p ? ~0u : 0u); }
+// 16-byte accesses through global (address space 1) pointers: the compiler's own vector types (HIP's uint4 is a class on the host pass)
+typedef uint32_t np_u32x4 __attribute__((ext_vector_type(4)));
+typedef double np_f64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ uint4 np_load(const __attribute__((address_space(1))) np_u32x4* p) { const np_u32x4 v = *p; return make_uint4(v.x, v.y, v.z, v.w); }
+__device__ __forceinline__ void np_store(__attribute__((address_space(1))) np_u32x4* p, uint32_t x, uint32_t y, uint32_t z, uint32_t w) {
+    np_u32x4 v; v.x = x; v.y = y; v.z = z; v.w = w; *p = v;
+}
+__device__ __forceinline__ uint32_t pick(uint32_t m, uint32_t a, uint32_t b) { return (a & m) | (b & ~m); }   // m ? a : b, bitwise
+
+template <class = void>
+__device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& T, const StepCfg* __restrict__ Cp, const StepIO& io) {
+    const StepCfg& C = *Cp;
+#ifdef MCBS_DIAG
+    unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#endif
+    STAMP_NOWAIT(0);
+    const uint32_t e = blockIdx.x * 64u + threadIdx.x;
+    const bool active = e < S.E;
+    const uint32_t ec = active ? e : 0u;
+    // ---------------- level 1, as in step_body: header, action row, lists word, node rows, sets, {cum_reward, availability}, episode ----------------
+    uint8_t* body = S.body + (size_t)ec * S.body_stride;
+    const uint4 h0 = S.h0[ec];
+    const uint32_t* ap = reinterpret_cast<const uint32_t*>(io.actions) + (size_t)ec * 5;
+    const uint4 a03 = make_uint4(ap[0], ap[1], ap[2], ap[3]);
+    const uint32_t a4 = ap[4];
+    const uint4 lists0 = reinterpret_cast<const uint4*>(S.masks)[S.E + ec];
+    uint4 rw0, rw1, rw2, rw3 = make_uint4(0, 0, 0, 0);
+    {
+        const uint4* rp = reinterpret_cast<const uint4*>(body);
+        rw0 = rp[0]; rw1 = rp[1]; rw2 = rp[2];
+        if (S.N > 12u) rw3 = rp[3];
+    }
+    const uint4 pk = reinterpret_cast<const uint4*>(S.masks)[ec];   // {DISC | INST << 16, EVER | RUN << 16, PLO | PHI << 16, GATH | CACH << 16}
+    double2 h1 = S.h1[ec];
+    const uint32_t episode = S.episode[ec];
+    const double2 h1_in = h1;
+    STAMP_NOWAIT(1);
+    // the config words, in ONE pinned batch behind the vector loads (step_body)
+    uint32_t cL = C.L, cR = C.R, cP = C.P;
+    unsigned long long g_reward = __double_as_longlong(C.goal_reward), g_low = __double_as_longlong(C.goal_low_availability),
+                       g_sla = __double_as_longlong(C.maintain_sla),
+                       g_win = __double_as_longlong(C.winning_reward), g_lose = __double_as_longlong(C.losing_reward);
+    uint32_t a_node = C.hot_node, a_desc = C.hot_desc, a_payload = C.hot_payload, a_auth = C.hot_auth, a_aw = C.auth_words, a_leak = C.max_leak,
+             g_image = C.init_image_ok;
+    uint32_t g_has = C.has_attacker_goal, g_own = C.goal_own_atleast, g_evict = C.defender_goal_eviction, g_auto = C.auto_reset, g_max = C.max_episode_steps,
+             g_pctmin = C.goal_own_pct_min;
+    // ... and the kernel arguments past the level-1 block (the hot image's base, the row format, the output pointers): left alone, their
+    // scalar load goes out between the decode and the table loads, with its wait in front of them
+    uint64_t q_hot = (uint64_t)T.hot;   // (an integer through the pin, a global — not generic — pointer after it)
+    float* o_reward = io.reward;
+    uint8_t* o_term = io.terminated;
+    uint32_t tiny_p = S.tiny_p, tiny_v = S.tiny_v;
+    asm volatile("" : "+s"(cL), "+s"(cR), "+s"(cP), "+s"(g_reward), "+s"(g_low), "+s"(g_pctmin), "+s"(g_sla), "+s"(g_win), "+s"(g_lose), "+s"(g_has),
+                      "+s"(g_own), "+s"(g_evict), "+s"(g_auto), "+s"(g_max), "+s"(g_image), "+s"(a_node), "+s"(a_desc), "+s"(a_payload),
+                      "+s"(a_auth), "+s"(a_aw), "+s"(a_leak), "+s"(q_hot), "+s"(o_reward), "+s"(o_term), "+s"(tiny_p), "+s"(tiny_v));
+#define MCBS_GLOBAL(T, q) reinterpret_cast<__attribute__((address_space(1))) T*>(q)
+    const auto* const tb = MCBS_GLOBAL(const uint8_t, q_hot);
+    STAMP(2);
+    bool need_reset = false;
+    if (active) {
+        const uint32_t old_flags = h0.y;
+        const bool ended = (old_flags & (F_DONE | F_TRUNC)) != 0;
+        const bool skip_env = (int)a03.x == MCBS_ACTION_SKIP;
+        const bool live = !ended & !skip_env;
+        const uint32_t n_disc = h0.z & 0xFFFFu, n_creds = h0.z >> 16;
+        const uint64_t ldisc = (uint64_t)lists0.x | ((uint64_t)lists0.y << 32), lcred = (uint64_t)lists0.z | ((uint64_t)lists0.w << 32);
+        // ---------------- __execute_action: index checks and the three picks, as in step_body ----------------
+        const int kind = (int)a03.x;
+        const uint32_t a1 = a03.y, a2 = a03.z, a3 = a03.w;
+        const bool k0 = kind == 0, k1 = kind == 1, k2 = kind == 2;
+        const bool skip = k2 & (a4 >= n_creds);
+        const bool bad = (a1 >= n_disc) | (a2 >= (k0 ? cL : n_disc)) | (!k0 & (a3 >= (k1 ? cR : cP)));
+        const bool oob = live & (!(k0 | k1 | k2) | (!skip & bad));
+        const bool X = live & !skip & !oob & (k0 | k1 | k2);
+        const uint32_t i1 = X ? a1 : 0u, i2 = (X & !k0) ? a2 : i1, i4 = (X & k2) ? a4 : 0u;
+        const uint32_t src = nibble_of(ldisc, i1), tgt = nibble_of(ldisc, i2), triple = nibble_of(lcred, i4);
+        const uint32_t col = X ? (k0 ? a2 : (k1 ? cL + a3 : 0u)) : 0u, port = (X & k2) ? a3 : 0u;
+        const uint32_t pw0 = dword_of(rw0, rw1, rw2, rw3, tgt);   // the target's row word as loaded
+        STAMP(3);
+        // ---------------- the table loads: node record, source firewall word, authorisation word, descriptor (three vectors) ----------------
+        // byte offsets into the hot image (32 bits: HotLayout::bytes is); triple < 16, so its authorisation bit is in the low dword of word 0
+        const uint32_t o_tgt = a_node + tgt * (uint32_t)sizeof(HotNode), o_src = a_node + src * (uint32_t)sizeof(HotNode);
+        const uint32_t o_auth = a_auth + ((tgt * cP + port) * a_aw) * 8u;
+        const uint32_t o_desc = a_desc + (tgt * (cL + cR) + col) * (uint32_t)sizeof(HotDesc);
+        const auto* tp = MCBS_GLOBAL(const np_u32x4, tb + o_tgt);
+        const uint4 t0 = np_load(tp), t1 = np_load(tp + 1);              // {props lo, hi, value, fw_in_allow} {fw_out_allow, listen, svc, flags}
+        const uint32_t src_fw_out = *MCBS_GLOBAL(const uint32_t, tb + o_src + offsetof(HotNode, fw_out_allow));
+        const uint32_t auth = *MCBS_GLOBAL(const uint32_t, tb + o_auth);
+        const auto* dp = MCBS_GLOBAL(const np_u32x4, tb + o_desc);
+        const uint4 d0 = np_load(dp), d1 = np_load(dp + 1);   // {cost lo,hi, probe lo,hi} {payload_off, cnt | tt << 16, kind | level << 8 | slot << 16, -}
+        const uint4 d2 = np_load(dp + 2);              // the one payload entry {node | cred << 16, triple | port << 16}
+        __builtin_amdgcn_sched_barrier(0);    // all seven go out together (Lane::act)
+
+        // ---------------- what the level-1 data alone decide ----------------
+        const uint32_t live_m = lanes_mask(live), X_m = lanes_mask(X), k2_m = lanes_mask(k2), oob_f = lanes_mask(oob) & F_OOB;
+        const uint32_t so_m = X_m & bit_mask(pk.x, src + 16u);          // the source is owned (agent installed), else INVALID_ACTION
+        const uint32_t running_m = bit_mask(pk.y, tgt + 16u), already_m = bit_mask(pk.x, tgt + 16u), ever_m = bit_mask(pk.y, tgt);
+        const uint32_t nopriv_m = ~(bit_mask(pk.z, tgt) | bit_mask(pk.z, tgt + 16u));
+        const uint32_t tbit = 1u << tgt;
+        const uint32_t step = h0.x - live_m;                             // a live env's step counter always moves
+        const uint32_t trunc_pre = lanes_mask(live & (g_max != 0) & (step >= g_max));
+        const uint32_t dead_flags = old_flags & ~live_m;                 // an ended or skipped env keeps its flags
+        const uint32_t s_ever = tiny_p + 4u, s_since = s_ever + tiny_v;   // (tiny_v == 0: no slot, nothing is ever shifted there)
+        const uint32_t ever_f = __builtin_amdgcn_ubfe(pw0, s_ever, tiny_v), since_f = __builtin_amdgcn_ubfe(pw0, s_since, tiny_v);
+        const uint32_t props0 = pw0 & ((1u << tiny_p) - 1u);
+        // the seven store addresses, as global (not generic) pointers: the output pointers went through the pin as plain values
+        const uint64_t q_lists = (uint64_t)(reinterpret_cast<uint4*>(S.masks) + S.E + e), q_sets = (uint64_t)(reinterpret_cast<uint4*>(S.masks) + e),
+                 q_row = (uint64_t)(reinterpret_cast<uint32_t*>(body) + tgt), q_h0 = (uint64_t)(S.h0 + e), q_h1 = (uint64_t)(S.h1 + e),
+                 q_reward = (uint64_t)(o_reward + e), q_term = (uint64_t)(o_term + e);
+        auto* const p_lists = MCBS_GLOBAL(np_u32x4, q_lists);
+        auto* const p_sets = MCBS_GLOBAL(np_u32x4, q_sets);
+        auto* const p_row = MCBS_GLOBAL(uint32_t, q_row);
+        auto* const p_h0 = MCBS_GLOBAL(np_u32x4, q_h0);
+        auto* const p_h1 = MCBS_GLOBAL(np_f64x2, q_h1);
+        auto* const p_reward = MCBS_GLOBAL(float, q_reward);
+        auto* const p_term = MCBS_GLOBAL(uint8_t, q_term);
+#undef MCBS_GLOBAL
+        __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): every load of the step has landed; the stores start below (Lane::act)
+
+        // ---------------- the checks, as masks ----------------
+        // connect: both firewalls and the listening port are one word test; then running, then the credential.  Exploit: running, then
+        // the vulnerability exists.  The outcome kind as a one-hot word: kinds are < 10, 0xFF (absent) lands on bit 31.
+        const uint32_t reach_m = bit_mask(src_fw_out & t0.w & t1.y, port);
+        const uint32_t auth_m = bit_mask(auth, triple);
+        const uint32_t vk = d1.z & 0xFFu, kb = opaque(1u << (d1.z & 31u));
+        const uint32_t present_m = ~bit_mask(kb, 31u);
+        const uint32_t go_m = so_m & running_m & pick(k2_m, reach_m & auth_m, present_m);   // the action takes effect
+        const uint32_t xb_m = go_m & ~k2_m;                                                 // ... and is an exploit
+        // __mark_node_as_owned: a connect to a node not owned now; from NoAccess the privilege becomes LocalUser (bit-plane 0)
+        const uint32_t newly_m = go_m & k2_m & ~already_m;
+        const uint32_t first_m = newly_m & ~ever_m, chg_m = newly_m & nopriv_m;
+        uint4 add = make_uint4((tbit << 16) & newly_m, tbit & newly_m, tbit & chg_m, 0u);
+        const uint32_t owned = (h0.w & 0xFFFFu) - chg_m;
+        // exploit bookkeeping: probe, first / repeated attack of the slot, the one leak entry
+        const uint32_t probe_m = xb_m & bit_mask(kb, (uint32_t)MCBS_OUT_PROBE_SUCCEEDED);
+        const uint32_t pr_lo = d0.z & probe_m, pr_hi = d0.w & probe_m;       // (a packed row has no property above bit 31: all of pr_hi is new)
+        const uint32_t slot = (d1.z >> 16) & 0x1Fu, sb = (1u << slot) & xb_m;
+        const uint32_t e_m = bit_mask(ever_f, slot), s_m = bit_mask(since_f, slot);
+        int vi = (int)(first_m & t0.z);                                       // connect: the node's value the first time it is owned
+        vi += 2 * (__popc(pr_lo & ~props0) + __popc(pr_hi));
+        vi += (int)(xb_m & pick(e_m, s_m, 7u));                               // repeated since re-imaging -1, repeated 0, first time +7
+        const uint32_t addrow = (newly_m & t0.x) | pr_lo | (sb << s_ever) | (sb << s_since);
+        // the leak: no payload count of the topology is above 1 (no MCBS_TOPO_MULTI_LEAK), so "cnt != 0" is bit 0; node, credential and
+        // triple ids are < 16 (packed batch), and a bit extract reads five bits of its offset: no masking
+        const uint32_t creds_m = bit_mask(kb, (uint32_t)MCBS_OUT_LEAKED_CREDENTIALS);
+        const uint32_t on_m = xb_m & (creds_m | bit_mask(kb, (uint32_t)MCBS_OUT_LEAKED_NODES)) & bit_mask(d1.y, 0u);
+        const uint32_t new_n = on_m & ~bit_mask(pk.x, d2.x);
+        const uint32_t new_g = on_m & creds_m & ~bit_mask(pk.w, d2.x >> 16);
+        const uint32_t new_c = on_m & creds_m & ~bit_mask(pk.w, d2.y | 16u);
+        add.x |= (1u << (d2.x & 31u)) & new_n;
+        add.w = ((1u << ((d2.x >> 16) & 31u)) & new_g) | ((0x10000u << (d2.y & 15u)) & new_c);
+        const uint64_t dl = (uint64_t)(d2.x & 0xFu & new_n) << ((n_disc & 15u) * 4u), cl = (uint64_t)(d2.y & 0xFu & new_c) << ((n_creds & 15u) * 4u);
+        vi += (int)((new_n & 5u) + (new_g & 3u));
+        // max(0, raw) (env.py:1169).  raw is positive only for an action that took effect: the integer above minus the vulnerability's
+        // cost (an exploit; a connect costs nothing).  (double)vi - 0.0 is (double)vi, and a difference of an integer and a cost is
+        // -0.0 for no pair of values (x - y is -0.0 only for x = -0.0, y = +0.0), so the maximum with +0.0 is the reference's choice
+        const double raw = (double)vi - __hiloint2double((int)(d0.y & xb_m), (int)(d0.x & xb_m));
+        const double r_pos = fmax(raw, 0.0);
+
+        // ---------------- stores of the attacker's action: lists word, row, as old | add where that differs ----------------
+        if (MCBS_CHANGED(((uint32_t)dl | (uint32_t)(dl >> 32) | (uint32_t)cl | (uint32_t)(cl >> 32)) != 0u))
+            np_store(p_lists, lists0.x | (uint32_t)dl, lists0.y | (uint32_t)(dl >> 32), lists0.z | (uint32_t)cl, lists0.w | (uint32_t)(cl >> 32));
+        if (MCBS_CHANGED((addrow & ~pw0) != 0u)) *p_row = pw0 | addrow;
+        STAMP(4);
+        // ---------------- goals (env.py:1080-1116), reward, flags, header ----------------
+        const bool play = live & !oob;
+        const bool win = play & (g_has != 0) & !(h1.x < __longlong_as_double(g_reward)) & !(owned < g_own) & !(owned < g_pctmin);
+        const bool lose = play & !win & (g_evict != 0) & (owned == 0);
+        const uint32_t win_m = lanes_mask(win), lose_m = lanes_mask(lose), done_m = win_m | lose_m;
+        // (an env that does not play has r_pos == 0: its action did not execute)
+        const uint32_t r_lo = ((uint32_t)g_win & win_m) | ((uint32_t)g_lose & lose_m) | ((uint32_t)__double2loint(r_pos) & ~done_m);
+        const uint32_t r_hi = ((uint32_t)(g_win >> 32) & win_m) | ((uint32_t)(g_lose >> 32) & lose_m) | ((uint32_t)__double2hiint(r_pos) & ~done_m);
+        const double reward = __hiloint2double((int)r_hi, (int)r_lo);
+        h1.x += reward;
+        const uint32_t trunc_m = trunc_pre & ~done_m;
+        *p_reward = (float)reward;
+        *p_term = (uint8_t)(((done_m | dead_flags) & F_DONE));
+        need_reset = ((done_m | trunc_m) != 0u) & (g_auto != 0);
+        const uint32_t okind = go_m & pick(k2_m, (uint32_t)MCBS_OUT_LATERAL_MOVE, vk);
+        const uint32_t flags = dead_flags | oob_f | (okind << F_KIND_SHIFT) | (new_n & (1u << F_NEWNODES_SHIFT)) | (new_c & (1u << F_NEWCREDS_SHIFT)) |
+                               (done_m & F_DONE) | (trunc_m & F_TRUNC);
+        // a live env's step counter always moves; an ended or skipped env's header stays as it was
+        if (MCBS_CHANGED(live)) np_store(p_h0, step, flags, h0.z - new_n + (new_c & 0x10000u), h0.w - chg_m);
+        if (MCBS_CHANGED(differs(h1, h1_in))) { np_f64x2 v; v.x = h1.x; v.y = h1.y; *p_h1 = v; }
+        if (MCBS_CHANGED(((add.x & ~pk.x) | (add.y & ~pk.y) | (add.z & ~pk.z) | (add.w & ~pk.w)) != 0u))
+            np_store(p_sets, pk.x | add.x, pk.y | add.y, pk.z | add.z, pk.w | add.w);
+    }
+    STAMP(5);
+    // an env that just ended is re-initialised by its own lane, with stores only (step_body)
+    if (need_reset) {
+        uint4* dst = reinterpret_cast<uint4*>(S.body + (size_t)e * S.body_stride);
+        const uint32_t nv = S.body_stride >> 4;
+#pragma unroll
+        for (uint32_t i = 0; i < 16u; ++i)
+            if (i < nv) dst[i] = make_uint4(C.init_image[4 * i], C.init_image[4 * i + 1], C.init_image[4 * i + 2], C.init_image[4 * i + 3]);
+        reinterpret_cast<uint4*>(S.masks)[e] = make_uint4(C.init_packed[0], C.init_packed[1], C.init_packed[2], C.init_packed[3]);
+        reinterpret_cast<uint4*>(S.masks)[S.E + e] = make_uint4(C.init_lists[0], C.init_lists[1], C.init_lists[2], C.init_lists[3]);
+        S.h0[e] = make_uint4(0u, 0u, C.n_init, C.n_init);
+        S.h1[e] = make_double2(0.0, 1.0);
+        S.episode[e] = episode + 1u;
+        S.pending[e] = 0.0;
+    }
+#ifdef MCBS_DIAG
+    STAMP(6);
+    if (io.stamps && (threadIdx.x & 63u) == 0) {
+        unsigned long long* o = io.stamps + (size_t)(e >> 6) * 8;
+        for (int i = 0; i < 7; ++i) o[i] = st_[i];
+        o[7] = __builtin_amdgcn_s_memrealtime();
+    }
+#endif
+}
+
 // One launch = one CyberBattleEnv.step of every env.  The argument list must stay below 256 bytes (mcbs_api.hip make_io): the random
 // agent's parameters therefore travel only with the looping variant below, which is launched once per K steps.
 template <int PHASE, int WTP, bool TOPO_LDS, int DEFK>
@@ -959,8 +1201,13 @@ __global__ __launch_bounds__(256) void step_kernel(const StepCfg* __restrict__ C
 #ifdef MCBS_DIAG
     io.stamps = a.stamps;
 #endif
+#if MCBS_NARROW_PRED
+    static_assert(kNarrowStepCan == (MCBS_TOPO_PROBE | MCBS_TOPO_WIDE_ROWS), "step_body_narrow is written for exactly these traits");
+    step_body_narrow(S, T, Cp, io);
+#else
     NoHook nh;
     step_body<0, 0, MCBS_DEFENDER_NONE, false, true, NoHook, kNarrowStepCan>(S, T, Cp, io, RollArgs{}, nh);
+#endif
 }
 
 // mcbs_step_many / mcbs_rollout_random: io.n_steps consecutive steps in one launch; `roll` is a kernel ARGUMENT (nothing in device
