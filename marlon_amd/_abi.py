@@ -1,4 +1,5 @@
-"""ctypes mirrors of the structs in include/mcbs.h (same field order, natural alignment)."""
+"""The C ABI of include/mcbs.h as Python states it: its constants, ctypes mirrors of its structs (same field order, natural alignment) and
+PROTOTYPES, the one table of its functions."""
 from __future__ import annotations
 
 import ctypes as C
@@ -13,6 +14,10 @@ RNG_PHILOX, RNG_TAPE = 0, 1
 # MCBS_TOPO_* (include/mcbs.h): what a topology's descriptors and node count make possible (mcbs_topology_traits, mcbs_step_topo_traits)
 TOPO_ESCALATION, TOPO_LATERAL_EXPLOIT, TOPO_PRECONDITION, TOPO_PROBE, TOPO_MULTI_LEAK, TOPO_WIDE_ROWS = 1, 2, 4, 8, 16, 32
 TOPO_ANY = 63
+CATEGORICAL_MODES = {"sample": 0, "argmax": 1, "evaluate": 2}      # MCBS_CATEGORICAL_SAMPLE / _ARGMAX / _EVALUATE
+CATEGORICAL_PHILOX_DOMAIN = 0xCA7E6041                              # MCBS_CATEGORICAL_PHILOX_DOMAIN
+MCBS_MAX_ACTION_DIMS, MCBS_MULTICATEGORICAL_PHILOX_DOMAIN = 16, 0x3C47E6A1     # the MultiDiscrete head
+MCBS_LINEAR_MAX_H, MCBS_LINEAR_GRAD_ROW_BLOCK = 512, 512                       # the masked action head from the latent and its gradient
 
 
 class BatchCfg(C.Structure):
@@ -82,42 +87,115 @@ class GaeIO(C.Structure):
 assert C.sizeof(GaeIO) == 144
 
 
-# the MultiDiscrete head (include/mcbs.h): its two constants and the prototypes of its two entry points
-MCBS_MAX_ACTION_DIMS = 16
-MCBS_MULTICATEGORICAL_PHILOX_DOMAIN = 0x3C47E6A1
-MULTICATEGORICAL_ARGTYPES = {
-    # batch, nvec (host), n_dims, n_rows, logits, dtype, row_stride, mode, actions, log_prob, entropy, uniforms, seed, step, row_key_base,
-    # bad_actions, stream
-    "mcbs_multicategorical": [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_int32, C.c_void_p,
-                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p],
-    # batch, nvec (host), n_dims, n_rows, logits, dtype, row_stride, actions, grad_log_prob, grad_entropy, grad_logits, grad_row_stride, stream
-    "mcbs_multicategorical_grad": [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32, C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p,
-                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
-}
-
-
-# the masked action head from the latent (include/mcbs.h): the prototypes of its two entry points
-MCBS_LINEAR_MAX_H = 512
-# latent, latent_row_stride, weight, weight_row_stride, bias, H, dtype, mode, actions, log_prob, entropy, n_allowed, uniforms, seed, step,
-# bad_actions, stream
-_LINEAR_CATEGORICAL_TAIL = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-LINEAR_CATEGORICAL_ARGTYPES = {
-    "mcbs_masked_linear_categorical": [C.c_void_p] + _LINEAR_CATEGORICAL_TAIL,                                          # batch
-    "mcbs_masked_linear_categorical_packed": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64] + _LINEAR_CATEGORICAL_TAIL,   # batch, bits, bits_row_words, n_rows
-    # batch, n_rows, H -> bytes
-    "mcbs_masked_linear_categorical_grad_workspace": [C.c_void_p, C.c_uint64, C.c_uint32],
-    # batch, bits, bits_row_words, n_rows, latent, latent_row_stride, weight, weight_row_stride, bias, H, dtype, actions, grad_log_prob,
-    # grad_entropy, grad_latent, grad_latent_row_stride, grad_weight, grad_weight_row_stride, grad_bias, workspace, workspace_bytes, stream
-    "mcbs_masked_linear_categorical_grad": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
-                                            C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                            C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p],
-}
-LINEAR_CATEGORICAL_RESTYPES = {"mcbs_masked_linear_categorical_grad_workspace": C.c_size_t}
-MCBS_LINEAR_GRAD_ROW_BLOCK = 512
-
 class InfoBuffers(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("network_availability", "step_count", "truncated", "out_of_bound", "raw_reward")]
+
+
+class RowCopies(C.Structure):
+    """mcbs_row_copies (include/mcbs.h): up to eight (src, dst, row_bytes) triples for mcbs_copy_rows_masked."""
+    _fields_ = [("n", C.c_uint32), ("pad", C.c_uint32), ("src", C.c_void_p * 8), ("dst", C.c_void_p * 8), ("row_bytes", C.c_size_t * 8)]
+
+
+# ---- the prototypes of include/mcbs.h: THE declaration of the C ABI on the Python side.  engine.load_library applies it, engine.EXPORTS is
+# its keys, and tests/test_native_library.py holds every entry (and every struct and constant of this file) to the header.  A new entry
+# point is bound by adding its line here, in the header's order, with the header's parameter names beside it. ----
+_int, _i32, _u32, _u64, _size, _f32 = C.c_int, C.c_int32, C.c_uint32, C.c_uint64, C.c_size_t, C.c_float
+_H = C.c_void_p                    # a handle: mcbs_batch*, mcbs_topology*, mcbs_feature_layout*, mcbs_obs_packing*
+_P = C.c_void_p                    # an array on the device or the host, or an argument block handed over with byref()
+_S = C.c_void_p                    # void* stream (a hipStream_t)
+_NEW = C.POINTER(C.c_void_p)       # mcbs_x** out: receives a new handle
+_OBS, _INFO, _DOBS = C.POINTER(ObsBuffers), C.POINTER(InfoBuffers), C.POINTER(DefenderObs)
+# logits, dtype, row_stride, mode, actions, log_prob, entropy, n_allowed, uniforms, seed, step, bad_actions, stream
+_CAT = [_P, _i32, _size, _i32, _P, _P, _P, _P, _P, _u64, _u64, _P, _S]
+# latent, latent_row_stride, weight, weight_row_stride, bias, H, dtype, mode, actions, log_prob, entropy, n_allowed, uniforms, seed, step,
+# bad_actions, stream
+_LIN = [_P, _size, _P, _size, _P, _u32, _i32, _i32, _P, _P, _P, _P, _P, _u64, _u64, _P, _S]
+_BITS = [_H, _P, _size, _u64]      # batch, bits, bits_row_words, n_rows
+
+PROTOTYPES = {
+    "mcbs_last_error": (C.c_char_p, []),
+    "mcbs_abi_version": (_u32, []),
+    "mcbs_topology_create": (_int, [_P, _size, _i32, _NEW]),                                  # blob, nbytes, device, out
+    "mcbs_topology_destroy": (None, [_H]),
+    "mcbs_batch_create": (_int, [_H, C.POINTER(BatchCfg), _NEW]),                             # topology, cfg, out
+    "mcbs_batch_destroy": (None, [_H]),
+    "mcbs_reset": (_int, [_H, _P, _S]),                                                       # batch, env_mask, stream
+    "mcbs_rewind": (_int, [_H, _S]),
+    "mcbs_step": (_int, [_H, _P, _P, _P, _INFO, _S]),                                         # batch, actions, reward, terminated, info, stream
+    "mcbs_step_many": (_int, [_H, _P, _P, _P, _u32, _S]),                                     # batch, actions, reward, terminated, n_steps, stream
+    # batch, valid, seed, first_step, n_steps, actions_out, reward, terminated, stream
+    "mcbs_rollout_random": (_int, [_H, _i32, _u64, _u64, _u32, _P, _P, _P, _S]),
+    "mcbs_step_observe": (_int, [_H, _P, _P, _P, _INFO, _OBS, _S]),                           # batch, actions, reward, terminated, info, obs, stream
+    "mcbs_observe": (_int, [_H, _OBS, _S]),                                                   # batch, obs, stream
+    "mcbs_observe_masked": (_int, [_H, _OBS, _P, _S]),                                        # batch, obs, env_mask, stream
+    "mcbs_action_mask": (_int, [_H, _OBS, _S]),                                               # batch, masks, stream
+    "mcbs_set_mask_discrete_stride": (_int, [_H, _size]),                                     # batch, stride_bytes
+    "mcbs_step_info": (_int, [_H, _INFO, _S]),                                                # batch, info, stream
+    "mcbs_sample_actions": (_int, [_H, _i32, _u64, _u64, _P, _S]),                            # batch, valid, seed, step, actions_out, stream
+    "mcbs_decode_attacker_actions": (_int, [_H, _P, _P, _P, _P, _S]),                         # batch, multidiscrete, discrete, actions_out, invalid_out, stream
+    "mcbs_discrete_action_count": (_u64, [_H]),
+    "mcbs_mask_logits": (_int, [_H, _P, _i32, _size, _f32, _S]),                              # batch, logits, dtype, row_stride, fill, stream
+    "mcbs_pack_action_mask": (_int, [_H, _P, _size, _S]),                                     # batch, bits, row_words, stream
+    # batch, bits, bits_row_words, logits, dtype, logits_row_stride, n_rows, fill, stream
+    "mcbs_apply_packed_mask": (_int, [_H, _P, _size, _P, _i32, _size, _u64, _f32, _S]),
+    "mcbs_unpack_action_mask": (_int, [_H, _P, _size, _P, _size, _u64, _S]),                  # batch, bits, bits_row_words, out, out_row_stride, n_rows, stream
+    "mcbs_mask_key_words": (_u64, [_H]),
+    "mcbs_store_mask_keys": (_int, [_H, _P, _size, _S]),                                      # batch, keys, row_words, stream
+    # batch, keys, key_row_words, index, n_source_rows, bits, bits_row_words, n_rows, stream
+    "mcbs_expand_mask_keys": (_int, [_H, _P, _size, _P, _u64, _P, _size, _u64, _S]),
+    "mcbs_masked_categorical": (_int, [_H] + _CAT),                                           # batch, then _CAT
+    "mcbs_masked_categorical_packed": (_int, _BITS + _CAT),                                   # _BITS, then _CAT
+    "mcbs_masked_linear_categorical": (_int, [_H] + _LIN),                                    # batch, then _LIN
+    "mcbs_masked_linear_categorical_packed": (_int, _BITS + _LIN),                            # _BITS, then _LIN
+    # _BITS, logits, dtype, row_stride, actions, grad_log_prob, grad_entropy, grad_logits, grad_row_stride, stream
+    "mcbs_masked_categorical_grad": (_int, _BITS + [_P, _i32, _size, _P, _P, _P, _P, _size, _S]),
+    "mcbs_masked_linear_categorical_grad_workspace": (_size, [_H, _u64, _u32]),               # batch, n_rows, H -> bytes
+    # _BITS, latent, latent_row_stride, weight, weight_row_stride, bias, H, dtype, actions, grad_log_prob, grad_entropy, grad_latent,
+    # grad_latent_row_stride, grad_weight, grad_weight_row_stride, grad_bias, workspace, workspace_bytes, stream
+    "mcbs_masked_linear_categorical_grad": (_int, _BITS + [_P, _size, _P, _size, _P, _u32, _i32, _P, _P, _P, _P, _size, _P, _size, _P, _P, _size, _S]),
+    # batch, nvec (host), n_dims, n_rows, logits, dtype, row_stride, mode, actions, log_prob, entropy, uniforms, seed, step, row_key_base,
+    # bad_actions, stream
+    "mcbs_multicategorical": (_int, [_H, C.POINTER(_u32), _u32, _u64, _P, _i32, _size, _i32, _P, _P, _P, _P, _u64, _u64, _u64, _P, _S]),
+    # batch, nvec (host), n_dims, n_rows, logits, dtype, row_stride, actions, grad_log_prob, grad_entropy, grad_logits, grad_row_stride, stream
+    "mcbs_multicategorical_grad": (_int, [_H, C.POINTER(_u32), _u32, _u64, _P, _i32, _size, _P, _P, _P, _P, _size, _S]),
+    "mcbs_gae": (_int, [_H, C.POINTER(GaeIO), _S]),                                           # batch, io, stream
+    "mcbs_feature_layout_create": (_int, [_H, _P, _size, _P, _size, _NEW]),                   # batch, desc, n_desc, mask_ranges, n_mask_ranges, out
+    "mcbs_feature_layout_destroy": (None, [_H]),
+    "mcbs_feature_layout_width": (_u64, [_H]),
+    # batch, layout, obs, bits, bits_row_words, out, dtype, out_row_stride, n_rows, out_of_range, stream
+    "mcbs_encode_features": (_int, [_H, _H, _OBS, _P, _size, _P, _i32, _size, _u64, _P, _S]),
+    "mcbs_obs_packing_create": (_int, [_H, _P, _size, _NEW]),                                 # batch, valid_codes, n_values, out
+    "mcbs_obs_packing_destroy": (None, [_H]),
+    "mcbs_obs_packing_words": (_u64, [_H]),
+    "mcbs_pack_observation": (_int, [_H, _H, _OBS, _P, _size, _u64, _P, _S]),                 # batch, packing, obs, out, out_row_words, n_rows, out_of_range, stream
+    # batch, packing, packed, row_words, index, n_source_rows, n_rows, out, stream
+    "mcbs_unpack_observation": (_int, [_H, _H, _P, _size, _P, _u64, _u64, _OBS, _S]),
+    # batch, layout, packing, packed, packed_row_words, bits, bits_row_words, index, n_source_rows, out, dtype, out_row_stride, n_rows,
+    # out_of_range, stream
+    "mcbs_encode_features_packed": (_int, [_H, _H, _H, _P, _size, _P, _size, _P, _u64, _P, _i32, _size, _u64, _P, _S]),
+    "mcbs_defender_step": (_int, [_H, _P, _P, _P, _P, _DOBS, _S]),                            # batch, actions, valid, availability, evicted, obs, stream
+    "mcbs_defender_observe": (_int, [_H, _DOBS, _S]),                                         # batch, obs, stream
+    "mcbs_set_draw_tape": (_int, [_H, _P, _u32]),                                             # batch, tape, draws_per_step
+    "mcbs_attacker_wrapper_post": (_int, [_H, _P, _f32, _i32, _S]),                           # batch, w, invalid_action_reward_modifier, max_timesteps, stream
+    "mcbs_attacker_wrapper_clear": (_int, [_H, _P, _S]),                                      # batch, w, stream
+    "mcbs_copy_rows_masked": (_int, [_H, _P, _P, _S]),                                        # batch, copies, env_mask, stream
+    # batch, multidiscrete, discrete, decoded, info, obs, w, invalid_action_reward_modifier, max_timesteps, auto_reset, keep, fresh, stream
+    "mcbs_attacker_wrapper_step": (_int, [_H, _P, _P, _P, _P, _P, _P, _f32, _i32, _i32, _P, _P, _S]),
+    # batch, w, invalid_action_reward_modifier, max_timesteps, auto_reset, keep, fresh, stream
+    "mcbs_attacker_wrapper_finish": (_int, [_H, _P, _f32, _i32, _i32, _P, _P, _S]),
+    "mcbs_attacker_wrapper_step_launches": (_i32, [_H, _i32]),                                # batch, with_masks
+    "mcbs_defender_wrapper_post": (_int, [_H, _P, _P, _S]),                                   # batch, w, cfg, stream
+    "mcbs_defender_wrapper_step": (_int, [_H, _P, _P, _P, _P, _S]),                           # batch, actions, obs, w, cfg, stream
+    "mcbs_state_record_bytes": (_size, [_H]),
+    "mcbs_get_state": (_int, [_H, _P, _size]),                                                # batch, host_buf, nbytes
+    "mcbs_set_state": (_int, [_H, _P, _size]),                                                # batch, host_buf, nbytes
+    "mcbs_batch_variant": (_int, [_H, C.POINTER(BatchVariantInfo)]),                          # batch, out
+    "mcbs_step_is_lean": (_i32, [_H, _i32]),                                                  # batch, with_info
+    "mcbs_topology_traits": (_int, [_P, _size, C.POINTER(_u32)]),                             # blob, nbytes, traits
+    "mcbs_step_topo_traits": (_i32, [_H, _i32, C.POINTER(_u32)]),                             # batch, with_info, traits
+    "mcbs_timing_enable": (_int, [_H, _i32]),                                                 # batch, on
+    "mcbs_timing_read": (_int, [_H, C.POINTER(C.c_double), C.POINTER(_u64)]),                 # batch, total_ms, launches
+}
 
 
 STATE_HEADER_DT = np.dtype([
@@ -220,7 +298,3 @@ class EnvSpec:
         c.env_id_base = int(self.env_id_base)
         return c
 
-
-class RowCopies(C.Structure):
-    """mcbs_row_copies (include/mcbs.h): up to eight (src, dst, row_bytes) triples for mcbs_copy_rows_masked."""
-    _fields_ = [("n", C.c_uint32), ("pad", C.c_uint32), ("src", C.c_void_p * 8), ("dst", C.c_void_p * 8), ("row_bytes", C.c_size_t * 8)]

@@ -14,31 +14,14 @@ from typing import Dict, Iterable, Optional
 
 import numpy as np
 
-from ._abi import (LINEAR_CATEGORICAL_ARGTYPES, LINEAR_CATEGORICAL_RESTYPES, MCBS_LINEAR_GRAD_ROW_BLOCK, MCBS_LINEAR_MAX_H, MULTICATEGORICAL_ARGTYPES, BatchCfg, BatchVariantInfo, DefenderObs, EnvSpec, GaeIO, InfoBuffers, ObsBuffers,
-                   split_state, state_record_bytes)
+from ._abi import (CATEGORICAL_MODES, CATEGORICAL_PHILOX_DOMAIN, MCBS_LINEAR_MAX_H, PROTOTYPES, BatchCfg, BatchVariantInfo, DefenderObs,  # noqa: F401
+                   EnvSpec, GaeIO, InfoBuffers, ObsBuffers, RowCopies, STATE_HEADER_DT, STATE_NODE_DT, split_state, state_record_bytes)
 from .flatten import FlatTopology
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmcbs.so")
 
-EXPORTS = [
-    "mcbs_last_error", "mcbs_abi_version", "mcbs_topology_create", "mcbs_topology_destroy", "mcbs_batch_create",
-    "mcbs_batch_destroy", "mcbs_reset", "mcbs_rewind", "mcbs_step", "mcbs_step_observe", "mcbs_observe", "mcbs_observe_masked", "mcbs_action_mask", "mcbs_step_info",
-    "mcbs_step_many", "mcbs_rollout_random", "mcbs_attacker_wrapper_post", "mcbs_attacker_wrapper_clear", "mcbs_defender_wrapper_post", "mcbs_sample_actions", "mcbs_decode_attacker_actions", "mcbs_defender_step", "mcbs_defender_observe", "mcbs_set_draw_tape", "mcbs_state_record_bytes", "mcbs_get_state", "mcbs_set_state",
-    "mcbs_timing_enable", "mcbs_timing_read", "mcbs_mask_logits", "mcbs_discrete_action_count", "mcbs_copy_rows_masked", "mcbs_attacker_wrapper_finish", "mcbs_attacker_wrapper_step",
-    "mcbs_attacker_wrapper_step_launches", "mcbs_set_mask_discrete_stride", "mcbs_defender_wrapper_step",
-    "mcbs_pack_action_mask", "mcbs_apply_packed_mask", "mcbs_unpack_action_mask", "mcbs_batch_variant", "mcbs_step_is_lean",
-    "mcbs_topology_traits", "mcbs_step_topo_traits",
-    "mcbs_feature_layout_create", "mcbs_feature_layout_destroy", "mcbs_feature_layout_width", "mcbs_encode_features",
-    "mcbs_masked_categorical", "mcbs_masked_categorical_packed", "mcbs_masked_categorical_grad",
-    "mcbs_masked_linear_categorical", "mcbs_masked_linear_categorical_packed",
-    "mcbs_masked_linear_categorical_grad_workspace", "mcbs_masked_linear_categorical_grad",
-    "mcbs_multicategorical", "mcbs_multicategorical_grad",
-    "mcbs_gae",
-    "mcbs_obs_packing_create", "mcbs_obs_packing_destroy", "mcbs_obs_packing_words", "mcbs_pack_observation", "mcbs_unpack_observation",
-    "mcbs_encode_features_packed",
-    "mcbs_mask_key_words", "mcbs_store_mask_keys", "mcbs_expand_mask_keys",
-]
+EXPORTS = list(PROTOTYPES)          # every function of include/mcbs.h: _abi.PROTOTYPES is where the C ABI is declared
 
 _lib = None
 
@@ -69,95 +52,11 @@ def load_library(path: Optional[str] = None):
     except ImportError:
         pass
     lib = C.CDLL(p)
-    lib.mcbs_last_error.restype = C.c_char_p
-    lib.mcbs_abi_version.restype = C.c_uint32
-    lib.mcbs_topology_create.argtypes = [C.c_void_p, C.c_size_t, C.c_int32, C.POINTER(C.c_void_p)]
-    lib.mcbs_topology_destroy.argtypes = [C.c_void_p]
-    lib.mcbs_batch_create.argtypes = [C.c_void_p, C.POINTER(BatchCfg), C.POINTER(C.c_void_p)]
-    lib.mcbs_batch_destroy.argtypes = [C.c_void_p]
-    lib.mcbs_reset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mcbs_rewind.argtypes = [C.c_void_p, C.c_void_p]
-    lib.mcbs_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(InfoBuffers), C.c_void_p]
-    lib.mcbs_step_many.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
-    lib.mcbs_attacker_wrapper_post.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_void_p]
-    lib.mcbs_defender_wrapper_post.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mcbs_attacker_wrapper_clear.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mcbs_rollout_random.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mcbs_step_observe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(InfoBuffers),
-                                      C.POINTER(ObsBuffers), C.c_void_p]
-    lib.mcbs_observe.argtypes = [C.c_void_p, C.POINTER(ObsBuffers), C.c_void_p]
-    lib.mcbs_observe_masked.argtypes = [C.c_void_p, C.POINTER(ObsBuffers), C.c_void_p, C.c_void_p]
-    lib.mcbs_action_mask.argtypes = [C.c_void_p, C.POINTER(ObsBuffers), C.c_void_p]
-    lib.mcbs_step_info.argtypes = [C.c_void_p, C.POINTER(InfoBuffers), C.c_void_p]
-    lib.mcbs_sample_actions.argtypes = [C.c_void_p, C.c_int32, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.mcbs_decode_attacker_actions.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mcbs_defender_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(DefenderObs), C.c_void_p]
-    lib.mcbs_defender_observe.argtypes = [C.c_void_p, C.POINTER(DefenderObs), C.c_void_p]
-    lib.mcbs_defender_wrapper_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mcbs_set_draw_tape.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
-    lib.mcbs_state_record_bytes.restype = C.c_size_t
-    lib.mcbs_state_record_bytes.argtypes = [C.c_void_p]
-    lib.mcbs_get_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.mcbs_set_state.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    lib.mcbs_discrete_action_count.restype = C.c_uint64
-    lib.mcbs_discrete_action_count.argtypes = [C.c_void_p]
-    lib.mcbs_mask_logits.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t, C.c_float, C.c_void_p]
-    lib.mcbs_pack_action_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.mcbs_apply_packed_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_size_t, C.c_uint64, C.c_float, C.c_void_p]
-    lib.mcbs_unpack_action_mask.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]
-    lib.mcbs_mask_key_words.restype = C.c_uint64
-    lib.mcbs_mask_key_words.argtypes = [C.c_void_p]
-    lib.mcbs_store_mask_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    # batch, keys, key_row_words, index, n_source_rows, bits, bits_row_words, n_rows, stream
-    lib.mcbs_expand_mask_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p]
-    lib.mcbs_feature_layout_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
-    lib.mcbs_feature_layout_destroy.argtypes = [C.c_void_p]
-    lib.mcbs_feature_layout_destroy.restype = None
-    lib.mcbs_feature_layout_width.restype = C.c_uint64
-    lib.mcbs_feature_layout_width.argtypes = [C.c_void_p]
-    lib.mcbs_encode_features.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ObsBuffers), C.c_void_p, C.c_size_t, C.c_void_p, C.c_int32, C.c_size_t,
-                                         C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.mcbs_obs_packing_create.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]
-    lib.mcbs_obs_packing_destroy.argtypes = [C.c_void_p]
-    lib.mcbs_obs_packing_destroy.restype = None
-    lib.mcbs_obs_packing_words.restype = C.c_uint64
-    lib.mcbs_obs_packing_words.argtypes = [C.c_void_p]
-    lib.mcbs_pack_observation.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(ObsBuffers), C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p]
-    lib.mcbs_unpack_observation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint64, C.c_uint64,
-                                            C.POINTER(ObsBuffers), C.c_void_p]
-    # layout, packing, packed, packed_row_words, bits, bits_row_words, index, n_source_rows, out, dtype, out_row_stride, n_rows, out_of_range, stream
-    lib.mcbs_encode_features_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p,
-                                                C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_uint64, C.c_void_p, C.c_void_p]
-    _cat =[C.c_void_p, C.c_int32, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
-            C.c_void_p, C.c_void_p]           # logits, dtype, row_stride, mode, actions, log_prob, entropy, n_allowed, uniforms, seed, step, bad_actions, stream
-    lib.mcbs_masked_categorical.argtypes = [C.c_void_p] + _cat
-    lib.mcbs_masked_categorical_packed.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64] + _cat
-    # bits, bits_row_words, n_rows, logits, dtype, row_stride, actions, grad_log_prob, grad_entropy, grad_logits, grad_row_stride, stream
-    lib.mcbs_masked_categorical_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    lib.mcbs_gae.argtypes = [C.c_void_p, C.POINTER(GaeIO), C.c_void_p]
-    lib.mcbs_copy_rows_masked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mcbs_attacker_wrapper_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
-                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mcbs_attacker_wrapper_finish.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.mcbs_attacker_wrapper_step_launches.restype = C.c_int32
-    lib.mcbs_attacker_wrapper_step_launches.argtypes = [C.c_void_p, C.c_int32]
-    lib.mcbs_set_mask_discrete_stride.argtypes = [C.c_void_p, C.c_size_t]
-    lib.mcbs_batch_variant.argtypes = [C.c_void_p, C.POINTER(BatchVariantInfo)]
-    lib.mcbs_step_is_lean.restype = C.c_int32
-    lib.mcbs_step_is_lean.argtypes = [C.c_void_p, C.c_int32]
-    lib.mcbs_topology_traits.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32)]
-    lib.mcbs_step_topo_traits.restype = C.c_int32
-    lib.mcbs_step_topo_traits.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32)]
-    lib.mcbs_timing_enable.argtypes = [C.c_void_p, C.c_int32]
-    lib.mcbs_timing_read.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
-    for name in EXPORTS:
-        if not hasattr(lib, name):
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name, None)
+        if fn is None:
             raise NativeLibraryMissing(f"{p} does not export {name}")
-    for name, argtypes in {**MULTICATEGORICAL_ARGTYPES, **LINEAR_CATEGORICAL_ARGTYPES}.items():
-        getattr(lib, name).argtypes = argtypes
-    for name, restype in LINEAR_CATEGORICAL_RESTYPES.items():
-        getattr(lib, name).restype = restype
+        fn.restype, fn.argtypes = restype, argtypes
     if path is None:
         _lib = lib
     return lib
@@ -166,6 +65,35 @@ def load_library(path: Optional[str] = None):
 def _check(lib, rc: int, what: str) -> None:
     if rc != 0:
         raise McbsError(f"{what} failed ({rc}): {lib.mcbs_last_error().decode(errors='replace')}")
+
+
+def _ptr(x):
+    """The device pointer of an optional tensor (None: NULL)."""
+    return x.data_ptr() if x is not None else None
+
+
+_U64 = 2 ** 64 - 1
+
+
+def _u64(v) -> int:
+    """A seed, step or row key as the uint64_t the library takes (negative and oversized Python ints wrap)."""
+    return int(v) & _U64
+
+
+def _describe(x) -> str:
+    """What a refused argument was, for the message: a tensor's dtype, shape, strides and device, else its type."""
+    if hasattr(x, "stride") and hasattr(x, "device"):
+        return f"{x.dtype} {list(x.shape)} with strides {list(x.stride())} on {x.device}"
+    return type(x).__name__
+
+
+def _row_stride(x, rows: int) -> int:
+    """The row stride in elements handed to the library for x, a 2-D tensor whose row count `rows` the caller has already checked
+    (x None: 0).  torch reports an arbitrary stride(0) for a dimension of size 1, so a one-row tensor's is raised to its width: the C
+    side refuses a stride below the columns it uses."""
+    if x is None:
+        return 0
+    return x.stride(0) if rows > 1 else max(x.stride(0), x.shape[1])
 
 
 def topology_traits(topo: FlatTopology) -> int:
@@ -229,8 +157,6 @@ class ObservationPackingHandle:
 
 # what BatchEngine.masked_categorical returns: actions int64 [n], log_prob float32 [n], entropy float32 [n], n_allowed int32 [n]
 MaskedCategorical = collections.namedtuple("MaskedCategorical", ["actions", "log_prob", "entropy", "n_allowed"])
-CATEGORICAL_MODES = {"sample": 0, "argmax": 1, "evaluate": 2}      # MCBS_CATEGORICAL_*
-CATEGORICAL_PHILOX_DOMAIN = 0xCA7E6041                              # MCBS_CATEGORICAL_PHILOX_DOMAIN
 
 _MASKED_EVALUATE = None
 
@@ -382,6 +308,8 @@ class BatchEngine:
                          raw_reward=torch.zeros(self.E, dtype=f32, device=dev))
         self._info_struct = InfoBuffers(**{k: v.data_ptr() for k, v in self.info.items()})
         self._feature_rows = {k: int(np.prod(self._shapes[k][0])) for k in FEATURE_FIELDS}        # int32 values per row of each field
+        # fixed at creation, and wanted by the checks of nearly every call below: asked of the library once
+        self._A, self._Wk = int(self.lib.mcbs_discrete_action_count(self._h)), int(self.lib.mcbs_mask_key_words(self._h))
         self._nvec_blocks = {}                             # multicategorical: nvec tuple -> (host uint32 array, D, A)
         self._feature_dtypes = {torch.float32: (0, 4), torch.bfloat16: (1, 2), torch.float16: (2, 2)}  # MCBS_FEATURES_* code, item size
 
@@ -390,6 +318,7 @@ class BatchEngine:
             self.torch.cuda.synchronize(self.device)
             self.lib.mcbs_batch_destroy(self._h)
             self._h = None
+            self._A = self._Wk = 0                  # what the library answers for a null batch
         if getattr(self, "_topo_h", None):
             self.lib.mcbs_topology_destroy(self._topo_h)
             self._topo_h = None
@@ -438,6 +367,39 @@ class BatchEngine:
         if tuple(a.shape) != (self.E, 5):
             raise ValueError(f"actions must have shape ({self.E}, 5), got {tuple(a.shape)}")
         return a
+
+    # the checks on tensor arguments every call below shares: each raises ValueError naming the argument, and returns the tensor
+    def _arr(self, x, dtype, shape, what: str):
+        """x: a contiguous device tensor of exactly this dtype and shape."""
+        if not isinstance(x, self.torch.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != shape or not x.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous device {dtype} tensor {list(shape)}, got {_describe(x)}")
+        return x
+
+    def _rows(self, x, dtypes, what: str, n=None, min_cols: int = 0):
+        """x: a device tensor [n, >= min_cols] (n None: any count) of one of `dtypes` with unit inner stride; the rows may lie further
+        apart.  The C side sees only the row stride: a view narrower than min_cols would have its rows read or written past their end."""
+        if (not isinstance(x, self.torch.Tensor) or x.dtype not in dtypes or x.dim() != 2 or (n is not None and x.shape[0] != n)
+                or x.stride(1) != 1 or x.device != self.device or x.shape[1] < min_cols):
+            names = " or ".join(str(d).replace("torch.", "") for d in dtypes)
+            raise ValueError(f"{what} must be a device {names} tensor [{'n' if n is None else n}, >= {min_cols}] with contiguous rows, "
+                             f"got {_describe(x)}")
+        return x
+
+    def _counter(self, x, what: str):
+        """x: the device int32 tensor of one element a call adds a count to (bad_actions, out_of_range)."""
+        if not isinstance(x, self.torch.Tensor) or x.dtype != self.torch.int32 or x.numel() != 1 or x.device != self.device:
+            raise ValueError(f"{what} must be a device int32 tensor of one element, got {_describe(x)}")
+        return x
+
+    def _dtype_code(self, x) -> int:
+        """MCBS_LOGITS_F32 / MCBS_LOGITS_BF16 of a tensor already checked to be one of the two."""
+        return 0 if x.dtype == self.torch.float32 else 1
+
+    def _logits(self, x, n, A: int):
+        """x: float32 or bfloat16 logits [n, >= A] (n None: any count) -> (pointer, dtype code, row stride): the three arguments every
+        entry point takes for them (a call with a uniform law passes None, 0, 0 for logits=None)."""
+        self._rows(x, (self.torch.float32, self.torch.bfloat16), "logits", n, A)
+        return x.data_ptr(), self._dtype_code(x), _row_stride(x, x.shape[0] if n is None else n)
 
     # -- the C ABI --
     def reset(self, env_mask=None) -> None:
@@ -491,7 +453,7 @@ class BatchEngine:
         rewards = t.empty((n_steps, self.E), dtype=t.float32, device=self.device)
         terminated = t.empty((n_steps, self.E), dtype=t.uint8, device=self.device)
         actions = t.empty((n_steps, self.E, 5), dtype=t.int32, device=self.device) if record_actions else None
-        _check(self.lib, self.lib.mcbs_rollout_random(self._h, int(bool(valid)), int(seed) & (2 ** 64 - 1), int(first_step), int(n_steps),
+        _check(self.lib, self.lib.mcbs_rollout_random(self._h, int(bool(valid)), _u64(seed), int(first_step), int(n_steps),
                                                       None if actions is None else actions.data_ptr(), rewards.data_ptr(),
                                                       terminated.data_ptr(), self._stream()), "mcbs_rollout_random")
         return rewards, terminated, actions
@@ -508,7 +470,6 @@ class BatchEngine:
     def copy_rows_masked(self, pairs, env_mask) -> None:
         """dst[e] = src[e] for the envs whose byte in env_mask (uint8 [E], device) is set, for up to eight (src, dst) pairs of
         contiguous [E, ...] tensors in one launch."""
-        from ._abi import RowCopies
         if not 0 < len(pairs) <= 8:
             raise ValueError("copy_rows_masked takes one to eight (src, dst) pairs")
         rc = RowCopies()
@@ -520,7 +481,6 @@ class BatchEngine:
         _check(self.lib, self.lib.mcbs_copy_rows_masked(self._h, C.byref(rc), env_mask.data_ptr(), self._stream()), "mcbs_copy_rows_masked")
 
     def _row_copies(self, pairs, one_row_src: bool):
-        from ._abi import RowCopies
         if len(pairs) > 8:
             raise ValueError("at most eight (src, dst) pairs per list")
         rc = RowCopies()
@@ -537,7 +497,6 @@ class BatchEngine:
         """mcbs_attacker_wrapper_finish: the wrapper's bookkeeping and — for the envs it flags done — terminal observation (`keep`:
         (obs, terminal) pairs), env reset, reset observation (`fresh`: ([1, ...] row of a freshly reset env, obs) pairs) and cleared
         counters, all in one launch.  `keep` / `fresh` may be argument blocks built once with `row_copies()`."""
-        from ._abi import RowCopies
         k = keep if isinstance(keep, RowCopies) else self._row_copies(list(keep), False)
         f = fresh if isinstance(fresh, RowCopies) else self._row_copies(list(fresh), True)
         _check(self.lib, self.lib.mcbs_attacker_wrapper_finish(self._h, C.byref(bufs), float(modifier), int(max_timesteps), int(bool(auto_reset)),
@@ -650,37 +609,25 @@ class BatchEngine:
 
     def discrete_action_count(self) -> int:
         """Size of MaskedDiscreteAttackerWrapper's Discrete space: N*N*P*C + N*L + N*N*R (action_masking.py:74-80)."""
-        return int(self.lib.mcbs_discrete_action_count(self._h))
+        return self._A
 
     def mask_logits(self, logits, fill: float = -1e8):
         """In place: logits[e, a] = mask(e, a) ? logits[e, a] : fill for the Discrete action mask of the LAST observation call
         (step_observe / observe / action_mask), rebuilt on the device from that call's per-env digest — the mask itself is never
         written.  logits: device float32 or bfloat16 [E, >= discrete_action_count()], rows contiguous."""
-        t = self.torch
-        if logits.dtype not in (t.float32, t.bfloat16):
-            raise ValueError("logits must be float32 or bfloat16")
-        # the C side sees only the row stride: a view narrower than A (wide[:, :A-1]) would have its rows written past their end
-        if (logits.dim() != 2 or logits.shape[0] != self.E or logits.stride(1) != 1 or logits.device != self.device
-                or logits.shape[1] < self.discrete_action_count()):
-            raise ValueError(f"logits must be a device tensor [{self.E}, >= {self.discrete_action_count()}] with contiguous rows")
-        _check(self.lib, self.lib.mcbs_mask_logits(self._h, logits.data_ptr(), 0 if logits.dtype == t.float32 else 1, logits.stride(0),
-                                                   float(fill), self._stream()), "mcbs_mask_logits")
+        _check(self.lib, self.lib.mcbs_mask_logits(self._h, *self._logits(logits, self.E, self._A), float(fill), self._stream()), "mcbs_mask_logits")
         return logits
 
     # -- bit-packed Discrete action masks (include/mcbs.h): int32 tensors [rows, row_words], bit a of a row = bit (a & 31) of word a >> 5 --
     def packed_mask_words(self):
         """-> (W, row_words): W = ceil(A / 32) words carry a row's mask; row_words = W rounded up to whole 16-byte groups (the rows
         pack_action_mask allocates)."""
-        W = (self.discrete_action_count() + 31) // 32
+        W = (self._A + 31) // 32
         return W, (W + 3) // 4 * 4
 
-    def _packed_rows(self, bits, what: str):
-        t = self.torch
-        if bits.dtype != t.int32 or bits.dim() != 2 or bits.stride(1) != 1 or bits.device != self.device:
-            raise ValueError(f"{what} must be a device int32 tensor [n, >= W] with contiguous rows")
-        if bits.shape[1] < self.packed_mask_words()[0]:
-            raise ValueError(f"{what} rows hold {bits.shape[1]} words, the mask needs {self.packed_mask_words()[0]}")
-        return bits
+    def _packed_rows(self, bits, what: str, n=None):
+        """bits: int32 rows of at least W words, the packed masks of n rows (None: any count)."""
+        return self._rows(bits, (self.torch.int32,), what, n, (self._A + 31) // 32)
 
     def pack_action_mask(self, out=None):
         """The Discrete action mask of the LAST observation call as one bit per action, rebuilt on the device from that call's per-env
@@ -689,57 +636,41 @@ class BatchEngine:
         t = self.torch
         if out is None:
             out = t.zeros((self.E, self.packed_mask_words()[1]), dtype=t.int32, device=self.device)
-        self._packed_rows(out, "out")
-        if out.shape[0] != self.E:
-            raise ValueError(f"out must have {self.E} rows, got {out.shape[0]}")
-        _check(self.lib, self.lib.mcbs_pack_action_mask(self._h, out.data_ptr(), out.stride(0), self._stream()), "mcbs_pack_action_mask")
+        self._packed_rows(out, "out", self.E)
+        _check(self.lib, self.lib.mcbs_pack_action_mask(self._h, out.data_ptr(), _row_stride(out, self.E), self._stream()), "mcbs_pack_action_mask")
         return out
 
     def apply_packed_mask(self, bits, logits, fill: float = -1e8):
         """In place: logits[i, a] = bit(i, a) ? logits[i, a] : fill for every row i of bits [n, >= W] and logits float32 / bfloat16
         [n, >= A] (any n: a minibatch gathered from stored masks).  Write-only, like mask_logits; no digest involved."""
-        t = self.torch
-        self._packed_rows(bits, "bits")
-        if logits.dtype not in (t.float32, t.bfloat16):
-            raise ValueError("logits must be float32 or bfloat16")
-        if logits.dim() != 2 or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < self.discrete_action_count():
-            raise ValueError(f"logits must be a device tensor [n, >= {self.discrete_action_count()}] with contiguous rows")
-        if logits.shape[0] != bits.shape[0]:
-            raise ValueError(f"bits has {bits.shape[0]} rows, logits {logits.shape[0]}")
-        if bits.shape[0]:
-            _check(self.lib, self.lib.mcbs_apply_packed_mask(self._h, bits.data_ptr(), bits.stride(0), logits.data_ptr(),
-                                                             0 if logits.dtype == t.float32 else 1, logits.stride(0), bits.shape[0],
-                                                             float(fill), self._stream()), "mcbs_apply_packed_mask")
+        n = self._packed_rows(bits, "bits").shape[0]
+        lg = self._logits(logits, n, self._A)       # one row of logits per row of bits
+        if n:
+            _check(self.lib, self.lib.mcbs_apply_packed_mask(self._h, bits.data_ptr(), _row_stride(bits, n), *lg, n, float(fill), self._stream()),
+                   "mcbs_apply_packed_mask")
         return logits
 
     def unpack_action_mask(self, bits, out=None):
         """bits [n, >= W] -> the bool mask [n, A] (out: device bool / uint8 [n, >= A] with contiguous rows; bytes from A on untouched)."""
         t = self.torch
         self._packed_rows(bits, "bits")
-        A = self.discrete_action_count()
+        n, A = bits.shape[0], self._A
         if out is None:
-            out = t.empty((bits.shape[0], A), dtype=t.bool, device=self.device)
-        if out.dtype not in (t.bool, t.uint8) or out.dim() != 2 or out.stride(1) != 1 or out.device != self.device or out.shape[1] < A:
-            raise ValueError(f"out must be a device bool or uint8 tensor [n, >= {A}] with contiguous rows")
-        if out.shape[0] != bits.shape[0]:
-            raise ValueError(f"bits has {bits.shape[0]} rows, out {out.shape[0]}")
-        if bits.shape[0]:
-            _check(self.lib, self.lib.mcbs_unpack_action_mask(self._h, bits.data_ptr(), bits.stride(0), out.data_ptr(), out.stride(0),
-                                                              bits.shape[0], self._stream()), "mcbs_unpack_action_mask")
+            out = t.empty((n, A), dtype=t.bool, device=self.device)
+        self._rows(out, (t.bool, t.uint8), "out", n, A)            # one row per row of bits
+        if n:
+            _check(self.lib, self.lib.mcbs_unpack_action_mask(self._h, bits.data_ptr(), _row_stride(bits, n), out.data_ptr(), _row_stride(out, n),
+                                                              n, self._stream()), "mcbs_unpack_action_mask")
         return out
 
     # -- action-mask keys (include/mcbs.h): int32 tensors [rows, >= Wk]; a key row expands to the packed mask of the step it was stored at --
     def mask_key_words(self) -> int:
         """Wk = 1 + ceil(Nk / 32) + ceil(Nk / 4): the words of one key row (mask_keys.key_words on the host)."""
-        return int(self.lib.mcbs_mask_key_words(self._h))
+        return self._Wk
 
-    def _key_rows(self, keys, what: str):
-        t = self.torch
-        if keys.dtype != t.int32 or keys.dim() != 2 or keys.stride(1) != 1 or keys.device != self.device:
-            raise ValueError(f"{what} must be a device int32 tensor [n, >= Wk] with contiguous rows")
-        if keys.shape[1] < self.mask_key_words():
-            raise ValueError(f"{what} rows hold {keys.shape[1]} words, a mask key needs {self.mask_key_words()}")
-        return keys
+    def _key_rows(self, keys, what: str, n=None):
+        """keys: int32 rows of at least Wk words, the mask keys of n rows (None: any count)."""
+        return self._rows(keys, (self.torch.int32,), what, n, self._Wk)
 
     def store_mask_keys(self, out=None):
         """The key of the Discrete action mask of the LAST observation call: the digest's counts and owned-source bits plus the
@@ -748,10 +679,8 @@ class BatchEngine:
         t = self.torch
         if out is None:
             out = t.zeros((self.E, self.mask_key_words()), dtype=t.int32, device=self.device)
-        self._key_rows(out, "out")
-        if out.shape[0] != self.E:
-            raise ValueError(f"out must have {self.E} rows, got {out.shape[0]}")
-        _check(self.lib, self.lib.mcbs_store_mask_keys(self._h, out.data_ptr(), out.stride(0), self._stream()), "mcbs_store_mask_keys")
+        self._key_rows(out, "out", self.E)
+        _check(self.lib, self.lib.mcbs_store_mask_keys(self._h, out.data_ptr(), _row_stride(out, self.E), self._stream()), "mcbs_store_mask_keys")
         return out
 
     def expand_mask_keys(self, keys, index=None, out=None):
@@ -762,18 +691,14 @@ class BatchEngine:
         under every defender kind."""
         t = self.torch
         self._key_rows(keys, "keys")
-        if index is not None and (index.dtype != t.int64 or index.dim() != 1 or not index.is_contiguous() or index.device != self.device):
-            raise ValueError("index must be a contiguous device int64 tensor [n]")
-        n = keys.shape[0] if index is None else index.shape[0]
+        idx, n = self._row_index(index, keys.shape[0])
         if out is None:
             out = t.zeros((n, self.packed_mask_words()[1]), dtype=t.int32, device=self.device)
-        self._packed_rows(out, "out")
-        if out.shape[0] != n:
-            raise ValueError(f"out must have {n} rows, got {out.shape[0]}")
+        self._packed_rows(out, "out", n)
         if n:
-            _check(self.lib, self.lib.mcbs_expand_mask_keys(self._h, keys.data_ptr(), keys.stride(0), None if index is None else index.data_ptr(),
-                                                            keys.shape[0], out.data_ptr(), out.stride(0), n, self._stream()),
-                   "mcbs_expand_mask_keys")
+            m = keys.shape[0]
+            _check(self.lib, self.lib.mcbs_expand_mask_keys(self._h, keys.data_ptr(), _row_stride(keys, m), idx, m, out.data_ptr(),
+                                                            _row_stride(out, n), n, self._stream()), "mcbs_expand_mask_keys")
         return out
 
     def _categorical_outputs(self, n, mode, actions, uniforms, out, bad_actions):
@@ -781,31 +706,24 @@ class BatchEngine:
         t = self.torch
         if mode not in CATEGORICAL_MODES:
             raise ValueError(f"mode must be one of {sorted(CATEGORICAL_MODES)}, got {mode!r}")
-
-        def vec(x, dtype, what):
-            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != (n,) or not x.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous device {dtype} tensor [{n}]")
-            return x
-
         if out is not None and len(out) != 4:
             raise ValueError("out must be (actions, log_prob, entropy, n_allowed)")
         o_act, o_lp, o_ent, o_k = out if out is not None else (None, None, None, None)
         if mode == "evaluate":
             if actions is None:
                 raise ValueError('mode="evaluate" needs actions (int64 [n])')
-            o_act = vec(actions, t.int64, "actions")
+            o_act = self._arr(actions, t.int64, (n,), "actions")
+        elif actions is not None:
+            raise ValueError('actions are an input of mode="evaluate" only (preallocate outputs with out=)')
         else:
-            if actions is not None:
-                raise ValueError('actions are an input of mode="evaluate" only (preallocate outputs with out=)')
-            o_act = vec(o_act, t.int64, "out.actions") if o_act is not None else t.empty(n, dtype=t.int64, device=self.device)
-        o_lp = vec(o_lp, t.float32, "out.log_prob") if o_lp is not None else t.empty(n, dtype=t.float32, device=self.device)
-        o_ent = vec(o_ent, t.float32, "out.entropy") if o_ent is not None else t.empty(n, dtype=t.float32, device=self.device)
-        o_k = vec(o_k, t.int32, "out.n_allowed") if o_k is not None else t.empty(n, dtype=t.int32, device=self.device)
+            o_act = self._arr(o_act, t.int64, (n,), "out.actions") if o_act is not None else t.empty(n, dtype=t.int64, device=self.device)
+        o_lp = self._arr(o_lp, t.float32, (n,), "out.log_prob") if o_lp is not None else t.empty(n, dtype=t.float32, device=self.device)
+        o_ent = self._arr(o_ent, t.float32, (n,), "out.entropy") if o_ent is not None else t.empty(n, dtype=t.float32, device=self.device)
+        o_k = self._arr(o_k, t.int32, (n,), "out.n_allowed") if o_k is not None else t.empty(n, dtype=t.int32, device=self.device)
         if uniforms is not None:
-            vec(uniforms, t.float32, "uniforms")
-        if bad_actions is not None and (not isinstance(bad_actions, t.Tensor) or bad_actions.dtype != t.int32 or bad_actions.numel() != 1
-                                        or bad_actions.device != self.device):
-            raise ValueError("bad_actions must be a device int32 tensor of one element")
+            self._arr(uniforms, t.float32, (n,), "uniforms")
+        if bad_actions is not None:
+            self._counter(bad_actions, "bad_actions")
         return o_act, o_lp, o_ent, o_k
 
     # -- masked categorical head (include/mcbs.h): sample / log-prob / entropy of `Categorical(logits=where(mask, logits, -1e8))` --
@@ -820,7 +738,6 @@ class BatchEngine:
         optional device int32 [1], increased, not zeroed).  seed / step key the row's Philox number unless `uniforms` (device float32 [n]
         in [0, 1)) is given.  out: optional (actions, log_prob, entropy, n_allowed) of preallocated device tensors (int64, float32, float32,
         int32, each [n]).  -> MaskedCategorical(actions, log_prob, entropy, n_allowed)."""
-        t = self.torch
         if mode not in CATEGORICAL_MODES:
             raise ValueError(f"mode must be one of {sorted(CATEGORICAL_MODES)}, got {mode!r}")
         if bits is not None:
@@ -828,24 +745,15 @@ class BatchEngine:
             n = bits.shape[0]
         else:
             n = self.E
-        A = self.discrete_action_count()
-        if logits is not None:
-            if not isinstance(logits, t.Tensor) or logits.dtype not in (t.float32, t.bfloat16):
-                raise ValueError("logits must be a float32 or bfloat16 tensor (or None for the uniform law)")
-            # the C side sees only the row stride: a view narrower than A would have its rows read past their end
-            if logits.dim() != 2 or logits.shape[0] != n or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < A:
-                raise ValueError(f"logits must be a device tensor [{n}, >= {A}] with contiguous rows")
+        lg = self._logits(logits, n, self._A) if logits is not None else (None, 0, 0)          # None: the uniform law
         o_act, o_lp, o_ent, o_k = self._categorical_outputs(n, mode, actions, uniforms, out, bad_actions)
-        common = (logits.data_ptr() if logits is not None else None, 0 if logits is None or logits.dtype == t.float32 else 1,
-                  (logits.stride(0) if n > 1 else max(logits.stride(0), logits.shape[1])) if logits is not None else 0,
-                  CATEGORICAL_MODES[mode], o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), o_k.data_ptr(),
-                  uniforms.data_ptr() if uniforms is not None else None, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
-                  bad_actions.data_ptr() if bad_actions is not None else None, self._stream())
+        common = (*lg, CATEGORICAL_MODES[mode], o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), o_k.data_ptr(), _ptr(uniforms), _u64(seed),
+                  _u64(step), _ptr(bad_actions), self._stream())
         if bits is None:
             _check(self.lib, self.lib.mcbs_masked_categorical(self._h, *common), "mcbs_masked_categorical")
         elif n:
-            _check(self.lib, self.lib.mcbs_masked_categorical_packed(self._h, bits.data_ptr(), bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1]),
-                                                                     n, *common), "mcbs_masked_categorical_packed")
+            _check(self.lib, self.lib.mcbs_masked_categorical_packed(self._h, bits.data_ptr(), _row_stride(bits, n), n, *common),
+                   "mcbs_masked_categorical_packed")
         return MaskedCategorical(o_act, o_lp, o_ent, o_k)
 
     def masked_linear_categorical(self, latent, weight, bias=None, *, bits=None, mode: str = "sample", actions=None, seed: int = 0, step: int = 0,
@@ -856,32 +764,27 @@ class BatchEngine:
         1 <= H <= 512.  bits, mode, actions, seed, step, uniforms, out, bad_actions and the result as for masked_categorical, whose outputs
         on logits holding the same values these are bit for bit; torch.nn.functional.linear sums in another order, so against it the
         logits agree to rounding.  This call builds no autograd graph: masked_linear_evaluate is mode="evaluate" with one."""
-        t = self.torch
         if bits is not None:
             self._packed_rows(bits, "bits")
             n = bits.shape[0]
         else:
             n = self.E
-        A = self.discrete_action_count()
         H = self._linear_head_inputs(latent, weight, bias, n)
         o_act, o_lp, o_ent, o_k = self._categorical_outputs(n, mode, actions, uniforms, out, bad_actions)
-        common = (latent.data_ptr(), latent.stride(0) if n > 1 else max(latent.stride(0), H), weight.data_ptr(),
-                  weight.stride(0) if A > 1 else max(weight.stride(0), H), bias.data_ptr() if bias is not None else None, H,
-                  0 if latent.dtype == t.float32 else 1, CATEGORICAL_MODES[mode], o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), o_k.data_ptr(),
-                  uniforms.data_ptr() if uniforms is not None else None, int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1),
-                  bad_actions.data_ptr() if bad_actions is not None else None, self._stream())
+        common = (latent.data_ptr(), _row_stride(latent, n), weight.data_ptr(), _row_stride(weight, self._A), _ptr(bias), H, self._dtype_code(latent),
+                  CATEGORICAL_MODES[mode], o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), o_k.data_ptr(), _ptr(uniforms), _u64(seed),
+                  _u64(step), _ptr(bad_actions), self._stream())
         if bits is None:
             _check(self.lib, self.lib.mcbs_masked_linear_categorical(self._h, *common), "mcbs_masked_linear_categorical")
         elif n:
-            _check(self.lib, self.lib.mcbs_masked_linear_categorical_packed(
-                self._h, bits.data_ptr(), bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1]), n, *common),
-                "mcbs_masked_linear_categorical_packed")
+            _check(self.lib, self.lib.mcbs_masked_linear_categorical_packed(self._h, bits.data_ptr(), _row_stride(bits, n), n, *common),
+                   "mcbs_masked_linear_categorical_packed")
         return MaskedCategorical(o_act, o_lp, o_ent, o_k)
 
     def _linear_head_inputs(self, latent, weight, bias, n) -> int:
         """The checks on (latent, weight, bias) the calls of the head from the latent share: -> H."""
         t = self.torch
-        A = self.discrete_action_count()
+        A = self._A
         for x, what in ((latent, "latent"), (weight, "weight")) + (((bias, "bias"),) if bias is not None else ()):
             if not isinstance(x, t.Tensor) or x.dtype not in (t.float32, t.bfloat16):
                 raise ValueError(f"{what} must be a float32 or bfloat16 tensor")
@@ -918,19 +821,9 @@ class BatchEngine:
             raise ValueError("bits must be a device int32 tensor [n, >= W] (the gradient exists in the packed form only)")
         self._packed_rows(bits, "bits")
         n = bits.shape[0]
-        A = self.discrete_action_count()
+        A = self._A
         H = self._linear_head_inputs(latent, weight, bias, n)
-
-        def vec(x, dtype, what):
-            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != (n,) or not x.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous device {dtype} tensor [{n}]")
-            return x
-
-        vec(actions, t.int64, "actions")
-        if grad_log_prob is not None:
-            vec(grad_log_prob, t.float32, "grad_log_prob")
-        if grad_entropy is not None:
-            vec(grad_entropy, t.float32, "grad_entropy")
+        self._grad_inputs(n, actions, (n,), grad_log_prob, grad_entropy)
         if out is not None and len(out) != 3:
             raise ValueError("out must be (grad_latent, grad_weight, grad_bias)")
         if len(want) != 3:
@@ -952,14 +845,12 @@ class BatchEngine:
         elif (not isinstance(workspace, t.Tensor) or workspace.dtype != t.uint8 or workspace.device != self.device or not workspace.is_contiguous()
               or workspace.numel() < need):
             raise ValueError(f"workspace must be a contiguous device uint8 tensor of at least {need} bytes")
-        stride = lambda x, rows: x.stride(0) if rows > 1 else max(x.stride(0), x.shape[1])
-        ptr = lambda x: x.data_ptr() if x is not None else None
         g_lat, g_w, g_b = outs
         _check(self.lib, self.lib.mcbs_masked_linear_categorical_grad(
-            self._h, bits.data_ptr(), stride(bits, n), n, latent.data_ptr(), stride(latent, n), weight.data_ptr(), stride(weight, A), ptr(bias), H,
-            0 if latent.dtype == t.float32 else 1, actions.data_ptr(), ptr(grad_log_prob), ptr(grad_entropy),
-            ptr(g_lat), stride(g_lat, n) if g_lat is not None else 0, ptr(g_w), stride(g_w, A) if g_w is not None else 0, ptr(g_b),
-            workspace.data_ptr() if need else None, workspace.numel(), self._stream()), "mcbs_masked_linear_categorical_grad")
+            self._h, bits.data_ptr(), _row_stride(bits, n), n, latent.data_ptr(), _row_stride(latent, n), weight.data_ptr(), _row_stride(weight, A),
+            _ptr(bias), H, self._dtype_code(latent), actions.data_ptr(), _ptr(grad_log_prob), _ptr(grad_entropy), _ptr(g_lat), _row_stride(g_lat, n),
+            _ptr(g_w), _row_stride(g_w, A), _ptr(g_b), workspace.data_ptr() if need else None, workspace.numel(), self._stream()),
+            "mcbs_masked_linear_categorical_grad")
         return MaskedLinearGrad(g_lat, g_w, g_b)
 
     def masked_linear_evaluate(self, latent, weight, bias, bits, actions, bad_actions=None) -> MaskedCategorical:
@@ -981,35 +872,30 @@ class BatchEngine:
             raise ValueError("bits must be a device int32 tensor [n, >= W] (the gradient exists in the packed form only)")
         self._packed_rows(bits, "bits")
         n = bits.shape[0]
-        A = self.discrete_action_count()
-        if not isinstance(logits, t.Tensor) or logits.dtype not in (t.float32, t.bfloat16):
-            raise ValueError("logits must be a float32 or bfloat16 tensor (the uniform law has no gradient)")
-        if logits.dim() != 2 or logits.shape[0] != n or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < A:
-            raise ValueError(f"logits must be a device tensor [{n}, >= {A}] with contiguous rows")
-
-        def vec(x, dtype, what):
-            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != (n,) or not x.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous device {dtype} tensor [{n}]")
-            return x
-
-        vec(actions, t.int64, "actions")
-        if grad_log_prob is not None:
-            vec(grad_log_prob, t.float32, "grad_log_prob")
-        if grad_entropy is not None:
-            vec(grad_entropy, t.float32, "grad_entropy")
-        if out is None:
-            out = t.empty((n, A), dtype=logits.dtype, device=self.device)
-        elif (not isinstance(out, t.Tensor) or out.dtype != logits.dtype or out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1
-              or out.device != self.device or out.shape[1] < A):
-            raise ValueError(f"out must be a device {logits.dtype} tensor [{n}, >= {A}] with contiguous rows")
+        A = self._A
+        lg = self._logits(logits, n, A)             # no None here: the uniform law has no gradient
+        self._grad_inputs(n, actions, (n,), grad_log_prob, grad_entropy)
+        out = self._grad_logits_out(out, logits, n, A)
         if n:
-            stride = lambda x: x.stride(0) if n > 1 else max(x.stride(0), x.shape[1])
             _check(self.lib, self.lib.mcbs_masked_categorical_grad(
-                self._h, bits.data_ptr(), stride(bits), n, logits.data_ptr(), 0 if logits.dtype == t.float32 else 1, stride(logits),
-                actions.data_ptr(), grad_log_prob.data_ptr() if grad_log_prob is not None else None,
-                grad_entropy.data_ptr() if grad_entropy is not None else None, out.data_ptr(), stride(out), self._stream()),
-                "mcbs_masked_categorical_grad")
+                self._h, bits.data_ptr(), _row_stride(bits, n), n, *lg, actions.data_ptr(), _ptr(grad_log_prob), _ptr(grad_entropy),
+                out.data_ptr(), _row_stride(out, n), self._stream()), "mcbs_masked_categorical_grad")
         return out
+
+    def _grad_inputs(self, n, actions, actions_shape, grad_log_prob, grad_entropy) -> None:
+        """The checks the backward passes share: the forward's int64 actions and the two optional incoming gradients, float32 [n]."""
+        t = self.torch
+        self._arr(actions, t.int64, actions_shape, "actions")
+        if grad_log_prob is not None:
+            self._arr(grad_log_prob, t.float32, (n,), "grad_log_prob")
+        if grad_entropy is not None:
+            self._arr(grad_entropy, t.float32, (n,), "grad_entropy")
+
+    def _grad_logits_out(self, out, logits, n, A):
+        """out= of the two gradients with respect to logits: rows of the logits' dtype [n, >= A], or None for a new [n, A] tensor."""
+        if out is None:
+            return self.torch.empty((n, A), dtype=logits.dtype, device=self.device)
+        return self._rows(out, (logits.dtype,), "out", n, A)
 
     def masked_evaluate(self, logits, bits, actions, bad_actions=None) -> MaskedCategorical:
         """masked_categorical(bits=..., mode="evaluate") as a node of torch's autograd graph: log_prob and entropy carry a graph into
@@ -1047,42 +933,31 @@ class BatchEngine:
         if out is not None and len(out) != 3:
             raise ValueError("out must be (actions, log_prob, entropy)")
         o_act, o_lp, o_ent = out if out is not None else (None, None, None)
+        # This method's wall time at 64 rows is mostly Python, and each helper call is 50 ns of it: what _logits, _action_rows, _ptr and
+        # _u64 do elsewhere is written out here.  The checks themselves (_rows, _arr, _counter) and the stride rule (_row_stride) are shared.
         if logits is not None:
-            if not isinstance(logits, t.Tensor) or logits.dtype not in (t.float32, t.bfloat16):
-                raise ValueError("logits must be a float32 or bfloat16 tensor (or None for the uniform law)")
-            # the C side sees only the row stride: a view narrower than A would have its rows read past their end
-            if logits.dim() != 2 or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < A:
-                raise ValueError(f"logits must be a device tensor [n, >= {A}] with contiguous rows")
-            n = logits.shape[0]
-        else:
+            n = self._rows(logits, (t.float32, t.bfloat16), "logits", None, A).shape[0]
+            lg = (logits.data_ptr(), 0 if logits.dtype == t.float32 else 1, _row_stride(logits, n))
+        else:                                       # the uniform law
             given = [x for x in (actions, uniforms, o_act, o_lp, o_ent) if isinstance(x, t.Tensor) and x.dim() >= 1]
-            n = given[0].shape[0] if given else self.E
-
-        def arr(x, dtype, shape, what):
-            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != shape or not x.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous device {dtype} tensor {list(shape)}")
-            return x
-
+            lg, n = (None, 0, 0), given[0].shape[0] if given else self.E
         if mode == "evaluate":
             if actions is None:
                 raise ValueError('mode="evaluate" needs actions (int64 [n, D])')
-            o_act = arr(actions, t.int64, (n, D), "actions")
+            o_act = self._arr(actions, t.int64, (n, D), "actions")
+        elif actions is not None:
+            raise ValueError('actions are an input of mode="evaluate" only (preallocate outputs with out=)')
         else:
-            if actions is not None:
-                raise ValueError('actions are an input of mode="evaluate" only (preallocate outputs with out=)')
-            o_act = arr(o_act, t.int64, (n, D), "out.actions") if o_act is not None else t.empty((n, D), dtype=t.int64, device=self.device)
-        o_lp = arr(o_lp, t.float32, (n,), "out.log_prob") if o_lp is not None else t.empty(n, dtype=t.float32, device=self.device)
-        o_ent = arr(o_ent, t.float32, (n,), "out.entropy") if o_ent is not None else t.empty(n, dtype=t.float32, device=self.device)
+            o_act = self._arr(o_act, t.int64, (n, D), "out.actions") if o_act is not None else t.empty((n, D), dtype=t.int64, device=self.device)
+        o_lp = self._arr(o_lp, t.float32, (n,), "out.log_prob") if o_lp is not None else t.empty(n, dtype=t.float32, device=self.device)
+        o_ent = self._arr(o_ent, t.float32, (n,), "out.entropy") if o_ent is not None else t.empty(n, dtype=t.float32, device=self.device)
         if uniforms is not None:
-            arr(uniforms, t.float32, (n, D), "uniforms")
-        if bad_actions is not None and (not isinstance(bad_actions, t.Tensor) or bad_actions.dtype != t.int32 or bad_actions.numel() != 1
-                                        or bad_actions.device != self.device):
-            raise ValueError("bad_actions must be a device int32 tensor of one element")
+            self._arr(uniforms, t.float32, (n, D), "uniforms")
+        if bad_actions is not None:
+            self._counter(bad_actions, "bad_actions")
         _check(self.lib, self.lib.mcbs_multicategorical(
-            self._h, block, D, n, logits.data_ptr() if logits is not None else None, 0 if logits is None or logits.dtype == t.float32 else 1,
-            (logits.stride(0) if n > 1 else max(logits.stride(0), logits.shape[1])) if logits is not None else 0, CATEGORICAL_MODES[mode],
-            o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(), uniforms.data_ptr() if uniforms is not None else None,
-            int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), int(row_key_base) & (2 ** 64 - 1),
+            self._h, block, D, n, *lg, CATEGORICAL_MODES[mode], o_act.data_ptr(), o_lp.data_ptr(), o_ent.data_ptr(),
+            uniforms.data_ptr() if uniforms is not None else None, int(seed) & _U64, int(step) & _U64, int(row_key_base) & _U64,
             bad_actions.data_ptr() if bad_actions is not None else None, self._stream()), "mcbs_multicategorical")
         return MultiCategorical(o_act, o_lp, o_ent)
 
@@ -1092,34 +967,14 @@ class BatchEngine:
         bfloat16 [n, >= A], actions int64 [n, D] as in the forward.  out: a device tensor of the logits' dtype [n, >= A] with contiguous
         rows that does not overlap logits, or None for a new [n, A] one; columns [0, A) are written entirely (a row with a component
         outside its range: +0.0), columns from A on never.  -> grad_logits."""
-        t = self.torch
         block, D, A = self._nvec_block(nvec)
-        if not isinstance(logits, t.Tensor) or logits.dtype not in (t.float32, t.bfloat16):
-            raise ValueError("logits must be a float32 or bfloat16 tensor (the uniform law has no gradient)")
-        if logits.dim() != 2 or logits.stride(1) != 1 or logits.device != self.device or logits.shape[1] < A:
-            raise ValueError(f"logits must be a device tensor [n, >= {A}] with contiguous rows")
+        lg = self._logits(logits, None, A)          # no None here: the uniform law has no gradient
         n = logits.shape[0]
-
-        def arr(x, dtype, shape, what):
-            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != shape or not x.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous device {dtype} tensor {list(shape)}")
-            return x
-
-        arr(actions, t.int64, (n, D), "actions")
-        if grad_log_prob is not None:
-            arr(grad_log_prob, t.float32, (n,), "grad_log_prob")
-        if grad_entropy is not None:
-            arr(grad_entropy, t.float32, (n,), "grad_entropy")
-        if out is None:
-            out = t.empty((n, A), dtype=logits.dtype, device=self.device)
-        elif (not isinstance(out, t.Tensor) or out.dtype != logits.dtype or out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1
-              or out.device != self.device or out.shape[1] < A):
-            raise ValueError(f"out must be a device {logits.dtype} tensor [{n}, >= {A}] with contiguous rows")
-        stride = lambda x: x.stride(0) if n > 1 else max(x.stride(0), x.shape[1])
+        self._grad_inputs(n, actions, (n, D), grad_log_prob, grad_entropy)
+        out = self._grad_logits_out(out, logits, n, A)
         _check(self.lib, self.lib.mcbs_multicategorical_grad(
-            self._h, block, D, n, logits.data_ptr(), 0 if logits.dtype == t.float32 else 1, stride(logits), actions.data_ptr(),
-            grad_log_prob.data_ptr() if grad_log_prob is not None else None, grad_entropy.data_ptr() if grad_entropy is not None else None,
-            out.data_ptr(), stride(out), self._stream()), "mcbs_multicategorical_grad")
+            self._h, block, D, n, *lg, actions.data_ptr(), _ptr(grad_log_prob), _ptr(grad_entropy), out.data_ptr(), _row_stride(out, n),
+            self._stream()), "mcbs_multicategorical_grad")
         return out
 
     def multicategorical_evaluate(self, logits, nvec, actions, bad_actions=None) -> MultiCategorical:
@@ -1151,27 +1006,20 @@ class BatchEngine:
                 raise ValueError(f"{what} must have unit inner stride and rows at least E elements apart (strides {x.stride()})")
             return x
 
-        def vec(x, dtype, what, n):
-            if not isinstance(x, t.Tensor) or x.dtype != dtype or x.device != self.device or tuple(x.shape) != (n,) or not x.is_contiguous():
-                raise ValueError(f"{what} must be a contiguous device {dtype} tensor [{n}]")
-            return x
-
         rows(rewards, t.float32, "rewards")
         T, E = rewards.shape
         shape = (T, E)
         rows(values, t.float32, "values", shape)
         rows(episode_starts, t.uint8, "episode_starts", shape)
-        vec(last_values, t.float32, "last_values", E)
-        vec(last_dones, t.uint8, "last_dones", E)
+        self._arr(last_values, t.float32, (E,), "last_values")
+        self._arr(last_dones, t.uint8, (E,), "last_dones")
         if bootstrap is not None:
             rows(bootstrap, t.float32, "bootstrap", shape)
         advantages = t.empty(shape, dtype=t.float32, device=self.device) if advantages is None else rows(advantages, t.float32, "advantages", shape)
         returns = t.empty(shape, dtype=t.float32, device=self.device) if returns is None else rows(returns, t.float32, "returns", shape)
-        stride = lambda x: x.stride(0) if T > 1 else max(x.stride(0), E)
-        io = GaeIO(rewards.data_ptr(), values.data_ptr(), episode_starts.data_ptr(), bootstrap.data_ptr() if bootstrap is not None else None,
-                   last_values.data_ptr(), last_dones.data_ptr(), advantages.data_ptr(), returns.data_ptr(), T, E,
-                   stride(rewards), stride(values), stride(episode_starts), stride(bootstrap) if bootstrap is not None else 0,
-                   stride(advantages), stride(returns), float(gamma), float(gae_lambda))
+        io = GaeIO(rewards.data_ptr(), values.data_ptr(), episode_starts.data_ptr(), _ptr(bootstrap), last_values.data_ptr(), last_dones.data_ptr(),
+                   advantages.data_ptr(), returns.data_ptr(), T, E, _row_stride(rewards, T), _row_stride(values, T), _row_stride(episode_starts, T),
+                   _row_stride(bootstrap, T), _row_stride(advantages, T), _row_stride(returns, T), float(gamma), float(gae_lambda))
         _check(self.lib, self.lib.mcbs_gae(self._h, C.byref(io), self._stream()), "mcbs_gae")
         return advantages, returns
 
@@ -1204,28 +1052,20 @@ class BatchEngine:
         code = self._feature_dtypes[out.dtype][0]
         if dtype is not None and out.dtype != dtype:
             raise ValueError(f"out is {out.dtype}, dtype asks for {dtype}")
-        # the C side sees only the row stride: a view narrower than F would have its rows written past their end
-        if out.dim() != 2 or out.shape[0] != n or out.stride(1) != 1 or out.device != self.device or out.shape[1] < F:
-            raise ValueError(f"out must be a device tensor [{n}, >= {F}] with contiguous rows")
-        if out_of_range is not None and (out_of_range.dtype != t.int32 or out_of_range.numel() != 1 or out_of_range.device != self.device):
-            raise ValueError("out_of_range must be a device int32 tensor of one element")
+        self._rows(out, (out.dtype,), "out", n, F)
+        if out_of_range is not None:
+            self._counter(out_of_range, "out_of_range")
         return out, code
 
-    def encode_features(self, handle: FeatureLayoutHandle, obs: dict, bits=None, out=None, dtype=None, out_of_range=None):
-        """Feature rows [n, F] of n observation rows, one launch (mcbs_encode_features).  obs: the int32 fields `scalars`,
-        `leaked_credentials`, `credential_cache_matrix`, `discovered_nodes_properties`, `nodes_privilegelevel` as contiguous device
-        tensors with a leading row axis n — the live observation (n = E) or rows gathered from a rollout buffer (any n); a field the
-        layout does not read may be missing.  bits: packed masks int32 [n, >= W] (pack_action_mask's format), needed when the layout has
-        mask columns.  out: device float32 / bfloat16 / float16 [n, >= F] with contiguous rows (columns from F on are not touched), or
-        None for a new tensor of `dtype` (default float32) whose rows are padded to whole 128-byte lines; returns the [n, F] view.
-        Every column below F is written.  out_of_range: optional device int32 [1]; the number of elements whose value lay outside its
-        class count is ADDED to it (such an element's columns are all zero)."""
+    def _int_fields(self, obs: dict, all_five: bool):
+        """The observation's int32 fields in `obs` as contiguous device tensors with a leading row axis -> (ObsBuffers block, rows n)."""
         t = self.torch
-        F = handle.width
         ptrs, n = {}, None
         for k, per_row in self._feature_rows.items():
             v = obs.get(k)
             if v is None:
+                if all_five:
+                    raise ValueError(f"obs lacks {k!r}: all five int32 fields are packed")
                 continue
             if v.dtype != t.int32 or v.device != self.device or not v.is_contiguous() or v.dim() < 1 or v.numel() != v.shape[0] * per_row:
                 raise ValueError(f"obs[{k!r}] must be a contiguous device int32 tensor of {per_row} values per row")
@@ -1236,20 +1076,29 @@ class BatchEngine:
             ptrs[k] = v.data_ptr()
         if n is None:
             raise ValueError("obs holds none of the observation's int32 fields")
+        return ObsBuffers(**ptrs), n
+
+    def encode_features(self, handle: FeatureLayoutHandle, obs: dict, bits=None, out=None, dtype=None, out_of_range=None):
+        """Feature rows [n, F] of n observation rows, one launch (mcbs_encode_features).  obs: the int32 fields `scalars`,
+        `leaked_credentials`, `credential_cache_matrix`, `discovered_nodes_properties`, `nodes_privilegelevel` as contiguous device
+        tensors with a leading row axis n — the live observation (n = E) or rows gathered from a rollout buffer (any n); a field the
+        layout does not read may be missing.  bits: packed masks int32 [n, >= W] (pack_action_mask's format), needed when the layout has
+        mask columns.  out: device float32 / bfloat16 / float16 [n, >= F] with contiguous rows (columns from F on are not touched), or
+        None for a new tensor of `dtype` (default float32) whose rows are padded to whole 128-byte lines; returns the [n, F] view.
+        Every column below F is written.  out_of_range: optional device int32 [1]; the number of elements whose value lay outside its
+        class count is ADDED to it (such an element's columns are all zero)."""
+        fields, n = self._int_fields(obs, all_five=False)
         if handle.has_masks:
             if bits is None:
                 raise ValueError("the layout has mask columns: bits (packed action masks [n, >= W]) is required")
-            self._packed_rows(bits, "bits")
-            if bits.shape[0] != n:
-                raise ValueError(f"bits has {bits.shape[0]} rows, the observation {n}")
+            self._packed_rows(bits, "bits", n)
+        else:
+            bits = None                             # read by a layout with mask columns only
         out, code = self._feature_out(handle, n, out, dtype, out_of_range)
         if n:
-            stride = out.stride(0) if n > 1 else max(out.stride(0), out.shape[1])
-            _check(self.lib, self.lib.mcbs_encode_features(self._h, handle.ptr, C.byref(ObsBuffers(**ptrs)), bits.data_ptr() if handle.has_masks else None,
-                                                           (bits.stride(0) if n > 1 else max(bits.stride(0), bits.shape[1])) if handle.has_masks else 0, out.data_ptr(), code, stride, n,
-                                                           out_of_range.data_ptr() if out_of_range is not None else None, self._stream()),
-                   "mcbs_encode_features")
-        return out[:, :F]
+            _check(self.lib, self.lib.mcbs_encode_features(self._h, handle.ptr, C.byref(fields), _ptr(bits), _row_stride(bits, n), out.data_ptr(), code,
+                                                           _row_stride(out, n), n, _ptr(out_of_range), self._stream()), "mcbs_encode_features")
+        return out[:, :handle.width]
 
     # -- packed observations (include/mcbs.h): int32 tensors [rows, >= W_obs], every value of the five fields a bit field --
     def observation_packing(self, packing) -> ObservationPackingHandle:
@@ -1263,11 +1112,9 @@ class BatchEngine:
             raise McbsError(f"observation packing: the library counts {handle.words} words per row, the host mirror {packing.words}")
         return handle
 
-    def _packed_obs_rows(self, x, handle: ObservationPackingHandle, what: str):
-        t = self.torch
-        if x.dtype != t.int32 or x.dim() != 2 or x.stride(1) != 1 or x.device != self.device or x.shape[1] < handle.words:
-            raise ValueError(f"{what} must be a device int32 tensor [n, >= {handle.words}] with contiguous rows")
-        return x.stride(0) if x.shape[0] > 1 else max(x.stride(0), x.shape[1])
+    def _packed_obs_rows(self, x, handle: ObservationPackingHandle, what: str, n=None):
+        """x: int32 rows of at least W_obs words, n packed observations (None: any count)."""
+        return self._rows(x, (self.torch.int32,), what, n, handle.words)
 
     def _row_index(self, index, n_source: int, what: str = "index"):
         """-> (pointer or None, rows asked): index int64 [n] on the device, or None for rows 0 .. n_source - 1"""
@@ -1284,29 +1131,15 @@ class BatchEngine:
         rollout buffer (words from W_obs on are not touched, every word below is written), or None for a new [n, W_obs] tensor.
         out_of_range: optional device int32 [1]; the number of values stored as their out-of-range code is ADDED to it."""
         t = self.torch
-        ptrs, n = {}, None
-        for k, per_row in self._feature_rows.items():
-            v = obs.get(k)
-            if v is None:
-                raise ValueError(f"obs lacks {k!r}: all five int32 fields are packed")
-            if v.dtype != t.int32 or v.device != self.device or not v.is_contiguous() or v.dim() < 1 or v.numel() != v.shape[0] * per_row:
-                raise ValueError(f"obs[{k!r}] must be a contiguous device int32 tensor of {per_row} values per row")
-            if n is None:
-                n = v.shape[0]
-            elif v.shape[0] != n:
-                raise ValueError(f"obs[{k!r}] has {v.shape[0]} rows, other fields {n}")
-            ptrs[k] = v.data_ptr()
+        fields, n = self._int_fields(obs, all_five=True)
         if out is None:
             out = t.empty((n, handle.words), dtype=t.int32, device=self.device)
-        stride = self._packed_obs_rows(out, handle, "out")
-        if out.shape[0] != n:
-            raise ValueError(f"out must have {n} rows, got {out.shape[0]}")
-        if out_of_range is not None and (out_of_range.dtype != t.int32 or out_of_range.numel() != 1 or out_of_range.device != self.device):
-            raise ValueError("out_of_range must be a device int32 tensor of one element")
+        self._packed_obs_rows(out, handle, "out", n)
+        if out_of_range is not None:
+            self._counter(out_of_range, "out_of_range")
         if n:
-            _check(self.lib, self.lib.mcbs_pack_observation(self._h, handle.ptr, C.byref(ObsBuffers(**ptrs)), out.data_ptr(), stride, n,
-                                                            out_of_range.data_ptr() if out_of_range is not None else None, self._stream()),
-                   "mcbs_pack_observation")
+            _check(self.lib, self.lib.mcbs_pack_observation(self._h, handle.ptr, C.byref(fields), out.data_ptr(), _row_stride(out, n), n,
+                                                            _ptr(out_of_range), self._stream()), "mcbs_pack_observation")
         return out
 
     def unpack_observation(self, handle: ObservationPackingHandle, packed, index=None, out=None):
@@ -1315,7 +1148,7 @@ class BatchEngine:
         out-of-range codes); without it n = m.  out: dict of contiguous device int32 tensors with n rows for the fields wanted (None:
         all five, newly allocated)."""
         t = self.torch
-        stride = self._packed_obs_rows(packed, handle, "packed")
+        self._packed_obs_rows(packed, handle, "packed")
         idx, n = self._row_index(index, packed.shape[0])
         if out is None:
             out = {k: t.empty((n,) + self._shapes[k][0], dtype=t.int32, device=self.device) for k in FEATURE_FIELDS}
@@ -1328,7 +1161,7 @@ class BatchEngine:
                 raise ValueError(f"out[{k!r}] must be a contiguous device int32 tensor of {n} rows of {per_row} values")
             ptrs[k] = v.data_ptr()
         if n and ptrs:
-            _check(self.lib, self.lib.mcbs_unpack_observation(self._h, handle.ptr, packed.data_ptr(), stride, idx, packed.shape[0], n,
+            _check(self.lib, self.lib.mcbs_unpack_observation(self._h, handle.ptr, packed.data_ptr(), _row_stride(packed, packed.shape[0]), idx, packed.shape[0], n,
                                                               C.byref(ObsBuffers(**ptrs)), self._stream()), "mcbs_unpack_observation")
         return out
 
@@ -1339,25 +1172,21 @@ class BatchEngine:
         columns.  index: optional device int64 [n]: output row i is built from row index[i] of BOTH packed and bits — pass a rollout
         buffer's whole [T * E, ...] storage and a minibatch's row index, nothing is gathered first.  An index outside [0, m) reads
         nothing: that row is all zero and out_of_range grows by the layout's element count."""
-        F = feature_handle.width
-        pstride = self._packed_obs_rows(packed, packing_handle, "packed")
+        self._packed_obs_rows(packed, packing_handle, "packed")
         m = packed.shape[0]
         idx, n = self._row_index(index, m)
         if feature_handle.has_masks:
             if bits is None:
                 raise ValueError("the layout has mask columns: bits (packed action masks [m, >= W]) is required")
-            self._packed_rows(bits, "bits")
-            if bits.shape[0] != m:
-                raise ValueError(f"bits has {bits.shape[0]} rows, packed {m}")
+            self._packed_rows(bits, "bits", m)
+        else:
+            bits = None                             # read by a layout with mask columns only
         out, code = self._feature_out(feature_handle, n, out, dtype, out_of_range)
         if n:
-            stride = out.stride(0) if n > 1 else max(out.stride(0), out.shape[1])
-            masks = feature_handle.has_masks
             _check(self.lib, self.lib.mcbs_encode_features_packed(
-                self._h, feature_handle.ptr, packing_handle.ptr, packed.data_ptr(), pstride, bits.data_ptr() if masks else None,
-                (bits.stride(0) if m > 1 else max(bits.stride(0), bits.shape[1])) if masks else 0, idx, m, out.data_ptr(), code, stride, n,
-                out_of_range.data_ptr() if out_of_range is not None else None, self._stream()), "mcbs_encode_features_packed")
-        return out[:, :F]
+                self._h, feature_handle.ptr, packing_handle.ptr, packed.data_ptr(), _row_stride(packed, m), _ptr(bits), _row_stride(bits, m), idx, m,
+                out.data_ptr(), code, _row_stride(out, n), n, _ptr(out_of_range), self._stream()), "mcbs_encode_features_packed")
+        return out[:, :feature_handle.width]
 
     # -- learned defender (batches created with defender=("external",)) --
     def alloc_defender_obs(self) -> dict:
@@ -1403,7 +1232,6 @@ class BatchEngine:
 
     def set_state(self, hdr, nodes, order, cache) -> None:
         """Inverse of get_state (parity / debugging): upload canonical state records."""
-        from ._abi import STATE_HEADER_DT, STATE_NODE_DT
         N, Cm = self.topo.n_nodes, self.spec.maximum_total_credentials
         rb = state_record_bytes(N, Cm)
         raw = np.zeros((self.E, rb), np.uint8)

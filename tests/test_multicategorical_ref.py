@@ -103,15 +103,16 @@ def test_abi_declares_the_entry_points_and_constants():
     ctype = {"const mcbs_batch*": C.c_void_p, "const uint32_t*": C.POINTER(C.c_uint32), "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
              "const void*": C.c_void_p, "int32_t": C.c_int32, "size_t": C.c_size_t, "int64_t*": C.c_void_p, "const int64_t*": C.c_void_p,
              "float*": C.c_void_p, "const float*": C.c_void_p, "uint32_t*": C.c_void_p, "void*": C.c_void_p}
-    assert set(_abi.MULTICATEGORICAL_ARGTYPES) == {"mcbs_multicategorical", "mcbs_multicategorical_grad"}
-    for name, argtypes in _abi.MULTICATEGORICAL_ARGTYPES.items():
+    for name in ("mcbs_multicategorical", "mcbs_multicategorical_grad"):
+        restype, argtypes = _abi.PROTOTYPES[name]
+        assert restype is C.c_int
         params = re.search(r"int\s+%s\((.*?)\);" % name, code, flags=re.S).group(1)
         declared = [" ".join(p.split()[:-1]) if len(p.split()) > 1 and not p.split()[-1].endswith("*") else " ".join(p.split())
                     for p in params.split(",")]
         assert [ctype[t] for t in declared] == argtypes, name
         assert name in engine.EXPORTS
     lib = engine.load_library()
-    assert lib.mcbs_multicategorical.argtypes == _abi.MULTICATEGORICAL_ARGTYPES["mcbs_multicategorical"]
+    assert lib.mcbs_multicategorical.argtypes == _abi.PROTOTYPES["mcbs_multicategorical"][1]
     # refusals that need no GPU: a null batch
     assert lib.mcbs_multicategorical(None, None, 0, 0, None, 0, 0, 0, None, None, None, None, 0, 0, 0, None, None) == -1
     assert b"batch" in lib.mcbs_last_error()

@@ -30,6 +30,150 @@ def test_library_exports_every_declared_symbol():
     assert lib.mcbs_abi_version() == 1
 
 
+# ---- the Python declaration of the C ABI (marlon_amd/_abi.py) against include/mcbs.h: every prototype, struct mirror and constant ----
+SCALARS = {"int32_t": C.c_int32, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t, "float": C.c_float,
+           "double": C.c_double, "int": C.c_int, "uint8_t": C.c_uint8, "uint16_t": C.c_uint16, "int64_t": C.c_int64, "int8_t": C.c_int8}
+# the C struct each ctypes.Structure of _abi.py mirrors; test_every_struct_mirror_matches_the_header refuses a Structure missing here
+MIRRORS = {"mcbs_batch_cfg": "BatchCfg", "mcbs_obs_buffers": "ObsBuffers", "mcbs_info_buffers": "InfoBuffers",
+           "mcbs_wrapper_buffers": "WrapperBuffers", "mcbs_defender_wrapper_buffers": "DefenderWrapperBuffers",
+           "mcbs_defender_wrapper_cfg": "DefenderWrapperCfg", "mcbs_defender_obs": "DefenderObs",
+           "mcbs_batch_variant_info": "BatchVariantInfo", "mcbs_gae_io": "GaeIO", "mcbs_row_copies": "RowCopies"}
+
+
+def header_code():
+    """include/mcbs.h without its comments"""
+    return re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "mcbs.h")).read(), flags=re.S)
+
+
+def header_prototypes():
+    """name -> (return type, [parameter declarations]) for every `ret mcbs_name(params);` of the header"""
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w ]*?\**)\s+(mcbs_[a-z_]+)\s*\(([^()]*)\)\s*;", header_code()):
+        assert name not in out, name
+        params = [" ".join(p.split()) for p in params.split(",")]
+        out[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return out
+
+
+def header_structs():
+    """struct name -> [(C type without const, pointer?, member name, array length or None)] for every `typedef struct x { ... } x;`"""
+    out = {}
+    for name, body in re.findall(r"typedef struct (\w+) \{(.*?)\} \1;", header_code(), flags=re.S):
+        members = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            base, star, names = re.fullmatch(r"(?:const )?(\w+) ?(\*?) ?(.+)", decl).groups()
+            for m in names.split(","):
+                member, length = re.fullmatch(r"(\w+)(?:\[(\d+)\])?", m.strip()).groups()
+                members.append((base, bool(star), member, int(length) if length else None))
+        out[name] = members
+    return out
+
+
+def stated_struct_sizes():
+    """struct name -> the size its opening line states in a comment (`typedef struct x { /* 64 bytes */`)"""
+    text = open(os.path.join(REPO, "include", "mcbs.h")).read()
+    return {n: int(b) for n, b in re.findall(r"typedef struct (\w+) \{\s*/\* (\d+) bytes", text)}
+
+
+def check_parameter(decl, ctype, where):
+    """One parameter declaration of the header against the ctypes type the Python side gives it."""
+    from marlon_amd import _abi
+    if "*" in decl:
+        base = decl[:decl.index("*")].replace("const", "").strip()
+        if ctype is C.c_char_p:
+            assert base == "char", where
+        elif ctype is not C.c_void_p:
+            assert isinstance(ctype, type) and issubclass(ctype, C._Pointer), f"{where}: `{decl}` is a pointer, bound as {ctype}"
+            if decl.count("*") == 2:
+                assert ctype._type_ is C.c_void_p, where
+            elif base in MIRRORS:
+                assert ctype._type_ is getattr(_abi, MIRRORS[base]), f"{where}: `{decl}` bound as a pointer to {ctype._type_}"
+            else:
+                assert ctype._type_ is SCALARS[base], f"{where}: `{decl}` bound as a pointer to {ctype._type_}"
+    else:
+        words = decl.split()
+        ctype_name = " ".join(words[:-1]) if len(words) > 1 else words[0]          # a scalar parameter carries a name
+        assert ctype is SCALARS[ctype_name], f"{where}: `{decl}` bound as {ctype}"
+
+
+def check_prototypes(protos, table, where):
+    assert set(table) == set(protos)
+    for name, (ret, params) in protos.items():
+        restype, argtypes = table[name]
+        assert len(argtypes) == len(params), f"{where} {name}: {len(argtypes)} argtypes, the header has {len(params)} parameters"
+        for i, (decl, ctype) in enumerate(zip(params, argtypes)):
+            check_parameter(decl, ctype, f"{where} {name} argument {i}")
+        if ret == "void":
+            assert restype is None, f"{where} {name}"
+        else:
+            check_parameter(ret if "*" in ret else ret + " result", restype, f"{where} {name} result")
+
+
+def test_every_prototype_matches_the_header():
+    """Each function of include/mcbs.h, argument by argument and result by result, against _abi.PROTOTYPES and against what
+    load_library() left on the loaded library: a pointer is a c_void_p / c_char_p / POINTER (of the struct's own mirror), a scalar maps
+    exactly (size_t and uint64_t are not interchangeable), the counts agree."""
+    from marlon_amd import _abi
+    protos = header_prototypes()
+    assert len(protos) == len(declared_functions()) == len(_abi.PROTOTYPES) and sorted(protos) == declared_functions()
+    assert list(_abi.PROTOTYPES) == engine.EXPORTS == list(protos), "PROTOTYPES keeps the header's order"
+    check_prototypes(protos, _abi.PROTOTYPES, "PROTOTYPES")
+    lib = engine.load_library()
+    check_prototypes(protos, {n: (getattr(lib, n).restype, list(getattr(lib, n).argtypes)) for n in protos}, "libmcbs.so")
+
+
+def test_every_struct_mirror_matches_the_header():
+    """Each ctypes.Structure of _abi.py has the members of the C struct it mirrors, by name, in order and by type (pointers are c_void_p,
+    arrays ctypes arrays); the numpy dtypes that mirror header structs likewise; sizes where the header states one."""
+    from marlon_amd import _abi
+    structs, sizes = header_structs(), stated_struct_sizes()
+    found = {n for n, v in vars(_abi).items() if isinstance(v, type) and issubclass(v, C.Structure) and v is not C.Structure}
+    assert found == set(MIRRORS.values()), "a ctypes.Structure of _abi.py that MIRRORS does not tie to its C struct (or the reverse)"
+    for cname, pyname in MIRRORS.items():
+        want = []
+        for base, pointer, member, length in structs[cname]:
+            ctype = C.c_void_p if pointer else SCALARS[base]
+            want.append((member, ctype * length if length else ctype))
+        assert list(getattr(_abi, pyname)._fields_) == want, f"{pyname} against {cname}"
+        if cname in sizes:
+            assert C.sizeof(getattr(_abi, pyname)) == sizes[cname], pyname
+    np_code = {"uint8_t": "u1", "uint16_t": "<u2", "uint32_t": "<u4", "int32_t": "<i4", "uint64_t": "<u8", "double": "<f8"}
+    for cname, dt in (("mcbs_topo_header", flatten.HEADER_DT), ("mcbs_node_static", flatten.NODE_DT), ("mcbs_vuln_slot", flatten.SLOT_DT),
+                      ("mcbs_payload", flatten.PAYLOAD_DT), ("mcbs_service", flatten.SERVICE_DT), ("mcbs_triple", flatten.TRIPLE_DT),
+                      ("mcbs_ere_tables", flatten.ERE_DT), ("mcbs_state_header", _abi.STATE_HEADER_DT), ("mcbs_state_node", _abi.STATE_NODE_DT)):
+        assert list(dt.names) == [member for _, _, member, _ in structs[cname]], cname
+        for base, pointer, member, length in structs[cname]:
+            assert not pointer and dt.fields[member][0] == np.dtype((np_code[base], (length,)) if length else np_code[base]), (cname, member)
+        assert dt.itemsize == sizes[cname], cname
+    assert C.sizeof(_abi.BatchCfg) == 136 and C.sizeof(_abi.GaeIO) == 144
+
+
+def test_every_mirrored_constant_matches_the_header():
+    """Each Python constant that restates a `#define MCBS_*` equals it."""
+    from marlon_amd import _abi
+    modes = _abi.CATEGORICAL_MODES
+    pairs = [("ABI_VERSION", _abi.ABI_VERSION), ("ABI_VERSION", flatten.ABI_VERSION), ("TOPO_MAGIC", flatten.TOPO_MAGIC),
+             ("DEFENDER_NONE", _abi.DEFENDER_NONE), ("DEFENDER_SCAN_AND_REIMAGE", _abi.DEFENDER_SCAN_AND_REIMAGE),
+             ("DEFENDER_EXTERNAL", _abi.DEFENDER_EXTERNAL), ("DEFENDER_RANDOM_EVENTS", _abi.DEFENDER_RANDOM_EVENTS),
+             ("RNG_PHILOX", _abi.RNG_PHILOX), ("RNG_TAPE", _abi.RNG_TAPE),
+             ("TOPO_ESCALATION", _abi.TOPO_ESCALATION), ("TOPO_LATERAL_EXPLOIT", _abi.TOPO_LATERAL_EXPLOIT),
+             ("TOPO_PRECONDITION", _abi.TOPO_PRECONDITION), ("TOPO_PROBE", _abi.TOPO_PROBE), ("TOPO_MULTI_LEAK", _abi.TOPO_MULTI_LEAK),
+             ("TOPO_WIDE_ROWS", _abi.TOPO_WIDE_ROWS), ("TOPO_ANY", _abi.TOPO_ANY),
+             ("CATEGORICAL_SAMPLE", modes["sample"]), ("CATEGORICAL_ARGMAX", modes["argmax"]), ("CATEGORICAL_EVALUATE", modes["evaluate"]),
+             ("CATEGORICAL_PHILOX_DOMAIN", _abi.CATEGORICAL_PHILOX_DOMAIN), ("CATEGORICAL_PHILOX_DOMAIN", engine.CATEGORICAL_PHILOX_DOMAIN),
+             ("MAX_ACTION_DIMS", _abi.MCBS_MAX_ACTION_DIMS), ("MULTICATEGORICAL_PHILOX_DOMAIN", _abi.MCBS_MULTICATEGORICAL_PHILOX_DOMAIN),
+             ("LINEAR_MAX_H", _abi.MCBS_LINEAR_MAX_H), ("LINEAR_GRAD_ROW_BLOCK", _abi.MCBS_LINEAR_GRAD_ROW_BLOCK),
+             ("MAX_NODES", flatten.MAX_NODES), ("MAX_PORTS", flatten.MAX_PORTS), ("MAX_PROPS", flatten.MAX_PROPS),
+             ("MAX_SLOTS", flatten.MAX_SLOTS), ("MAX_LOCAL_VULNS", flatten.MAX_LOCAL), ("MAX_VULN_COLUMNS", flatten.MAX_COLUMNS),
+             ("MAX_CRED_STRINGS", flatten.MAX_CRED_STRINGS), ("MAX_TRIPLES", flatten.MAX_TRIPLES),
+             ("NODE_INSTALLED0", flatten.NODE_INSTALLED0), ("NODE_REIMAGABLE", flatten.NODE_REIMAGABLE)]
+    code = header_code()
+    assert len(modes) == 3 and engine.CATEGORICAL_MODES is modes
+    for name, value in pairs:
+        m = re.search(rf"#define MCBS_{name}\s+(0x[0-9A-Fa-f]+|\d+)u?\b", code)
+        assert m and int(m.group(1), 0) == value, name
+
+
 def test_abi_struct_sizes_match_header():
     # compiled against include/mcbs.h by gcc in tests/test_oracle_*: here only the Python mirrors
     assert C.sizeof(BatchCfg) == 136
