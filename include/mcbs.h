@@ -816,6 +816,74 @@ int  mcbs_encode_features_packed(const mcbs_batch*, const mcbs_feature_layout*, 
                                  uint64_t n_source_rows, void* out, int32_t dtype, size_t out_row_stride, uint64_t n_rows,
                                  uint32_t* out_of_range, void* stream);
 
+/* ---- first layer from the observation: Linear(F, H) on the one-hot feature row without the feature row, and its gradient ----
+ * The row mcbs_encode_features writes holds exactly one 1 per one-hot element, so the policy's first torch.nn.Linear on it is the bias
+ * plus one column of the weight matrix per element, picked by the element's source value.  These calls compute that from the source
+ * values themselves — the five dense int32 fields, or stored packed rows through a row index — and no [n, F] tensor exists.
+ *
+ * For a feature layout with n_elements one-hot elements in ROW ORDER (ascending first column; element e has first column c_e and k_e
+ * classes) and a row i whose source value of element e is v_{i,e} (read as mcbs_encode_features[_packed] reads it):
+ *     acc = bias ? (float)bias[h] : +0.0f
+ *     for e = 0 .. n_elements - 1, in row order:
+ *         if 0 <= v_{i,e} < k_e:  acc = acc + (float)weight_t[c_e + v_{i,e}, h]          (one float32 add, no multiply)
+ *     out[i, h] = acc                              (float32, or rounded to nearest even to bfloat16)
+ * ONE accumulator, ONE chain, the elements in row order: out[i, h] is a function of the row's values, the table and the bias only, not
+ * of the row's index, the source form, the launch geometry, alignment or strides, and two calls give the same bits.  This is
+ * torch.nn.functional.linear(features, W, b) with W = weight_t transposed, summed in this order (a GEMM sums in another: the two agree
+ * to rounding, exactly where every partial sum is exact).  An out-of-range value contributes nothing; out_of_range (optional device
+ * uint32_t) is INCREASED by the number of such elements, as mcbs_encode_features does.
+ *
+ *   weight_t    [F, weight_row_stride]: the TRANSPOSE of torch.nn.Linear's weight, so that the H values of one feature column are
+ *               contiguous; float32 or bfloat16 (weight_dtype: MCBS_FEATURES_F32 / MCBS_FEATURES_BF16; bfloat16 widens exactly)
+ *   bias        [H] of the same dtype, or NULL
+ *   H           1 <= H <= MCBS_LINEAR_MAX_H; every stride is in elements and >= H; any alignment
+ *   out         [n_rows, out_row_stride], float32 or bfloat16 (out_dtype), chosen independently of weight_dtype.  Every out[i, 0 .. H) is
+ *               written, nothing from H up to the stride is touched.
+ * mcbs_first_layer: the rows are the five dense int32 fields of obs, n_rows rows, read as mcbs_encode_features reads them (a field the
+ *   layout never reads may be NULL; no digest is read: every defender kind is served).
+ * mcbs_first_layer_packed: the source values of output row i are those of packed row index[i] (index NULL: row i, n_rows <=
+ *   n_source_rows), by the rules of mcbs_encode_features_packed: the gather happens inside the launch; an index outside
+ *   [0, n_source_rows) reads no memory, that row comes out as the bias alone (+0.0 without one) and out_of_range grows by n_elements;
+ *   MCBS_EINVAL where the layout gives a value more classes than the packing has valid codes.
+ * Each is ONE launch, no allocation, no host synchronisation, asynchronous on `stream`, capturable in a graph; n_rows == 0 succeeds
+ * without a launch.
+ *
+ * mcbs_first_layer_grad: the backward pass of both forms.  The source is EITHER obs (dense; packing and packed NULL) OR packing +
+ *   packed (+ index, n_source_rows; obs NULL), exactly as the forward took it.
+ *   grad_out       float [n_rows, grad_out_row_stride]: the incoming gradient of out
+ *   grad_weight_t  float [F, grad_weight_row_stride]   grad_weight_t[c, h] = sum of grad_out[i, h] over the rows i whose element selects c
+ *   grad_bias      float [H]                           grad_bias[h]        = sum of grad_out[i, h] over all rows
+ *   Each may be NULL, not both.  WRITE-ONLY: every element [c, 0 .. H) for c < F and [0 .. H) is written (the caller need not clear
+ *   them; a column no row selects is +0.0), elements from H up to the stride never.  No floating-point atomics; two calls give
+ *   identical bits whatever the workspace held.  The order, the scheme of mcbs_masked_linear_categorical_grad: the rows are cut into
+ *   blocks of MCBS_FIRST_LAYER_GRAD_ROW_BLOCK consecutive rows; the partial of a block for (c, h) starts at +0.0 and does
+ *   s = s + grad_out[i, h] over the block's rows that select c, in ascending i; the result is the partials added in ascending block
+ *   order, starting FROM partial 0: (..(p_0 + p_1) + p_2 ..).  grad_bias[h]: the same over all rows of a block.  A row whose index
+ *   lies outside the storage contributes to grad_bias only.  n_rows == 0 writes +0.0 everywhere.
+ *   workspace: device memory of at least mcbs_first_layer_grad_workspace(batch, layout, n_rows, H) bytes = blocks * (F + 1) * H * 4
+ *   (8.3 MB for 16 384 Chain-10 rows at H = 64; 0 for n_rows == 0, an H out of range or a layout with mask columns); its contents on
+ *   entry do not matter and are undefined on return.  TWO launches (the row-block pass, the pass that adds the partials), no
+ *   allocation, no host synchronisation, capturable in a graph.
+ *
+ * MCBS_EINVAL, all with a message: a layout that has mask columns (include_masks is out of scope of these calls); H outside
+ * [1, MCBS_LINEAR_MAX_H]; a stride below H; a dtype other than the two; a NULL required pointer (a field the layout reads, weight_t, out,
+ * packed, grad_out; both gradients NULL; both sources or neither); a layout or packing of another batch geometry; packed_row_words <
+ * W_obs; no index and n_rows > n_source_rows; a workspace that is NULL or too small; an output or the workspace sharing a byte with an
+ * input or with each other (the extents from the first to the last byte of each array are compared). */
+#define MCBS_FIRST_LAYER_GRAD_ROW_BLOCK 512
+int  mcbs_first_layer(const mcbs_batch*, const mcbs_feature_layout*, const mcbs_obs_buffers* obs, uint64_t n_rows, const void* weight_t,
+                      size_t weight_row_stride, const void* bias, int32_t weight_dtype, uint32_t H, void* out, int32_t out_dtype,
+                      size_t out_row_stride, uint32_t* out_of_range, void* stream);
+int  mcbs_first_layer_packed(const mcbs_batch*, const mcbs_feature_layout*, const mcbs_obs_packing*, const uint32_t* packed,
+                             size_t packed_row_words, const int64_t* index, uint64_t n_source_rows, uint64_t n_rows, const void* weight_t,
+                             size_t weight_row_stride, const void* bias, int32_t weight_dtype, uint32_t H, void* out, int32_t out_dtype,
+                             size_t out_row_stride, uint32_t* out_of_range, void* stream);
+size_t mcbs_first_layer_grad_workspace(const mcbs_batch*, const mcbs_feature_layout*, uint64_t n_rows, uint32_t H);
+int  mcbs_first_layer_grad(const mcbs_batch*, const mcbs_feature_layout*, const mcbs_obs_buffers* obs, const mcbs_obs_packing*,
+                           const uint32_t* packed, size_t packed_row_words, const int64_t* index, uint64_t n_source_rows, uint64_t n_rows,
+                           const float* grad_out, size_t grad_out_row_stride, uint32_t H, float* grad_weight_t, size_t grad_weight_row_stride,
+                           float* grad_bias, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- learned defender: marlon/baseline_models/env_wrappers/defend_wrapper.py:197-327,329-412,492-534
  * and marlon/defender_agents/defender.py:31-107, for batches created with MCBS_DEFENDER_EXTERNAL ---- */
 typedef struct mcbs_defender_obs {   /* DefenderEnvWrapper.observe: four MultiBinary fields, int8, network node order */

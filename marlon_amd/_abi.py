@@ -18,6 +18,7 @@ CATEGORICAL_MODES = {"sample": 0, "argmax": 1, "evaluate": 2}      # MCBS_CATEGO
 CATEGORICAL_PHILOX_DOMAIN = 0xCA7E6041                              # MCBS_CATEGORICAL_PHILOX_DOMAIN
 MCBS_MAX_ACTION_DIMS, MCBS_MULTICATEGORICAL_PHILOX_DOMAIN = 16, 0x3C47E6A1     # the MultiDiscrete head
 MCBS_LINEAR_MAX_H, MCBS_LINEAR_GRAD_ROW_BLOCK = 512, 512                       # the masked action head from the latent and its gradient
+MCBS_FIRST_LAYER_GRAD_ROW_BLOCK = 512                                          # the first layer from the observation: rows per block partial
 
 
 class BatchCfg(C.Structure):
@@ -111,6 +112,8 @@ _CAT = [_P, _i32, _size, _i32, _P, _P, _P, _P, _P, _u64, _u64, _P, _S]
 # bad_actions, stream
 _LIN = [_P, _size, _P, _size, _P, _u32, _i32, _i32, _P, _P, _P, _P, _P, _u64, _u64, _P, _S]
 _BITS = [_H, _P, _size, _u64]      # batch, bits, bits_row_words, n_rows
+# weight_t, weight_row_stride, bias, weight_dtype, H, out, out_dtype, out_row_stride, out_of_range, stream
+_FL = [_P, _size, _P, _i32, _u32, _P, _i32, _size, _P, _S]
 
 PROTOTYPES = {
     "mcbs_last_error": (C.c_char_p, []),
@@ -173,6 +176,14 @@ PROTOTYPES = {
     # batch, layout, packing, packed, packed_row_words, bits, bits_row_words, index, n_source_rows, out, dtype, out_row_stride, n_rows,
     # out_of_range, stream
     "mcbs_encode_features_packed": (_int, [_H, _H, _H, _P, _size, _P, _size, _P, _u64, _P, _i32, _size, _u64, _P, _S]),
+    # batch, layout, obs, n_rows, then _FL
+    "mcbs_first_layer": (_int, [_H, _H, _OBS, _u64] + _FL),
+    # batch, layout, packing, packed, packed_row_words, index, n_source_rows, n_rows, then _FL
+    "mcbs_first_layer_packed": (_int, [_H, _H, _H, _P, _size, _P, _u64, _u64] + _FL),
+    "mcbs_first_layer_grad_workspace": (_size, [_H, _H, _u64, _u32]),                         # batch, layout, n_rows, H -> bytes
+    # batch, layout, obs, packing, packed, packed_row_words, index, n_source_rows, n_rows, grad_out, grad_out_row_stride, H, grad_weight_t,
+    # grad_weight_row_stride, grad_bias, workspace, workspace_bytes, stream
+    "mcbs_first_layer_grad": (_int, [_H, _H, _OBS, _H, _P, _size, _P, _u64, _u64, _P, _size, _u32, _P, _size, _P, _P, _size, _S]),
     "mcbs_defender_step": (_int, [_H, _P, _P, _P, _P, _DOBS, _S]),                            # batch, actions, valid, availability, evicted, obs, stream
     "mcbs_defender_observe": (_int, [_H, _DOBS, _S]),                                         # batch, obs, stream
     "mcbs_set_draw_tape": (_int, [_H, _P, _u32]),                                             # batch, tape, draws_per_step

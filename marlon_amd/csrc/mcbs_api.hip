@@ -29,6 +29,7 @@
 #include "mcbs_gae.hip"
 #include "mcbs_features.hip"
 #include "mcbs_obs_packing.hip"
+#include "mcbs_first_layer.hip"
 #include "mcbs_wrapper_fused.hip"
 #include "mcbs_mask_keys.hip"
 
@@ -1841,6 +1842,7 @@ struct mcbs_feature_layout {
     FeatGeom G{};
     uint32_t* desc_dev = nullptr;
     uint2* elems_dev = nullptr;     // per source value: (first one-hot column, classes) of its element; NULL when two elements share a value
+    FlElem* order_dev = nullptr;    // per element in row order: (first one-hot column, classes, source value): what the first-layer calls walk
     uint32_t fields_used = 0;       // bit k: some descriptor reads observation field k
     uint64_t A = 0;                 // Discrete actions of the batch the layout was made for
     uint32_t n_elements = 0;        // one-hot elements of a row
@@ -1860,6 +1862,7 @@ extern "C" int mcbs_feature_layout_create(const mcbs_batch* b, const uint32_t* d
     uint32_t used = 0;
     std::vector<uint2> elems((size_t)V, make_uint2(0u, 0u));
     std::vector<uint32_t> src_classes((size_t)V, 0u);
+    std::vector<FlElem> order;
     bool elems_ok = true;
     uint32_t cur = 0, n_elements = 0;
     for (size_t j = 0; j < n_desc; ++j) {
@@ -1869,6 +1872,7 @@ extern "C" int mcbs_feature_layout_create(const mcbs_batch* b, const uint32_t* d
             if (cls != 0u) return fail(MCBS_EINVAL, "feature layout: column %zu starts an element with class %u", j, cls);
             if (elems[s].y) elems_ok = false;
             elems[s] = make_uint2((uint32_t)j, 1u);
+            order.push_back(make_uint4((uint32_t)j, 1u, s, 0u));
             cur = s;
             ++n_elements;
         } else {
@@ -1876,6 +1880,7 @@ extern "C" int mcbs_feature_layout_create(const mcbs_batch* b, const uint32_t* d
             if (!j || ((p >> 16) & (FEAT_MAX_SRC - 1u)) != s || (p & (FEAT_MAX_CLASS - 1u)) + 1u != cls)
                 return fail(MCBS_EINVAL, "feature layout: column %zu does not continue the element before it (classes 0, 1, 2, ... of one value)", j);
             elems[cur].y += 1u;
+            order.back().y += 1u;
         }
         if (cls + 1u > src_classes[s]) src_classes[s] = cls + 1u;
         uint32_t k = 0;
@@ -1912,9 +1917,14 @@ extern "C" int mcbs_feature_layout_create(const mcbs_batch* b, const uint32_t* d
             e = hipMalloc(&l->elems_dev, elems.size() * sizeof(uint2));
             if (e == hipSuccess) e = hipMemcpy(l->elems_dev, elems.data(), elems.size() * sizeof(uint2), hipMemcpyHostToDevice);
         }
+        if (e == hipSuccess) {
+            e = hipMalloc(&l->order_dev, order.size() * sizeof(FlElem));
+            if (e == hipSuccess) e = hipMemcpy(l->order_dev, order.data(), order.size() * sizeof(FlElem), hipMemcpyHostToDevice);
+        }
         if (e != hipSuccess) {
             if (l->desc_dev) (void)hipFree(l->desc_dev);
             if (l->elems_dev) (void)hipFree(l->elems_dev);
+            if (l->order_dev) (void)hipFree(l->order_dev);
             delete l;
             return fail(MCBS_EHIP, "feature layout: descriptor upload failed: %s", hipGetErrorString(e));
         }
@@ -1928,6 +1938,7 @@ extern "C" void mcbs_feature_layout_destroy(mcbs_feature_layout* l) {
     DeviceGuard guard(l->device);
     if (l->desc_dev) (void)hipFree(l->desc_dev);
     if (l->elems_dev) (void)hipFree(l->elems_dev);
+    if (l->order_dev) (void)hipFree(l->order_dev);
     delete l;
 }
 
@@ -2127,6 +2138,172 @@ extern "C" int mcbs_encode_features_packed(const mcbs_batch* b, const mcbs_featu
                                 n_rows, (T)one, out_of_range);
     });
     return launch_ok("encode features from packed observations");
+}
+
+// ------------------------------------------------------------------ first layer from the observation
+// [first byte, last byte) of an array of `rows` rows `stride` elements apart whose first `width` elements are used; `out`: the call writes it
+struct FlExtent { const char* name; uintptr_t lo, hi; bool out; };
+static FlExtent fl_extent(const char* name, const void* p, uint64_t rows, size_t stride, size_t width, size_t elem, bool out) {
+    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
+    return FlExtent{name, lo, p && rows && width ? lo + (uintptr_t)(((rows - 1u) * stride + width) * elem) : lo, out};
+}
+// no output may share a byte with an input or another output
+static int fl_disjoint(const char* who, const std::vector<FlExtent>& ext) {
+    for (size_t i = 0; i < ext.size(); ++i)
+        for (size_t k = 0; k < ext.size(); ++k)
+            if (i != k && ext[i].out && (k > i || !ext[k].out) && ext[i].lo < ext[i].hi && ext[k].lo < ext[k].hi && ext[i].lo < ext[k].hi &&
+                ext[k].lo < ext[i].hi)
+                return fail(MCBS_EINVAL, "%s: %s overlaps %s", who, ext[i].name, ext[k].name);
+    return MCBS_OK;
+}
+
+// The checks on (batch, layout, source) the three calls share; fills S and appends the source's extents.  obs: the dense form; else
+// packing + packed (+ index).
+static int fl_source(const char* who, const mcbs_batch* b, const mcbs_feature_layout* l, const mcbs_obs_buffers* obs, const mcbs_obs_packing* p,
+                     const uint32_t* packed, size_t packed_row_words, const int64_t* index, uint64_t n_source_rows, uint64_t n_rows, FlSrc& S,
+                     std::vector<FlExtent>& ext) {
+    const FeatGeom& G = l->G;
+    if (G.n_ranges || G.W) return fail(MCBS_EINVAL, "%s: the layout has mask columns; include_masks is out of scope of the first-layer calls", who);
+    uint64_t lens[5];
+    obs_field_lens(b, lens);
+    bool same = l->device == b->cfg.device && l->A == mcbs_discrete_action_count(b);
+    for (int k = 0; k < 5; ++k) same = same && G.len[k] == lens[k];
+    if (!same) return fail(MCBS_EINVAL, "%s: the layout was created for a batch of another device or geometry", who);
+    S = FlSrc{};
+    static const char* const names[5] = {"scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel"};
+    if (obs) {
+        S.dense = FeatSrc{{obs->scalars, obs->leaked_credentials, obs->credential_cache_matrix, obs->discovered_nodes_properties, obs->nodes_privilegelevel}};
+        for (uint32_t k = 0; k < 5u; ++k) {
+            if (!((l->fields_used >> k) & 1u)) { S.dense.f[k] = nullptr; continue; }
+            if (!S.dense.f[k]) return fail(MCBS_EINVAL, "%s: the layout reads obs->%s, which is NULL", who, names[k]);
+            ext.push_back(fl_extent(names[k], S.dense.f[k], n_rows ? 1u : 0u, 0u, (size_t)n_rows * G.len[k], 4u, false));
+        }
+        return MCBS_OK;
+    }
+    if (!p || !packed) return fail(MCBS_EINVAL, "%s: packing or packed is NULL", who);
+    if (!obs_packing_fits(b, p)) return fail(MCBS_EINVAL, "%s: the packing was created for a batch of another device or geometry", who);
+    for (size_t s = 0; s < p->valid.size(); ++s)
+        if (l->src_classes[s] > p->valid[s])
+            return fail(MCBS_EINVAL, "%s: the layout gives value %zu %u classes, the packing %u valid codes", who, s, l->src_classes[s], p->valid[s]);
+    if (packed_row_words < p->P.W) return fail(MCBS_EINVAL, "%s: packed_row_words %zu is shorter than the %u words of a packed row", who, packed_row_words, p->P.W);
+    if (!index && n_rows > n_source_rows)
+        return fail(MCBS_EINVAL, "%s: %llu rows asked of %llu stored ones and no index", who, (unsigned long long)n_rows, (unsigned long long)n_source_rows);
+    S.pdesc = p->desc_dev; S.packed = packed; S.packed_row_words = packed_row_words; S.index = index; S.n_source_rows = n_source_rows;
+    ext.push_back(fl_extent("packed", packed, n_source_rows, packed_row_words, p->P.W, 4u, false));
+    ext.push_back(fl_extent("index", index, n_rows ? 1u : 0u, 0u, (size_t)n_rows, 8u, false));
+    return MCBS_OK;
+}
+
+static int first_layer_forward(const char* who, const mcbs_batch* b, const mcbs_feature_layout* l, const mcbs_obs_buffers* obs, const mcbs_obs_packing* p,
+                               const uint32_t* packed, size_t packed_row_words, const int64_t* index, uint64_t n_source_rows, uint64_t n_rows,
+                               const void* weight_t, size_t weight_row_stride, const void* bias, int32_t weight_dtype, uint32_t H, void* out,
+                               int32_t out_dtype, size_t out_row_stride, uint32_t* out_of_range, void* stream) {
+    if (H < 1u || H > MCBS_LINEAR_MAX_H) return fail(MCBS_EINVAL, "%s: H %u: from 1 to %u", who, H, (uint32_t)MCBS_LINEAR_MAX_H);
+    if ((weight_dtype != MCBS_FEATURES_F32 && weight_dtype != MCBS_FEATURES_BF16) || (out_dtype != MCBS_FEATURES_F32 && out_dtype != MCBS_FEATURES_BF16))
+        return fail(MCBS_EINVAL, "%s: weight_dtype and out_dtype must be MCBS_FEATURES_F32 or MCBS_FEATURES_BF16", who);
+    if (!weight_t || !out) return fail(MCBS_EINVAL, "%s: weight_t and out must not be NULL", who);
+    if (weight_row_stride < H) return fail(MCBS_EINVAL, "%s: weight_row_stride %zu is shorter than H = %u", who, weight_row_stride, H);
+    if (out_row_stride < H) return fail(MCBS_EINVAL, "%s: out_row_stride %zu is shorter than H = %u", who, out_row_stride, H);
+    FlSrc S;
+    std::vector<FlExtent> ext;
+    const size_t wes = weight_dtype == MCBS_FEATURES_F32 ? 4u : 2u, oes = out_dtype == MCBS_FEATURES_F32 ? 4u : 2u;
+    ext.push_back(fl_extent("out", out, n_rows, out_row_stride, H, oes, true));
+    ext.push_back(fl_extent("weight_t", weight_t, l->G.F, weight_row_stride, H, wes, false));
+    ext.push_back(fl_extent("bias", bias, 1u, 0u, H, wes, false));
+    ext.push_back(fl_extent("out_of_range", out_of_range, 1u, 0u, 1u, 4u, false));
+    int rc;
+    if ((rc = fl_source(who, b, l, obs, p, packed, packed_row_words, index, n_source_rows, n_rows, S, ext))) return rc;
+    if ((rc = fl_disjoint(who, ext))) return rc;
+    if (n_rows == 0) return MCBS_OK;
+    const uint64_t groups = (n_rows + FL_ROWS - 1u) / FL_ROWS;
+    if (groups > 0x7FFFFFFFull) return fail(MCBS_EINVAL, "%s: too many rows", who);
+    const dim3 grid((uint32_t)groups, (H + 63u) / 64u), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    pick<2, 4>((int)wes, [&](auto we) {
+        using WT = std::conditional_t<decltype(we)::value == 4, float, uint16_t>;
+        pick<2, 4>((int)oes, [&](auto oe) {
+            using OT = std::conditional_t<decltype(oe)::value == 4, float, uint16_t>;
+            pick<0, 1>(obs ? 0 : 1, [&](auto pk) {
+                hipLaunchKernelGGL((first_layer_kernel<WT, OT, decltype(pk)::value != 0>), grid, block, 0, st, l->G, S, l->order_dev, l->n_elements,
+                                   static_cast<const WT*>(weight_t), weight_row_stride, static_cast<const WT*>(bias), H, static_cast<OT*>(out),
+                                   out_row_stride, n_rows, out_of_range);
+            });
+        });
+    });
+    return launch_ok("first layer");
+}
+
+extern "C" int mcbs_first_layer(const mcbs_batch* b, const mcbs_feature_layout* l, const mcbs_obs_buffers* obs, uint64_t n_rows, const void* weight_t,
+                                size_t weight_row_stride, const void* bias, int32_t weight_dtype, uint32_t H, void* out, int32_t out_dtype,
+                                size_t out_row_stride, uint32_t* out_of_range, void* stream) {
+    if (!b || !l || !obs) return fail(MCBS_EINVAL, "mcbs_first_layer: null argument");
+    MCBS_ON_DEVICE(b);
+    return first_layer_forward("mcbs_first_layer", b, l, obs, nullptr, nullptr, 0u, nullptr, 0u, n_rows, weight_t, weight_row_stride, bias, weight_dtype, H,
+                               out, out_dtype, out_row_stride, out_of_range, stream);
+}
+
+extern "C" int mcbs_first_layer_packed(const mcbs_batch* b, const mcbs_feature_layout* l, const mcbs_obs_packing* p, const uint32_t* packed,
+                                       size_t packed_row_words, const int64_t* index, uint64_t n_source_rows, uint64_t n_rows, const void* weight_t,
+                                       size_t weight_row_stride, const void* bias, int32_t weight_dtype, uint32_t H, void* out, int32_t out_dtype,
+                                       size_t out_row_stride, uint32_t* out_of_range, void* stream) {
+    if (!b || !l || !p || !packed) return fail(MCBS_EINVAL, "mcbs_first_layer_packed: null argument");
+    MCBS_ON_DEVICE(b);
+    return first_layer_forward("mcbs_first_layer_packed", b, l, nullptr, p, packed, packed_row_words, index, n_source_rows, n_rows, weight_t,
+                               weight_row_stride, bias, weight_dtype, H, out, out_dtype, out_row_stride, out_of_range, stream);
+}
+
+extern "C" size_t mcbs_first_layer_grad_workspace(const mcbs_batch* b, const mcbs_feature_layout* l, uint64_t n_rows, uint32_t H) {
+    if (!b || !l || l->G.n_ranges || l->G.W || H < 1u || H > MCBS_LINEAR_MAX_H) return 0;
+    const uint64_t n_blocks = (n_rows + MCBS_FIRST_LAYER_GRAD_ROW_BLOCK - 1u) / MCBS_FIRST_LAYER_GRAD_ROW_BLOCK;
+    return (size_t)n_blocks * ((size_t)l->G.F + 1u) * H * sizeof(float);
+}
+
+extern "C" int mcbs_first_layer_grad(const mcbs_batch* b, const mcbs_feature_layout* l, const mcbs_obs_buffers* obs, const mcbs_obs_packing* p,
+                                     const uint32_t* packed, size_t packed_row_words, const int64_t* index, uint64_t n_source_rows, uint64_t n_rows,
+                                     const float* grad_out, size_t grad_out_row_stride, uint32_t H, float* grad_weight_t, size_t grad_weight_row_stride,
+                                     float* grad_bias, void* workspace, size_t workspace_bytes, void* stream) {
+    static const char* who = "mcbs_first_layer_grad";
+    static_assert(FLG_ROW_BLOCK == MCBS_FIRST_LAYER_GRAD_ROW_BLOCK, "the kernel's row block is the header's");
+    if (!b || !l) return fail(MCBS_EINVAL, "%s: null argument", who);
+    MCBS_ON_DEVICE(b);
+    if ((obs != nullptr) == (p != nullptr || packed != nullptr))
+        return fail(MCBS_EINVAL, "%s: give either obs (the dense fields) or packing and packed, not both and not neither", who);
+    if (H < 1u || H > MCBS_LINEAR_MAX_H) return fail(MCBS_EINVAL, "%s: H %u: from 1 to %u", who, H, (uint32_t)MCBS_LINEAR_MAX_H);
+    if (!grad_weight_t && !grad_bias) return fail(MCBS_EINVAL, "%s: grad_weight_t and grad_bias are both NULL", who);
+    if (grad_weight_t && grad_weight_row_stride < H) return fail(MCBS_EINVAL, "%s: grad_weight_row_stride %zu is shorter than H = %u", who, grad_weight_row_stride, H);
+    if (n_rows) {
+        if (!grad_out) return fail(MCBS_EINVAL, "%s: grad_out must not be NULL", who);
+        if (grad_out_row_stride < H) return fail(MCBS_EINVAL, "%s: grad_out_row_stride %zu is shorter than H = %u", who, grad_out_row_stride, H);
+    }
+    FlSrc S;
+    std::vector<FlExtent> ext;
+    const uint32_t F = l->G.F;
+    const size_t need = mcbs_first_layer_grad_workspace(b, l, n_rows, H);
+    ext.push_back(fl_extent("grad_weight_t", grad_weight_t, F, grad_weight_row_stride, H, 4u, true));
+    ext.push_back(fl_extent("grad_bias", grad_bias, 1u, 0u, H, 4u, true));
+    ext.push_back(fl_extent("workspace", workspace, need ? 1u : 0u, 0u, need, 1u, true));
+    ext.push_back(fl_extent("grad_out", grad_out, n_rows, grad_out_row_stride, H, 4u, false));
+    int rc;
+    if ((rc = fl_source(who, b, l, obs, p, packed, packed_row_words, index, n_source_rows, n_rows, S, ext))) return rc;
+    if (need && (!workspace || workspace_bytes < need))
+        return fail(MCBS_EINVAL, "%s: the workspace must hold %zu bytes (mcbs_first_layer_grad_workspace), got %zu at %p", who, need, workspace_bytes, workspace);
+    if ((rc = fl_disjoint(who, ext))) return rc;
+    const uint64_t n_blocks = (n_rows + FLG_ROW_BLOCK - 1u) / FLG_ROW_BLOCK;
+    const uint32_t n_slabs = grad_weight_t ? (l->n_elements + FLG_WAVES * FLG_EPW - 1u) / (FLG_WAVES * FLG_EPW) : 1u;
+    if (n_blocks * (n_slabs ? n_slabs : 1u) > 0x7FFFFFFFull) return fail(MCBS_EINVAL, "%s: too many rows", who);
+    hipStream_t st = (hipStream_t)stream;
+    float* partials = static_cast<float*>(workspace);
+    if (n_rows) {
+        const dim3 grid((uint32_t)n_blocks * (n_slabs ? n_slabs : 1u), (H + 63u) / 64u), block(256);
+        pick<0, 1>(obs ? 0 : 1, [&](auto pk) {
+            hipLaunchKernelGGL((first_layer_grad_kernel<decltype(pk)::value != 0>), grid, block, 0, st, l->G, S, l->order_dev, l->n_elements,
+                               n_slabs ? n_slabs : 1u, grad_out, grad_out_row_stride, H, partials, n_rows, grad_weight_t != nullptr, grad_bias != nullptr);
+        });
+    }
+    const uint64_t cells = ((uint64_t)F + 1u) * H, blocks = (cells + 255u) / 256u;
+    hipLaunchKernelGGL(first_layer_grad_reduce_kernel, dim3(blocks < 65536u ? (uint32_t)blocks : 65536u), dim3(256), 0, st, partials, (uint32_t)n_blocks, F, H,
+                       grad_weight_t, grad_weight_row_stride, grad_bias);
+    return launch_ok("first layer gradient");
 }
 
 // ------------------------------------------------------------------ learned defender

@@ -265,6 +265,40 @@ def _multicategorical_evaluate_function(torch):
     return MultiCategoricalEvaluate
 
 
+# what BatchEngine.first_layer_grad returns: float32 [F, H] and [H]; None for a gradient that was not asked for
+FirstLayerGrad = collections.namedtuple("FirstLayerGrad", ["grad_weight_t", "grad_bias"])
+
+_FIRST_LAYER_EVALUATE = None
+
+
+def _first_layer_evaluate_function(torch):
+    """The torch.autograd.Function behind BatchEngine.first_layer_evaluate (made on first use, like _masked_evaluate_function)."""
+    global _FIRST_LAYER_EVALUATE
+    if _FIRST_LAYER_EVALUATE is not None:
+        return _FIRST_LAYER_EVALUATE
+
+    class FirstLayerEvaluate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, weight, bias, eng, handle, source, dtype, out_of_range, weight_t):
+            if weight_t is None:
+                weight_t = weight.detach().t().contiguous()          # torch's [H, F] -> the [F, H] the kernel reads (Chain-10 at H = 64: 259 KB)
+            ctx.eng, ctx.handle, ctx.source = eng, handle, source    # (integer inputs: no gradient, nothing for autograd to track)
+            ctx.dtypes = (weight.dtype, None if bias is None else bias.dtype)
+            return eng.first_layer(handle, weight_t, None if bias is None else bias.detach(), dtype=dtype, out_of_range=out_of_range, **source)
+
+        @staticmethod
+        def backward(ctx, g):
+            want = (ctx.needs_input_grad[0], ctx.dtypes[1] is not None and ctx.needs_input_grad[1])
+            if g is None or not any(want):
+                return (None,) * 8
+            r = ctx.eng.first_layer_grad(ctx.handle, g.float().contiguous(), want=want, **ctx.source)
+            return (None if r.grad_weight_t is None else r.grad_weight_t.t().to(ctx.dtypes[0]),
+                    None if r.grad_bias is None else r.grad_bias.to(ctx.dtypes[1])) + (None,) * 6
+
+    _FIRST_LAYER_EVALUATE = FirstLayerEvaluate
+    return FirstLayerEvaluate
+
+
 FEATURE_FIELDS = ("scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel")
 
 
@@ -1187,6 +1221,125 @@ class BatchEngine:
                 self._h, feature_handle.ptr, packing_handle.ptr, packed.data_ptr(), _row_stride(packed, m), _ptr(bits), _row_stride(bits, m), idx, m,
                 out.data_ptr(), code, _row_stride(out, n), n, _ptr(out_of_range), self._stream()), "mcbs_encode_features_packed")
         return out[:, :feature_handle.width]
+
+    # -- the first layer from the observation (include/mcbs.h): Linear(F, H) on the feature row without the feature row --
+    def _first_layer_source(self, handle: FeatureLayoutHandle, obs, packing, packed, index):
+        """The source of the three first-layer calls: EITHER obs (the dense int32 fields, as encode_features takes them) OR packing +
+        packed (+ index), as encode_features_packed takes them -> (obs block or None, packing pointer, packed pointer, packed row
+        stride, index pointer, source rows, rows n, the tensors kept alive)."""
+        if handle.has_masks:
+            raise ValueError("the layout has mask columns: the first-layer calls serve layouts without them (include_masks is out of scope)")
+        if (obs is None) == (packed is None):
+            raise ValueError("give either obs= (the dense int32 fields) or packing= and packed= (stored packed rows)")
+        if obs is not None:
+            if packing is not None or index is not None:
+                raise ValueError("packing= and index= belong to packed=: the dense fields are read row for row")
+            fields, n = self._int_fields(obs, all_five=False)
+            return fields, None, None, 0, None, 0, n
+        if not isinstance(packing, ObservationPackingHandle):
+            raise ValueError("packed= needs packing=, the handle of observation_packing()")
+        self._packed_obs_rows(packed, packing, "packed")
+        m = packed.shape[0]
+        idx, n = self._row_index(index, m)
+        return None, packing.ptr, packed.data_ptr(), _row_stride(packed, m), idx, m, n
+
+    def _first_layer_weight(self, handle: FeatureLayoutHandle, weight_t, bias) -> int:
+        """weight_t [F, H] (rows may lie further apart) and bias [H] or None, float32 or bfloat16, one dtype -> H"""
+        t = self.torch
+        self._rows(weight_t, (t.float32, t.bfloat16), "weight_t", handle.width, 1)
+        H = weight_t.shape[1]
+        if H > MCBS_LINEAR_MAX_H:
+            raise ValueError(f"weight_t is [F, H = {H}]: H is at most {MCBS_LINEAR_MAX_H}")
+        if bias is not None:
+            self._arr(bias, weight_t.dtype, (H,), "bias")
+        return H
+
+    def first_layer(self, handle: FeatureLayoutHandle, weight_t, bias=None, *, obs=None, packing=None, packed=None, index=None, out=None,
+                    dtype=None, out_of_range=None):
+        """torch.nn.functional.linear(encode_features(...), weight_t.T, bias) without the feature rows, one launch (mcbs_first_layer /
+        mcbs_first_layer_packed): out[i] = bias + the weight column every one-hot element of row i selects, one float32 accumulator, the
+        elements in row order.  handle: a feature_layout() without mask columns.  weight_t: device float32 / bfloat16 [F, H] with
+        contiguous rows (rows may lie further apart) — the TRANSPOSE of torch's Linear.weight; bias [H] of the same dtype or None.
+        Source: obs= the int32 fields with a leading row axis (as encode_features), or packing= + packed= [m, >= W_obs] (+ index= device
+        int64 [n]: output row i is stored row index[i]; an index outside [0, m) gives the bias alone).  out: device float32 / bfloat16
+        [n, >= H] with contiguous rows (columns from H on are not touched), or None for a new [n, H] tensor of `dtype` (default float32;
+        independent of the weights' dtype); returns the [n, H] view.  out_of_range: optional device int32 [1]; the number of elements
+        whose value lay outside its class count (they select nothing) is ADDED to it."""
+        t = self.torch
+        fields, pk, pp, prs, idx, m, n = self._first_layer_source(handle, obs, packing, packed, index)
+        H = self._first_layer_weight(handle, weight_t, bias)
+        if out is None:
+            out = t.empty((n, H), dtype=dtype or t.float32, device=self.device)
+        if out.dtype not in (t.float32, t.bfloat16) or (dtype is not None and out.dtype != dtype):
+            raise ValueError(f"out must be float32 or bfloat16{'' if dtype is None else f' and of dtype {dtype}'}, got {_describe(out)}")
+        self._rows(out, (out.dtype,), "out", n, H)
+        if out_of_range is not None:
+            self._counter(out_of_range, "out_of_range")
+        tail = (weight_t.data_ptr(), _row_stride(weight_t, handle.width), _ptr(bias), self._dtype_code(weight_t), H, out.data_ptr(),
+                self._dtype_code(out), _row_stride(out, n), _ptr(out_of_range), self._stream())
+        if fields is not None:
+            _check(self.lib, self.lib.mcbs_first_layer(self._h, handle.ptr, C.byref(fields), n, *tail), "mcbs_first_layer")
+        else:
+            _check(self.lib, self.lib.mcbs_first_layer_packed(self._h, handle.ptr, pk, pp, prs, idx, m, n, *tail), "mcbs_first_layer_packed")
+        return out[:, :H]
+
+    def first_layer_grad_workspace(self, handle: FeatureLayoutHandle, n: int, H: int) -> int:
+        """The bytes of device workspace first_layer_grad needs for n rows and a layer of width H."""
+        return int(self.lib.mcbs_first_layer_grad_workspace(self._h, handle.ptr, int(n), int(H)))
+
+    def first_layer_grad(self, handle: FeatureLayoutHandle, grad_out, *, obs=None, packing=None, packed=None, index=None, out=None,
+                         want=(True, True), workspace=None) -> FirstLayerGrad:
+        """The backward pass of first_layer (mcbs_first_layer_grad), two launches: grad_weight_t [F, H] — every row's grad_out added into
+        the weight columns that row selected — and grad_bias [H], from grad_out, a device float32 [n, >= H'] tensor with contiguous rows
+        whose width is H, and the same source the forward took (obs=, or packing= + packed= + index=).  -> FirstLayerGrad(grad_weight_t,
+        grad_bias), float32, every element written (a column no row selects: +0.0), bit-identical from call to call.  want: which of the
+        two to compute (None in the result for the other).  out: optional (grad_weight_t, grad_bias) of preallocated device float32
+        tensors [F, >= H] with contiguous rows and [H] contiguous; None entries are allocated, an entry given is computed whatever `want`
+        says.  workspace: an optional device uint8 tensor of at least first_layer_grad_workspace(handle, n, H) bytes; otherwise
+        torch.empty."""
+        t = self.torch
+        fields, pk, pp, prs, idx, m, n = self._first_layer_source(handle, obs, packing, packed, index)
+        self._rows(grad_out, (t.float32,), "grad_out", n, 1)
+        H, F = grad_out.shape[1], handle.width
+        if H > MCBS_LINEAR_MAX_H:
+            raise ValueError(f"grad_out is [n, H = {H}]: H is at most {MCBS_LINEAR_MAX_H}")
+        if (out is not None and len(out) != 2) or len(want) != 2:
+            raise ValueError("out must be (grad_weight_t, grad_bias) and want two booleans")
+        g_w, g_b = out if out is not None else (None, None)
+        if g_w is None:
+            g_w = t.empty((F, H), dtype=t.float32, device=self.device) if want[0] else None
+        else:
+            self._rows(g_w, (t.float32,), "out.grad_weight_t", F, H)
+        if g_b is None:
+            g_b = t.empty((H,), dtype=t.float32, device=self.device) if want[1] else None
+        else:
+            self._arr(g_b, t.float32, (H,), "out.grad_bias")
+        if g_w is None and g_b is None:
+            raise ValueError("no gradient asked for: want is all False and out gives none")
+        need = self.first_layer_grad_workspace(handle, n, H)
+        if workspace is None:
+            workspace = t.empty(need, dtype=t.uint8, device=self.device)
+        elif (not isinstance(workspace, t.Tensor) or workspace.dtype != t.uint8 or workspace.device != self.device or not workspace.is_contiguous()
+              or workspace.numel() < need):
+            raise ValueError(f"workspace must be a contiguous device uint8 tensor of at least {need} bytes")
+        _check(self.lib, self.lib.mcbs_first_layer_grad(
+            self._h, handle.ptr, None if fields is None else C.byref(fields), pk, pp, prs, idx, m, n, grad_out.data_ptr(), _row_stride(grad_out, n), H,
+            _ptr(g_w), _row_stride(g_w, F), _ptr(g_b), workspace.data_ptr() if need else None, workspace.numel(), self._stream()),
+            "mcbs_first_layer_grad")
+        return FirstLayerGrad(None if g_w is None else g_w[:, :H], g_b)
+
+    def first_layer_evaluate(self, handle: FeatureLayoutHandle, weight, bias=None, *, obs=None, packing=None, packed=None, index=None, dtype=None,
+                             out_of_range=None, weight_t=None):
+        """first_layer as a node of torch's autograd graph, taking torch's own parameters: weight [H, F] (Linear.weight) and bias [H].
+        Forward transposes once (weight.t().contiguous(); or pass weight_t=, a transposed copy made once per update) and calls
+        first_layer: the same bits.  Backward casts the upstream gradient to contiguous float32, calls first_layer_grad once for the
+        gradients autograd asks for and returns them in the parameters' shapes ([H, F], [H]) and dtypes; the integer inputs have no
+        gradient."""
+        t = self.torch
+        if not isinstance(weight, t.Tensor) or weight.dim() != 2 or weight.shape[1] != handle.width:
+            raise ValueError(f"weight must be torch's Linear.weight [H, F = {handle.width}], got {_describe(weight)}")
+        source = dict(obs=obs, packing=packing, packed=packed, index=index)
+        return _first_layer_evaluate_function(t).apply(weight, bias, self, handle, source, dtype, out_of_range, weight_t)
 
     # -- learned defender (batches created with defender=("external",)) --
     def alloc_defender_obs(self) -> dict:

@@ -165,6 +165,83 @@ class FeatureLayout:
                 out[:, c0:c0 + w] = (np.asarray(obs[k]).reshape(n, w) != 0)
         return (out, bad) if return_out_of_range else out
 
+    # -- the first layer from the observation (include/mcbs.h "first layer from the observation") on the host --
+    def _selected_columns(self, obs: dict, index=None):
+        """-> (cols int64 [n, n_elements]: the column each element of each row selects, in row order, -1 where its value lies outside its
+        classes; out-of-range count).  index: output row i is row index[i] of obs; an index outside the rows selects nothing and counts
+        every element."""
+        if self.mask_columns or any(k in MASK_KEYS for k in self.keys):
+            raise ValueError("the first-layer calls serve layouts without mask columns (include_masks is out of scope)")
+        vals = self._values(obs)
+        inside = None
+        if index is not None:
+            index = np.asarray(index, dtype=np.int64)
+            inside = (index >= 0) & (index < vals.shape[0])
+            vals = vals[np.where(inside, index, 0)]
+        cols = np.full((vals.shape[0], self.n_elements), -1, dtype=np.int64)
+        col = 0
+        for e, (_, src, ncls) in enumerate(self.groups):              # row order: the groups' columns follow each other
+            v = vals[:, src]
+            ok = (v >= 0) & (v < ncls)
+            if inside is not None:
+                ok &= inside
+            cols[ok, e] = col + v[ok]
+            col += ncls
+        return cols, int((cols < 0).sum())
+
+    def first_layer_host(self, obs: dict, weight_t, bias=None, out_dtype=np.float32, index=None, return_out_of_range: bool = False):
+        """mcbs_first_layer[_packed] in NumPy float32, operation for operation in the contract's order: for every row ONE accumulator
+        that starts at the bias (+0.0 without one) and takes one float32 add per element, in row order, of the weight column the
+        element's value selects — torch.nn.functional.linear(encode_host(obs), weight_t.T, bias) summed in that order.
+        weight_t [F, H] and bias [H]: float32 arrays (bfloat16 weights as the float32 values they widen to).  out_dtype: np.float32, or
+        "bfloat16" for the result rounded to nearest even to bfloat16 and returned as the float32 values that holds.  index: as the
+        packed form's (a row outside obs comes out as the bias alone, every element of it counted).  -> [n, H] float32, with
+        return_out_of_range also the number of elements that selected nothing."""
+        cols, bad = self._selected_columns(obs, index)
+        w = np.ascontiguousarray(weight_t, dtype=np.float32)
+        if w.ndim != 2 or w.shape[0] != self.width:
+            raise ValueError(f"weight_t must be [{self.width}, H], got {w.shape}")
+        n, H = cols.shape[0], w.shape[1]
+        acc = np.zeros((n, H), dtype=np.float32)
+        if bias is not None:
+            acc[:] = np.asarray(bias, dtype=np.float32).reshape(1, H)  # acc STARTS at the bias (a -0.0 stays -0.0)
+        for e in range(self.n_elements):
+            ok = cols[:, e] >= 0
+            acc[ok] = acc[ok] + w[cols[ok, e]]
+        if out_dtype in ("bfloat16", "bf16"):
+            acc = _round_to_bfloat16(acc)
+        elif np.dtype(out_dtype) != np.float32:
+            raise ValueError("out_dtype must be np.float32 or 'bfloat16'")
+        return (acc, bad) if return_out_of_range else acc
+
+    def first_layer_grad_host(self, obs: dict, grad_out, H: int, row_block: int = 512, index=None):
+        """mcbs_first_layer_grad in NumPy float32, operation for operation in the contract's order -> (grad_weight_t [F, H], grad_bias
+        [H]).  The rows are cut into blocks of row_block; a block's partial of (column c, h) starts at +0.0 and does s = s + grad_out[i, h]
+        over the block's rows, in ascending i, whose element selects c (the bias row: over all of them); the result is the partials added
+        in ascending block order starting from partial 0.  A row whose index lies outside obs contributes to grad_bias only."""
+        cols, _ = self._selected_columns(obs, index)
+        g = np.ascontiguousarray(grad_out, dtype=np.float32)
+        n, F = cols.shape[0], self.width
+        if g.shape != (n, H):
+            raise ValueError(f"grad_out must be [{n}, {H}], got {g.shape}")
+        total = np.zeros((F + 1, H), dtype=np.float32)
+        for b0 in range(0, n, row_block):
+            part = np.zeros((F + 1, H), dtype=np.float32)
+            for i in range(b0, min(b0 + row_block, n)):
+                c = cols[i]
+                c = np.append(c[c >= 0], F)                           # a row's columns are distinct: one add each
+                part[c] = part[c] + g[i]
+            total = part if b0 == 0 else total + part
+        return total[:F], total[F]
+
+
+def _round_to_bfloat16(x: np.ndarray) -> np.ndarray:
+    """float32 -> the float32 values of x rounded to nearest even to bfloat16 (a NaN stays a quiet NaN): the device's rule restated"""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    r = np.where(nan, (u >> 16) | 0x40, (u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF
+    return (r << 16).astype(np.uint32).view(np.float32).reshape(x.shape)
+
 
 class ObservationPacking:
     """The packed row format of the attacker observation of `topo` under `spec`'s bounds (include/mcbs.h "packed observations"): the

@@ -342,6 +342,17 @@ class MarlonVecEnv:
     def evaluate_masked_from_latent(self, bits, latent, weight, bias, actions, differentiable: bool = False):
         return self.venv.evaluate_masked_from_latent(bits, latent, weight, bias, actions, differentiable=differentiable)
 
+    # the policy's first layer straight from the observation (AttackerVecEnv.first_layer / encode_first_layer / encode_first_layer_packed):
+    # device tensors in and out whatever numpy_outputs says
+    def first_layer(self, weight, bias=None, **kwargs):
+        return self.venv.first_layer(weight, bias, **kwargs)
+
+    def encode_first_layer(self, obs, weight, bias=None, **kwargs):
+        return self.venv.encode_first_layer(obs, weight, bias, **kwargs)
+
+    def encode_first_layer_packed(self, packed, weight, bias=None, **kwargs):
+        return self.venv.encode_first_layer_packed(packed, weight, bias, **kwargs)
+
     def get_attr(self, attr_name: str, indices=None) -> List[Any]:
         val = getattr(self.venv, attr_name)
         idx = self._indices(indices)

@@ -387,6 +387,47 @@ class AttackerVecEnv(_MultiDiscreteHead):
         return self.engine.encode_features_packed(self._feature_handle(bits is not None, reference_counts), self._packing_handle(), packed,
                                                   bits=bits, index=index, out=out, dtype=dtype, out_of_range=out_of_range)
 
+    # -- the policy's first layer straight from the observation (mcbs_first_layer): no feature rows --
+    def _first_layer_call(self, reference_counts: bool, weight, bias, source: dict, out, dtype, out_of_range, weight_t, differentiable: bool):
+        handle = self._feature_handle(False, reference_counts)
+        if differentiable:
+            if out is not None:
+                raise ValueError("differentiable=True allocates its output: out= is not supported")
+            return self.engine.first_layer_evaluate(handle, weight, bias, dtype=dtype, out_of_range=out_of_range, weight_t=weight_t, **source)
+        if weight_t is None:
+            weight_t = weight.detach().t().contiguous()
+        return self.engine.first_layer(handle, weight_t, None if bias is None else bias.detach(), out=out, dtype=dtype, out_of_range=out_of_range,
+                                       **source)
+
+    def first_layer(self, weight, bias=None, out=None, dtype=None, reference_counts: bool = False, out_of_range=None, weight_t=None):
+        """torch.nn.functional.linear(features(), weight, bias) of the observation this env last returned, without the [n_envs, F]
+        feature rows: one launch that adds, per env, the weight column each one-hot element selects to the bias ([n_envs, H] float32 or
+        bfloat16; engine.first_layer has the order of the sum).  weight [H, F] / bias [H]: torch's Linear parameters, float32 or
+        bfloat16 (F = feature_layout(reference_counts=...).width; the masks are not part of this layer's input).  weight_t=: the
+        transposed copy `weight.t().contiguous()` a rollout loop makes once per update instead of once per call.  To serve SB3's
+        policy_net[0] and value_net[0] with one call, concatenate their weights into one [2H, F] (and their biases into [2H])."""
+        return self._first_layer_call(reference_counts, weight, bias, dict(obs=self.observation_fields), out, dtype, out_of_range, weight_t, False)
+
+    def encode_first_layer(self, obs, weight, bias=None, out=None, dtype=None, reference_counts: bool = False, out_of_range=None, weight_t=None,
+                           differentiable: bool = False):
+        """first_layer() for any n stored observation rows: obs as encode_features() takes it (`scalars` [n, 7] or the seven named counts,
+        and the four array fields).  differentiable=True: the result carries an autograd graph into weight and bias whose backward is
+        one call of engine.first_layer_grad (no feature tensor is kept alive for it)."""
+        t = self.torch
+        if "scalars" not in obs:
+            obs = dict(obs, scalars=t.stack([obs[k] for k in SCALAR_KEYS], dim=1).to(t.int32))
+        fields = {k: obs[k].contiguous() for k in FLAT_FIELDS[:5] if k in obs}
+        return self._first_layer_call(reference_counts, weight, bias, dict(obs=fields), out, dtype, out_of_range, weight_t, differentiable)
+
+    def encode_first_layer_packed(self, packed, weight, bias=None, index=None, out=None, dtype=None, reference_counts: bool = False,
+                                  out_of_range=None, weight_t=None, differentiable: bool = False):
+        """first_layer() straight from stored packed rows [m, >= W_obs]; with index (device int64 [n]) the rows are read where they are
+        stored, as encode_features_packed reads them:
+            h = venv.encode_first_layer_packed(buf.observations["packed"].view(T * E, -1), lin.weight, lin.bias, index=batch.index,
+                                               differentiable=True)"""
+        source = dict(packing=self._packing_handle(), packed=packed, index=index)
+        return self._first_layer_call(reference_counts, weight, bias, source, out, dtype, out_of_range, weight_t, differentiable)
+
     # -- the rollout buffer (marlon_amd/rollout.py, mcbs_gae) --
     @property
     def observation_fields(self) -> Dict[str, object]:
