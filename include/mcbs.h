@@ -1013,6 +1013,45 @@ int  mcbs_defender_wrapper_post(mcbs_batch*, const mcbs_defender_wrapper_buffers
 int  mcbs_defender_wrapper_step(mcbs_batch*, const int64_t* actions, const mcbs_defender_obs* obs, const mcbs_defender_wrapper_buffers* w,
                                 const mcbs_defender_wrapper_cfg* cfg, void* stream);
 
+/* ---- the two-agent turn: marl_algorithm.run_episode's loop body (marlon/baseline_models/multiagent/marl_algorithm.py:197-250) ---- */
+typedef struct mcbs_episode_buffers {   /* 48 bytes: run_episode's per-env bookkeeping (marlon_amd/simulate.py), device arrays of n_envs */
+    uint8_t* alive;            /* in/out: the env's episode is still running */
+    double*  attacker_reward;  /* out: this turn's row of the attacker trace */
+    double*  defender_reward;  /* out: this turn's row of the defender trace */
+    int64_t* lengths;          /* in/out */
+    uint8_t* attacker_done;    /* in/out */
+    uint8_t* defender_done;    /* in/out */
+} mcbs_episode_buffers;
+
+/* 1: mcbs_two_agent_step serves this batch, in one launch; 0: it does not (the batch is outside the scope below; NULL: 0). */
+int32_t mcbs_two_agent_step_launches(const mcbs_batch*);
+/* One JOINT turn of both wrappers for every env in ONE launch (marlon_amd/csrc/mcbs_two_agent.hip): the attacker's wrapper step, the
+ * defender's wrapper step and run_episode's bookkeeping.  The reference's defender predicts from the observation its own previous
+ * step returned (marl_algorithm.py:222-225), so both agents' actions exist before the turn starts.
+ * Scope: batches and requests for which mcbs_attacker_wrapper_step is one launch (packed, at most 16 nodes and cached credentials, no
+ * mask field in obs, 16-byte aligned arrays) created with MCBS_DEFENDER_EXTERNAL, defender_obs given with its arrays on 16-byte
+ * boundaries.  Anything else is MCBS_EINVAL with a message naming the reason; then nothing was launched and no state
+ * changed.  There is no multi-launch fallback: a caller that needs one has mcbs_attacker_wrapper_step + mcbs_defender_wrapper_step.
+ * Per env e, with a = ep->alive[e] on entry (1 when ep is NULL), the call equals that sequence bit for bit:
+ *  1. the attacker half is mcbs_attacker_wrapper_step(..., auto_reset = 0, NULL, NULL) for EVERY env, alive or not: decode and
+ *     interception, step, the five-field observation and the digest — taken between the attacker's action and the defender's turn —,
+ *     `decoded`, every output of w and of info.  Attacker auto-reset is not part of this call: the episode boundary is the caller's.
+ *  2. d1 = a && (w->terminated[e] | w->truncated[e]);  attacker_reward[e] = a ? (double)w->rewards[e] : 0.0.
+ *  3. the defender half is mcbs_defender_wrapper_step for this env with the kind component of defender_actions[e] taken as -2 when
+ *     !a || d1 (the array itself is never written): validity on the state before the tick, tick, action, then the reward shaping
+ *     — which reads THIS turn's w->last_cyber_reward / has_cyber_reward and counts a parked env's turn as today's call does —,
+ *     dw->valid / availability / evicted and every output of dw, then the four fields of defender_obs from the state after the action.
+ *  4. stepped = a && !d1;  d2 = (stepped && (dw->terminated[e] | dw->truncated[e])) || d1;
+ *     defender_reward[e] = stepped ? dw->reward[e] : (d1 ? -attacker_reward[e] : 0.0)    (defend_wrapper.py:269-271, -0.0 included).
+ *  5. lengths[e] += a;  attacker_done[e] |= d1;  defender_done[e] |= d2 && a;  alive[e] = a && !(d1 || d2).
+ * ep may be NULL: steps 2, 4 and 5 store nothing, and the attacker's own dones of this turn still park the defender (step 3). */
+int  mcbs_two_agent_step(mcbs_batch*, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded,
+                         const mcbs_info_buffers* info, const mcbs_obs_buffers* obs, const mcbs_wrapper_buffers* w,
+                         float invalid_action_reward_modifier, int32_t attacker_max_timesteps,
+                         const int64_t* defender_actions, const mcbs_defender_obs* defender_obs,
+                         const mcbs_defender_wrapper_buffers* dw, const mcbs_defender_wrapper_cfg* dcfg,
+                         const mcbs_episode_buffers* ep, void* stream);
+
 /* Parity / debugging: canonical per-env state records (layout: mcbs_state_record below),
  * host buffers, synchronous.  The record does not carry what only MCBS_DEFENDER_RANDOM_EVENTS mutates (vulnerability keys,
  * service flags, firewall rule lists): mcbs_set_state puts those back to the topology's initial ones for the envs it writes. */

@@ -69,6 +69,20 @@ class DefenderObs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("infected_nodes", "incoming_firewall_status", "outgoing_firewall_status", "services_status")]
 
 
+# mcbs_episode_buffers (include/mcbs.h): six device pointers, these members in this order.  An array of six pointers, not a
+# Structure: byref() hands over the same 48 bytes, and the Structures of this module are exactly those tests/test_native_library.py
+# lists against the header — this block is held to the header by tests/test_two_agent_host.py.  Filled through episode_buffers()
+EPISODE_FIELDS = ("alive", "attacker_reward", "defender_reward", "lengths", "attacker_done", "defender_done")
+EpisodeBuffers = C.c_void_p * len(EPISODE_FIELDS)
+
+
+def episode_buffers(**arrays) -> "EpisodeBuffers":
+    """An mcbs_episode_buffers block from device pointers given by member name (every member of EPISODE_FIELDS)."""
+    if set(arrays) != set(EPISODE_FIELDS):
+        raise ValueError(f"mcbs_episode_buffers has exactly the members {EPISODE_FIELDS}")
+    return EpisodeBuffers(*[arrays[n] for n in EPISODE_FIELDS])
+
+
 class BatchVariantInfo(C.Structure):
     """mcbs_batch_variant_info (include/mcbs.h): the compiled variant a batch dispatches to"""
     _fields_ = [(n, C.c_uint32) for n in ("packed", "words_per_set", "wide", "coop", "lds_topo", "defender_kind", "fused_wrapper",
@@ -197,6 +211,10 @@ PROTOTYPES = {
     "mcbs_attacker_wrapper_step_launches": (_i32, [_H, _i32]),                                # batch, with_masks
     "mcbs_defender_wrapper_post": (_int, [_H, _P, _P, _S]),                                   # batch, w, cfg, stream
     "mcbs_defender_wrapper_step": (_int, [_H, _P, _P, _P, _P, _S]),                           # batch, actions, obs, w, cfg, stream
+    "mcbs_two_agent_step_launches": (_i32, [_H]),
+    # batch, multidiscrete, discrete, decoded, info, obs, w, invalid_action_reward_modifier, attacker_max_timesteps, defender_actions,
+    # defender_obs, dw, dcfg, ep (an EpisodeBuffers block or NULL), stream
+    "mcbs_two_agent_step": (_int, [_H, _P, _P, _P, _P, _P, _P, _f32, _i32, _P, _P, _P, _P, _P, _S]),
     "mcbs_state_record_bytes": (_size, [_H]),
     "mcbs_get_state": (_int, [_H, _P, _size]),                                                # batch, host_buf, nbytes
     "mcbs_set_state": (_int, [_H, _P, _size]),                                                # batch, host_buf, nbytes

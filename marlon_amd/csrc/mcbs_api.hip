@@ -31,6 +31,7 @@
 #include "mcbs_obs_packing.hip"
 #include "mcbs_first_layer.hip"
 #include "mcbs_wrapper_fused.hip"
+#include "mcbs_two_agent.hip"
 #include "mcbs_mask_keys.hip"
 
 using namespace mcbs;
@@ -1111,15 +1112,16 @@ extern "C" int32_t mcbs_attacker_wrapper_step_launches(const mcbs_batch* b, int3
 
 // The whole wrapper step in ONE launch (mcbs_wrapper_fused.hip) when the batch (variant.fused_wrapper) and the request fit it: no mask
 // field, observation rows of whole 16-byte vectors, every requested field paired with its terminal array and its reset row
-// (auto_reset).  Returns 1 when it launched, 0 when the caller should run the three launches, < 0 on error.
-static int try_fused_wrapper_step(mcbs_batch* b, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded, const StepIO& io,
-                                  const mcbs_obs_buffers* o, const mcbs_wrapper_buffers* w, float modifier, int32_t max_timesteps, int32_t auto_reset,
-                                  const mcbs_row_copies* keep, const mcbs_row_copies* fresh, hipStream_t st) {
+// (auto_reset).  fused_wrapper_args: the kernel's argument block -> true when batch and request fit (mcbs_two_agent_step shares it).
+static bool fused_wrapper_args(const mcbs_batch* b, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded, const mcbs_obs_buffers* o,
+                               const mcbs_wrapper_buffers* w, float modifier, int32_t max_timesteps, int32_t auto_reset, const mcbs_row_copies* keep,
+                               const mcbs_row_copies* fresh, FusedArgs* out) {
     const mcbs_topo_header* h = b->topo->H();
     const uint32_t Nm = b->cfg.maximum_node_count, Cm = b->cfg.maximum_total_credentials, K = b->cfg.maximum_discoverable_credentials_per_action;
-    if (!b->variant.fused_wrapper || o->mask_local || o->mask_remote || o->mask_connect || o->mask_discrete) return 0;
+    if (!b->variant.fused_wrapper || o->mask_local || o->mask_remote || o->mask_connect || o->mask_discrete) return false;
     const uint32_t NP = b->C.n_props;
-    FusedArgs A{};
+    FusedArgs& A = *out;
+    A = FusedArgs{};
     A.w = *w; A.modifier = modifier; A.max_timesteps = max_timesteps; A.auto_reset = auto_reset;
     A.Nmax = Nm; A.Cmax = Cm; A.K = K; A.NP = NP;
     A.md = multidiscrete; A.discrete = discrete; A.decoded = decoded;
@@ -1131,28 +1133,37 @@ static int try_fused_wrapper_step(mcbs_batch* b, const int64_t* multidiscrete, c
         const bool vec = f > 0 && dw[f] % 4u == 0 && !(f == 3 && NP < 4u);          // whole 16-byte vectors per env row, else dword by dword
         A.d_u4[f] = fast_div_host(vec ? dw[f] / 4u : (dw[f] ? dw[f] : 1u));
         if (!fields[f]) continue;
-        if (dw[f] == 0 || (vec && reinterpret_cast<uintptr_t>(fields[f]) % 16u != 0)) return 0;
+        if (dw[f] == 0 || (vec && reinterpret_cast<uintptr_t>(fields[f]) % 16u != 0)) return false;
         if (auto_reset) {
             int ki = -1, fi = -1;
             for (uint32_t i = 0; keep && i < keep->n; ++i) if (keep->src[i] == fields[f] && keep->row_bytes[i] == 4ull * dw[f]) ki = (int)i;
             for (uint32_t i = 0; fresh && i < fresh->n; ++i) if (fresh->dst[i] == fields[f] && fresh->row_bytes[i] == 4ull * dw[f]) fi = (int)i;
-            if (ki < 0 || fi < 0) return 0;
+            if (ki < 0 || fi < 0) return false;
             A.term[f] = static_cast<int32_t*>(keep->dst[ki]);
             A.fresh[f] = static_cast<const int32_t*>(fresh->src[fi]);
-            if (vec && reinterpret_cast<uintptr_t>(A.term[f]) % 16u != 0) return 0;
+            if (vec && reinterpret_cast<uintptr_t>(A.term[f]) % 16u != 0) return false;
         }
         off += (dw[f] + 3u) & ~3u;
     }
-    if (off > FUSED_FRESH_DWORDS) return 0;
+    if (off > FUSED_FRESH_DWORDS) return false;
     if (auto_reset) {          // every array the generic finish would copy must be one the fused kernel handles (no extra fields)
         uint32_t n_fields = 0;
         for (uint32_t f = 0; f < FUSED_FIELDS; ++f) n_fields += fields[f] ? 1u : 0u;
-        if ((keep ? keep->n : 0u) != n_fields || (fresh ? fresh->n : 0u) != n_fields) return 0;
+        if ((keep ? keep->n : 0u) != n_fields || (fresh ? fresh->n : 0u) != n_fields) return false;
     }
     A.dNP = fast_div_host(NP ? NP : 1u);
     A.digest = b->digest; A.reset_digest = b->reset_digest;
     A.triples = reinterpret_cast<const mcbs_triple*>(b->topo->dev + h->off_triple);
     A.n_triples = h->n_triples;
+    return true;
+}
+
+// Returns 1 when it launched, 0 when the caller should run the three launches, < 0 on error.
+static int try_fused_wrapper_step(mcbs_batch* b, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded, const StepIO& io,
+                                  const mcbs_obs_buffers* o, const mcbs_wrapper_buffers* w, float modifier, int32_t max_timesteps, int32_t auto_reset,
+                                  const mcbs_row_copies* keep, const mcbs_row_copies* fresh, hipStream_t st) {
+    FusedArgs A;
+    if (!fused_wrapper_args(b, multidiscrete, discrete, decoded, o, w, modifier, max_timesteps, auto_reset, keep, fresh, &A)) return 0;
     b->all_fresh = false;
     const dim3 grid((b->S.E + 63u) / 64u), block(FUSED_THREADS);
     pick<MCBS_DEFENDER_SCAN_AND_REIMAGE, MCBS_DEFENDER_EXTERNAL, MCBS_DEFENDER_NONE>((int)b->cfg.defender_kind, [&](auto def) {
@@ -2386,6 +2397,52 @@ extern "C" int mcbs_defender_observe(mcbs_batch* b, const mcbs_defender_obs* obs
     MCBS_ON_DEVICE(b);
     if (const int rc = learned_defender_ok(b)) return rc;
     return launch_defender_obs(b, obs, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ the two-agent turn (mcbs_two_agent.hip)
+// the batch-level half of mcbs_two_agent_step's scope: -> nullptr when the batch fits, else the reason
+static const char* two_agent_batch_reason(const mcbs_batch* b) {
+    if (b->cfg.defender_kind != MCBS_DEFENDER_EXTERNAL) return "batch was not created with MCBS_DEFENDER_EXTERNAL";
+    if (!b->variant.fused_wrapper) return "the attacker's wrapper step of this batch is not one launch (packed batch, at most 16 nodes and cached credentials)";
+    if (!b->variant.fused_defender_obs || b->S.WT != 1u) return "the defender's turn of this batch cannot write its own observation";
+    return nullptr;
+}
+
+extern "C" int32_t mcbs_two_agent_step_launches(const mcbs_batch* b) {
+    return (b && !two_agent_batch_reason(b)) ? 1 : 0;
+}
+
+extern "C" int mcbs_two_agent_step(mcbs_batch* b, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded, const mcbs_info_buffers* info,
+                                   const mcbs_obs_buffers* obs, const mcbs_wrapper_buffers* w, float modifier, int32_t attacker_max_timesteps,
+                                   const int64_t* defender_actions, const mcbs_defender_obs* defender_obs, const mcbs_defender_wrapper_buffers* dw,
+                                   const mcbs_defender_wrapper_cfg* dcfg, const mcbs_episode_buffers* ep, void* stream) {
+    if (!b || !w || !decoded || !obs || !defender_actions || !defender_obs || !dw || !dcfg) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    // every check before the launch: a refused call launches nothing and changes no state
+    if (const char* why = two_agent_batch_reason(b)) return fail(MCBS_EINVAL, "two-agent turn: %s", why);
+    WrapperFinishArgs unused;
+    int rc = finish_args(b, w, modifier, attacker_max_timesteps, 0, nullptr, nullptr, &unused);
+    if (rc) return rc;
+    if ((rc = draws_ok(b))) return rc;
+    if (!multidiscrete == !discrete) return fail(MCBS_EINVAL, "need exactly one action encoding");
+    if (!arrays_set(dw, 0)) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
+    if (ep && !arrays_set(ep, 0)) return fail(MCBS_EINVAL, "mcbs_episode_buffers: every array is required");
+    TwoAgentArgs D{};
+    D.actions = defender_actions; D.dw = *dw; D.dcfg = *dcfg;
+    D.obs = fused_defender_obs(b, defender_obs);
+    if (!D.obs.fused) return fail(MCBS_EINVAL, "two-agent turn: the defender's observation arrays must lie on 16-byte boundaries");
+    if (ep) D.ep = *ep;
+    FusedArgs A;
+    if (!fused_wrapper_args(b, multidiscrete, discrete, decoded, obs, w, modifier, attacker_max_timesteps, 0, nullptr, nullptr, &A))
+        return fail(MCBS_EINVAL, "two-agent turn: the attacker's request is outside the one-launch wrapper step (a mask field, or an observation "
+                                 "array that is not on a 16-byte boundary)");
+    const StepIO io = make_io(b, decoded, const_cast<float*>(w->reward), const_cast<uint8_t*>(w->terminated), info);
+    b->all_fresh = false;
+    hipLaunchKernelGGL(two_agent_kernel, dim3((b->S.E + 63u) / 64u), dim3(FUSED_THREADS), 0, (hipStream_t)stream, b->S, b->T, b->C_dev, io, A, D);
+    rc = launch_ok("two-agent turn");
+    if (rc) return rc;
+    b->digest_state = 1;       // every env's digest was written (or, for an intercepted action, stands)
+    return MCBS_OK;
 }
 
 // ------------------------------------------------------------------ state export / import (debug, synchronous)

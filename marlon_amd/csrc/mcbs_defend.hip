@@ -18,9 +18,10 @@
 namespace mcbs {
 
 // One env's defender turn (env e < S.E).  -> ok (the action was valid), avail (availability after the tick), evicted
-template <int WT>
+// PARK (the two-agent turn, mcbs_two_agent.hip): `parked` replaces the action's kind by -2 without touching the caller's array
+template <int WT, bool PARK = false>
 __device__ __forceinline__ void defender_turn(const DevState& S, const Topo& T, const StepCfg& C, const int64_t* actions, uint32_t e,
-                                              bool& ok_out, double& avail_out, bool& evicted_out) {
+                                              bool& ok_out, double& avail_out, bool& evicted_out, const bool parked = false) {
     const uint4 h0 = S.h0[e];
     double2 h1 = S.h1[e];
     uint8_t* body = S.body + (size_t)e * S.body_stride;
@@ -47,7 +48,7 @@ __device__ __forceinline__ void defender_turn(const DevState& S, const Topo& T, 
     int64_t a[12];
 #pragma unroll
     for (int i = 0; i < 12; ++i) a[i] = ap[i];
-    const int kind = (int)a[0];
+    const int kind = (PARK && parked) ? -2 : (int)a[0];              // (every kind <= -2 means the same: the caller's own stays what it is)
     if (kind <= -2) {                                                // env not taking part in this turn (e.g. its episode just ended)
         ok_out = false; avail_out = h1.y; evicted_out = false;
         return;
@@ -112,38 +113,49 @@ struct DefObs {
     FastDiv dN, d6N, dS;                 // divisors: nodes, six bytes per node, services
 };
 constexpr uint32_t DEF_WG = 128u, DEF_NMAX = 32u, DEF_SMAX = 256u;
-struct DefStage { uint32_t inst[DEF_WG]; uint16_t fw[DEF_WG * DEF_NMAX]; uint8_t svc[DEF_SMAX]; };      // 8.9 KB per workgroup
+template <uint32_t ENVS>
+struct DefStageT { uint32_t inst[ENVS]; uint16_t fw[ENVS * DEF_NMAX]; uint8_t svc[DEF_SMAX]; };
+using DefStage = DefStageT<DEF_WG>;      // 8.9 KB per workgroup (the turn kernels); DefStageT<64>, 4.6 KB: the two-agent turn
 
-template <int WT>
-__device__ __forceinline__ void defender_observe_wg(const DevState& S, const Topo& T, const DefObs& o, const uint32_t e, const bool valid, DefStage& st) {
-    const uint32_t tid = threadIdx.x, N = S.N, e0 = blockIdx.x * DEF_WG;
-    const uint32_t n_env = S.E - e0 < DEF_WG ? S.E - e0 : DEF_WG;
-    if (valid) {
-        const uint8_t* body = S.body + (size_t)e * S.body_stride;
-        const uint16_t* fw = reinterpret_cast<const uint16_t*>(body + S.off_fw);
-        const mcbs_node_static* NS = reinterpret_cast<const mcbs_node_static*>(T.base + T.H().off_node);
-        st.inst[tid] = (uint32_t)S.get(M_INST, 0u, e);                   // N <= 32: the low bits of word 0
-        for (uint32_t n = 0; n < N; ++n) {                               // (uniform: node statics through the scalar cache)
-            const uint32_t lists = NS[n].fw_lists;
-            st.fw[tid * DEF_NMAX + n] = (uint16_t)((fw[lists & 0xFFFFu] & 63u) | ((fw[lists >> 16] & 63u) << 8));
-        }
+// the lane that took env e's turn parks the env's bits in slot `slot` of its workgroup's stage
+template <int WT, uint32_t ENVS>
+__device__ __forceinline__ void defender_park(const DevState& S, const Topo& T, const uint32_t e, const uint32_t slot, DefStageT<ENVS>& st) {
+    const uint32_t N = S.N;
+    const uint8_t* body = S.body + (size_t)e * S.body_stride;
+    const uint16_t* fw = reinterpret_cast<const uint16_t*>(body + S.off_fw);
+    const mcbs_node_static* NS = reinterpret_cast<const mcbs_node_static*>(T.base + T.H().off_node);
+    st.inst[slot] = (uint32_t)S.get(M_INST, 0u, e);                  // N <= 32: the low bits of word 0
+    for (uint32_t n = 0; n < N; ++n) {                               // (uniform: node statics through the scalar cache)
+        const uint32_t lists = NS[n].fw_lists;
+        st.fw[slot * DEF_NMAX + n] = (uint16_t)((fw[lists & 0xFFFFu] & 63u) | ((fw[lists >> 16] & 63u) << 8));
     }
-    if (o.services) {                                                    // services never change state (see below): the initial flags
+}
+// services never change state (see below): the initial flags, by threads t of nt
+template <uint32_t ENVS>
+__device__ __forceinline__ void defender_park_services(const Topo& T, const DefObs& o, const uint32_t t, const uint32_t nt, DefStageT<ENVS>& st) {
+    if (o.services) {
         const mcbs_service* sv = reinterpret_cast<const mcbs_service*>(T.base + T.H().off_service);
-        for (uint32_t k = tid; k < o.n_services; k += DEF_WG) st.svc[k] = sv[k].running ? 1 : 0;
+        for (uint32_t k = t; k < o.n_services; k += nt) st.svc[k] = sv[k].running ? 1 : 0;
     }
-    __syncthreads();
+}
+
+// ... and, once the stage is complete (the caller's barrier), thread tid of THREADS streams the observation of the workgroup's envs
+// e0 .. e0 + ENVS - 1 out of it
+template <uint32_t ENVS, uint32_t THREADS>
+__device__ __forceinline__ void defender_stream(const DevState& S, const DefObs& o, const uint32_t tid, const uint32_t e0, const DefStageT<ENVS>& st) {
+    const uint32_t N = S.N;
+    const uint32_t n_env = S.E - e0 < ENVS ? S.E - e0 : ENVS;
     // byte j of a 16-byte chunk held in four dwords
 #define MCBS_PUT_BYTE(w, j, v) w[(j) >> 2] |= (uint32_t)(v) << (8u * ((j) & 3u))
     if (o.infected) {
         int8_t* p = o.infected + (size_t)e0 * N;
         const uint32_t R = n_env * N;
-        for (uint32_t b0 = tid * 16u; b0 < R; b0 += DEF_WG * 16u) {
+        for (uint32_t b0 = tid * 16u; b0 < R; b0 += THREADS * 16u) {
             uint32_t env = fdiv(b0, o.dN), node = b0 - env * N, bits = st.inst[env], w[4] = {0, 0, 0, 0};
 #pragma unroll
             for (uint32_t j = 0; j < 16u; ++j) {
                 MCBS_PUT_BYTE(w, j, (bits >> node) & 1u);
-                if (++node == N) { node = 0; env = env + 1u < DEF_WG ? env + 1u : env; bits = st.inst[env]; }
+                if (++node == N) { node = 0; env = env + 1u < ENVS ? env + 1u : env; bits = st.inst[env]; }
             }
             if (b0 + 16u <= R) *reinterpret_cast<uint4*>(p + b0) = make_uint4(w[0], w[1], w[2], w[3]);
             else {
@@ -156,7 +168,7 @@ __device__ __forceinline__ void defender_observe_wg(const DevState& S, const Top
     auto stream_fw = [&](int8_t* dst, const uint32_t shift) {            // six 0 / 1 bytes per (env, node): two per step (6 is even)
         int8_t* p = dst + (size_t)e0 * 6u * N;
         const uint32_t R = n_env * 6u * N;
-        for (uint32_t b0 = tid * 16u; b0 < R; b0 += DEF_WG * 16u) {
+        for (uint32_t b0 = tid * 16u; b0 < R; b0 += THREADS * 16u) {
             uint32_t env = fdiv(b0, o.d6N);
             const uint32_t rem = b0 - env * 6u * N;
             uint32_t node = rem / 6u, k = rem - node * 6u, f = (uint32_t)st.fw[env * DEF_NMAX + node] >> shift, w[4] = {0, 0, 0, 0};
@@ -167,7 +179,7 @@ __device__ __forceinline__ void defender_observe_wg(const DevState& S, const Top
                 k += 2u;
                 if (k == 6u) {
                     k = 0;
-                    if (++node == N) { node = 0; env = env + 1u < DEF_WG ? env + 1u : env; }
+                    if (++node == N) { node = 0; env = env + 1u < ENVS ? env + 1u : env; }
                     f = (uint32_t)st.fw[env * DEF_NMAX + node] >> shift;
                 }
             }
@@ -184,7 +196,7 @@ __device__ __forceinline__ void defender_observe_wg(const DevState& S, const Top
     if (o.services && o.n_services) {
         const uint32_t Sv = o.n_services, R = n_env * Sv;
         int8_t* p = o.services + (size_t)e0 * Sv;
-        for (uint32_t b0 = tid * 16u; b0 < R; b0 += DEF_WG * 16u) {
+        for (uint32_t b0 = tid * 16u; b0 < R; b0 += THREADS * 16u) {
             uint32_t k = b0 - fdiv(b0, o.dS) * Sv, w[4] = {0, 0, 0, 0};
 #pragma unroll
             for (uint32_t j = 0; j < 16u; ++j) {
@@ -200,6 +212,15 @@ __device__ __forceinline__ void defender_observe_wg(const DevState& S, const Top
         }
     }
 #undef MCBS_PUT_BYTE
+}
+
+template <int WT>
+__device__ __forceinline__ void defender_observe_wg(const DevState& S, const Topo& T, const DefObs& o, const uint32_t e, const bool valid, DefStage& st) {
+    const uint32_t tid = threadIdx.x;
+    if (valid) defender_park<WT>(S, T, e, tid, st);
+    defender_park_services(T, o, tid, DEF_WG, st);
+    __syncthreads();
+    defender_stream<DEF_WG, DEF_WG>(S, o, tid, blockIdx.x * DEF_WG, st);
 }
 
 template <int WT>
@@ -220,7 +241,9 @@ __global__ __launch_bounds__(128) void defender_kernel(DevState S, Topo T, const
 }
 
 // DefenderEnvWrapper.step's reward shaping (defend_wrapper.py:228-282) for one env, from the turn's results (in registers or loaded)
-__device__ __forceinline__ void defender_shape(const mcbs_defender_wrapper_buffers& w, const mcbs_defender_wrapper_cfg& c, uint32_t e, bool valid, double avail,
+// -> what it stored to w.reward / terminated / truncated (the two-agent turn books the episode from them)
+struct DefShaped { double reward; bool terminated, truncated; };
+__device__ __forceinline__ DefShaped defender_shape(const mcbs_defender_wrapper_buffers& w, const mcbs_defender_wrapper_cfg& c, uint32_t e, bool valid, double avail,
                                                bool won) {
     if (valid) w.valid_action_count[e] += 1; else w.invalid_action_count[e] += 1;
     double reward = (valid ? 0.0 : 1.0) * c.invalid_action_penalty;
@@ -243,6 +266,7 @@ __device__ __forceinline__ void defender_shape(const mcbs_defender_wrapper_buffe
     w.truncated[e] = t >= c.max_timesteps ? 1 : 0;
     w.breached[e] = breached ? 1 : 0;
     w.won[e] = won ? 1 : 0;
+    return DefShaped{reward, terminated, t >= c.max_timesteps};
 }
 
 __global__ __launch_bounds__(256) void defender_wrapper_post_kernel(uint32_t E, mcbs_defender_wrapper_buffers w, mcbs_defender_wrapper_cfg c) {

@@ -572,6 +572,28 @@ class BatchEngine:
                 _check(lib, rc, "mcbs_defender_wrapper_step")
         return call
 
+    def two_agent_step_launches(self) -> int:
+        """1 when mcbs_two_agent_step serves this batch (both wrappers' steps and the episode bookkeeping in one launch), else 0."""
+        return int(self.lib.mcbs_two_agent_step_launches(self._h))
+
+    def two_agent_step_call(self, discrete: bool, decoded, obs_struct, bufs, modifier: float, max_timesteps: int, defender_obs_struct, defender_bufs,
+                            defender_cfg):
+        """callable(attacker_actions_ptr, defender_actions_ptr, episode_block or None): mcbs_two_agent_step with every argument block but
+        the episode's bound once, like wrapper_step_call / defender_wrapper_step_call.  `episode_block`: an _abi.EpisodeBuffers the caller
+        keeps alive (its two reward rows move from turn to turn)."""
+        fn, eng, lib, stream = self.lib.mcbs_two_agent_step, self, self.lib, self._stream
+        refs = (C.byref(self._info_struct), C.byref(obs_struct), C.byref(bufs), C.byref(defender_obs_struct), C.byref(defender_bufs),
+                C.byref(defender_cfg))
+        rows, mod, mt = decoded.data_ptr(), float(modifier), int(max_timesteps)
+        alive = (decoded, obs_struct, bufs, defender_obs_struct, defender_bufs, defender_cfg, self._info_struct)
+
+        def call(p: int, q: int, ep=None, _alive=alive) -> None:
+            rc = fn(eng._h, None if discrete else p, p if discrete else None, rows, refs[0], refs[1], refs[2], mod, mt, q, refs[3], refs[4], refs[5],
+                    C.byref(ep) if ep is not None else None, stream())
+            if rc:
+                _check(lib, rc, "mcbs_two_agent_step")
+        return call
+
     def wrapper_step_launches(self, with_masks: bool) -> int:
         """Kernel launches per mcbs_attacker_wrapper_step of this batch (1: the whole wrapper step is one launch; 3 otherwise)."""
         return int(self.lib.mcbs_attacker_wrapper_step_launches(self._h, int(bool(with_masks))))

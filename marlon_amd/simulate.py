@@ -114,6 +114,49 @@ def run_episode(att: AttackerVecEnv, dfd: Optional[DefenderVecEnv] = None, attac
     return out
 
 
+def run_episode_joint(att: AttackerVecEnv, dfd: DefenderVecEnv, attacker_policy: Optional[Callable] = None,
+                      defender_policy: Optional[Callable] = None, max_steps: int = 2000, sync_every: int = 16) -> Dict[str, object]:
+    """`run_episode` with the joint turn: per loop iteration the two policy calls and ONE library call (`TwoAgentVecEnv.step`:
+    both wrappers' steps, the parking of finished envs and the bookkeeping in one launch).  Returns the same dict as `run_episode`,
+    equal bit for bit for the same policies.  The kernel writes each turn's two reward rows straight into trace storage allocated in
+    chunks of `sync_every` rows, and the host looks at `alive.any()` only every `sync_every` iterations; the up to `sync_every - 1`
+    iterations past the last env's end step parked envs only, and their rows are trimmed (`steps == lengths.max()`).
+
+    The defender's policy is called BEFORE the attacker's step of the turn — the reference's data flow: `defender_agent.predict(obs2)`
+    uses the observation the defender's own previous step returned (marl_algorithm.py:222).  A policy that peeks at attacker state
+    through `dfd.attacker` therefore sees it one half-turn earlier than under `run_episode`; and both policies are called for the
+    trimmed iterations too.  Needs a batch `TwoAgentVecEnv` accepts (`TwoAgentVecEnv.supported(att)`): ValueError otherwise."""
+    from .wrappers import TwoAgentVecEnv
+    if sync_every < 1:
+        raise ValueError("sync_every must be positive")
+    joint = TwoAgentVecEnv(att, dfd)
+    t = att.torch
+    dev = att.engine.device
+    E = att.num_envs
+    attacker_policy = attacker_policy or random_policy()
+    defender_policy = defender_policy or random_defender_policy()
+    att.reset()
+    dfd.reset()
+    ep = joint.episode_state()
+    a_rew, d_rew = [], []
+    n_steps = 0
+    while n_steps < max_steps:
+        row = n_steps % sync_every
+        if row == 0:
+            a_rew.append(t.zeros((sync_every, E), dtype=t.float64, device=dev))
+            d_rew.append(t.zeros((sync_every, E), dtype=t.float64, device=dev))
+        actions1 = attacker_policy(att)
+        actions2 = defender_policy(dfd)
+        joint.step(actions1, actions2, episode=ep, reward_rows=(a_rew[-1][row], d_rew[-1][row]))
+        n_steps += 1
+        if n_steps % sync_every == 0 and not bool(ep.alive.any()):
+            break
+    steps = min(n_steps, int(ep.lengths.max())) if n_steps else 0          # the iterations run_episode would have taken
+    return dict(attacker_rewards=t.cat(a_rew)[:steps] if a_rew else t.zeros((0, E), dtype=t.float64, device=dev),
+                defender_rewards=t.cat(d_rew)[:steps] if d_rew else t.zeros((0, E), dtype=t.float64, device=dev),
+                lengths=ep.lengths, attacker_done=ep.attacker_done.bool(), defender_done=ep.defender_done.bool(), steps=steps)
+
+
 def uniform_attacker_policy(seed: int = 0) -> Callable[[AttackerVecEnv], object]:
     """`action_space.sample()` of AttackerEnvWrapper's MultiDiscrete space — what RandomMarlonAgent does when the wrapper exposes no
     action masks (random_marlon_agent.py:72-96), i.e. in `marlon.simulate.simulate`'s default universe.  Mostly out-of-range actions."""
@@ -132,14 +175,16 @@ def uniform_attacker_policy(seed: int = 0) -> Callable[[AttackerVecEnv], object]
 
 def simulate(timesteps: int, attacker_option: str = "Random", defender_option: str = "None", attacker_file=None, defender_file=None,
              n_envs: int = 1, seed: int = 0, device: Optional[str] = None, maximum_node_count: int = 100, maximum_total_credentials: int = 1000,
-             maximum_discoverable_credentials_per_action: int = 5, attacker_action_masking: bool = False) -> Dict[str, object]:
+             maximum_discoverable_credentials_per_action: int = 5, attacker_action_masking: bool = False, joint: bool = False) -> Dict[str, object]:
     """`marlon.simulate.simulate(timesteps, attacker_option, defender_option, attacker_file, defender_file)` (marlon/simulate.py:14-35) for a
     batch of `n_envs` universes: `MultiAgentUniverse.build` (multiagent_universe.py:77-199) with its defaults — CyberBattleToyCtf-v0
     (own_atleast 6, eviction goal), `max_timesteps=2000`, both invalid-action reward modifiers 0 as simulate passes them, and with a
     defender `DefenderConstraint(maintain_sla=0.60)`, `losing_reward=-5000` — then one `run_episode(max_steps=timesteps)`.  Options:
     'Random' (RandomMarlonAgent: uniform over the action masks if the wrapper has them, else uniform over the action space) and 'None'
     (defender only).  'Load' needs Stable-Baselines3 / the Q-learning pickles of the reference and is not available here.
-    Returns run_episode's reward traces instead of the reference's plotly frames (rendering is out of scope)."""
+    Returns run_episode's reward traces instead of the reference's plotly frames (rendering is out of scope).
+    joint=True: the episode runs through `run_episode_joint` (one launch per joint turn) where the batch allows it — a defender, a small
+    topology, no materialised masks —, else through `run_episode` as before; the result is the same either way."""
     from .cyberbattle_env import AttackerGoal, DefenderConstraint
     from .samples import toy_ctf
     if attacker_option == "None":
@@ -154,12 +199,18 @@ def simulate(timesteps: int, attacker_option: str = "Random", defender_option: s
               maximum_discoverable_credentials_per_action=maximum_discoverable_credentials_per_action,
               attacker_goal=AttackerGoal(own_atleast=6), max_timesteps=2000, invalid_action_reward_modifier=0,
               discrete=attacker_action_masking, auto_reset=False, device=device, seed=seed)
+    if joint and with_defender and not attacker_action_masking:
+        kw.update(materialize_masks=False)         # (the uniform attacker never reads the masks)
     if with_defender:
         kw.update(defender_constraint=DefenderConstraint(maintain_sla=0.60), losing_reward=-5000.0, learned_defender=True)
     att = AttackerVecEnv(toy_ctf.new_environment(), n_envs, **kw)
     dfd = DefenderVecEnv(att, max_timesteps=2000, invalid_action_reward=0, reset_on_constraint_broken=True, loss_reward=-5000.0) if with_defender else None
     a_pol = random_policy(seed) if attacker_action_masking else uniform_attacker_policy(seed)
     try:
+        if joint and with_defender:
+            from .wrappers import TwoAgentVecEnv
+            if TwoAgentVecEnv.supported(att):
+                return run_episode_joint(att, dfd, a_pol, random_defender_policy(seed + 1), max_steps=timesteps)
         return run_episode(att, dfd, a_pol, random_defender_policy(seed + 1) if with_defender else None, max_steps=timesteps)
     finally:
         att.close()

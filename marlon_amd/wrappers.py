@@ -547,9 +547,16 @@ class AttackerVecEnv(_MultiDiscreteHead):
                                     "network_availability": self.engine.info["network_availability"], "step_count": self.engine.info["step_count"],
                                     "episode_return": self._ret_out, "episode_length": self._len_out})
             return self._graph_out
-        # eager: the step's outputs alternate between TWO sets of tensors allocated once (a step's outputs stay valid until the step after
-        # next; consumers that keep them longer clone them).  Seven allocations and a rebuilt argument block per step cost more host time
-        # than the device needs for the whole wrapper step (20 us at 65 536 envs).
+        o, _, info = self._next_output_set()
+        self._step_device(actions)
+        return self.observation, o["rewards"], o["terminated"], o["truncated"], dict(info)
+
+    def _next_output_set(self):
+        """eager: the step's outputs alternate between TWO sets of tensors allocated once (a step's outputs stay valid until the step after
+        next; consumers that keep them longer clone them).  Seven allocations and a rebuilt argument block per step cost more host time
+        than the device needs for the whole wrapper step (20 us at 65 536 envs).  -> (tensors, WrapperBuffers, info) of the set the
+        coming step writes, installed as the wrapper's current outputs."""
+        t = self.torch
         E, dev = self.num_envs, self.engine.device
         if self._ring is None:
             self._ring = []
@@ -567,8 +574,7 @@ class AttackerVecEnv(_MultiDiscreteHead):
         o, wb, info = self._ring[self._slot]
         self._invalid, self._executed, self._rewards, self._truncated = o["invalid"], o["executed"], o["rewards"], o["truncated"]
         self._ret_out, self._len_out, self._terminated_out, self._wb = o["ret"], o["length"], o["terminated"], wb
-        self._step_device(actions)
-        return self.observation, o["rewards"], o["terminated"], o["truncated"], dict(info)
+        return o, wb, info
 
     def close(self) -> None:
         self.engine.close()
@@ -680,28 +686,10 @@ class DefenderVecEnv(_MultiDiscreteHead):
             a = actions if isinstance(actions, t.Tensor) else t.as_tensor(np.asarray(actions))
             self._act_in.copy_(a.to(device=self.engine.device).reshape(self._act_in.shape), non_blocking=True)
             actions = self._act_in
-        # eager: ONE library call per turn (mcbs_defender_wrapper_step: the turn and the reward shaping in one launch, then the observation);
-        # the turn's outputs alternate between two sets of tensors allocated once (valid until the turn after next)
+        # eager: ONE library call per turn (mcbs_defender_wrapper_step: the turn and the reward shaping in one launch, then the observation)
         E, dev = self.num_envs, self.engine.device
         if self._ring is None:
-            from ._abi import DefenderObs, DefenderWrapperBuffers, DefenderWrapperCfg
-            self._evicted = t.zeros(E, dtype=t.uint8, device=dev)
-            self._obs_block = DefenderObs(**{k: x.data_ptr() for k, x in self._obs.items()})
-            self._wc = DefenderWrapperCfg(self.invalid_action_penalty, self.loss_reward, self.sla_worsening_penalty_scale, self.maintain_sla,
-                                          self.winning_reward, int(self.reset_on_constraint_broken), self.max_timesteps)
-            self._ring = []
-            for _ in range(2):
-                o = dict(valid=t.empty(E, dtype=t.uint8, device=dev), availability=t.empty(E, dtype=t.float64, device=dev),
-                         reward=t.empty(E, dtype=t.float64, device=dev), terminated=t.empty(E, dtype=t.uint8, device=dev),
-                         truncated=t.empty(E, dtype=t.uint8, device=dev), breached=t.empty(E, dtype=t.uint8, device=dev),
-                         won=t.empty(E, dtype=t.uint8, device=dev))
-                wb = DefenderWrapperBuffers(*[x.data_ptr() for x in (
-                    o["valid"], o["availability"], self._evicted, self.attacker.has_cyber_reward, self.attacker.last_cyber_reward, self.timesteps,
-                    self.valid_action_count, self.invalid_action_count, self.has_breached_sla, self.prev_availability, o["reward"], o["terminated"],
-                    o["truncated"], o["breached"], o["won"])])
-                info = {"valid_action": o["valid"].view(t.bool), "network_availability": o["availability"], "sla_breached": o["breached"].view(t.bool),
-                        "defender_won": o["won"].view(t.bool)}
-                self._ring.append((o, wb, info, self.engine.defender_wrapper_step_call(self._obs_block, wb, self._wc)))
+            self._output_ring()
         if not self.use_graph:
             self._slot ^= 1
         o, wb, info, call = self._ring[self._slot]
@@ -714,3 +702,149 @@ class DefenderVecEnv(_MultiDiscreteHead):
         call(a.data_ptr())
         self._out = o
         return self._obs, o["reward"], o["terminated"], o["truncated"], dict(info)
+
+    def _output_ring(self) -> None:
+        """The turn's outputs alternate between two sets of tensors allocated once (valid until the turn after next): per set the tensors,
+        the DefenderWrapperBuffers block, the info dict and the bound library call."""
+        t = self.torch
+        E, dev = self.num_envs, self.engine.device
+        from ._abi import DefenderObs, DefenderWrapperBuffers, DefenderWrapperCfg
+        self._evicted = t.zeros(E, dtype=t.uint8, device=dev)
+        self._obs_block = DefenderObs(**{k: x.data_ptr() for k, x in self._obs.items()})
+        self._wc = DefenderWrapperCfg(self.invalid_action_penalty, self.loss_reward, self.sla_worsening_penalty_scale, self.maintain_sla,
+                                      self.winning_reward, int(self.reset_on_constraint_broken), self.max_timesteps)
+        self._ring = []
+        for _ in range(2):
+            o = dict(valid=t.empty(E, dtype=t.uint8, device=dev), availability=t.empty(E, dtype=t.float64, device=dev),
+                     reward=t.empty(E, dtype=t.float64, device=dev), terminated=t.empty(E, dtype=t.uint8, device=dev),
+                     truncated=t.empty(E, dtype=t.uint8, device=dev), breached=t.empty(E, dtype=t.uint8, device=dev),
+                     won=t.empty(E, dtype=t.uint8, device=dev))
+            wb = DefenderWrapperBuffers(*[x.data_ptr() for x in (
+                o["valid"], o["availability"], self._evicted, self.attacker.has_cyber_reward, self.attacker.last_cyber_reward, self.timesteps,
+                self.valid_action_count, self.invalid_action_count, self.has_breached_sla, self.prev_availability, o["reward"], o["terminated"],
+                o["truncated"], o["breached"], o["won"])])
+            info = {"valid_action": o["valid"].view(t.bool), "network_availability": o["availability"], "sla_breached": o["breached"].view(t.bool),
+                    "defender_won": o["won"].view(t.bool)}
+            self._ring.append((o, wb, info, self.engine.defender_wrapper_step_call(self._obs_block, wb, self._wc)))
+
+
+class EpisodeState:
+    """The six arrays of mcbs_episode_buffers (marl_algorithm.run_episode's per-env bookkeeping) as device tensors: `alive`,
+    `attacker_done`, `defender_done` uint8 [E], `lengths` int64 [E], and the turn's two reward rows `attacker_reward` / `defender_reward`
+    float64 [E] — its own by default; a driver that keeps traces points them at the turn's rows of its storage (TwoAgentVecEnv.step)."""
+
+    def __init__(self, torch, n_envs: int, device):
+        t = torch
+        self.alive = t.ones(n_envs, dtype=t.uint8, device=device)
+        self.lengths = t.zeros(n_envs, dtype=t.int64, device=device)
+        self.attacker_done = t.zeros(n_envs, dtype=t.uint8, device=device)
+        self.defender_done = t.zeros(n_envs, dtype=t.uint8, device=device)
+        self.attacker_reward = t.zeros(n_envs, dtype=t.float64, device=device)
+        self.defender_reward = t.zeros(n_envs, dtype=t.float64, device=device)
+        self._block = None
+
+    def tensors(self) -> Dict[str, object]:
+        from ._abi import EPISODE_FIELDS
+        return {k: getattr(self, k) for k in EPISODE_FIELDS}
+
+    def block(self, attacker_row=None, defender_row=None):
+        """The _abi.EpisodeBuffers argument block, built once; the two reward members follow the rows given for this turn."""
+        from ._abi import EPISODE_FIELDS, episode_buffers
+        if self._block is None:
+            self._block = episode_buffers(**{k: x.data_ptr() for k, x in self.tensors().items()})
+        a = self.attacker_reward if attacker_row is None else attacker_row
+        d = self.defender_reward if defender_row is None else defender_row
+        for x in (a, d):
+            if x.dtype != self.attacker_reward.dtype or x.shape != self.attacker_reward.shape or not x.is_contiguous() or x.device != self.alive.device:
+                raise ValueError("a reward row is a contiguous float64 device tensor [n_envs]")
+        self._block[EPISODE_FIELDS.index("attacker_reward")] = a.data_ptr()
+        self._block[EPISODE_FIELDS.index("defender_reward")] = d.data_ptr()
+        self._rows = (a, d)                                # (kept alive while the block names them)
+        return self._block
+
+
+class TwoAgentVecEnv:
+    """Both wrappers' steps of one joint turn — `att.step(attacker_actions)`, then `dfd.step(defender_actions)` with run_episode's parking
+    of finished envs — and the episode bookkeeping in ONE launch (mcbs_two_agent_step, marlon_amd/csrc/mcbs_two_agent.hip).
+
+    `att` must be `AttackerVecEnv(..., learned_defender=True, auto_reset=False, materialize_masks=False)` on a small topology (the batch's
+    wrapper step is one launch) and `dfd` the `DefenderVecEnv` on it; anything else is a ValueError (`supported(att)` asks first).  The
+    joint step writes into the two wrappers' own persistent state — counters, `att.observation`, `dfd.observation`, the alternating
+    output sets — so everything that reads it (`att.mask_logits`, `att.features()`, `dfd.features()`, `sample_masked*`, ...) works as
+    after the separate steps, and separate and joint steps may be mixed.
+
+    The defender's action of a turn is chosen BEFORE the attacker's step of that turn, from the observation the defender's own previous
+    step returned: the reference's data flow (marl_algorithm.py:222-225)."""
+
+    def __init__(self, att: AttackerVecEnv, dfd: "DefenderVecEnv"):
+        why = self._refusal(att, dfd)
+        if why:
+            raise ValueError(f"TwoAgentVecEnv: {why}")
+        self.att, self.dfd = att, dfd
+        self.engine, self.torch, self.num_envs = att.engine, att.torch, att.num_envs
+        self._obs_block = self.engine.obs_struct(att._obs)
+        self._calls = {}
+
+    @staticmethod
+    def _refusal(att, dfd=None) -> Optional[str]:
+        from ._abi import DEFENDER_EXTERNAL
+        if not isinstance(att, AttackerVecEnv):
+            return "the attacker side must be an AttackerVecEnv"
+        if att.engine._cfg.defender_kind != DEFENDER_EXTERNAL:
+            return "the AttackerVecEnv must be created with learned_defender=True"
+        if att.auto_reset:
+            return "the AttackerVecEnv must be created with auto_reset=False (the episode boundary belongs to the caller)"
+        if att.materialize_masks:
+            return "the AttackerVecEnv must be created with materialize_masks=False (the joint turn writes no mask field)"
+        if att.use_graph:
+            return "the AttackerVecEnv must be created with use_graph=False"
+        if att.engine.two_agent_step_launches() != 1:
+            return "the library does not serve this batch with a joint turn (mcbs_two_agent_step_launches: small packed topologies only)"
+        if dfd is not None and not (isinstance(dfd, DefenderVecEnv) and dfd.attacker is att and not dfd.use_graph):
+            return "the defender side must be the DefenderVecEnv created on this AttackerVecEnv (use_graph=False)"
+        return None
+
+    @staticmethod
+    def supported(att) -> bool:
+        """Whether TwoAgentVecEnv(att, DefenderVecEnv(att)) would be accepted."""
+        return TwoAgentVecEnv._refusal(att) is None
+
+    def episode_state(self) -> EpisodeState:
+        """Freshly allocated episode bookkeeping: every env alive, nothing counted."""
+        return EpisodeState(self.torch, self.num_envs, self.engine.device)
+
+    def _actions(self, a, shape, what: str):
+        t = self.torch
+        if not (type(a) is t.Tensor and a.dtype is t.int64 and a.is_cuda and a.get_device() == self.att._dev_index and a.is_contiguous()):
+            a = a if isinstance(a, t.Tensor) else t.as_tensor(np.asarray(a))
+            a = a.to(device=self.engine.device, dtype=t.int64).contiguous()
+        if a.shape != shape:
+            raise ValueError(f"{what} actions must have shape {tuple(shape)}, got {tuple(a.shape)}")
+        return a
+
+    def step(self, attacker_actions, defender_actions, episode: Optional[EpisodeState] = None, reward_rows=None):
+        """-> ((obs, rewards, terminated, truncated, info), (dobs, dreward, dterminated, dtruncated, dinfo)): exactly the tuples
+        `att.step(attacker_actions)` and `dfd.step(defender_actions)` return.  The defender's turn of an env whose episode is over — `episode.alive`
+        is 0, or the attacker's step has just ended it — is parked (kind -2), whatever `defender_actions` says; the array is not modified.
+        `episode`: an episode_state() to book the turn into (mcbs.h states the rules); `reward_rows` = (attacker row, defender row), float64
+        [E] device tensors that receive the turn's two trace rows instead of `episode.attacker_reward` / `.defender_reward`."""
+        att, dfd = self.att, self.dfd
+        a = self._actions(attacker_actions, att._action_shape, "attacker")
+        d = self._actions(defender_actions, (self.num_envs, 12), "defender")
+        if reward_rows is not None and episode is None:
+            raise ValueError("reward_rows go with an episode state")
+        block = episode.block(*(reward_rows or ())) if episode is not None else None
+        o, wb, info = att._next_output_set()
+        if dfd._ring is None:
+            dfd._output_ring()
+        dfd._slot ^= 1
+        do, dwb, dinfo, _ = dfd._ring[dfd._slot]
+        key = (id(wb), id(dwb), att.invalid_action_reward_modifier, att.max_timesteps)
+        call = self._calls.get(key)
+        if call is None:
+            call = self._calls[key] = self.engine.two_agent_step_call(att.discrete, att._rows, self._obs_block, wb, att.invalid_action_reward_modifier,
+                                                                      att.max_timesteps, dfd._obs_block, dwb, dfd._wc)
+        call(a.data_ptr(), d.data_ptr(), block)
+        dfd._out = do
+        return ((att.observation, o["rewards"], o["terminated"], o["truncated"], dict(info)),
+                (dfd._obs, do["reward"], do["terminated"], do["truncated"], dict(dinfo)))
