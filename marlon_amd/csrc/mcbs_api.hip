@@ -614,7 +614,8 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     if (e != hipSuccess) { (void)hipFree(b->arena); delete b; return fail(MCBS_EHIP, "initial reset failed: %s", hipGetErrorString(e)); }
     b->variant = batch_variant(b);
     b->lean_step = S.packed && cfg->defender_kind == MCBS_DEFENDER_NONE && C.init_image_ok && !S.ring;
-    b->narrow_step = b->lean_step && !(topo->hot.traits & ~kNarrowStepCan);
+    // (the narrow kernel fetches the fourth row vector where body_stride > 48: a lean body is its 4-byte rows alone, so that is N > 12)
+    b->narrow_step = b->lean_step && !(topo->hot.traits & ~kNarrowStepCan) && ((S.N > 12u) == (S.body_stride > 48u));
     *out = b;
     return MCBS_OK;
 }
@@ -755,8 +756,9 @@ static int launch_step(mcbs_batch* b, const StepIO& io, hipStream_t st, const ch
 #ifdef MCBS_DIAG
         a.stamps = io.stamps;
 #endif
-        // ... instantiated for what the batch's topology can do, where that is no more than the narrow kernel handles
-        if (b->narrow_step) hipLaunchKernelGGL((step_kernel<0, 0, false, MCBS_DEFENDER_NONE>), step_grid(b), dim3(64), 0, st, b->C_dev, NarrowStepArgs{a});
+        // ... instantiated for what the batch's topology can do, where that is no more than the narrow kernel handles: a kernel built
+        // in a translation unit of its own (mcbs_step_narrow_tu.hip), whose argument list is this block's members but N
+        if (b->narrow_step) launch_step_narrow(step_grid(b), st, b->C_dev, a);
         else hipLaunchKernelGGL((step_kernel<0, 0, false, MCBS_DEFENDER_NONE>), step_grid(b), dim3(64), 0, st, b->C_dev, a);
         return launch_ok(what);
     }

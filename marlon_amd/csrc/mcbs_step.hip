@@ -144,8 +144,8 @@ __device__ __forceinline__ uint32_t dword_of(const uint4& r0, const uint4& r1, c
 }
 
 // What a topology can do, as a template argument of step_body and Lane::act (MCBS_TOPO_* bits, mcbs.h): a clear bit compiles the rule
-// out.  MCBS_TOPO_ANY, the default of both, is every kernel but one; the narrow lean step (step_kernel(cfg, NarrowStepArgs) at the end of
-// this file) is instantiated with kNarrowStepCan, and mcbs_api.hip launches it only for a batch whose topology has no other trait.
+// out.  MCBS_TOPO_ANY, the default of both, is every kernel but one; the narrow lean step (step_kernel in
+// mcbs_step_narrow_tu.hip) is instantiated with kNarrowStepCan, and mcbs_api.hip launches it only for a batch whose topology has no other trait.
 // The narrow kernel assumes away escalations, lateral-move exploits, preconditions and multi-entry leaks; each was measured to pay on the
 // headline (profiles/step_topo_traits.md).  Probes stay (Chain-10 has them).  "At most 12 nodes" — three row vectors and a narrower
 // select tree — was built, measured SLOWER and left out: MCBS_TOPO_WIDE_ROWS is derived and reported, and no kernel code reads it.
@@ -923,6 +923,8 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
 //   * the raw reward is not materialised: the kernel has no raw-reward output, so all that reaches memory is max(0, raw), and every
 //     failure arm of the reference (0, -1, -5, -10, -20, -50) is <= 0.  What can be positive is an integer (the node's value the first
 //     time it is owned; probe, first-exploit and leak bonuses) minus the vulnerability's cost, formed only for an action that took effect;
+//   * the level-1 block of the arguments is in SGPRs when the wavefront starts (kernel-argument preload, mcbs_step_narrow_tu.hip), so no
+//     scalar load stands in front of the level-1 loads; the fourth row vector is decided from the body stride, which is in that block;
 //   * the kernel arguments past the level-1 block are pinned with the config words, and what the level-1 data alone decide (step + 1,
 //     the truncation test, the old flags, the masks of source and target) is written ahead of the wait for the tables.
 // Built, measured and left out (profiles/step_narrow_predicates.md): 24-bit multiplies for the table offsets (no gain), and forming the
@@ -969,7 +971,7 @@ __device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& 
     {
         const uint4* rp = reinterpret_cast<const uint4*>(body);
         rw0 = rp[0]; rw1 = rp[1]; rw2 = rp[2];
-        if (S.N > 12u) rw3 = rp[3];
+        if (S.body_stride > 48u) rw3 = rp[3];   // more than 12 nodes (mcbs_batch_create checks the equivalence): N is not in the level-1 block
     }
     const uint4 pk = reinterpret_cast<const uint4*>(S.masks)[ec];   // {DISC | INST << 16, EVER | RUN << 16, PLO | PHI << 16, GATH | CACH << 16}
     double2 h1 = S.h1[ec];
@@ -1184,31 +1186,8 @@ __global__ __launch_bounds__(256) void step_kernel(const StepCfg* __restrict__ C
     step_body<0, 0, MCBS_DEFENDER_NONE, false, true>(S, T, Cp, io, RollArgs{}, nh);
 }
 
-// The narrow lean launch: the kernel above instantiated for what the batch's topology can do (kNarrowStepCan).  Chosen once, in
-// mcbs_batch_create, for a lean batch whose topology has no other trait (MCBS_TOPO_*, found on the host with the hot image): Chain-10,
-// the headline.  Same name again; the argument block is a type of its own.
-template <int PHASE, int WTP, bool TOPO_LDS, int DEFK>
-__global__ __launch_bounds__(256) void step_kernel(const StepCfg* __restrict__ Cp, NarrowStepArgs na) {
-    static_assert(PHASE == 0 && WTP == 0 && !TOPO_LDS && DEFK == MCBS_DEFENDER_NONE, "the lean argument block serves the packed, attacker-only whole step");
-    const LeanStepArgs& a = na.a;
-    DevState S{};
-    S.h0 = a.h0; S.masks = a.masks; S.body = a.body; S.h1 = a.h1; S.episode = a.episode; S.pending = a.pending;
-    S.E = a.E; S.body_stride = a.body_stride; S.N = a.N; S.tiny_p = a.tiny_p; S.tiny_v = a.tiny_v;
-    S.NW = S.SW = S.TW = S.WT = 1u; S.packed = 1u;
-    const Topo T{nullptr, a.hot};
-    StepIO io{};
-    io.actions = a.actions; io.reward = a.reward; io.terminated = a.terminated;
-#ifdef MCBS_DIAG
-    io.stamps = a.stamps;
-#endif
-#if MCBS_NARROW_PRED
-    static_assert(kNarrowStepCan == (MCBS_TOPO_PROBE | MCBS_TOPO_WIDE_ROWS), "step_body_narrow is written for exactly these traits");
-    step_body_narrow(S, T, Cp, io);
-#else
-    NoHook nh;
-    step_body<0, 0, MCBS_DEFENDER_NONE, false, true, NoHook, kNarrowStepCan>(S, T, Cp, io, RollArgs{}, nh);
-#endif
-}
+// The narrow lean launch — the kernel above for what the batch's topology can do (kNarrowStepCan), same name again, an argument list of
+// its own — is defined in mcbs_step_narrow_tu.hip, which includes this file and is compiled apart from the rest of the library.
 
 // mcbs_step_many / mcbs_rollout_random: io.n_steps consecutive steps in one launch; `roll` is a kernel ARGUMENT (nothing in device
 // memory is patched per call, so launches on different streams or inside a stream capture cannot see each other's mode).
