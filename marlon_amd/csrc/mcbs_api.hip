@@ -758,7 +758,7 @@ static int launch_step(mcbs_batch* b, const StepIO& io, hipStream_t st, const ch
 #endif
         // ... instantiated for what the batch's topology can do, where that is no more than the narrow kernel handles: a kernel built
         // in a translation unit of its own (mcbs_step_narrow_tu.hip), whose argument list is this block's members but N
-        if (b->narrow_step) launch_step_narrow(step_grid(b), st, b->C_dev, a);
+        if (b->narrow_step) launch_step_narrow(step_grid(b), st, b->C_dev, b->C, a);
         else hipLaunchKernelGGL((step_kernel<0, 0, false, MCBS_DEFENDER_NONE>), step_grid(b), dim3(64), 0, st, b->C_dev, a);
         return launch_ok(what);
     }

@@ -291,9 +291,10 @@ static_assert(offsetof(LeanStepArgs, N) == 56, "the level-1 block of LeanStepArg
 // The narrow instantiation of the lean step (mcbs_step_narrow_tu.hip) shares the kernel's name — the benchmark, the profiling tools and
 // the committed traces find the headline kernel by it — and differs in its argument list: the level-1 block above (the first 14 dwords)
 // as eight scalar / pointer parameters of their own, which gfx950 preloads into SGPRs (nothing of a struct passed by value is
-// preloaded), then the config pointer, then the rest of this block but N.  LeanStepArgs is the host-side carrier that launch_step fills.
+// preloaded), then the config pointer, then the rest of this block but N together with the main path's config words (taken from C, the
+// batch's host StepCfg, at every launch).  LeanStepArgs is the host-side carrier that launch_step fills.
 // (A translation unit of its own, built with the kernel-argument preload option: the Makefile.)
-void launch_step_narrow(dim3 grid, hipStream_t st, const StepCfg* C_dev, const LeanStepArgs& a);
+void launch_step_narrow(dim3 grid, hipStream_t st, const StepCfg* C_dev, const StepCfg& C, const LeanStepArgs& a);
 
 struct FastDiv { uint32_t mul, sh1, sh2; };   // n / d for 32-bit n (Granlund-Montgomery round-up form), set up on the host
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, FastDiv d) {

@@ -925,10 +925,16 @@ __device__ __forceinline__ void step_body(const DevState& S, const Topo& T, cons
 //     time it is owned; probe, first-exploit and leak bonuses) minus the vulnerability's cost, formed only for an action that took effect;
 //   * the level-1 block of the arguments is in SGPRs when the wavefront starts (kernel-argument preload, mcbs_step_narrow_tu.hip), so no
 //     scalar load stands in front of the level-1 loads; the fourth row vector is decided from the body stride, which is in that block;
-//   * the kernel arguments past the level-1 block are pinned with the config words, and what the level-1 data alone decide (step + 1,
-//     the truncation test, the old flags, the masks of source and target) is written ahead of the wait for the tables.
-// Built, measured and left out (profiles/step_narrow_predicates.md): 24-bit multiplies for the table offsets (no gain), and forming the
-// seven store addresses behind a second scheduling fence while the table loads are in flight (slower in every run).
+//   * the main path's config words and the kernel arguments past the level-1 block arrive as ONE by-value argument (NarrowCfg), filled
+//     at launch from the batch's StepCfg: one scalar round trip behind the level-1 loads, where config words read through Cp took two;
+//   * what the level-1 data alone decide (step + 1, the truncation test, the old flags, the masks of source and target, the row pick,
+//     the seven store addresses, the cumulative-reward half of the goal) runs while the table loads are in flight.  That takes two
+//     things beside writing it ahead of the wait: a scheduling fence in front of the wait, and every dword the table loads write
+//     kept alive up to it (see there) — without them the block ran behind the tables, not beside them (profiles/step_decode.md).
+// Built, measured and left out: 24-bit multiplies for the table offsets (no gain, profiles/step_narrow_predicates.md); and
+// (profiles/step_decode.md) the table loads issued from clamped, unchecked indices with the validity checks behind them (25 fewer
+// instructions in front of the loads, no faster: the checks stand where the wavefront waits for the lists word anyway), the
+// row pick out of three vectors where the body has no fourth (slower again), and the header-only checks ahead of the nibble picks.
 // MCBS_NARROW_PRED=0 builds the narrow kernel on step_body again.
 #ifndef MCBS_NARROW_PRED
 #define MCBS_NARROW_PRED 1
@@ -950,9 +956,20 @@ __device__ __forceinline__ void np_store(__attribute__((address_space(1))) np_u3
 }
 __device__ __forceinline__ uint32_t pick(uint32_t m, uint32_t a, uint32_t b) { return (a & m) | (b & ~m); }   // m ? a : b, bitwise
 
+// The main path's config words and the kernel arguments past the level-1 block, one by-value kernel argument.  launch_step_narrow fills
+// it at every launch from the batch's own StepCfg (no entry point changes a word of that after mcbs_batch_create) and LeanStepArgs.
+struct NarrowCfg {
+    unsigned long long goal_reward, winning_reward, losing_reward;   // doubles, as bit patterns
+    const uint8_t* hot;
+    float* reward;
+    uint8_t* terminated;
+    uint32_t L, R, P, has_attacker_goal, goal_own_atleast, goal_own_pct_min, defender_goal_eviction, auto_reset, max_episode_steps;
+    uint32_t hot_node, hot_desc, hot_auth, auth_words, tiny_p, tiny_v;
+};
+
 template <class = void>
-__device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& T, const StepCfg* __restrict__ Cp, const StepIO& io) {
-    const StepCfg& C = *Cp;
+__device__ __forceinline__ void step_body_narrow(const DevState& S, const NarrowCfg& K, const StepCfg* __restrict__ Cp, const StepIO& io) {
+    const StepCfg& C = *Cp;   // the reset tail alone reads it
 #ifdef MCBS_DIAG
     unsigned long long st_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
@@ -978,24 +995,22 @@ __device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& 
     const uint32_t episode = S.episode[ec];
     const double2 h1_in = h1;
     STAMP_NOWAIT(1);
-    // the config words, in ONE pinned batch behind the vector loads (step_body)
-    uint32_t cL = C.L, cR = C.R, cP = C.P;
-    unsigned long long g_reward = __double_as_longlong(C.goal_reward), g_low = __double_as_longlong(C.goal_low_availability),
-                       g_sla = __double_as_longlong(C.maintain_sla),
-                       g_win = __double_as_longlong(C.winning_reward), g_lose = __double_as_longlong(C.losing_reward);
-    uint32_t a_node = C.hot_node, a_desc = C.hot_desc, a_payload = C.hot_payload, a_auth = C.hot_auth, a_aw = C.auth_words, a_leak = C.max_leak,
-             g_image = C.init_image_ok;
-    uint32_t g_has = C.has_attacker_goal, g_own = C.goal_own_atleast, g_evict = C.defender_goal_eviction, g_auto = C.auto_reset, g_max = C.max_episode_steps,
-             g_pctmin = C.goal_own_pct_min;
-    // ... and the kernel arguments past the level-1 block (the hot image's base, the row format, the output pointers): left alone, their
-    // scalar load goes out between the decode and the table loads, with its wait in front of them
-    uint64_t q_hot = (uint64_t)T.hot;   // (an integer through the pin, a global — not generic — pointer after it)
-    float* o_reward = io.reward;
-    uint8_t* o_term = io.terminated;
-    uint32_t tiny_p = S.tiny_p, tiny_v = S.tiny_v;
-    asm volatile("" : "+s"(cL), "+s"(cR), "+s"(cP), "+s"(g_reward), "+s"(g_low), "+s"(g_pctmin), "+s"(g_sla), "+s"(g_win), "+s"(g_lose), "+s"(g_has),
-                      "+s"(g_own), "+s"(g_evict), "+s"(g_auto), "+s"(g_max), "+s"(g_image), "+s"(a_node), "+s"(a_desc), "+s"(a_payload),
-                      "+s"(a_auth), "+s"(a_aw), "+s"(a_leak), "+s"(q_hot), "+s"(o_reward), "+s"(o_term), "+s"(tiny_p), "+s"(tiny_v));
+    // the config words and the arguments past the level-1 block (the hot image's base, the row format, the output pointers), in ONE
+    // pinned batch of scalar loads on the argument pointer behind the vector loads: left alone, a part of it goes out between the decode
+    // and the table loads, with its wait in front of them.  The fence keeps the batch from rising between two level-1 vector loads.
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t cL = K.L, cR = K.R, cP = K.P;
+    unsigned long long g_reward = K.goal_reward, g_win = K.winning_reward, g_lose = K.losing_reward;
+    uint32_t a_node = K.hot_node, a_desc = K.hot_desc, a_auth = K.hot_auth, a_aw = K.auth_words;
+    uint32_t g_has = K.has_attacker_goal, g_own = K.goal_own_atleast, g_evict = K.defender_goal_eviction, g_auto = K.auto_reset, g_max = K.max_episode_steps,
+             g_pctmin = K.goal_own_pct_min;
+    uint64_t q_hot = (uint64_t)K.hot;   // (an integer through the pin, a global — not generic — pointer after it)
+    float* o_reward = K.reward;
+    uint8_t* o_term = K.terminated;
+    uint32_t tiny_p = K.tiny_p, tiny_v = K.tiny_v;
+    asm volatile("" : "+s"(cL), "+s"(cR), "+s"(cP), "+s"(g_reward), "+s"(g_pctmin), "+s"(g_win), "+s"(g_lose), "+s"(g_has), "+s"(g_own), "+s"(g_evict),
+                      "+s"(g_auto), "+s"(g_max), "+s"(a_node), "+s"(a_desc), "+s"(a_auth), "+s"(a_aw), "+s"(q_hot), "+s"(o_reward), "+s"(o_term),
+                      "+s"(tiny_p), "+s"(tiny_v));
 #define MCBS_GLOBAL(T, q) reinterpret_cast<__attribute__((address_space(1))) T*>(q)
     const auto* const tb = MCBS_GLOBAL(const uint8_t, q_hot);
     STAMP(2);
@@ -1018,7 +1033,6 @@ __device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& 
         const uint32_t i1 = X ? a1 : 0u, i2 = (X & !k0) ? a2 : i1, i4 = (X & k2) ? a4 : 0u;
         const uint32_t src = nibble_of(ldisc, i1), tgt = nibble_of(ldisc, i2), triple = nibble_of(lcred, i4);
         const uint32_t col = X ? (k0 ? a2 : (k1 ? cL + a3 : 0u)) : 0u, port = (X & k2) ? a3 : 0u;
-        const uint32_t pw0 = dword_of(rw0, rw1, rw2, rw3, tgt);   // the target's row word as loaded
         STAMP(3);
         // ---------------- the table loads: node record, source firewall word, authorisation word, descriptor (three vectors) ----------------
         // byte offsets into the hot image (32 bits: HotLayout::bytes is); triple < 16, so its authorisation bit is in the low dword of word 0
@@ -1026,7 +1040,8 @@ __device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& 
         const uint32_t o_auth = a_auth + ((tgt * cP + port) * a_aw) * 8u;
         const uint32_t o_desc = a_desc + (tgt * (cL + cR) + col) * (uint32_t)sizeof(HotDesc);
         const auto* tp = MCBS_GLOBAL(const np_u32x4, tb + o_tgt);
-        const uint4 t0 = np_load(tp), t1 = np_load(tp + 1);              // {props lo, hi, value, fw_in_allow} {fw_out_allow, listen, svc, flags}
+        const uint4 t0 = np_load(tp);                                    // {props lo, hi, value, fw_in_allow}
+        const uint32_t tgt_listen = *MCBS_GLOBAL(const uint32_t, tb + o_tgt + offsetof(HotNode, listen));
         const uint32_t src_fw_out = *MCBS_GLOBAL(const uint32_t, tb + o_src + offsetof(HotNode, fw_out_allow));
         const uint32_t auth = *MCBS_GLOBAL(const uint32_t, tb + o_auth);
         const auto* dp = MCBS_GLOBAL(const np_u32x4, tb + o_desc);
@@ -1035,21 +1050,27 @@ __device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& 
         __builtin_amdgcn_sched_barrier(0);    // all seven go out together (Lane::act)
 
         // ---------------- what the level-1 data alone decide ----------------
-        const uint32_t live_m = lanes_mask(live), X_m = lanes_mask(X), k2_m = lanes_mask(k2), oob_f = lanes_mask(oob) & F_OOB;
+        const uint32_t live_m = lanes_mask(live), X_m = lanes_mask(X), k2_m = lanes_mask(k2), oob_m = lanes_mask(oob), oob_f = oob_m & F_OOB;
+        const uint32_t step = h0.x - live_m;                             // a live env's step counter always moves
+        const uint32_t trunc_pre = live_m & lanes_mask((g_max != 0) & (step >= g_max));
+        const uint32_t dead_flags = old_flags & ~live_m;                 // an ended or skipped env keeps its flags
+        const uint32_t pw0 = dword_of(rw0, rw1, rw2, rw3, tgt);   // the target's row word as loaded
         const uint32_t so_m = X_m & bit_mask(pk.x, src + 16u);          // the source is owned (agent installed), else INVALID_ACTION
         const uint32_t running_m = bit_mask(pk.y, tgt + 16u), already_m = bit_mask(pk.x, tgt + 16u), ever_m = bit_mask(pk.y, tgt);
         const uint32_t nopriv_m = ~(bit_mask(pk.z, tgt) | bit_mask(pk.z, tgt + 16u));
         const uint32_t tbit = 1u << tgt;
-        const uint32_t step = h0.x - live_m;                             // a live env's step counter always moves
-        const uint32_t trunc_pre = lanes_mask(live & (g_max != 0) & (step >= g_max));
-        const uint32_t dead_flags = old_flags & ~live_m;                 // an ended or skipped env keeps its flags
         const uint32_t s_ever = tiny_p + 4u, s_since = s_ever + tiny_v;   // (tiny_v == 0: no slot, nothing is ever shifted there)
         const uint32_t ever_f = __builtin_amdgcn_ubfe(pw0, s_ever, tiny_v), since_f = __builtin_amdgcn_ubfe(pw0, s_since, tiny_v);
         const uint32_t props0 = pw0 & ((1u << tiny_p) - 1u);
         // the seven store addresses, as global (not generic) pointers: the output pointers went through the pin as plain values
-        const uint64_t q_lists = (uint64_t)(reinterpret_cast<uint4*>(S.masks) + S.E + e), q_sets = (uint64_t)(reinterpret_cast<uint4*>(S.masks) + e),
+        uint64_t q_lists = (uint64_t)(reinterpret_cast<uint4*>(S.masks) + S.E + e), q_sets = (uint64_t)(reinterpret_cast<uint4*>(S.masks) + e),
                  q_row = (uint64_t)(reinterpret_cast<uint32_t*>(body) + tgt), q_h0 = (uint64_t)(S.h0 + e), q_h1 = (uint64_t)(S.h1 + e),
                  q_reward = (uint64_t)(o_reward + e), q_term = (uint64_t)(o_term + e);
+        // ... formed HERE: left alone, the address arithmetic sinks behind the wait, to each store.  So are the shifts of the two list
+        // appends and the half of the attacker's goal that the cumulative reward decides
+        asm volatile("" : "+v"(q_lists), "+v"(q_sets), "+v"(q_row), "+v"(q_h0), "+v"(q_h1), "+v"(q_reward), "+v"(q_term));
+        const uint32_t sh_disc = opaque((n_disc & 15u) * 4u), sh_cred = opaque((n_creds & 15u) * 4u);
+        const uint32_t rich_m = lanes_mask((g_has != 0) & !(h1.x < __longlong_as_double(g_reward)));
         auto* const p_lists = MCBS_GLOBAL(np_u32x4, q_lists);
         auto* const p_sets = MCBS_GLOBAL(np_u32x4, q_sets);
         auto* const p_row = MCBS_GLOBAL(uint32_t, q_row);
@@ -1058,12 +1079,20 @@ __device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& 
         auto* const p_reward = MCBS_GLOBAL(float, q_reward);
         auto* const p_term = MCBS_GLOBAL(uint8_t, q_term);
 #undef MCBS_GLOBAL
+        __builtin_amdgcn_sched_barrier(0);    // nothing of the block above sinks behind the wait
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): every load of the step has landed; the stores start below (Lane::act)
+        // Every dword the table loads write stays spoken for up to this wait, the ones no rule reads included (props hi, the descriptor's
+        // padding, the payload entry's second half).  Left dead, they are free registers to the allocator from the load onwards: it put
+        // the first temporaries of the block above into them, and a write to a register that a load in flight still owns took an
+        // s_waitcnt vmcnt(1) in front of the whole block.  (The target's listen word is a load of its own for the same reason: as the
+        // second dword of a 16-byte load it brought three such registers.)
+        asm volatile("" :: "v"(t0.x), "v"(t0.y), "v"(t0.z), "v"(t0.w), "v"(tgt_listen), "v"(src_fw_out), "v"(auth));
+        asm volatile("" :: "v"(d0.x), "v"(d0.y), "v"(d0.z), "v"(d0.w), "v"(d1.x), "v"(d1.y), "v"(d1.z), "v"(d1.w), "v"(d2.x), "v"(d2.y), "v"(d2.z), "v"(d2.w));
 
         // ---------------- the checks, as masks ----------------
         // connect: both firewalls and the listening port are one word test; then running, then the credential.  Exploit: running, then
         // the vulnerability exists.  The outcome kind as a one-hot word: kinds are < 10, 0xFF (absent) lands on bit 31.
-        const uint32_t reach_m = bit_mask(src_fw_out & t0.w & t1.y, port);
+        const uint32_t reach_m = bit_mask(src_fw_out & t0.w & tgt_listen, port);
         const uint32_t auth_m = bit_mask(auth, triple);
         const uint32_t vk = d1.z & 0xFFu, kb = opaque(1u << (d1.z & 31u));
         const uint32_t present_m = ~bit_mask(kb, 31u);
@@ -1092,7 +1121,7 @@ __device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& 
         const uint32_t new_c = on_m & creds_m & ~bit_mask(pk.w, d2.y | 16u);
         add.x |= (1u << (d2.x & 31u)) & new_n;
         add.w = ((1u << ((d2.x >> 16) & 31u)) & new_g) | ((0x10000u << (d2.y & 15u)) & new_c);
-        const uint64_t dl = (uint64_t)(d2.x & 0xFu & new_n) << ((n_disc & 15u) * 4u), cl = (uint64_t)(d2.y & 0xFu & new_c) << ((n_creds & 15u) * 4u);
+        const uint64_t dl = (uint64_t)(d2.x & 0xFu & new_n) << sh_disc, cl = (uint64_t)(d2.y & 0xFu & new_c) << sh_cred;
         vi += (int)((new_n & 5u) + (new_g & 3u));
         // max(0, raw) (env.py:1169).  raw is positive only for an action that took effect: the integer above minus the vulnerability's
         // cost (an exploit; a connect costs nothing).  (double)vi - 0.0 is (double)vi, and a difference of an integer and a cost is
@@ -1106,10 +1135,9 @@ __device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& 
         if (MCBS_CHANGED((addrow & ~pw0) != 0u)) *p_row = pw0 | addrow;
         STAMP(4);
         // ---------------- goals (env.py:1080-1116), reward, flags, header ----------------
-        const bool play = live & !oob;
-        const bool win = play & (g_has != 0) & !(h1.x < __longlong_as_double(g_reward)) & !(owned < g_own) & !(owned < g_pctmin);
-        const bool lose = play & !win & (g_evict != 0) & (owned == 0);
-        const uint32_t win_m = lanes_mask(win), lose_m = lanes_mask(lose), done_m = win_m | lose_m;
+        const uint32_t play_m = live_m & ~oob_m;
+        const uint32_t win_m = play_m & rich_m & lanes_mask(!(owned < g_own) & !(owned < g_pctmin));
+        const uint32_t lose_m = play_m & ~win_m & lanes_mask((g_evict != 0) & (owned == 0)), done_m = win_m | lose_m;
         // (an env that does not play has r_pos == 0: its action did not execute)
         const uint32_t r_lo = ((uint32_t)g_win & win_m) | ((uint32_t)g_lose & lose_m) | ((uint32_t)__double2loint(r_pos) & ~done_m);
         const uint32_t r_hi = ((uint32_t)(g_win >> 32) & win_m) | ((uint32_t)(g_lose >> 32) & lose_m) | ((uint32_t)__double2hiint(r_pos) & ~done_m);
@@ -1123,7 +1151,7 @@ __device__ __forceinline__ void step_body_narrow(const DevState& S, const Topo& 
         const uint32_t flags = dead_flags | oob_f | (okind << F_KIND_SHIFT) | (new_n & (1u << F_NEWNODES_SHIFT)) | (new_c & (1u << F_NEWCREDS_SHIFT)) |
                                (done_m & F_DONE) | (trunc_m & F_TRUNC);
         // a live env's step counter always moves; an ended or skipped env's header stays as it was
-        if (MCBS_CHANGED(live)) np_store(p_h0, step, flags, h0.z - new_n + (new_c & 0x10000u), h0.w - chg_m);
+        if (MCBS_CHANGED(live_m != 0u)) np_store(p_h0, step, flags, h0.z - new_n + (new_c & 0x10000u), h0.w - chg_m);
         if (MCBS_CHANGED(differs(h1, h1_in))) { np_f64x2 v; v.x = h1.x; v.y = h1.y; *p_h1 = v; }
         if (MCBS_CHANGED(((add.x & ~pk.x) | (add.y & ~pk.y) | (add.z & ~pk.z) | (add.w & ~pk.w)) != 0u))
             np_store(p_sets, pk.x | add.x, pk.y | add.y, pk.z | add.z, pk.w | add.w);

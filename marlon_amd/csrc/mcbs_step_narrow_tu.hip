@@ -17,11 +17,14 @@
 //   * the node count is not among them, so the fourth row vector is decided from body_stride (step_body_narrow), and N does not travel;
 //   * the config pointer follows as a __restrict__ parameter of its own, as in the lean kernel (mcbs_step.hip): the reset tail keeps reading
 //     the reset image through the scalar cache behind the step's stores;
-//   * then what the main path needs later (hot image base, output pointers, row format) and `pending` for the reset tail.
-// Built, measured and left out (profiles/step_arg_preload.md): the main path's config words as kernel arguments too (one scalar round
-// trip behind the level-1 loads instead of two): faster in every run, by less than the criterion asks.
+//   * then ONE by-value block (NarrowCfg, mcbs_step.hip): what the main path needs later (hot image base, output pointers, row format)
+//     and the main path's config words, copied at every launch from the batch's host StepCfg — one scalar round trip on the argument
+//     pointer behind the level-1 loads, where config words read through Cp took two (profiles/step_decode.md; left out once for a
+//     noisy job, profiles/step_arg_preload.md); `pending` for the reset tail closes the list.
 // -DMCBS_NARROW_PRED=0 builds the kernel on step_body with the lean kernel's struct argument list (nothing of it is preloaded).
 #include <hip/hip_runtime.h>
+
+#include <cstring>
 
 #include "mcbs.h"
 #include "mcbs_device.h"
@@ -40,28 +43,35 @@ namespace mcbs {
 
 template <int PHASE, int WTP, bool TOPO_LDS, int DEFK>
 __global__ __launch_bounds__(256) void step_kernel(uint4* h0, uint64_t* masks, uint8_t* body, double2* h1, const int32_t* actions, uint32_t* episode,
-                                                   uint32_t E, uint32_t body_stride, const StepCfg* __restrict__ Cp, const uint8_t* hot, float* reward,
-                                                   uint8_t* terminated, double* pending, uint32_t tiny_p, uint32_t tiny_v MCBS_NARROW_STAMPS_PARAM) {
+                                                   uint32_t E, uint32_t body_stride, const StepCfg* __restrict__ Cp, NarrowCfg K,
+                                                   double* pending MCBS_NARROW_STAMPS_PARAM) {
     static_assert(PHASE == 0 && WTP == 0 && !TOPO_LDS && DEFK == MCBS_DEFENDER_NONE, "the narrow kernel serves the packed, attacker-only whole step");
     static_assert(kNarrowStepCan == (MCBS_TOPO_PROBE | MCBS_TOPO_WIDE_ROWS), "step_body_narrow is written for exactly these traits");
     DevState S{};
     S.h0 = h0; S.masks = masks; S.body = body; S.h1 = h1; S.episode = episode; S.pending = pending;
-    S.E = E; S.body_stride = body_stride; S.tiny_p = tiny_p; S.tiny_v = tiny_v;   // (step_body_narrow does not read N)
+    S.E = E; S.body_stride = body_stride; S.tiny_p = K.tiny_p; S.tiny_v = K.tiny_v;   // (step_body_narrow does not read N)
     S.NW = S.SW = S.TW = S.WT = 1u; S.packed = 1u;
-    const Topo T{nullptr, hot};
     StepIO io{};
-    io.actions = actions; io.reward = reward; io.terminated = terminated;
+    io.actions = actions; io.reward = K.reward; io.terminated = K.terminated;
 #ifdef MCBS_DIAG
     io.stamps = stamps;
 #endif
-    step_body_narrow(S, T, Cp, io);
+    step_body_narrow(S, K, Cp, io);
 }
 
-void launch_step_narrow(dim3 grid, hipStream_t st, const StepCfg* C_dev, const LeanStepArgs& a) {
-    // the level-1 block, five pointers, two words; with the hidden arguments' first 16 bytes within 256 bytes (mcbs_api.hip make_io)
-    static_assert(offsetof(LeanStepArgs, N) + 5 * sizeof(void*) + 2 * sizeof(uint32_t) + 16 <= 256, "step kernel arguments spill into a fifth cache line (make_io)");
+void launch_step_narrow(dim3 grid, hipStream_t st, const StepCfg* C_dev, const StepCfg& C, const LeanStepArgs& a) {
+    NarrowCfg K{};
+    memcpy(&K.goal_reward, &C.goal_reward, 8); memcpy(&K.winning_reward, &C.winning_reward, 8); memcpy(&K.losing_reward, &C.losing_reward, 8);
+    K.hot = a.hot; K.reward = a.reward; K.terminated = a.terminated;
+    K.L = C.L; K.R = C.R; K.P = C.P; K.has_attacker_goal = C.has_attacker_goal; K.goal_own_atleast = C.goal_own_atleast;
+    K.goal_own_pct_min = C.goal_own_pct_min; K.defender_goal_eviction = C.defender_goal_eviction; K.auto_reset = C.auto_reset;
+    K.max_episode_steps = C.max_episode_steps; K.hot_node = C.hot_node; K.hot_desc = C.hot_desc; K.hot_auth = C.hot_auth;
+    K.auth_words = C.auth_words; K.tiny_p = a.tiny_p; K.tiny_v = a.tiny_v;
+    // the level-1 block, the config pointer, the block, `pending` (and the stamps); with the hidden arguments' first 16 bytes within 256
+    // bytes (mcbs_api.hip make_io)
+    static_assert(offsetof(LeanStepArgs, N) + sizeof(void*) + sizeof(NarrowCfg) + 2 * sizeof(void*) + 16 <= 256, "step kernel arguments spill into a fifth cache line (make_io)");
     hipLaunchKernelGGL((step_kernel<0, 0, false, MCBS_DEFENDER_NONE>), grid, dim3(64), 0, st, a.h0, a.masks, a.body, a.h1, a.actions, a.episode, a.E,
-                       a.body_stride, C_dev, a.hot, a.reward, a.terminated, a.pending, a.tiny_p, a.tiny_v MCBS_NARROW_STAMPS_ARG);
+                       a.body_stride, C_dev, K, a.pending MCBS_NARROW_STAMPS_ARG);
 }
 
 #else   // MCBS_NARROW_PRED=0: step_body instantiated with kNarrowStepCan, the lean kernel's argument list in a type of its own
@@ -86,7 +96,7 @@ __global__ __launch_bounds__(256) void step_kernel(const StepCfg* __restrict__ C
     step_body<0, 0, MCBS_DEFENDER_NONE, false, true, NoHook, kNarrowStepCan>(S, T, Cp, io, RollArgs{}, nh);
 }
 
-void launch_step_narrow(dim3 grid, hipStream_t st, const StepCfg* C_dev, const LeanStepArgs& a) {
+void launch_step_narrow(dim3 grid, hipStream_t st, const StepCfg* C_dev, const StepCfg&, const LeanStepArgs& a) {
     hipLaunchKernelGGL((step_kernel<0, 0, false, MCBS_DEFENDER_NONE>), grid, dim3(64), 0, st, C_dev, NarrowStepArgs{a});
 }
 
