@@ -787,7 +787,11 @@ int  mcbs_encode_features(const mcbs_batch*, const mcbs_feature_layout*, const m
  *   Inside the library a value is one 32-bit descriptor, the table shared by all rows: bits 0-15 n_s - 1, bits 16-31 the field's first
  *   bit 32 * word + shift; b_s follows from n_s.
  * mcbs_obs_packing_create: valid_codes[n_values], n_values = the batch's V (MCBS_EINVAL otherwise); a count of 0 or above 65 536, or more
- *   than 2 048 words: MCBS_ELIMIT.  Word and shift are derived here by the rule above; the descriptors are uploaded once.
+ *   than 2 048 words: MCBS_ELIMIT.  Word and shift are derived here by the rule above; the descriptors are uploaded once, and behind them
+ *   a table of W_obs + 1 entries, each word's first value index in bits 0-30 (the values of a word are a contiguous run:
+ *   what mcbs_attacker_wrapper_step_packed builds its words from); bit 31 of an entry is reserved for the library: it marks a word
+ *   whose values are all two-code properties, which that kernel builds by a bit-spread.  ObservationPacking.word_first on the host is
+ *   the plain index.
  * mcbs_pack_observation: obs = the five fields as DENSE int32 rows, n_rows of them, all five required; out[i, 0 .. W_obs) is written for
  *   every i < n_rows (each word whole: the buffer need not be cleared), out_row_words >= W_obs (MCBS_EINVAL otherwise), words from W_obs
  *   on are never touched.  out_of_range (optional device uint32_t) is INCREASED by the number of values stored as their out-of-range
@@ -979,6 +983,32 @@ int  mcbs_attacker_wrapper_finish(mcbs_batch*, const mcbs_wrapper_buffers* w, fl
  * cached credentials) when no mask field is requested (with_masks == 0) — the whole step, observation included, is then ONE launch
  * (marlon_amd/csrc/mcbs_wrapper_fused.hip) and replaying it from a hipGraph would only add the graph's own launch cost —, else 3. */
 int32_t mcbs_attacker_wrapper_step_launches(const mcbs_batch*, int32_t with_masks);
+
+/* mcbs_attacker_wrapper_step for a trainer that stores PACKED observations: the same step — decode, environment step, observation taken
+ * before the defender's turn, bookkeeping, auto-reset — in ONE launch whose observation is the packed row of `packing` ("packed
+ * observations" above) instead of the five int32 fields: W_obs words per env (Chain-10 at 12/12: 72 B instead of 924 B), built from the
+ * kernel's own records; no int32 field is written or read, no second launch packs anything.
+ *   packed           [n_envs, row_words]: the live rows.  Row e receives the observation of this step; an env whose action was intercepted
+ *                    keeps the row it has, so the array must be the one the previous step (or a pack of the reset observation) wrote.
+ *   packed_terminal  [n_envs, row_words]: row e receives the episode's last observation for the envs this step ends (the row that stands,
+ *                    for an env that ends on an intercepted action); other rows are not touched.
+ *   packed_fresh     [W_obs]: the packed row of a freshly reset env (mcbs_pack_observation of the reset observation), which becomes the
+ *                    live row of every env this step ends.
+ *   packed_terminal and packed_fresh are required with auto_reset != 0 and ignored (may be NULL) without it.  row_words >= W_obs; every
+ *   word below W_obs of a written row is stored whole, words from W_obs on are never touched.  A value outside its valid codes is stored
+ *   as its out-of-range code (nothing is counted here: mcbs_encode_features_packed counts at use).
+ * The digests (mcbs_mask_logits, mcbs_pack_action_mask, mcbs_store_mask_keys) and every array of `w`, `decoded` and `info` are written
+ * exactly as by mcbs_attacker_wrapper_step's single launch.  Stream-ordered, no host synchronisation, hipGraph-capturable.
+ * Scope: batches for which mcbs_attacker_wrapper_step_launches(batch, 0) is 1; there is no multi-launch fallback.  MCBS_EINVAL (nothing
+ * launched, no state changed) for a batch outside that scope, a packing created for another device or geometry, row_words < W_obs, a
+ * row beyond the room the kernel keeps in LDS (W_obs <= 128 and W_obs + 1 + V <= 896: every batch in scope with the default bounds),
+ * missing terminal or fresh rows under auto_reset, both or neither action encodings, and arrays that share bytes (packed,
+ * packed_terminal, decoded against each other, the fresh row, the actions and every array of `w` and `info`).  MCBS_ESTATE as for mcbs_attacker_wrapper_step. */
+int  mcbs_attacker_wrapper_step_packed(mcbs_batch*, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded,
+                                       const mcbs_info_buffers* info, const mcbs_obs_packing* packing, uint32_t* packed,
+                                       uint32_t* packed_terminal, const uint32_t* packed_fresh, size_t row_words,
+                                       const mcbs_wrapper_buffers* w, float invalid_action_reward_modifier, int32_t max_timesteps,
+                                       int32_t auto_reset, void* stream);
 
 /* The reward shaping of marlon's DefenderEnvWrapper.step (defend_wrapper.py:228-282) around mcbs_defender_step, for every env in one
  * launch and in the wrapper's own order of double-precision operations: invalid-action penalty, minus the attacker's last environment

@@ -209,6 +209,9 @@ PROTOTYPES = {
     # batch, w, invalid_action_reward_modifier, max_timesteps, auto_reset, keep, fresh, stream
     "mcbs_attacker_wrapper_finish": (_int, [_H, _P, _f32, _i32, _i32, _P, _P, _S]),
     "mcbs_attacker_wrapper_step_launches": (_i32, [_H, _i32]),                                # batch, with_masks
+    # batch, multidiscrete, discrete, decoded, info, packing, packed, packed_terminal, packed_fresh, row_words, w,
+    # invalid_action_reward_modifier, max_timesteps, auto_reset, stream
+    "mcbs_attacker_wrapper_step_packed": (_int, [_H, _P, _P, _P, _P, _H, _P, _P, _P, _size, _P, _f32, _i32, _i32, _S]),
     "mcbs_defender_wrapper_post": (_int, [_H, _P, _P, _S]),                                   # batch, w, cfg, stream
     "mcbs_defender_wrapper_step": (_int, [_H, _P, _P, _P, _P, _S]),                           # batch, actions, obs, w, cfg, stream
     "mcbs_two_agent_step_launches": (_i32, [_H]),

@@ -2005,6 +2005,7 @@ struct mcbs_obs_packing {
     int32_t device = 0;
     ObsPackGeom P{};
     uint32_t* desc_dev = nullptr;
+    uint32_t* word_first_dev = nullptr;     // [W + 1] first value index of each word (| FUSED_WORD_PROPS), behind the descriptors in one allocation
     std::vector<uint32_t> valid;    // per source value: its valid codes
 };
 
@@ -2031,7 +2032,7 @@ extern "C" int mcbs_obs_packing_create(const mcbs_batch* b, const uint32_t* vali
     obs_field_lens(b, lens);
     for (int k = 0; k < 5; ++k) { P.len[k] = (uint32_t)lens[k]; P.off[k] = (uint32_t)V; V += lens[k]; }
     if (n_values != V) return fail(MCBS_EINVAL, "observation packing: %zu valid-code counts for the %llu values of a row", n_values, (unsigned long long)V);
-    std::vector<uint32_t> desc(n_values);
+    std::vector<uint32_t> desc(n_values), word_first(1, 0u);       // word_first[w]: the first value of word w; the last entry: V
     uint64_t word = 0;
     uint32_t shift = 0;                                    // the next free bit is bit `shift` of word `word`
     for (size_t s = 0; s < n_values; ++s) {
@@ -2039,20 +2040,31 @@ extern "C" int mcbs_obs_packing_create(const mcbs_batch* b, const uint32_t* vali
         if (n == 0u || n > OBS_PACK_MAX_CODES) return fail(MCBS_ELIMIT, "observation packing: value %zu has %u valid codes (1 to %u)", s, n, OBS_PACK_MAX_CODES);
         uint32_t width = 0;
         while ((n >> width) != 0u) ++width;                // bit_length(n)
-        if (shift + width > 32u) { ++word; shift = 0; }    // a field never straddles a word
+        if (shift + width > 32u) { ++word; shift = 0; word_first.push_back((uint32_t)s); }    // a field never straddles a word
         if (word >= OBS_PACK_MAX_WORDS) return fail(MCBS_ELIMIT, "observation packing: a row needs more than %u words", OBS_PACK_MAX_WORDS);
         desc[s] = (n - 1u) | (((uint32_t)word * 32u + shift) << 16);
         shift += width;
     }
     P.V = (uint32_t)V;
     P.W = (uint32_t)word + (shift ? 1u : 0u);
+    word_first.resize(P.W);                                // (V == 0: no word)
+    word_first.push_back(P.V);
+    // the packed wrapper step (mcbs_wrapper_fused.hip) builds a word of two-code property values as a bit-spread: flag those words
+    for (uint32_t w = 0; w < P.W; ++w) {
+        const uint32_t first = word_first[w], last = word_first[w + 1u] & ~FUSED_WORD_PROPS;
+        bool props = first >= P.off[3] && last <= P.off[3] + P.len[3];
+        for (uint32_t s = first; props && s < last; ++s) props = valid_codes[s] == 2u;
+        if (props) word_first[w] |= FUSED_WORD_PROPS;
+    }
+    desc.insert(desc.end(), word_first.begin(), word_first.end());       // one upload: descriptors [V] | word_first [W + 1]
     DeviceGuard guard(b->cfg.device);
     if (guard.err != hipSuccess) return fail(MCBS_EHIP, "cannot select device %d: %s", b->cfg.device, hipGetErrorString(guard.err));
     mcbs_obs_packing* p = new (std::nothrow) mcbs_obs_packing();
     if (!p) return fail(MCBS_ENOMEM, "out of memory");
     p->device = b->cfg.device; p->P = P; p->valid.assign(valid_codes, valid_codes + n_values);
-    hipError_t e = hipMalloc(&p->desc_dev, n_values * sizeof(uint32_t));
-    if (e == hipSuccess) e = hipMemcpy(p->desc_dev, desc.data(), n_values * sizeof(uint32_t), hipMemcpyHostToDevice);
+    hipError_t e = hipMalloc(&p->desc_dev, desc.size() * sizeof(uint32_t));
+    if (e == hipSuccess) e = hipMemcpy(p->desc_dev, desc.data(), desc.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+    p->word_first_dev = p->desc_dev ? p->desc_dev + n_values : nullptr;
     if (e != hipSuccess) {
         if (p->desc_dev) (void)hipFree(p->desc_dev);
         delete p;
@@ -2099,6 +2111,83 @@ extern "C" int mcbs_unpack_observation(const mcbs_batch* b, const mcbs_obs_packi
     hipLaunchKernelGGL(unpack_observation_kernel, rows_grid(n_rows, 2048u), dim3(256), 0, (hipStream_t)stream, p->P, p->desc_dev, packed, row_words,
                        index, n_source_rows, dst, n_rows);
     return launch_ok("unpack observation");
+}
+
+// The one-launch wrapper step with the packed store side (mcbs_wrapper_fused.hip wrapper_fused_packed_kernel): the argument block of
+// the int32 step with no observation field (fused_wrapper_args), and the packed rows' own.  Every check before the launch: a refused
+// call launches nothing and changes no state.
+extern "C" int mcbs_attacker_wrapper_step_packed(mcbs_batch* b, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded,
+                                                 const mcbs_info_buffers* info, const mcbs_obs_packing* p, uint32_t* packed, uint32_t* packed_terminal,
+                                                 const uint32_t* packed_fresh, size_t row_words, const mcbs_wrapper_buffers* w, float modifier,
+                                                 int32_t max_timesteps, int32_t auto_reset, void* stream) {
+    const char* who = "mcbs_attacker_wrapper_step_packed";
+    if (!b || !w || !decoded || !p || !packed) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    WrapperFinishArgs F;
+    int rc = finish_args(b, w, modifier, max_timesteps, auto_reset, nullptr, nullptr, &F);
+    if (rc) return rc;
+    if ((rc = draws_ok(b))) return rc;
+    if (!multidiscrete == !discrete) return fail(MCBS_EINVAL, "need exactly one action encoding");
+    if (!b->variant.fused_wrapper)
+        return fail(MCBS_EINVAL, "%s: the wrapper step of this batch is not one launch (packed batch, at most 16 nodes and cached credentials, not "
+                                 "the random-events defender); there is no multi-launch form of the packed step", who);
+    if (!obs_packing_fits(b, p)) return fail(MCBS_EINVAL, "%s: the packing was created for a batch of another device or geometry", who);
+    const uint32_t W = p->P.W, V = p->P.V;
+    if (row_words < W) return fail(MCBS_EINVAL, "row_words %zu is shorter than the %u words of a packed row", row_words, W);
+    if (W > FUSED_PACKED_MAX_WORDS || W + 1u + V > FUSED_PACKED_TABLE_DWORDS)
+        return fail(MCBS_EINVAL, "%s: a packed row of %u words and %u values is beyond the LDS room the step keeps for the fresh row (%u words) and "
+                                 "its tables (%u entries)", who, W, V, FUSED_PACKED_MAX_WORDS, FUSED_PACKED_TABLE_DWORDS);
+    if (auto_reset && (!packed_terminal || !packed_fresh))
+        return fail(MCBS_EINVAL, "%s: auto_reset needs packed_terminal (the rows of the envs that end) and packed_fresh (the row of a reset env)", who);
+    if (!auto_reset) packed_terminal = nullptr, packed_fresh = nullptr;                 // (neither is touched)
+    // the three arrays this entry point adds may share no byte with each other, with an input or with an array of `w` / `info`, which the
+    // same launch writes
+    {
+        const uint64_t E = b->S.E;
+        struct Extent { const char* name; uintptr_t lo, hi; bool out; };
+        auto extent = [](const char* name, const void* q, uint64_t bytes, bool out) {
+            const uintptr_t lo = reinterpret_cast<uintptr_t>(q);
+            return Extent{name, lo, q ? lo + (uintptr_t)bytes : lo, out};
+        };
+        const uint64_t rows_bytes = ((E - 1u) * row_words + W) * 4u;
+        const Extent ext[] = {
+            extent("packed", packed, rows_bytes, true), extent("packed_terminal", packed_terminal, rows_bytes, true),
+            extent("decoded", decoded, E * 20u, true), extent("packed_fresh", packed_fresh, (uint64_t)W * 4u, false),
+            extent("multidiscrete", multidiscrete, E * 80u, false), extent("discrete", discrete, E * 8u, false),
+            extent("w->invalid", w->invalid, E, false), extent("w->reward", w->reward, E * 4u, false), extent("w->terminated", w->terminated, E, false),
+            extent("w->timesteps", w->timesteps, E * 4u, false), extent("w->valid_action_count", w->valid_action_count, E * 8u, false),
+            extent("w->invalid_action_count", w->invalid_action_count, E * 8u, false), extent("w->episode_returns", w->episode_returns, E * 8u, false),
+            extent("w->last_cyber_reward", w->last_cyber_reward, E * 4u, false), extent("w->has_cyber_reward", w->has_cyber_reward, E, false),
+            extent("w->rewards", w->rewards, E * 4u, false), extent("w->truncated", w->truncated, E, false), extent("w->dones", w->dones, E, false),
+            extent("w->episode_return_out", w->episode_return_out, E * 8u, false), extent("w->episode_length_out", w->episode_length_out, E * 4u, false),
+            extent("w->executed", w->executed, E, false),
+            extent("info->network_availability", info ? info->network_availability : nullptr, E * 8u, false),
+            extent("info->step_count", info ? info->step_count : nullptr, E * 4u, false), extent("info->truncated", info ? info->truncated : nullptr, E, false),
+            extent("info->out_of_bound", info ? info->out_of_bound : nullptr, E, false), extent("info->raw_reward", info ? info->raw_reward : nullptr, E * 4u, false),
+        };
+        constexpr size_t NE = sizeof(ext) / sizeof(ext[0]);
+        for (size_t i = 0; i < NE; ++i)
+            for (size_t k = i + 1u; k < NE; ++k)
+                if (ext[i].out && ext[i].lo < ext[i].hi && ext[k].lo < ext[k].hi && ext[i].lo < ext[k].hi && ext[k].lo < ext[i].hi)
+                    return fail(MCBS_EINVAL, "%s: %s overlaps %s", who, ext[i].name, ext[k].name);
+    }
+    const StepIO io = make_io(b, decoded, const_cast<float*>(w->reward), const_cast<uint8_t*>(w->terminated), info);
+    const mcbs_obs_buffers none{};
+    FusedArgs A;
+    if (!fused_wrapper_args(b, multidiscrete, discrete, decoded, &none, w, modifier, max_timesteps, auto_reset, nullptr, nullptr, &A))
+        return fail(MCBS_EINVAL, "%s: the wrapper step of this batch is not one launch", who);
+    FusedPackedArgs PA{};
+    PA.packed = packed; PA.term = packed_terminal; PA.fresh = packed_fresh; PA.desc = p->desc_dev; PA.word_first = p->word_first_dev;
+    PA.row_words = row_words; PA.W = W; PA.V = V;
+    PA.off1 = p->P.off[1]; PA.off2 = p->P.off[2]; PA.off3 = p->P.off[3]; PA.off4 = p->P.off[4];
+    b->all_fresh = false;
+    const dim3 grid((b->S.E + 63u) / 64u), block(FUSED_THREADS);
+    pick<MCBS_DEFENDER_SCAN_AND_REIMAGE, MCBS_DEFENDER_EXTERNAL, MCBS_DEFENDER_NONE>((int)b->cfg.defender_kind, [&](auto def) {
+        hipLaunchKernelGGL((wrapper_fused_packed_kernel<decltype(def)::value>), grid, block, 0, (hipStream_t)stream, b->S, b->T, b->C_dev, io, A, PA);
+    });
+    if ((rc = launch_ok("wrapper step (one launch, packed rows)"))) return rc;
+    b->digest_state = 1;       // every env's digest was written (or, for an intercepted action, stands)
+    return MCBS_OK;
 }
 
 extern "C" int mcbs_encode_features_packed(const mcbs_batch* b, const mcbs_feature_layout* l, const mcbs_obs_packing* p, const uint32_t* packed,

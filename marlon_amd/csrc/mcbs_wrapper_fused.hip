@@ -30,8 +30,12 @@
 // requested (the policy masks its logits with mcbs_mask_logits), observation rows whose dword counts are multiples of four
 // (Chain-10 @12/12: 168 / 12 / 24 / 20; ToyCtf @12/10: 120 / 12 / 20 / 20), not the random-events defender.
 #pragma once
+#include <cstddef>
+#include <type_traits>
+
 #include "mcbs_aux.hip"
 #include "mcbs_obs.hip"
+#include "mcbs_obs_packing.hip"
 #include "mcbs_step.hip"
 
 namespace mcbs {
@@ -128,6 +132,9 @@ struct FusedHook {
     __device__ __forceinline__ void fill_reset_rows(uint32_t t, uint32_t nt) {
         if (!A.auto_reset) return;
         fill_fresh<0>(t, nt); fill_fresh<1>(t, nt); fill_fresh<2>(t, nt); fill_fresh<3>(t, nt); fill_fresh<4>(t, nt);
+        fill_reset_digest(t);
+    }
+    __device__ __forceinline__ void fill_reset_digest(uint32_t t) {
         if (t < 16u) rdig_lds()[t] = reinterpret_cast<const uint32_t*>(A.reset_digest)[t];
     }
     // issued behind the step's own level-1 loads (same wait): the wrapper's counters and the triple table (into LDS)
@@ -318,6 +325,25 @@ struct FusedHook {
         return have ? (col == 0u ? 1u : (col == 1u ? ci : (col == 2u ? c & 0xFFu : c >> 8))) : 0u;
     }
 
+    // scalar j (0..6) of field 0 of the env whose LDS record is st (obs_tiny_kernel's values)
+    __device__ __forceinline__ int32_t scalar_value(const FusedStage& st, uint32_t j) const {
+        const uint32_t meta = st.meta(), flags = st.flags();
+        const uint32_t n_disc = meta & 0xFFu, n_creds = (meta >> 8) & 0xFFu;
+        const bool blank = meta & FM_BLANK;
+        const uint32_t kind = (flags >> F_KIND_SHIFT) & 0xFu, level = (flags >> F_LEVEL_SHIFT) & 3u, new_nodes = (flags >> F_NEWNODES_SHIFT) & 0x3FFu;
+        int32_t v = 0;
+        if (j == 6u) v = (int32_t)n_disc;
+        else if (!blank) {
+            if (j == 0u) v = (kind == MCBS_OUT_LEAKED_NODES || kind == MCBS_OUT_LEAKED_CREDENTIALS) ? (int32_t)new_nodes : 0;
+            else if (j == 1u) v = kind == MCBS_OUT_LATERAL_MOVE;
+            else if (j == 2u) v = kind == MCBS_OUT_CUSTOMER_DATA;
+            else if (j == 3u) v = kind == MCBS_OUT_PROBE_SUCCEEDED ? 2 : (kind == MCBS_OUT_PROBE_FAILED ? 1 : 0);
+            else if (j == 4u) v = kind == MCBS_OUT_PRIVILEGE_ESCALATION ? (int32_t)level : 0;
+            else v = (int32_t)n_creds;
+        }
+        return v;
+    }
+
     // ---- fields 1..4: whole 16-byte vectors, each inside one env's row; thread `lane` of `NT` ----
     template <uint32_t f>
     __device__ __forceinline__ void stream_field(uint32_t e0, uint32_t n_env) {
@@ -371,32 +397,22 @@ struct FusedHook {
         }
     }
 
+    // FIELDS = false: the digests only (wrapper_fused_packed_kernel has its own store side for the observation)
+    template <bool FIELDS = true>
     __device__ __forceinline__ void stream(const DevState& S, uint32_t e0) {
         const uint32_t n_env = S.E - e0 < 64u ? S.E - e0 : 64u;       // envs of this wavefront
         const uint32_t* fr = fresh_lds();
-        stream_field<1>(e0, n_env); stream_field<2>(e0, n_env); stream_field<3>(e0, n_env); stream_field<4>(e0, n_env);
+        if constexpr (FIELDS) { stream_field<1>(e0, n_env); stream_field<2>(e0, n_env); stream_field<3>(e0, n_env); stream_field<4>(e0, n_env); }
         // ---- field 0: seven scalars per env, dword by dword ----
-        if (A.obs[0]) {
+        if (FIELDS && A.obs[0]) {
             const uint32_t total = n_env * 7u;
             int32_t* out = A.obs[0] + (size_t)e0 * 7u;
             int32_t* tout = A.term[0] ? A.term[0] + (size_t)e0 * 7u : nullptr;
             for (uint32_t q = lane; q < total; q += FUSED_THREADS) {
                 const uint32_t env = fdiv(q, A.d_u4[0]), j = q - env * 7u;
                 const FusedStage st = stage(env);
-                const uint32_t meta = st.meta(), flags = st.flags();
-                const uint32_t n_disc = meta & 0xFFu, n_creds = (meta >> 8) & 0xFFu;
-                const bool blank = meta & FM_BLANK;
-                const uint32_t kind = (flags >> F_KIND_SHIFT) & 0xFu, level = (flags >> F_LEVEL_SHIFT) & 3u, new_nodes = (flags >> F_NEWNODES_SHIFT) & 0x3FFu;
-                int32_t v = 0;
-                if (j == 6u) v = (int32_t)n_disc;
-                else if (!blank) {
-                    if (j == 0u) v = (kind == MCBS_OUT_LEAKED_NODES || kind == MCBS_OUT_LEAKED_CREDENTIALS) ? (int32_t)new_nodes : 0;
-                    else if (j == 1u) v = kind == MCBS_OUT_LATERAL_MOVE;
-                    else if (j == 2u) v = kind == MCBS_OUT_CUSTOMER_DATA;
-                    else if (j == 3u) v = kind == MCBS_OUT_PROBE_SUCCEEDED ? 2 : (kind == MCBS_OUT_PROBE_FAILED ? 1 : 0);
-                    else if (j == 4u) v = kind == MCBS_OUT_PRIVILEGE_ESCALATION ? (int32_t)level : 0;
-                    else v = (int32_t)n_creds;
-                }
+                const uint32_t meta = st.meta();
+                const int32_t v = scalar_value(st, j);
                 if (meta & FM_ENDED) { if (meta & FM_LIVE) tout[q] = v; else tout[q] = out[q]; out[q] = (int32_t)fr[A.fresh_off[0] + j]; }
                 else if (meta & FM_LIVE) out[q] = v;
             }
@@ -437,8 +453,168 @@ __global__ __launch_bounds__(FUSED_THREADS) void wrapper_fused_kernel(DevState S
     MCBS_LDS_BARRIER();
     hook.convert_creds();
     MCBS_LDS_BARRIER();
-#undef MCBS_LDS_BARRIER
     hook.stream(S, blockIdx.x * 64u);
 }
+
+// ------------------------------------------------------------------ the same step, the observation written as PACKED rows
+// wrapper_fused_packed_kernel is wrapper_fused_kernel up to the last barrier — the same FusedHook, the same step_body, the same records
+// in LDS, the same digest stream — with another store side: instead of 231 int32 values per Chain-10 env (924 B) it writes the W_obs words
+// of the env's packed row (include/mcbs.h "packed observations"; 72 B), built from the LDS record.  One thread builds one (env, word) at
+// a time — a wavefront one word index for its 64 envs — and one thread stores one, q = 256 k + thread over the workgroup's 64 x W_obs
+// words: a wavefront's store covers 64 consecutive words of consecutive envs, one contiguous block when row_words == W_obs
+// (FusedPackedStore::stream).  The values of a word are a contiguous run of the descriptor table (word_first); every
+// value is the one the int32 stream writes (scalar_value, dword_value<1..4>), clamped to its code by the packing rule.  A word whose
+// values are all two-code properties (sixteen to a word: most of a row) is a bit-spread of the nodes' property bits instead of sixteen
+// trips through dword_value<3>.  Both tables are read from LDS, where the non-stepping wavefronts put them beside the fresh row: no
+// load is issued behind a store, but for the one read-back of an env that ended on an intercepted action (stream_field has the same).
+constexpr uint32_t FUSED_PACKED_MAX_WORDS = 128;                                         // LDS room for the fresh packed row ...
+constexpr uint32_t FUSED_PACKED_TABLE_DWORDS = FUSED_FRESH_DWORDS - FUSED_PACKED_MAX_WORDS;   // ... and for word_first [W + 1] | descriptors [V]
+constexpr uint32_t FUSED_WORD_PROPS = 1u << 31;                                          // word_first flag: the word holds two-code properties only
+
+struct FusedPackedArgs {                       // the packed store side's own argument block (FusedArgs keeps its layout; its obs / term / fresh stay NULL)
+    uint32_t* packed;                          // [E, row_words] live rows
+    uint32_t* term;                            // [E, row_words] terminal rows (auto_reset)
+    const uint32_t* fresh;                     // [W] the packed row of a freshly reset env (auto_reset)
+    const uint32_t* desc;                      // [V] descriptors (mcbs_obs_packing.hip obs_desc_*)
+    const uint32_t* word_first;                // [W + 1] first value index of each word | FUSED_WORD_PROPS
+    size_t row_words;
+    uint32_t W, V;
+    uint32_t off1, off2, off3, off4;           // first value index of fields 1..4 (field 0 starts at 0)
+};
+
+// The block is read WHERE IT IS USED, from the kernel-argument segment behind a compiler barrier: read as an ordinary by-value argument
+// its 19 scalar registers are loaded at kernel entry and stay live across step_body, whose own pressure then spills scalars to scratch
+// memory (68 bytes per lane under the in-env defender).  Scalar loads: they do not count among the vector loads and stores.
+// FusedPackedKernArgs restates wrapper_fused_packed_kernel's parameter list, member for parameter: explicit kernel arguments lie in the
+// segment in order, each at its natural alignment, which is how a struct lays out its members.  The static_assert behind the kernel
+// holds the two together: a parameter added, dropped, reordered or retyped there without the same change here does not compile.
+struct FusedPackedKernArgs { DevState S; Topo T; const StepCfg* Cp; StepIO io; FusedArgs A; FusedPackedArgs P; };
+template <class T>
+__device__ __forceinline__ T fused_karg(uint64_t address) {
+    typedef T __attribute__((address_space(4))) ConstantT;
+    return *reinterpret_cast<const ConstantT*>(address);
+}
+__device__ __forceinline__ FusedPackedArgs fused_packed_args() {
+    uint64_t q = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(FusedPackedKernArgs, P);
+    asm volatile("" : "+s"(q));
+#define MCBS_KARG(T, member) fused_karg<T>(q + offsetof(FusedPackedArgs, member))
+    FusedPackedArgs P;
+    P.packed = MCBS_KARG(uint32_t*, packed); P.term = MCBS_KARG(uint32_t*, term); P.fresh = MCBS_KARG(const uint32_t*, fresh);
+    P.desc = MCBS_KARG(const uint32_t*, desc); P.word_first = MCBS_KARG(const uint32_t*, word_first);
+    P.row_words = MCBS_KARG(size_t, row_words); P.W = MCBS_KARG(uint32_t, W); P.V = MCBS_KARG(uint32_t, V);
+    P.off1 = MCBS_KARG(uint32_t, off1); P.off2 = MCBS_KARG(uint32_t, off2); P.off3 = MCBS_KARG(uint32_t, off3); P.off4 = MCBS_KARG(uint32_t, off4);
+#undef MCBS_KARG
+    return P;
+}
+
+struct FusedPackedStore {
+    const FusedHook& H;
+    const FusedPackedArgs P;
+    __device__ __forceinline__ uint32_t* fresh_row() const { return H.fresh_lds(); }
+    __device__ __forceinline__ uint32_t* word_first() const { return H.fresh_lds() + FUSED_PACKED_MAX_WORDS; }
+    __device__ __forceinline__ uint32_t* desc() const { return word_first() + P.W + 1u; }
+
+    // the fresh row and the two tables into LDS, by the wavefronts that do not step (threads t of nt)
+    __device__ __forceinline__ void fill(uint32_t t, uint32_t nt) const {
+        if (H.A.auto_reset) for (uint32_t i = t; i < P.W; i += nt) fresh_row()[i] = P.fresh[i];
+        for (uint32_t i = t; i <= P.W; i += nt) word_first()[i] = P.word_first[i];
+        for (uint32_t i = t; i < P.V; i += nt) desc()[i] = P.desc[i];
+    }
+
+    // source value s of the env whose LDS record is st: what the int32 stream writes there
+    __device__ __forceinline__ uint32_t value(const FusedStage& st, uint32_t s) const {
+        if (s >= P.off4) return H.dword_value<4>(st, s - P.off4);
+        if (s >= P.off3) return H.dword_value<3>(st, s - P.off3);
+        if (s >= P.off2) return H.dword_value<2>(st, s - P.off2);
+        if (s >= P.off1) return H.dword_value<1>(st, s - P.off1);
+        return (uint32_t)H.scalar_value(st, s);
+    }
+
+    __device__ __forceinline__ uint32_t word(const FusedStage& st, uint32_t w) const {
+        const uint32_t f0 = word_first()[w], first = f0 & ~FUSED_WORD_PROPS, last = word_first()[w + 1u] & ~FUSED_WORD_PROPS;
+        if (f0 & FUSED_WORD_PROPS) {           // up to sixteen property bits, values first - off3 ..: code = the bit, 2 (out of range) when blank
+            const uint32_t cnt = last - first, keep = (1u << cnt) - 1u;
+            uint32_t x;
+            if (st.meta() & FM_BLANK) x = keep << 16;                                    // (spread below: bit 1 of every pair)
+            else {
+                const uint32_t idx = first - P.off3;
+                uint32_t i = fdiv(idx, H.A.dNP), p = idx - i * H.A.NP, got = 0;
+                x = 0;
+                while (got < cnt) { x |= (st.props(i) >> p) << got; got += H.A.NP - p; ++i; p = 0u; }      // (rows hold NP bits; i < Nmax)
+                x &= keep;
+            }
+            // bit k (code bit 0) -> bit 2k, bit 16 + k (code bit 1) -> bit 2k + 1
+            uint32_t lo = x & 0xFFFFu, hi = x >> 16;
+            lo = (lo | (lo << 8)) & 0x00FF00FFu; lo = (lo | (lo << 4)) & 0x0F0F0F0Fu; lo = (lo | (lo << 2)) & 0x33333333u; lo = (lo | (lo << 1)) & 0x55555555u;
+            hi = (hi | (hi << 8)) & 0x00FF00FFu; hi = (hi | (hi << 4)) & 0x0F0F0F0Fu; hi = (hi | (hi << 2)) & 0x33333333u; hi = (hi | (hi << 1)) & 0x55555555u;
+            return lo | (hi << 1);
+        }
+        uint32_t x = 0;
+        for (uint32_t s = first; s < last; ++s) {
+            const uint32_t d = desc()[s], n = obs_desc_codes(d), v = value(st, s);
+            x |= (v < n ? v : n) << (obs_desc_bit(d) & 31u);                             // (a negative value is huge as unsigned: out of range)
+        }
+        return x;
+    }
+
+    // live, ended and intercepted envs as stream_field has them, word by word
+    // BUILD: a wavefront takes one word index at a time, its lanes the 64 envs — the word's run of values, their fields and descriptors are
+    // the same for every lane (scalar branches, LDS broadcasts); with one (env, word) per lane in store order the lanes of a wavefront sat
+    // in different words, fields and trip counts and the launch took 42 us where the int32 stream takes 19 (profiles/packed_step.md).
+    // The words go to the hand-over records, which nobody reads after convert_creds (23 dwords per env, odd: all banks), FUSED_RAW_DWORDS
+    // words of a row at a time.  STORE: from there in store order, q = 256 k + thread over the 64 envs x the chunk's words.
+    __device__ __forceinline__ void stream(uint32_t e0, uint32_t n_env) const {
+        const uint32_t wave = __builtin_amdgcn_readfirstlane(H.lane >> 6), env_lane = H.lane & 63u;
+        for (uint32_t w0 = 0; w0 < P.W; w0 += FUSED_RAW_DWORDS) {                         // (uniform: every thread meets every barrier)
+            const uint32_t nw = P.W - w0 < FUSED_RAW_DWORDS ? P.W - w0 : FUSED_RAW_DWORDS;
+            if (w0) MCBS_LDS_BARRIER();                                                  // the previous chunk has been read
+            if (env_lane < n_env) {
+                const FusedStage st = H.stage(env_lane);
+                uint32_t* built = H.raw(env_lane).p;
+                for (uint32_t k = wave; k < nw; k += FUSED_THREADS / 64u) built[k] = word(st, w0 + k);
+            }
+            MCBS_LDS_BARRIER();
+            const uint32_t total = n_env * nw;
+            for (uint32_t q = H.lane; q < total; q += FUSED_THREADS) {
+                const uint32_t env = q / nw, k = q - env * nw, w = w0 + k;
+                const uint32_t meta = H.stage(env).meta();
+                if (!(meta & (FM_LIVE | FM_ENDED))) continue;                            // intercepted, not ended: the row stands
+                const size_t at = (size_t)(e0 + env) * P.row_words + w;
+                const uint32_t x = H.raw(env).p[k];
+                if (meta & FM_ENDED) { if (meta & FM_LIVE) P.term[at] = x; else P.term[at] = P.packed[at]; P.packed[at] = fresh_row()[w]; }
+                else P.packed[at] = x;
+            }
+        }
+    }
+};
+
+template <int DEFK>
+__global__ __launch_bounds__(FUSED_THREADS) void wrapper_fused_packed_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, StepIO io, FusedArgs A,
+                                                                             FusedPackedArgs P) {
+    __shared__ uint32_t lds[64u * (FUSED_STAGE_DWORDS + FUSED_RAW_DWORDS) + FUSED_FRESH_DWORDS + 32u + 16u];
+    const uint32_t tid = threadIdx.x;
+    FusedHook hook{A, lds, tid, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, {0, 0, 0, 0, 0}, false};
+    (void)P;                                                                             // (read through fused_packed_args)
+    if (tid < 64u) step_body<0, 0, DEFK, false>(S, T, Cp, io, RollArgs{}, hook);
+    else {
+        if (A.auto_reset) hook.fill_reset_digest(tid - 64u);                             // (no int32 field: FusedArgs' obs / term / fresh are never read)
+        FusedPackedStore{hook, fused_packed_args()}.fill(tid - 64u, FUSED_THREADS - 64u);
+    }
+    MCBS_LDS_BARRIER();
+    hook.convert_nodes(S);
+    MCBS_LDS_BARRIER();
+    hook.convert_creds();
+    MCBS_LDS_BARRIER();
+    const uint32_t e0 = blockIdx.x * 64u, n_env = S.E - e0 < 64u ? S.E - e0 : 64u;
+    FusedPackedStore{hook, fused_packed_args()}.stream(e0, n_env);
+    hook.template stream<false>(S, e0);                                                  // the digests
+}
+static_assert(std::is_same<decltype(&wrapper_fused_packed_kernel<0>), void (*)(DevState, Topo, const StepCfg*, StepIO, FusedArgs, FusedPackedArgs)>::value &&
+                  std::is_same<decltype(FusedPackedKernArgs::S), DevState>::value && std::is_same<decltype(FusedPackedKernArgs::T), Topo>::value &&
+                  std::is_same<decltype(FusedPackedKernArgs::Cp), const StepCfg*>::value && std::is_same<decltype(FusedPackedKernArgs::io), StepIO>::value &&
+                  std::is_same<decltype(FusedPackedKernArgs::A), FusedArgs>::value && std::is_same<decltype(FusedPackedKernArgs::P), FusedPackedArgs>::value &&
+                  sizeof(FusedPackedKernArgs) == offsetof(FusedPackedKernArgs, P) + sizeof(FusedPackedArgs) && std::is_trivially_copyable<FusedPackedKernArgs>::value,
+              "fused_packed_args() reads FusedPackedArgs at offsetof(FusedPackedKernArgs, P) of the kernel-argument segment: the struct must restate the kernel's parameter list");
+#undef MCBS_LDS_BARRIER
 
 } // namespace mcbs

@@ -560,6 +560,34 @@ class BatchEngine:
                 _check(lib, rc, "mcbs_attacker_wrapper_step")
         return call
 
+    def wrapper_step_packed_call(self, discrete: bool, decoded, packing: "ObservationPackingHandle", packed, packed_terminal, packed_fresh, bufs,
+                                 modifier: float, max_timesteps: int, auto_reset: bool):
+        """callable(actions_ptr): mcbs_attacker_wrapper_step_packed — the one-launch wrapper step that writes the packed observation row
+        instead of the five int32 fields — bound once like wrapper_step_call.  packed / packed_terminal: device int32 [E, >= W_obs] with
+        contiguous rows and one row stride (packed_terminal may be None without auto_reset); packed_fresh: int32 [>= W_obs] or
+        [1, >= W_obs], the packed row of a freshly reset env.  The library refuses a batch whose wrapper step is not one launch."""
+        t = self.torch
+        self._packed_obs_rows(packed, packing, "packed", self.E)
+        stride = _row_stride(packed, self.E)
+        if packed_terminal is not None:
+            self._packed_obs_rows(packed_terminal, packing, "packed_terminal", self.E)
+            if _row_stride(packed_terminal, self.E) != stride:
+                raise ValueError("packed and packed_terminal must have the same row stride")
+        if packed_fresh is not None:
+            if packed_fresh.dtype != t.int32 or packed_fresh.device != self.device or not packed_fresh.is_contiguous() or packed_fresh.numel() < packing.words:
+                raise ValueError(f"packed_fresh must be a contiguous device int32 tensor of at least {packing.words} words, got {_describe(packed_fresh)}")
+        fn, eng, lib, stream = self.lib.mcbs_attacker_wrapper_step_packed, self, self.lib, self._stream
+        refs = (C.byref(self._info_struct), C.byref(bufs))
+        rows, mod, mt, ar = decoded.data_ptr(), float(modifier), int(max_timesteps), int(bool(auto_reset))
+        ph, pp, pt, pf = packing.ptr, packed.data_ptr(), _ptr(packed_terminal), _ptr(packed_fresh)
+        alive = (decoded, packing, packed, packed_terminal, packed_fresh, bufs, self._info_struct)
+
+        def call(p: int, _alive=alive) -> None:
+            rc = fn(eng._h, None if discrete else p, p if discrete else None, rows, refs[0], ph, pp, pt, pf, stride, refs[1], mod, mt, ar, stream())
+            if rc:
+                _check(lib, rc, "mcbs_attacker_wrapper_step_packed")
+        return call
+
     def defender_wrapper_step_call(self, obs_struct, bufs, cfg):
         """callable(actions_ptr): defender_wrapper_step with the argument blocks bound once."""
         fn, eng, lib, stream = self.lib.mcbs_defender_wrapper_step, self, self.lib, self._stream

@@ -28,6 +28,8 @@ OBS_FIELDS = ["scalars", "leaked_credentials", "credential_cache_matrix", "disco
 
 MAX_SOURCE, MAX_CLASSES = 1 << 15, 1 << 16        # what a 32-bit column descriptor holds (class 16 bits, source index 15, first flag 1)
 FIRST = 1 << 31
+# the LDS room mcbs_attacker_wrapper_step_packed keeps (include/mcbs.h): W_obs words for the fresh row, W_obs + 1 + V table entries
+PACKED_STEP_MAX_WORDS, PACKED_STEP_TABLE_ENTRIES = 128, 896
 
 
 class FeatureLayout:
@@ -253,7 +255,8 @@ class ObservationPacking:
     n_s.bit_length() bits — always one spare code at least — at bit `shift[s]` of word `word[s]`: fields follow each other in source
     order from bit 0 of word 0, and one that does not fit in what is left of a word starts the next (no field straddles a word; unused
     bits are 0).  The stored code is v where 0 <= v < n_s, and n_s — the out-of-range code — for anything else; unpacking returns
-    the code.  `words`: the uint32 words of a row.
+    the code.  `words`: the uint32 words of a row.  `word_first` [words + 1]: the values of word w are the contiguous run
+    word_first[w] .. word_first[w + 1] - 1 (the mirror of the table mcbs_obs_packing_create uploads for the packed wrapper step).
 
     valid_codes, bits, word, shift: int arrays [V].  Pure NumPy."""
 
@@ -271,12 +274,21 @@ class ObservationPacking:
         self.word = np.zeros_like(codes)
         self.shift = np.zeros_like(codes)
         w = s = 0
+        first = [0]
         for i, b in enumerate(self.bits):
             if s + b > 32:
                 w, s = w + 1, 0
+                first.append(i)
             self.word[i], self.shift[i] = w, s
             s += int(b)
         self.words = w + (1 if s else 0)
+        self.word_first = np.array(first[:self.words] + [self.values_per_row], dtype=np.int64)
+
+    @property
+    def fits_packed_step(self) -> bool:
+        """Whether the one-launch wrapper step can write these rows itself (mcbs_attacker_wrapper_step_packed keeps the fresh row and both
+        tables in LDS)."""
+        return self.words <= PACKED_STEP_MAX_WORDS and self.words + 1 + self.values_per_row <= PACKED_STEP_TABLE_ENTRIES
 
     def _fields(self, vals: np.ndarray) -> dict:
         n = vals.shape[0]

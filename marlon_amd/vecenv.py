@@ -192,6 +192,9 @@ class MarlonVecEnv:
     def __init__(self, venv: AttackerVecEnv, monitor: bool = True, numpy_outputs: bool = True):
         if not venv.auto_reset:
             raise ValueError("MarlonVecEnv needs an AttackerVecEnv with auto_reset=True (DummyVecEnv resets an env that ended inside step_wait)")
+        if getattr(venv, "observation_format", "fields") != "fields":
+            raise ValueError("MarlonVecEnv hands SB3 the observation dict of int32 fields: it needs an AttackerVecEnv with "
+                             "observation_format='fields', not 'packed' (a packed-mode wrapper keeps no int32 field)")
         self.venv = venv
         self.num_envs = venv.num_envs
         self.monitor = bool(monitor)

@@ -15,7 +15,10 @@ through `DummyVecEnv([...])` (marlon/baseline_models/ppo_multi/train_marl_multi.
   * finished envs are reset inside `step` like a VecEnv does; the observation that ended the episode is kept in
     `terminal_observation` for the envs flagged in `dones`;
   * a step's output tensors (rewards, flags, info) are valid until the step after next (two alternating sets; with `use_graph` the
-    one persistent set is overwritten by the next step); the observation tensors are the wrapper's own persistent buffers.
+    one persistent set is overwritten by the next step); the observation tensors are the wrapper's own persistent buffers;
+  * `observation_format="packed"` (small topologies, `materialize_masks=False`): the step itself writes each env's observation as the
+    bit-packed row of `features.ObservationPacking` (mcbs_attacker_wrapper_step_packed, one launch) and no int32 field exists:
+    `observation` is `{"packed": int32 [E, W_obs]}`, `features()` / `first_layer()` / `rollout_buffer()` work from those rows.
 
 All simulation work is in the HIP kernels; the few tensor expressions here are the wrapper's own bookkeeping
 (timestep counters, reward modifier).
@@ -83,8 +86,19 @@ class AttackerVecEnv(_MultiDiscreteHead):
                  winning_reward=5000.0, losing_reward=0.0, max_timesteps: int = 2000, invalid_action_reward_modifier=-1,
                  discrete: bool = False, auto_reset: bool = True, device: Optional[str] = None, seed: int = 0,
                  env_id_base: int = 0, rng_kind: int = 0, learned_defender: bool = False, materialize_masks: bool = True,
-                 use_graph: bool = False):
+                 use_graph: bool = False, observation_format: str = "fields"):
         from .engine import BatchEngine
+        if observation_format not in ("fields", "packed"):
+            raise ValueError(f"observation_format must be 'fields' or 'packed', got {observation_format!r}")
+        # observation_format="packed": the step itself writes the packed row (features.ObservationPacking; Chain-10 at 12/12: 72 B per env
+        # instead of 924 B) and the wrapper keeps no int32 observation at all: `observation` is {"packed": rows}, features() and
+        # first_layer() read the rows, rollout_buffer() stores them.  One launch per step (mcbs_attacker_wrapper_step_packed): small
+        # topologies, no materialised masks.
+        self.observation_format = observation_format
+        self._packed_mode = observation_format == "packed"
+        if self._packed_mode and materialize_masks:
+            raise ValueError("observation_format='packed' needs materialize_masks=False: the packed step writes no mask field "
+                             "(apply the mask with mask_logits / action_masks_packed)")
         self.topo: FlatTopology = initial_environment if isinstance(initial_environment, FlatTopology) else flatten(initial_environment)
         # the wrapper owns truncation and resets (its clock counts invalid actions too), so the engine's own are off
         self.spec: EnvSpec = spec_from_kwargs(n_envs, maximum_total_credentials, maximum_node_count,
@@ -116,8 +130,26 @@ class AttackerVecEnv(_MultiDiscreteHead):
             # rows of the flat mask padded to whole 128-byte lines: dense rows (Chain-10: 14 172 bytes) share cache lines with their
             # neighbours, which cost the Discrete observation a quarter of its write bandwidth; consumers see [:, :discrete_n] views
             self.engine.set_mask_discrete_stride((self.discrete_n + 127) // 128 * 128)
-        self._obs = self.engine.alloc_obs(FLAT_FIELDS if self.materialize_masks else FLAT_FIELDS[:-1])
-        self._terminal = {k: t.zeros_like(v) for k, v in self._obs.items()}
+        self._obs_packing = None                                   # observation_packed(): the packing handle, made on first use
+        if self._packed_mode:
+            why = None
+            if self.engine.wrapper_step_launches(False) != 1:
+                why = ("the wrapper step of this batch is not one launch (engine.wrapper_step_launches(False) != 1: small topologies of at "
+                       "most 16 nodes and cached credentials, not the random-events defender)")
+            elif not self._packing_handle().packing.fits_packed_step:
+                why = "the packed row is beyond the room the step keeps for it (features.PACKED_STEP_MAX_WORDS)"
+            if why:
+                self.engine.close()
+                raise ValueError(f"observation_format='packed': {why}")
+            # no int32 observation is kept: the live rows (persistent: an intercepted env's row must stand), the terminal rows, one fresh row
+            W = self._packing_handle().words
+            self._obs = self._terminal = None
+            self.packed_observation = t.zeros((n_envs, W), dtype=t.int32, device=dev)
+            self.terminal_packed_observation = t.zeros((n_envs, W), dtype=t.int32, device=dev)
+            self._packed_fresh = None
+        else:
+            self._obs = self.engine.alloc_obs(FLAT_FIELDS if self.materialize_masks else FLAT_FIELDS[:-1])
+            self._terminal = {k: t.zeros_like(v) for k, v in self._obs.items()}
         self._mask_split = (N * N * P * Cm, N * L, (N, N, P, Cm), (N, L), (N, N, R))
         self._rows = t.zeros((n_envs, 5), dtype=t.int32, device=dev)
         self._invalid = t.zeros(n_envs, dtype=t.uint8, device=dev)
@@ -153,7 +185,6 @@ class AttackerVecEnv(_MultiDiscreteHead):
         self._executed = t.zeros(n_envs, dtype=t.bool, device=dev)
         self._graph_out = self._terminated_out = None
         self._feature_handles, self._feature_bits = {}, None       # features(): layout handles per option set, the packed-mask scratch
-        self._obs_packing = None                                   # observation_packed(): the packing handle, made on first use
         self.reset()
 
     # -- observation plumbing --
@@ -177,12 +208,16 @@ class AttackerVecEnv(_MultiDiscreteHead):
     def observation(self) -> Dict[str, object]:
         # views of the wrapper's persistent observation tensors: built once (a dozen view operations cost more host time than the
         # device needs for the whole step)
+        if self._packed_mode:
+            return {"packed": self.packed_observation}
         if self._obs_views is None:
             self._obs_views = self._public(self._obs)
         return dict(self._obs_views)
 
     @property
     def terminal_observation(self) -> Dict[str, object]:
+        if self._packed_mode:
+            return {"packed": self.terminal_packed_observation}
         if self._terminal_views is None:
             self._terminal_views = self._public(self._terminal)
         return dict(self._terminal_views)
@@ -340,6 +375,9 @@ class AttackerVecEnv(_MultiDiscreteHead):
                     self._feature_bits = self.torch.zeros((self.num_envs, self.engine.packed_mask_words()[1]), dtype=self.torch.int32,
                                                           device=self.engine.device)
                 bits = self.action_masks_packed(out=self._feature_bits)
+        if self._packed_mode:                               # the same bits from the rows the step wrote (mcbs_encode_features_packed)
+            return self.engine.encode_features_packed(self._feature_handle(include_masks, reference_counts), self._packing_handle(),
+                                                      self.packed_observation, bits=bits, out=out, dtype=dtype, out_of_range=out_of_range)
         return self.engine.encode_features(self._feature_handle(include_masks, reference_counts), self._obs, bits=bits, out=out, dtype=dtype,
                                            out_of_range=out_of_range)
 
@@ -371,7 +409,16 @@ class AttackerVecEnv(_MultiDiscreteHead):
         """The observation this env last returned as bit fields: device int32 [n_envs, W_obs], one launch — 72 B instead of 924 B per
         Chain-10 row.  out=: write straight into a preallocated [n_envs, >= W_obs] buffer, e.g.
         `buf.observations["packed"][buf.pos]` of rollout_buffer(pack_observations=True).  A value outside its valid codes is stored as
-        its out-of-range code (and counted into out_of_range), which encodes to the same all-zero group."""
+        its out-of-range code (and counted into out_of_range), which encodes to the same all-zero group.
+        observation_format="packed": the step has written the rows already — without out= they are returned as they are
+        (`packed_observation`, the wrapper's persistent tensor), with out= they are copied; nothing is packed, out_of_range is not
+        counted (encode_features_packed counts at use)."""
+        if self._packed_mode:
+            if out is None:
+                return self.packed_observation
+            self.engine._packed_obs_rows(out, self._packing_handle(), "out", self.num_envs)
+            out[:, :self.packed_observation.shape[1]].copy_(self.packed_observation)
+            return out
         return self.engine.pack_observation(self._packing_handle(), self.observation_fields, out=out, out_of_range=out_of_range)
 
     def unpack_observation(self, packed, index=None):
@@ -406,7 +453,11 @@ class AttackerVecEnv(_MultiDiscreteHead):
         bfloat16 (F = feature_layout(reference_counts=...).width; the masks are not part of this layer's input).  weight_t=: the
         transposed copy `weight.t().contiguous()` a rollout loop makes once per update instead of once per call.  To serve SB3's
         policy_net[0] and value_net[0] with one call, concatenate their weights into one [2H, F] (and their biases into [2H])."""
-        return self._first_layer_call(reference_counts, weight, bias, dict(obs=self.observation_fields), out, dtype, out_of_range, weight_t, False)
+        if self._packed_mode:                               # the same bits from the rows the step wrote (mcbs_first_layer_packed)
+            source = dict(packing=self._packing_handle(), packed=self.packed_observation, index=None)
+        else:
+            source = dict(obs=self.observation_fields)
+        return self._first_layer_call(reference_counts, weight, bias, source, out, dtype, out_of_range, weight_t, False)
 
     def encode_first_layer(self, obs, weight, bias=None, out=None, dtype=None, reference_counts: bool = False, out_of_range=None, weight_t=None,
                            differentiable: bool = False):
@@ -433,10 +484,13 @@ class AttackerVecEnv(_MultiDiscreteHead):
     def observation_fields(self) -> Dict[str, object]:
         """The observation this env last returned as the five int32 fields the engine writes (`scalars` [E, 7] unsplit, the others in
         their own shapes): what encode_features() accepts and what rollout_buffer() stores; the wrapper's persistent tensors, not copies."""
+        if self._packed_mode:
+            raise RuntimeError("this AttackerVecEnv was created with observation_format='packed' and keeps no int32 field: "
+                               "unpack_observation(venv.packed_observation) rebuilds them from the packed rows")
         return {k: self._obs[k] for k in FLAT_FIELDS[:5]}
 
     def rollout_buffer(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, store_observations: bool = True,
-                       pack_observations: bool = False, mask_storage: str = "bits"):
+                       pack_observations: Optional[bool] = None, mask_storage: str = "bits"):
         """A `rollout.DeviceRolloutBuffer` of n_steps x n_envs transitions for this env: it stores the int32 observation fields
         encode_features() accepts (not the mask fields — with discrete=True the packed masks of action_masks_packed() are stored
         instead, `mask_bits`), actions of this wrapper's shape, and computes advantages and returns with one launch.  Its add() takes
@@ -447,9 +501,15 @@ class AttackerVecEnv(_MultiDiscreteHead):
         store_observations=False: no observation storage (a trainer that keeps feature rows of its own).
         pack_observations=True: the observation storage is ONE key, `observations["packed"]` int32 [T, E, W_obs], instead of the five
         fields: fill row `pos` with observation_packed(out=buf.observations["packed"][buf.pos]) and pass obs=None to add(); at update
-        time encode_features_packed(..., index=batch.index) reads the storage itself."""
+        time encode_features_packed(..., index=batch.index) reads the storage itself.  The default is False, and True for a wrapper
+        created with observation_format="packed", which has nothing else to store: False is refused there."""
         from .rollout import DeviceRolloutBuffer
-        obs = self.observation_fields if store_observations else None
+        if pack_observations is None:
+            pack_observations = self._packed_mode
+        if self._packed_mode and store_observations and not pack_observations:
+            raise ValueError("rollout_buffer(pack_observations=False): this AttackerVecEnv was created with observation_format='packed' "
+                             "and keeps no int32 field to store")
+        obs = self.observation_fields if store_observations and not pack_observations else None
         if store_observations and pack_observations:
             obs = {"packed": self.torch.zeros((self.num_envs, self._packing_handle().words), dtype=self.torch.int32, device=self.engine.device)}
         if mask_storage not in ("bits", "keys"):
@@ -462,9 +522,17 @@ class AttackerVecEnv(_MultiDiscreteHead):
     # -- VecEnv surface --
     def reset(self):
         self.engine.reset()
-        self.engine.observe(self._obs)
-        if self._reset_rows is None:
-            self._reset_rows = {k: v[0:1].clone() for k, v in self._obs.items()}
+        if self._packed_mode:
+            # two launches into a transient int32 scratch (the library needs the reset observation's digest anyway), dropped afterwards
+            scratch = self.engine.observe(self.engine.alloc_obs(FLAT_FIELDS[:5]))
+            self.engine.pack_observation(self._packing_handle(), scratch, out=self.packed_observation)
+            del scratch
+            if self._packed_fresh is None:
+                self._packed_fresh = self.packed_observation[0:1].clone()
+        else:
+            self.engine.observe(self._obs)
+            if self._reset_rows is None:
+                self._reset_rows = {k: v[0:1].clone() for k, v in self._obs.items()}
         self.timesteps.zero_()
         self.valid_action_count.zero_()
         self.invalid_action_count.zero_()
@@ -492,6 +560,18 @@ class AttackerVecEnv(_MultiDiscreteHead):
         want = self._action_shape
         if a.shape != want:
             raise ValueError(f"expected actions of shape {want}, got {tuple(a.shape)}")
+        if self._packed_mode:
+            if self._wb is None:
+                self._wb = self._wrapper_buffers(self._invalid, self.engine.terminated if self.use_graph else self._terminated_out, self._rewards,
+                                                 self._truncated, self._ret_out, self._len_out, self._executed)
+            key = (id(self._wb), self.invalid_action_reward_modifier, self.max_timesteps, self.auto_reset)
+            call = self._calls.get(key)
+            if call is None:
+                call = self._calls[key] = self.engine.wrapper_step_packed_call(
+                    self.discrete, self._rows, self._packing_handle(), self.packed_observation, self.terminal_packed_observation, self._packed_fresh,
+                    self._wb, self.invalid_action_reward_modifier, self.max_timesteps, self.auto_reset)
+            call(a.data_ptr())
+            return
         if self._keep is None:
             eng = self.engine
             self._keep = eng.row_copies([(self._obs[k], self._terminal[k]) for k in self._obs])
@@ -798,6 +878,8 @@ class TwoAgentVecEnv:
             return "the AttackerVecEnv must be created with materialize_masks=False (the joint turn writes no mask field)"
         if att.use_graph:
             return "the AttackerVecEnv must be created with use_graph=False"
+        if att.observation_format != "fields":
+            return "the AttackerVecEnv must be created with observation_format='fields' (the joint turn writes the int32 fields, not packed rows)"
         if att.engine.two_agent_step_launches() != 1:
             return "the library does not serve this batch with a joint turn (mcbs_two_agent_step_launches: small packed topologies only)"
         if dfd is not None and not (isinstance(dfd, DefenderVecEnv) and dfd.attacker is att and not dfd.use_graph):
