@@ -1082,6 +1082,68 @@ int  mcbs_two_agent_step(mcbs_batch*, const int64_t* multidiscrete, const int64_
                          const mcbs_defender_wrapper_buffers* dw, const mcbs_defender_wrapper_cfg* dcfg,
                          const mcbs_episode_buffers* ep, void* stream);
 
+/* ---- the two-agent TRAINING turn: marl_algorithm.collect_rollouts' loop body (marlon/baseline_models/multiagent/marl_algorithm.py:17-54) ----
+ * There each agent takes one perform_step per turn through its own DummyVecEnv, which resets its wrapper as soon as that wrapper reports
+ * done.  Both wrappers share one environment, so a reset on one side reaches the other through the reset_request protocol
+ * (attack_wrapper.py:342-343, 433-435; defend_wrapper.py:269-271, 446-447, 479-482; environment_event_source.py:30-38). */
+typedef struct mcbs_training_buffers {   /* 136 bytes: device arrays of n_envs rows unless stated otherwise */
+    uint8_t* attacker_reset_request;     /* in/out: AttackerEnvWrapper.reset_request — the defender reset the shared env on its own last turn */
+    double*  defender_return;            /* in/out: the defender's running episode return */
+    int64_t* attacker_valid_out;         /* out: the attacker's action counts including this step, taken before a reset clears them */
+    int64_t* attacker_invalid_out;       /* out   (what the wrapper keeps as last_valid_action_count / last_invalid_action_count at a reset) */
+    double*  defender_return_out;        /* out: return, length and action counts of the defender's episode including this step */
+    int32_t* defender_length_out;        /* out */
+    int64_t* defender_valid_out;         /* out */
+    int64_t* defender_invalid_out;       /* out */
+    uint8_t* defender_dones;             /* out: dw->terminated | dw->truncated of this turn */
+    int8_t*  terminal_infected_nodes;            /* out [n_envs, N]: the defender's observation after its action — the terminal observation */
+    int8_t*  terminal_incoming_firewall_status;  /* out [n_envs, N, 6]   of the envs whose defender_dones is set; other rows hold the same */
+    int8_t*  terminal_outgoing_firewall_status;  /* out [n_envs, N, 6]   observation and mean nothing */
+    int8_t*  terminal_services_status;           /* out [n_envs, S] */
+    const int8_t* fresh_infected_nodes;           /* in [N]: the defender's observation of a freshly reset env, ONE row each */
+    const int8_t* fresh_incoming_firewall_status; /* in [N, 6] */
+    const int8_t* fresh_outgoing_firewall_status; /* in [N, 6] */
+    const int8_t* fresh_services_status;          /* in [S]   (services never change: required, compared by nobody) */
+} mcbs_training_buffers;
+
+/* 1: mcbs_two_agent_train_step serves this batch, in one launch; 0: it does not (NULL: 0).  The scope is mcbs_two_agent_step's. */
+int32_t mcbs_two_agent_train_step_launches(const mcbs_batch*);
+/* One training turn of both auto-resetting wrappers for every env in ONE launch (marlon_amd/csrc/mcbs_two_agent.hip): what
+ * collect_rollouts' two perform_step calls do to one shared environment, both DummyVecEnv resets and the hand-shake between them
+ * included.  Scope and refusals are mcbs_two_agent_step's — MCBS_EINVAL with a message naming the reason, nothing launched, no state
+ * changed, no multi-launch fallback — plus: keep / fresh must pair every requested observation field with its terminal array and its
+ * reset row (as mcbs_attacker_wrapper_step's single launch needs them), every array of `tr` is required, the defender's terminal arrays
+ * lie on 16-byte boundaries, and no array this call writes may share a byte with another array it reads or writes.  MCBS_ESTATE as
+ * for mcbs_attacker_wrapper_step with auto_reset.
+ * Per env e, with q = tr->attacker_reset_request[e] on entry, the call equals this sequence bit for bit:
+ *  1. the attacker half is mcbs_attacker_wrapper_step(..., auto_reset = 1, keep, fresh) with ONE addition: w->truncated[e] |= q, so that
+ *     w->dones[e] is raised as well (attack_wrapper.py:341-346).  With done1 = w->dones[e], everything that call does for an env that
+ *     ends happens unchanged: terminal rows (for an intercepted action the live row as it stood — after a defender-side reset that is the
+ *     gone episode's row), re-initialisation, wrapper_clear, fresh rows, a fresh digest, episode + 1.  tr->attacker_valid_out /
+ *     attacker_invalid_out receive the counts including this step.  n = done1 && !q: the attacker's reset notifies the defender only
+ *     when the attacker had not itself been asked (attack_wrapper.py:433-435).
+ *  2. the defender half is mcbs_defender_wrapper_step for this env on the state as it now stands — freshly re-initialised when done1,
+ *     and then without the attacker component, since step 1 cleared has_cyber_reward (the reference's cyber_rewards = []).
+ *     If n: dw->truncated[e] = 1 and dw->reward[e] = -(double)w->rewards[e], which overrides the shaped value, -0.0 included;
+ *     dw->terminated[e] stays as shaped (defend_wrapper.py:267-273).  done2 = dw->terminated[e] | dw->truncated[e] -> tr->defender_dones[e].
+ *     tr->defender_return[e] += dw->reward[e]; the four defender_*_out arrays receive return, dw->timesteps and both counts, all
+ *     including this step.  The four terminal_* arrays receive the observation after the defender's action.
+ *  3. if done2: the env is re-initialised AGAIN (episode + 1 once more: the reference's second cyber_env.reset(), which discards what the
+ *     defender just did); dw->timesteps, both counts, has_breached_sla and tr->defender_return go to zero, dw->prev_availability becomes
+ *     the availability of a re-initialised env, and the live defender observation becomes the fresh rows; otherwise it is the terminal
+ *     one.  tr->attacker_reset_request[e] = done2 && !n (defend_wrapper.py:446-447).  The attacker's observation rows, digest and
+ *     counters are NOT touched: it keeps predicting from the observation of the episode that is gone, and so does its action mask
+ *     (action_masking.py:90-94 builds it from the cached observation; the digest carries that observation's discovery order for it).
+ *     Only the range check of its next action sees the new env.
+ * The defender's actions are never written. */
+int  mcbs_two_agent_train_step(mcbs_batch*, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded,
+                               const mcbs_info_buffers* info, const mcbs_obs_buffers* obs, const mcbs_wrapper_buffers* w,
+                               float invalid_action_reward_modifier, int32_t attacker_max_timesteps,
+                               const mcbs_row_copies* keep, const mcbs_row_copies* fresh,
+                               const int64_t* defender_actions, const mcbs_defender_obs* defender_obs,
+                               const mcbs_defender_wrapper_buffers* dw, const mcbs_defender_wrapper_cfg* dcfg,
+                               const mcbs_training_buffers* tr, void* stream);
+
 /* Parity / debugging: canonical per-env state records (layout: mcbs_state_record below),
  * host buffers, synchronous.  The record does not carry what only MCBS_DEFENDER_RANDOM_EVENTS mutates (vulnerability keys,
  * service flags, firewall rule lists): mcbs_set_state puts those back to the topology's initial ones for the envs it writes. */

@@ -83,6 +83,22 @@ def episode_buffers(**arrays) -> "EpisodeBuffers":
     return EpisodeBuffers(*[arrays[n] for n in EPISODE_FIELDS])
 
 
+# mcbs_training_buffers (include/mcbs.h): seventeen device pointers, these members in this order — an array of pointers like
+# EpisodeBuffers, held to the header by tests/test_training_host.py.  Filled through training_buffers()
+TRAINING_FIELDS = ("attacker_reset_request", "defender_return", "attacker_valid_out", "attacker_invalid_out", "defender_return_out",
+                   "defender_length_out", "defender_valid_out", "defender_invalid_out", "defender_dones", "terminal_infected_nodes",
+                   "terminal_incoming_firewall_status", "terminal_outgoing_firewall_status", "terminal_services_status",
+                   "fresh_infected_nodes", "fresh_incoming_firewall_status", "fresh_outgoing_firewall_status", "fresh_services_status")
+TrainingBuffers = C.c_void_p * len(TRAINING_FIELDS)
+
+
+def training_buffers(**arrays) -> "TrainingBuffers":
+    """An mcbs_training_buffers block from device pointers given by member name (every member of TRAINING_FIELDS)."""
+    if set(arrays) != set(TRAINING_FIELDS):
+        raise ValueError(f"mcbs_training_buffers has exactly the members {TRAINING_FIELDS}")
+    return TrainingBuffers(*[arrays[n] for n in TRAINING_FIELDS])
+
+
 class BatchVariantInfo(C.Structure):
     """mcbs_batch_variant_info (include/mcbs.h): the compiled variant a batch dispatches to"""
     _fields_ = [(n, C.c_uint32) for n in ("packed", "words_per_set", "wide", "coop", "lds_topo", "defender_kind", "fused_wrapper",
@@ -218,6 +234,10 @@ PROTOTYPES = {
     # batch, multidiscrete, discrete, decoded, info, obs, w, invalid_action_reward_modifier, attacker_max_timesteps, defender_actions,
     # defender_obs, dw, dcfg, ep (an EpisodeBuffers block or NULL), stream
     "mcbs_two_agent_step": (_int, [_H, _P, _P, _P, _P, _P, _P, _f32, _i32, _P, _P, _P, _P, _P, _S]),
+    "mcbs_two_agent_train_step_launches": (_i32, [_H]),
+    # batch, multidiscrete, discrete, decoded, info, obs, w, invalid_action_reward_modifier, attacker_max_timesteps, keep, fresh,
+    # defender_actions, defender_obs, dw, dcfg, tr (a TrainingBuffers block), stream
+    "mcbs_two_agent_train_step": (_int, [_H, _P, _P, _P, _P, _P, _P, _f32, _i32, _P, _P, _P, _P, _P, _P, _P, _S]),
     "mcbs_state_record_bytes": (_size, [_H]),
     "mcbs_get_state": (_int, [_H, _P, _size]),                                                # batch, host_buf, nbytes
     "mcbs_set_state": (_int, [_H, _P, _size]),                                                # batch, host_buf, nbytes

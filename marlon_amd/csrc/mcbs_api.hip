@@ -116,6 +116,8 @@ struct mcbs_batch {
     // given a state (mcbs_set_state); 1 = every env's digest is the one its last observation wrote; 2 = some envs were reset by mask
     // since (their digests are stale until mcbs_observe_masked has re-observed them)
     int digest_state = 0;
+    bool digest_lists = false;           // some digests may carry the discovery order of their own observation (ObsDigest::pad: the two-agent training
+                                         // turn wrote them): the kernels that rebuild the mask from the digest run their OWN instantiations
     const double* tape = nullptr;
     uint32_t tape_dps = 0;
     unsigned long long* stamps = nullptr;   // diagnostic builds: device buffer [waves][8]
@@ -842,6 +844,7 @@ static int launch_obs_inner(mcbs_batch* b, const mcbs_obs_buffers* o, hipStream_
 static int launch_obs(mcbs_batch* b, const mcbs_obs_buffers* o, hipStream_t st, bool masks_only = false, const uint8_t* env_mask = nullptr) {
     const int rc = launch_obs_inner(b, o, st, masks_only, env_mask);
     if (rc) return rc;
+    if (!env_mask) b->digest_lists = false;                   // every digest rewritten, none with a list of its own
     if (!env_mask) b->digest_state = 1;                       // every observation kernel (masks-only ones too) leaves the env's digest
     else if (b->digest_state == 2) b->digest_state = 1;       // the envs reset by mask have been re-observed (the caller's protocol)
     return capture_reset_digest(b, st, !masks_only && !env_mask);
@@ -1346,8 +1349,10 @@ extern "C" int mcbs_mask_logits(mcbs_batch* b, void* logits, int32_t dtype, size
     rows_dispatch<4u, 4u>(dtype == MCBS_LOGITS_F32 ? 4u : 2u, logits, row_stride, [&](auto es, auto gw, auto vec) {
         using LT = LogitsElem<decltype(es)::value>;
         constexpr uint32_t GW = decltype(gw)::value;
-        hipLaunchKernelGGL((mask_logits_kernel<LT, GW, decltype(vec)::value>), grid_for(GW), dim3(256), 0, st, b->S, b->T, b->C_dev, b->digest,
-                           static_cast<LT*>(logits), row_stride, logits_fill<decltype(es)::value>(fill), G);
+        pick<0, 1>((int)b->digest_lists, [&](auto own) {
+            hipLaunchKernelGGL((mask_logits_kernel<LT, GW, decltype(vec)::value, decltype(own)::value != 0>), grid_for(GW), dim3(256), 0, st, b->S, b->T,
+                               b->C_dev, b->digest, static_cast<LT*>(logits), row_stride, logits_fill<decltype(es)::value>(fill), G);
+        });
     });
     return launch_ok("mask logits");
 }
@@ -1361,7 +1366,10 @@ extern "C" int mcbs_pack_action_mask(mcbs_batch* b, uint32_t* bits, size_t row_w
     LogitsGeom G;
     if ((rc = discrete_geom(b, G))) return rc;
     if ((rc = rows_hold(G.A, "row_words", row_words, nullptr, 0))) return rc;
-    hipLaunchKernelGGL(pack_mask_kernel, dim3((b->S.E + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, b->S, b->T, b->C_dev, b->digest, bits, row_words, G);
+    pick<0, 1>((int)b->digest_lists, [&](auto own) {
+        hipLaunchKernelGGL((pack_mask_kernel<decltype(own)::value != 0>), dim3((b->S.E + 3u) / 4u), dim3(256), 0, (hipStream_t)stream, b->S, b->T, b->C_dev,
+                           b->digest, bits, row_words, G);
+    });
     return launch_ok("pack action mask");
 }
 
@@ -1420,8 +1428,10 @@ extern "C" int mcbs_store_mask_keys(mcbs_batch* b, uint32_t* keys, size_t row_wo
     if (row_words < K.Wk) return fail(MCBS_EINVAL, "row_words %zu is shorter than the %u words of a mask key", row_words, K.Wk);
     const uint64_t total = (uint64_t)b->S.E * K.Wk;                  // one thread per key word
     if (total >= (1ull << 31)) return fail(MCBS_ELIMIT, "too many envs for one launch of mcbs_store_mask_keys");
-    hipLaunchKernelGGL(store_mask_keys_kernel, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream, b->S, b->digest, keys,
-                       row_words, K, (uint32_t)total);
+    pick<0, 1>((int)b->digest_lists, [&](auto own) {
+        hipLaunchKernelGGL((store_mask_keys_kernel<decltype(own)::value != 0>), dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, (hipStream_t)stream,
+                           b->S, b->digest, keys, row_words, K, (uint32_t)total);
+    });
     return launch_ok("store mask keys");
 }
 
@@ -1459,9 +1469,9 @@ static void categorical_launch(const mcbs_batch* b, bool live, const LogitsGeom&
                                const CatIO& io, hipStream_t st) {
     const dim3 grid = rows_grid(io.n_rows, 65536u), block(256);
     pick<2, 4>(dtype == MCBS_LOGITS_BF16 && io.logits ? 2 : 4, [&](auto es) {       // element size: bf16 patterns, else fp32 (also without logits)
-        pick<1, 0>((int)live, [&](auto lv) {
-            hipLaunchKernelGGL((masked_categorical_kernel<LogitsElem<(uint32_t)decltype(es)::value>, decltype(lv)::value != 0>), grid, block, 0, st,
-                               b->S, b->T, b->C_dev, b->digest, G, bits, bits_row_words, io);
+        pick<2, 1, 0>(live ? (b->digest_lists ? 2 : 1) : 0, [&](auto lv) {          // 2: live, digests with a discovery order of their own
+            hipLaunchKernelGGL((masked_categorical_kernel<LogitsElem<(uint32_t)decltype(es)::value>, decltype(lv)::value != 0, decltype(lv)::value == 2>),
+                               grid, block, 0, st, b->S, b->T, b->C_dev, b->digest, G, bits, bits_row_words, io);
         });
     });
 }
@@ -1514,9 +1524,9 @@ static void linear_categorical_launch(const mcbs_batch* b, bool live, const Logi
                                       const LinIO& lin, const CatIO& io, hipStream_t st) {
     const dim3 grid = rows_grid(io.n_rows, 65536u), block(256);
     pick<2, 4>(dtype == MCBS_LOGITS_BF16 ? 2 : 4, [&](auto es) {
-        pick<1, 0>((int)live, [&](auto lv) {
-            hipLaunchKernelGGL((masked_linear_categorical_kernel<LogitsElem<(uint32_t)decltype(es)::value>, decltype(lv)::value != 0>), grid, block, 0, st,
-                               b->S, b->T, b->C_dev, b->digest, G, bits, bits_row_words, lin, io);
+        pick<2, 1, 0>(live ? (b->digest_lists ? 2 : 1) : 0, [&](auto lv) {
+            hipLaunchKernelGGL((masked_linear_categorical_kernel<LogitsElem<(uint32_t)decltype(es)::value>, decltype(lv)::value != 0, decltype(lv)::value == 2>),
+                               grid, block, 0, st, b->S, b->T, b->C_dev, b->digest, G, bits, bits_row_words, lin, io);
         });
     });
 }
@@ -2532,6 +2542,113 @@ extern "C" int mcbs_two_agent_step(mcbs_batch* b, const int64_t* multidiscrete, 
     hipLaunchKernelGGL(two_agent_kernel, dim3((b->S.E + 63u) / 64u), dim3(FUSED_THREADS), 0, (hipStream_t)stream, b->S, b->T, b->C_dev, io, A, D);
     rc = launch_ok("two-agent turn");
     if (rc) return rc;
+    b->digest_state = 1;       // every env's digest was written (or, for an intercepted action, stands)
+    return MCBS_OK;
+}
+
+// ---- the training turn: both auto-resets and the reset_request hand-shake in the same launch (two_agent_train_kernel)
+extern "C" int32_t mcbs_two_agent_train_step_launches(const mcbs_batch* b) {
+    return (b && !two_agent_batch_reason(b)) ? 1 : 0;
+}
+
+extern "C" int mcbs_two_agent_train_step(mcbs_batch* b, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded, const mcbs_info_buffers* info,
+                                         const mcbs_obs_buffers* obs, const mcbs_wrapper_buffers* w, float modifier, int32_t attacker_max_timesteps,
+                                         const mcbs_row_copies* keep, const mcbs_row_copies* fresh, const int64_t* defender_actions,
+                                         const mcbs_defender_obs* defender_obs, const mcbs_defender_wrapper_buffers* dw,
+                                         const mcbs_defender_wrapper_cfg* dcfg, const mcbs_training_buffers* tr, void* stream) {
+    const char* who = "two-agent training turn";
+    if (!b || !w || !decoded || !obs || !keep || !fresh || !defender_actions || !defender_obs || !dw || !dcfg || !tr) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    // every check before the launch: a refused call launches nothing and changes no state
+    if (const char* why = two_agent_batch_reason(b)) return fail(MCBS_EINVAL, "%s: %s", who, why);
+    WrapperFinishArgs unused;
+    int rc = finish_args(b, w, modifier, attacker_max_timesteps, 1, keep, fresh, &unused);
+    if (rc) return rc;
+    if ((rc = draws_ok(b))) return rc;
+    if (!multidiscrete == !discrete) return fail(MCBS_EINVAL, "need exactly one action encoding");
+    if (!arrays_set(dw, 0)) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
+    if (!arrays_set(tr, 0)) return fail(MCBS_EINVAL, "mcbs_training_buffers: every array is required");
+    if (!defender_obs->infected_nodes || !defender_obs->incoming_firewall_status || !defender_obs->outgoing_firewall_status || !defender_obs->services_status)
+        return fail(MCBS_EINVAL, "%s: every field of the defender's observation is required", who);
+    TrainArgs D{};
+    D.actions = defender_actions; D.dw = *dw; D.dcfg = *dcfg;
+    D.obs = fused_defender_obs(b, defender_obs);
+    const mcbs_defender_obs terminal{tr->terminal_infected_nodes, tr->terminal_incoming_firewall_status, tr->terminal_outgoing_firewall_status,
+                                     tr->terminal_services_status};
+    D.term = fused_defender_obs(b, &terminal);
+    if (!D.obs.fused || !D.term.fused)
+        return fail(MCBS_EINVAL, "%s: the defender's live and terminal observation arrays must lie on 16-byte boundaries", who);
+    D.fresh_infected = tr->fresh_infected_nodes; D.fresh_fw_in = tr->fresh_incoming_firewall_status; D.fresh_fw_out = tr->fresh_outgoing_firewall_status;
+    D.request = tr->attacker_reset_request; D.dreturn = tr->defender_return;
+    D.a_valid_out = tr->attacker_valid_out; D.a_invalid_out = tr->attacker_invalid_out;
+    D.d_return_out = tr->defender_return_out; D.d_length_out = tr->defender_length_out;
+    D.d_valid_out = tr->defender_valid_out; D.d_invalid_out = tr->defender_invalid_out; D.d_dones = tr->defender_dones;
+    FusedArgs A;
+    if (!fused_wrapper_args(b, multidiscrete, discrete, decoded, obs, w, modifier, attacker_max_timesteps, 1, keep, fresh, &A))
+        return fail(MCBS_EINVAL, "%s: the attacker's request is outside the one-launch wrapper step (a mask field, an observation array that is "
+                                 "not on a 16-byte boundary, or a field without its terminal array in `keep` and its reset row in `fresh`)", who);
+    // no array this launch writes may share a byte with another array it reads or writes
+    {
+        const uint64_t E = b->S.E, N = b->S.N, Sv = b->C.n_services;
+        struct Extent { const char* name; uintptr_t lo, hi; bool out; };
+        std::vector<Extent> ext;
+        auto add = [&](const char* name, const void* q, uint64_t bytes, bool out) {
+            const uintptr_t lo = reinterpret_cast<uintptr_t>(q);
+            if (q && bytes) ext.push_back(Extent{name, lo, lo + (uintptr_t)bytes, out});
+        };
+        add("decoded", decoded, E * 20u, true); add("multidiscrete", multidiscrete, E * 80u, false); add("discrete", discrete, E * 8u, false);
+        add("defender_actions", defender_actions, E * 96u, false);
+        static const char* const fields[FUSED_FIELDS] = {"scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties",
+                                                         "nodes_privilegelevel"};
+        for (uint32_t f = 0; f < FUSED_FIELDS; ++f) {
+            add(fields[f], A.obs[f], E * 4u * A.dwords[f], true);
+            add("a terminal observation array (keep)", A.obs[f] ? A.term[f] : nullptr, E * 4u * A.dwords[f], true);
+            add("a reset row (fresh)", A.obs[f] ? A.fresh[f] : nullptr, 4ull * A.dwords[f], false);
+        }
+        add("w->invalid", w->invalid, E, true); add("w->reward", w->reward, E * 4u, true); add("w->terminated", w->terminated, E, true);
+        add("w->timesteps", w->timesteps, E * 4u, true); add("w->valid_action_count", w->valid_action_count, E * 8u, true);
+        add("w->invalid_action_count", w->invalid_action_count, E * 8u, true); add("w->episode_returns", w->episode_returns, E * 8u, true);
+        add("w->last_cyber_reward", w->last_cyber_reward, E * 4u, true); add("w->has_cyber_reward", w->has_cyber_reward, E, true);
+        add("w->rewards", w->rewards, E * 4u, true); add("w->truncated", w->truncated, E, true); add("w->dones", w->dones, E, true);
+        add("w->episode_return_out", w->episode_return_out, E * 8u, true); add("w->episode_length_out", w->episode_length_out, E * 4u, true);
+        add("w->executed", w->executed, E, true);
+        add("info->network_availability", info ? info->network_availability : nullptr, E * 8u, true);
+        add("info->step_count", info ? info->step_count : nullptr, E * 4u, true); add("info->truncated", info ? info->truncated : nullptr, E, true);
+        add("info->out_of_bound", info ? info->out_of_bound : nullptr, E, true); add("info->raw_reward", info ? info->raw_reward : nullptr, E * 4u, true);
+        add("defender_obs->infected_nodes", defender_obs->infected_nodes, E * N, true);
+        add("defender_obs->incoming_firewall_status", defender_obs->incoming_firewall_status, E * N * 6u, true);
+        add("defender_obs->outgoing_firewall_status", defender_obs->outgoing_firewall_status, E * N * 6u, true);
+        add("defender_obs->services_status", defender_obs->services_status, E * Sv, true);
+        add("dw->valid", dw->valid, E, true); add("dw->availability", dw->availability, E * 8u, true); add("dw->evicted", dw->evicted, E, true);
+        // (dw->attacker_has_cyber_reward / attacker_last_cyber_reward ARE w->has_cyber_reward / last_cyber_reward: read where the attacker half wrote)
+        add("dw->timesteps", dw->timesteps, E * 4u, true); add("dw->valid_action_count", dw->valid_action_count, E * 8u, true);
+        add("dw->invalid_action_count", dw->invalid_action_count, E * 8u, true); add("dw->has_breached_sla", dw->has_breached_sla, E, true);
+        add("dw->prev_availability", dw->prev_availability, E * 8u, true); add("dw->reward", dw->reward, E * 8u, true);
+        add("dw->terminated", dw->terminated, E, true); add("dw->truncated", dw->truncated, E, true); add("dw->breached", dw->breached, E, true);
+        add("dw->won", dw->won, E, true);
+        add("tr->attacker_reset_request", tr->attacker_reset_request, E, true); add("tr->defender_return", tr->defender_return, E * 8u, true);
+        add("tr->attacker_valid_out", tr->attacker_valid_out, E * 8u, true); add("tr->attacker_invalid_out", tr->attacker_invalid_out, E * 8u, true);
+        add("tr->defender_return_out", tr->defender_return_out, E * 8u, true); add("tr->defender_length_out", tr->defender_length_out, E * 4u, true);
+        add("tr->defender_valid_out", tr->defender_valid_out, E * 8u, true); add("tr->defender_invalid_out", tr->defender_invalid_out, E * 8u, true);
+        add("tr->defender_dones", tr->defender_dones, E, true);
+        add("tr->terminal_infected_nodes", tr->terminal_infected_nodes, E * N, true);
+        add("tr->terminal_incoming_firewall_status", tr->terminal_incoming_firewall_status, E * N * 6u, true);
+        add("tr->terminal_outgoing_firewall_status", tr->terminal_outgoing_firewall_status, E * N * 6u, true);
+        add("tr->terminal_services_status", tr->terminal_services_status, E * Sv, true);
+        add("tr->fresh_infected_nodes", tr->fresh_infected_nodes, N, false);
+        add("tr->fresh_incoming_firewall_status", tr->fresh_incoming_firewall_status, N * 6u, false);
+        add("tr->fresh_outgoing_firewall_status", tr->fresh_outgoing_firewall_status, N * 6u, false);
+        for (size_t i = 0; i < ext.size(); ++i)
+            for (size_t k = i + 1u; k < ext.size(); ++k)
+                if ((ext[i].out || ext[k].out) && ext[i].lo < ext[k].hi && ext[k].lo < ext[i].hi)
+                    return fail(MCBS_EINVAL, "%s: %s overlaps %s", who, ext[i].name, ext[k].name);
+    }
+    const StepIO io = make_io(b, decoded, const_cast<float*>(w->reward), const_cast<uint8_t*>(w->terminated), info);
+    b->all_fresh = false;
+    hipLaunchKernelGGL(two_agent_train_kernel, dim3((b->S.E + 63u) / 64u), dim3(FUSED_THREADS), 0, (hipStream_t)stream, b->S, b->T, b->C_dev, io, A, D);
+    rc = launch_ok("two-agent training turn");
+    if (rc) return rc;
+    b->digest_lists = true;    // the digests this launch wrote carry their observation's discovery order
     b->digest_state = 1;       // every env's digest was written (or, for an intercepted action, stands)
     return MCBS_OK;
 }

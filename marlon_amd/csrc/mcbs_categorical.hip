@@ -74,9 +74,9 @@ __device__ __forceinline__ V cat_wave_scan(V v, uint32_t lane) {            // i
 // SRC, the row's logit source: the row pointer, or an object with cat_logit(src, a) and a conversion to bool (false: all-zero logits)
 // such as LinSrc (mcbs_linear_categorical.hip), which computes the logit from the policy's latent row.
 template <typename SRC> inline constexpr bool cat_src_fills_word_cache = false;      // true: cw[0 .. CAT_CACHE) is valid BEFORE sweep 1
-template <typename LT, bool LIVE, typename SRC = const LT*>
+template <typename LT, bool LIVE, typename SRC = const LT*, typename MASK = DigestMask>
 struct CatRow {
-    const DigestMask* lv;      // LIVE: the env's digest as a mask (uniform per wavefront: scalar loads);  else
+    const MASK* lv;      // LIVE: the env's digest as a mask (uniform per wavefront: scalar loads);  else
     const uint32_t* brow;      // the row's stored packed words
     SRC row;                   // the row's logits, or NULL (all-zero logits)
     uint32_t W, tail, lane;    // tail: word W-1: bits from A on are ignored, not trusted to be zero
@@ -283,7 +283,7 @@ __device__ __forceinline__ void cat_row_finish(const ROW& R, const CatIO& io, ui
     }
 }
 
-template <typename LT, bool LIVE>
+template <typename LT, bool LIVE, bool OWN = false>
 __global__ __launch_bounds__(256) void masked_categorical_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, const ObsDigest* __restrict__ digest,
                                                                  LogitsGeom G, const uint32_t* __restrict__ bits, size_t bits_row_words, CatIO io) {
     __shared__ uint32_t c_word[4][CAT_CACHE];
@@ -299,8 +299,9 @@ __global__ __launch_bounds__(256) void masked_categorical_kernel(DevState S, Top
         const LT* row = L ? L + i * io.row_stride : nullptr;
         // the mask's source: the env's digest (uniform per wavefront: scalar loads) or the row's stored words
         const ObsDigest d = LIVE ? digest[i] : ObsDigest{};
-        const DigestMask lv = LIVE ? DigestMask::make(S, T, Cp, d, G, (uint32_t)i, 32u) : DigestMask{G, d, LiveDiscovery{S, nullptr, nullptr, 0u}, 0u, 0u, 0ull};
-        const CatRow<LT, LIVE> R{&lv, LIVE ? nullptr : bits + i * bits_row_words, row, W, tail, lane, cw, cs};
+        using Mask = DigestMaskOf<DiscoveryOf<OWN>>;
+        const Mask lv = LIVE ? Mask::make(S, T, Cp, d, G, (uint32_t)i, 32u) : Mask{G, d, DiscoveryOf<OWN>::of(S, nullptr, nullptr, 0u, d), 0u, 0u, 0ull};
+        const CatRow<LT, LIVE, const LT*, Mask> R{&lv, LIVE ? nullptr : bits + i * bits_row_words, row, W, tail, lane, cw, cs};
         cat_row_finish(R, io, i);
     }
 }

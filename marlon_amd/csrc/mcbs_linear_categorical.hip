@@ -132,7 +132,7 @@ __device__ __forceinline__ void lin_prepare(const ROW& R, const LinSrc<WT>& s, c
     lin_wave_sync();
 }
 
-template <typename WT, bool LIVE>
+template <typename WT, bool LIVE, bool OWN = false>
 __global__ __launch_bounds__(256) void masked_linear_categorical_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp,
                                                                         const ObsDigest* __restrict__ digest, LogitsGeom G,
                                                                         const uint32_t* __restrict__ bits, size_t bits_row_words, LinIO lin, CatIO io) {
@@ -150,8 +150,9 @@ __global__ __launch_bounds__(256) void masked_linear_categorical_kernel(DevState
                          c_lat[wv], c_word[wv], c_before[wv], c_stash[wv]};
     for (uint64_t i = (uint64_t)blockIdx.x * 4u + wv; i < io.n_rows; i += (uint64_t)gridDim.x * 4u) {     // wave-uniform
         const ObsDigest d = LIVE ? digest[i] : ObsDigest{};
-        const DigestMask lv = LIVE ? DigestMask::make(S, T, Cp, d, G, (uint32_t)i, 32u) : DigestMask{G, d, LiveDiscovery{S, nullptr, nullptr, 0u}, 0u, 0u, 0ull};
-        const CatRow<float, LIVE, LinSrc<WT>> R{&lv, LIVE ? nullptr : bits + i * bits_row_words, src, W, tail, lane, c_word[wv], c_sum[wv]};
+        using Mask = DigestMaskOf<DiscoveryOf<OWN>>;
+        const Mask lv = LIVE ? Mask::make(S, T, Cp, d, G, (uint32_t)i, 32u) : Mask{G, d, DiscoveryOf<OWN>::of(S, nullptr, nullptr, 0u, d), 0u, 0u, 0ull};
+        const CatRow<float, LIVE, LinSrc<WT>, Mask> R{&lv, LIVE ? nullptr : bits + i * bits_row_words, src, W, tail, lane, c_word[wv], c_sum[wv]};
         lin_prepare(R, src, latent + i * lin.latent_stride, c_lat[wv], c_before[wv], c_stash[wv]);
         cat_row_finish(R, io, i);
     }

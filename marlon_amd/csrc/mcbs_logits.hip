@@ -11,6 +11,8 @@
 // The logits are never READ: masked-out actions are overwritten, allowed ones left alone.  Bound: HBM write of the masked-out logits
 // (nearly all of them).
 #pragma once
+#include <type_traits>
+
 #include "mcbs_device.h"
 #include "mcbs_obs.hip"
 #include "mcbs_rowstore.h"
@@ -31,7 +33,25 @@ struct LiveDiscovery {
     const uint8_t* body;       // the env's body
     uint32_t e;
     __device__ __forceinline__ uint32_t local_mask(uint32_t i) const { return NS[S.disc_at(body, e, i)].local_mask; }
+    static __device__ __forceinline__ LiveDiscovery of(const DevState& S, const mcbs_node_static* NS, const uint8_t* body, uint32_t e, const ObsDigest&) {
+        return LiveDiscovery{S, NS, body, e};
+    }
 };
+// The same for a batch whose digests may carry the discovery order of their OWN observation (ObsDigest::pad != 0, the list in pad2[0..1]:
+// the two-agent training turn, which can re-initialise an env under an attacker observation that stands): such a digest's list is read
+// instead of the live one.  The kernels below are instantiated with it as well (OWN), and mcbs_api.hip launches those instantiations
+// only for a batch the training turn has stepped: every other batch runs the instructions it ran before.
+struct OwnListDiscovery {
+    LiveDiscovery live;
+    uint32_t own_list, list_lo, list_hi;
+    __device__ __forceinline__ uint32_t local_mask(uint32_t i) const {
+        return live.NS[own_list ? DevState::list_nibble(list_lo, list_hi, i & 15u) : live.S.disc_at(live.body, live.e, i)].local_mask;
+    }
+    static __device__ __forceinline__ OwnListDiscovery of(const DevState& S, const mcbs_node_static* NS, const uint8_t* body, uint32_t e, const ObsDigest& d) {
+        return OwnListDiscovery{LiveDiscovery{S, NS, body, e}, d.pad, d.pad2[0], d.pad2[1]};
+    }
+};
+template <bool OWN> using DiscoveryOf = std::conditional_t<OWN, OwnListDiscovery, LiveDiscovery>;
 
 // One env's digest seen as its Discrete mask: the predicates every kernel that rebuilds the mask of the last observation uses
 // (mask_logits_kernel, pack_mask_kernel, the live form of masked_categorical_kernel, expand_mask_keys_kernel).  Built once per
@@ -57,7 +77,7 @@ struct DigestMaskOf {
     // ... through the live list of env e
     static __device__ __forceinline__ DigestMaskOf make(const DevState& S, const Topo& T, const StepCfg* __restrict__ Cp, const ObsDigest& d,
                                                         const LogitsGeom& G, uint32_t e, uint32_t span) {
-        return from(G, d, LiveDiscovery{S, reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node), S.body + (size_t)e * S.body_stride, e},
+        return from(G, d, Disc::of(S, reinterpret_cast<const mcbs_node_static*>(T.base + Cp->off_node), S.body + (size_t)e * S.body_stride, e, d),
                     span);
     }
     __device__ __forceinline__ uint32_t remote0() const { return G.M + G.ML; }
@@ -142,7 +162,7 @@ using DigestMask = DigestMaskOf<>;
 // same time for half the bytes: bound by instruction issue and the two barriers; a persistent grid of such workgroups 950; this
 // kernel 745 / 414.  Reference points on the same buffer: a plain fill 536 / 270, this store pattern with no mask work at all 700 / 367,
 // torch.where with a materialised mask 1 440 / 830.  Non-temporal stores: no change.  tools/bench_logits.py.)
-template <typename LT, uint32_t GW, bool VEC>
+template <typename LT, uint32_t GW, bool VEC, bool OWN = false>
 __global__ __launch_bounds__(256) void mask_logits_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, const ObsDigest* __restrict__ digest,
                                                           LT* __restrict__ logits, size_t row_stride, LT fill, LogitsGeom G) {
     using RG = RowGroups<LT, GW, VEC>;
@@ -151,7 +171,7 @@ __global__ __launch_bounds__(256) void mask_logits_kernel(DevState S, Topo T, co
     const uint32_t e = blockIdx.y * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform
     if (e >= S.E) return;
     const ObsDigest d = digest[e];                       // uniform per wavefront: scalar loads
-    const DigestMask M = DigestMask::make(S, T, Cp, d, G, e, GW);
+    const auto M = DigestMaskOf<DiscoveryOf<OWN>>::make(S, T, Cp, d, G, e, GW);
     const uint32_t remote0 = M.remote0();
     LT* row = logits + (size_t)e * row_stride;
     // bit j: the (source, target) row that action rel + j of a block of `rowlen`-long rows belongs to is on (rowlen >= GW: two rows at most)
@@ -191,7 +211,7 @@ __global__ __launch_bounds__(256) void mask_logits_kernel(DevState S, Topo T, co
                 // the whole group lies in the connect block: at most two (source, target) rows, each on or off as a whole; within an
                 // on row the credential index just counts on modulo C (RL is a multiple of C)
                 const uint32_t rows = rows_mask(a0, G.dRL, G.RL, r0);
-                if (rows) m = M.cred_bits<GW>(r0 - fdiv(r0, G.dC) * G.C) & rows;
+                if (rows) m = M.template cred_bits<GW>(r0 - fdiv(r0, G.dC) * G.C) & rows;
             } else if (a0 >= remote0 && a0 + GW <= G.A && G.R >= GW) {
                 m = rows_mask(a0 - remote0, G.dR, G.R, r0);     // the whole group lies in the remote block: remote[s][t][r] = on(s, t)
             } else {

@@ -26,6 +26,7 @@ struct MaskKeyGeom {       // layout of a key row, set up on the host
 // owned-source word, four entries of the discovery list — side by side and unconditionally, then stores once: no load waits for
 // another's result, and none is issued behind a store.  List entries are fetched at indices clamped to the list and masked by the count
 // afterwards.  Words from Wk on are never written.
+template <bool OWN = false>
 __global__ __launch_bounds__(256) void store_mask_keys_kernel(DevState S, const ObsDigest* __restrict__ digest, uint32_t* __restrict__ keys,
                                                               size_t row_words, MaskKeyGeom K, uint32_t total) {
     const uint32_t x = blockIdx.x * 256u + threadIdx.x;
@@ -40,6 +41,11 @@ __global__ __launch_bounds__(256) void store_mask_keys_kernel(DevState S, const 
     uint32_t node[4];
 #pragma unroll
     for (uint32_t j = 0; j < 4u; ++j) node[j] = S.disc_at(body, e, i0 + j < S.N ? i0 + j : S.N - 1u);
+    if constexpr (OWN) {                                                             // a digest that carries its own discovery order (counts.w; mcbs_logits.hip)
+        const uint2 own_list = *reinterpret_cast<const uint2*>(digest[e].pad2);
+#pragma unroll
+        for (uint32_t j = 0; j < 4u; ++j) node[j] = counts.w ? DevState::list_nibble(own_list.x, own_list.y, (i0 + j) & 15u) : node[j];
+    }
     // ---------------- the word ----------------
     const uint32_t n_disc = counts.z ? 0u : (counts.x < K.Nk ? counts.x : K.Nk);    // the effective count: 0 for a blank observation
     auto below = [](uint32_t first, uint32_t n) -> uint32_t {                       // bit j: first + j < n

@@ -34,8 +34,9 @@ __device__ __forceinline__ void stream_store16(uint4* p, const uint4 v) {
 
 struct ObsDigest {          // 64 bytes per env
     uint64_t own_ext[4];    // bit i: the node at external index i has the agent installed
-    uint32_t n_disc, n_creds, blank, pad;
-    uint32_t pad2[4];
+    uint32_t n_disc, n_creds, blank, pad;   // pad != 0: pad2[0..1] hold the discovery order of the digest's own observation, a nibble per index
+    uint32_t pad2[4];                       // (packed batches; written by the two-agent training turn, whose env can be re-initialised under
+                                            // an observation that stands: mcbs_two_agent.hip).  Every other writer stores zeros
 };
 static_assert(sizeof(ObsDigest) == 64, "digest");
 

@@ -19,13 +19,14 @@ namespace mcbs {
 // to the row stride are never written.  A pure write stream; far below the bandwidth its 1 772 bytes per env would allow (DESIGN.md
 // section 7 has the measurements and the SQ counters).  (Kernel trace, 65 536 Chain-10 envs, one run, us per launch: lane k building
 // dwords 4k .. 4k+3 for one 16-byte store 387, this form 131 in the same run.)
+template <bool OWN = false>
 __global__ __launch_bounds__(256) void pack_mask_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, const ObsDigest* __restrict__ digest,
                                                         uint32_t* __restrict__ bits, size_t row_words, LogitsGeom G) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t e = blockIdx.x * 4u + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);      // wave-uniform
     if (e >= S.E) return;
     const ObsDigest d = digest[e];                       // uniform per wavefront: scalar loads
-    const DigestMask M = DigestMask::make(S, T, Cp, d, G, e, 32u);
+    const auto M = DigestMaskOf<DiscoveryOf<OWN>>::make(S, T, Cp, d, G, e, 32u);
     const uint32_t W = (G.A + 31u) / 32u;
     uint32_t* row = bits + (size_t)e * row_words;
     for (uint32_t w = lane; w < W; w += 64u) row[w] = M.word(w);

@@ -622,6 +622,29 @@ class BatchEngine:
                 _check(lib, rc, "mcbs_two_agent_step")
         return call
 
+    def two_agent_train_step_launches(self) -> int:
+        """1 when mcbs_two_agent_train_step serves this batch (the training turn: both wrappers' steps, both auto-resets and the
+        reset_request hand-shake in one launch), else 0."""
+        return int(self.lib.mcbs_two_agent_train_step_launches(self._h))
+
+    def two_agent_train_step_call(self, discrete: bool, decoded, obs_struct, bufs, modifier: float, max_timesteps: int, keep, fresh,
+                                  defender_obs_struct, defender_bufs, defender_cfg, training_block):
+        """callable(attacker_actions_ptr, defender_actions_ptr): mcbs_two_agent_train_step with every argument block bound once, like
+        two_agent_step_call.  keep / fresh: row_copies() blocks that pair every observation field with its terminal array and its reset
+        row; training_block: an _abi.TrainingBuffers whose arrays the caller keeps alive."""
+        fn, eng, lib, stream = self.lib.mcbs_two_agent_train_step, self, self.lib, self._stream
+        refs = (C.byref(self._info_struct), C.byref(obs_struct), C.byref(bufs), C.byref(keep), C.byref(fresh), C.byref(defender_obs_struct),
+                C.byref(defender_bufs), C.byref(defender_cfg), C.byref(training_block))
+        rows, mod, mt = decoded.data_ptr(), float(modifier), int(max_timesteps)
+        alive = (decoded, obs_struct, bufs, keep, fresh, defender_obs_struct, defender_bufs, defender_cfg, training_block, self._info_struct)
+
+        def call(p: int, q: int, _alive=alive) -> None:
+            rc = fn(eng._h, None if discrete else p, p if discrete else None, rows, refs[0], refs[1], refs[2], mod, mt, refs[3], refs[4], q, refs[5],
+                    refs[6], refs[7], refs[8], stream())
+            if rc:
+                _check(lib, rc, "mcbs_two_agent_train_step")
+        return call
+
     def wrapper_step_launches(self, with_masks: bool) -> int:
         """Kernel launches per mcbs_attacker_wrapper_step of this batch (1: the whole wrapper step is one launch; 3 otherwise)."""
         return int(self.lib.mcbs_attacker_wrapper_step_launches(self._h, int(bool(with_masks))))

@@ -157,6 +157,56 @@ def run_episode_joint(att: AttackerVecEnv, dfd: DefenderVecEnv, attacker_policy:
                 lengths=ep.lengths, attacker_done=ep.attacker_done.bool(), defender_done=ep.defender_done.bool(), steps=steps)
 
 
+def collect_rollouts(train, attacker_policy: Callable, defender_policy: Callable, attacker_buffer, defender_buffer, n_steps: int):
+    """`marl_algorithm.collect_rollouts` (marlon/baseline_models/multiagent/marl_algorithm.py:17-54) for a whole batch: `n_steps` training
+    turns of `train` (a `wrappers.TwoAgentTrainVecEnv`), each agent's transitions stored in its own `rollout.DeviceRolloutBuffer`
+    (`att.rollout_buffer(n_steps)`, `dfd.rollout_buffer(n_steps)`).  Per turn: the two policy calls and ONE library call; no host
+    synchronisation of this function's own inside the loop.
+
+    A policy is `policy(env) -> actions` or `-> (actions, values, log_probs)` (device tensors; values / log_probs float [E]; a policy
+    that returns actions alone leaves those two rows of its buffer as they are).  Both are called BEFORE the turn: the defender predicts
+    from the observation its own previous step returned (marl_algorithm.py:222).  Each buffer row holds the observation the action was
+    chosen from — for a Discrete attacker also its packed mask or mask key, the STALE one after a defender-side reset, as the
+    reference's policy saw it —, the action, the turn's reward, and `episode_starts` taken from the previous turn's dones (ones after
+    `train.reset()`, carried from call to call in `train.last_dones`).  Both buffers are emptied first, as SB3's collect_rollouts does.
+    -> (attacker dones, defender dones) of the last turn, uint8 [E] each, for `buffer.compute_returns_and_advantage(last_values, dones)`."""
+    att, dfd = train.att, train.dfd
+    if attacker_buffer.n_steps != n_steps or defender_buffer.n_steps != n_steps:
+        raise ValueError(f"both buffers must hold exactly n_steps = {n_steps} steps")
+
+    def split(out):
+        return out if isinstance(out, tuple) else (out, None, None)
+
+    def store_inputs(buf, fields, env):
+        p = buf.pos
+        if buf.observations is not None:
+            if set(buf.observations) == {"packed"}:
+                env.observation_packed(out=buf.observations["packed"][p])
+            else:
+                for k, dst in buf.observations.items():
+                    dst[p].copy_(fields[k].reshape(dst[p].shape))
+        if buf.mask_bits is not None:
+            env.action_masks_packed(out=buf.mask_bits[p])
+        elif buf.mask_keys is not None:
+            env.action_mask_keys(out=buf.mask_keys[p])
+
+    attacker_buffer.reset()
+    defender_buffer.reset()
+    starts_a, starts_d = train.last_dones
+    for _ in range(n_steps):
+        a1, v1, lp1 = split(attacker_policy(att))
+        a2, v2, lp2 = split(defender_policy(dfd))
+        # what each action was chosen from, before the turn overwrites the wrappers' persistent tensors
+        store_inputs(attacker_buffer, att.observation_fields, att)
+        store_inputs(defender_buffer, dfd.observation, dfd)
+        (_, r1, term1, trunc1, _), (_, r2, term2, trunc2, _) = train.step(a1, a2)
+        attacker_buffer.add(None, att.torch.as_tensor(a1, device=att.engine.device), r1, starts_a, v1, lp1)
+        defender_buffer.add(None, att.torch.as_tensor(a2, device=att.engine.device), r2, starts_d, v2, lp2)
+        starts_a, starts_d = term1 | trunc1, term2 | trunc2
+    train.last_dones = (starts_a, starts_d)
+    return train.last_dones
+
+
 def uniform_attacker_policy(seed: int = 0) -> Callable[[AttackerVecEnv], object]:
     """`action_space.sample()` of AttackerEnvWrapper's MultiDiscrete space — what RandomMarlonAgent does when the wrapper exposes no
     action masks (random_marlon_agent.py:72-96), i.e. in `marlon.simulate.simulate`'s default universe.  Mostly out-of-range actions."""

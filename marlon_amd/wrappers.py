@@ -930,3 +930,144 @@ class TwoAgentVecEnv:
         dfd._out = do
         return ((att.observation, o["rewards"], o["terminated"], o["truncated"], dict(info)),
                 (dfd._obs, do["reward"], do["terminated"], do["truncated"], dict(dinfo)))
+
+
+class TwoAgentTrainVecEnv:
+    """One TRAINING turn of both agents in ONE launch (mcbs_two_agent_train_step, marlon_amd/csrc/mcbs_two_agent.hip): what
+    `marl_algorithm.collect_rollouts` does per turn — `attacker.perform_step`, then `defender.perform_step`, each through its own
+    DummyVecEnv, which resets its wrapper as soon as it reports done — for a whole batch.  The two wrappers share one environment, so a
+    reset on one side reaches the other (reset_request: attack_wrapper.py:433-435, defend_wrapper.py:269-271, 446-447; include/mcbs.h
+    states the rules):
+
+      * the attacker ends (goal, its own timeout, or a request): its env is re-initialised, it gets a fresh observation, and — unless it
+        had been asked — the defender's step of the same turn returns `-1 * the attacker's last reward`, truncated, and is reset too;
+      * the defender ends on its own (SLA breach, eviction, its timeout): the env is re-initialised, the defender gets a fresh
+        observation, and `attacker_reset_request` is raised: the attacker's NEXT step is truncated, whatever it does.  Until then the
+        attacker keeps the observation — and the action mask — of the episode that is gone, as in the reference.
+
+    `att` must be `AttackerVecEnv(..., learned_defender=True, auto_reset=True, materialize_masks=False)` on a small topology and `dfd`
+    the `DefenderVecEnv` on it; anything else is a ValueError naming the reason (`supported(att)` asks first).  The turn writes into the
+    two wrappers' own persistent state, so `att.mask_logits`, `att.features()`, `dfd.features()`, `sample_masked*` ... work as after
+    separate steps.  But separate `att.step` / `dfd.step` calls must NOT be mixed with this class's `step`: they know nothing of the
+    request byte, of the defender's running return, or of the defender-side reset."""
+
+    def __init__(self, att: AttackerVecEnv, dfd: "DefenderVecEnv"):
+        why = self._refusal(att, dfd)
+        if why:
+            raise ValueError(f"TwoAgentTrainVecEnv: {why}")
+        self.att, self.dfd = att, dfd
+        self.engine, self.torch, self.num_envs = att.engine, att.torch, att.num_envs
+        t, E, dev = self.torch, self.num_envs, self.engine.device
+        self._request = t.zeros(E, dtype=t.uint8, device=dev)
+        self.defender_returns = t.zeros(E, dtype=t.float64, device=dev)
+        self._terminal = {k: t.zeros_like(v) for k, v in dfd._obs.items()}
+        self._fresh_rows = None
+        self._ring, self._slot = None, 0
+        self._calls = {}
+        self.reset()
+
+    @staticmethod
+    def _refusal(att, dfd=None) -> Optional[str]:
+        from ._abi import DEFENDER_EXTERNAL
+        if not isinstance(att, AttackerVecEnv):
+            return "the attacker side must be an AttackerVecEnv"
+        if att.engine._cfg.defender_kind != DEFENDER_EXTERNAL:
+            return "the AttackerVecEnv must be created with learned_defender=True"
+        if not att.auto_reset:
+            return "the AttackerVecEnv must be created with auto_reset=True (both agents' DummyVecEnv resets are part of the training turn)"
+        if att.materialize_masks:
+            return "the AttackerVecEnv must be created with materialize_masks=False (the training turn writes no mask field)"
+        if att.use_graph:
+            return "the AttackerVecEnv must be created with use_graph=False"
+        if att.observation_format != "fields":
+            return "the AttackerVecEnv must be created with observation_format='fields' (the training turn writes the int32 fields, not packed rows)"
+        if att.engine.two_agent_train_step_launches() != 1:
+            return "the library does not serve this batch with a training turn (mcbs_two_agent_train_step_launches: small packed topologies only)"
+        if dfd is not None and not (isinstance(dfd, DefenderVecEnv) and dfd.attacker is att and not dfd.use_graph):
+            return "the defender side must be the DefenderVecEnv created on this AttackerVecEnv (use_graph=False)"
+        return None
+
+    @staticmethod
+    def supported(att) -> bool:
+        """Whether TwoAgentTrainVecEnv(att, DefenderVecEnv(att)) would be accepted."""
+        return TwoAgentTrainVecEnv._refusal(att) is None
+
+    @property
+    def attacker_reset_request(self):
+        """bool [E]: the defender reset the shared env on its own last turn, so the attacker's next step is truncated
+        (AttackerEnvWrapper.reset_request).  A view of the byte the kernel reads and writes."""
+        return self._request.view(self.torch.bool)
+
+    @property
+    def terminal_observation(self) -> Dict[str, object]:
+        """The defender's observation after its action of the last turn: its episode's last observation for the envs whose defender
+        `dones` was set (SB3's infos[e]["terminal_observation"]); rows of other envs mean nothing.  The attacker's is
+        `att.terminal_observation`."""
+        return self._terminal
+
+    def reset(self):
+        """Both sides' `env.reset()` of marl_algorithm.setup_learn, and no request pending.  -> (attacker observation, defender observation)"""
+        obs = self.att.reset()
+        dobs = self.dfd.reset()
+        self._request.zero_()
+        self.defender_returns.zero_()
+        t = self.torch
+        # (attacker, defender) dones of the last turn: the next turn's episode_starts (simulate.collect_rollouts carries them here)
+        self.last_dones = (t.ones(self.num_envs, dtype=t.uint8, device=self.engine.device), t.ones(self.num_envs, dtype=t.uint8, device=self.engine.device))
+        if self._fresh_rows is None:
+            self._fresh_rows = {k: v[0:1].clone() for k, v in dobs.items()}     # every env resets to the same state
+        return obs, dobs
+
+    def _output_ring(self) -> None:
+        from ._abi import training_buffers
+        t, E, dev = self.torch, self.num_envs, self.engine.device
+        fixed = dict(attacker_reset_request=self._request.data_ptr(), defender_return=self.defender_returns.data_ptr())
+        fixed.update({"terminal_" + k: v.data_ptr() for k, v in self._terminal.items()})       # (the four keys of mcbs_defender_obs)
+        fixed.update({"fresh_" + k: v.data_ptr() for k, v in self._fresh_rows.items()})
+        self._ring = []
+        for _ in range(2):
+            o = dict(attacker_valid_out=t.empty(E, dtype=t.int64, device=dev), attacker_invalid_out=t.empty(E, dtype=t.int64, device=dev),
+                     defender_return_out=t.empty(E, dtype=t.float64, device=dev), defender_length_out=t.empty(E, dtype=t.int32, device=dev),
+                     defender_valid_out=t.empty(E, dtype=t.int64, device=dev), defender_invalid_out=t.empty(E, dtype=t.int64, device=dev),
+                     defender_dones=t.empty(E, dtype=t.uint8, device=dev))
+            self._ring.append((o, training_buffers(**fixed, **{k: v.data_ptr() for k, v in o.items()})))
+
+    _actions = TwoAgentVecEnv._actions
+
+    def step(self, attacker_actions, defender_actions):
+        """-> ((obs, rewards, terminated, truncated, info), (dobs, dreward, dterminated, dtruncated, dinfo)): what the two agents'
+        DummyVecEnvs return for this turn.  An env whose flags are set has ALREADY been reset: its observation is the fresh one, its
+        episode's last observation is in `att.terminal_observation` / `terminal_observation`, and the info dicts carry the episode that
+        ended — `episode_return`, `episode_length`, `episode_valid_actions`, `episode_invalid_actions` (what the reference logs at episode
+        end and keeps as last_valid_action_count / last_invalid_action_count), meaningful where `dones` is set.  The attacker's
+        `truncated` includes a reset request; the defender's reward on a request step is `-1 * the attacker's reward of this turn`.
+        Outputs are valid until the turn after next.  The defender's action of a turn is chosen before the attacker's step of that turn."""
+        att, dfd = self.att, self.dfd
+        a = self._actions(attacker_actions, att._action_shape, "attacker")
+        d = self._actions(defender_actions, (self.num_envs, 12), "defender")
+        if att._keep is None:
+            eng = self.engine
+            att._keep = eng.row_copies([(att._obs[k], att._terminal[k]) for k in att._obs])
+            att._fresh = eng.row_copies([(att._reset_rows[k], att._obs[k]) for k in att._obs], one_row_src=True)
+            att._obs_block = eng.obs_struct(att._obs)
+        o, wb, info = att._next_output_set()
+        if dfd._ring is None:
+            dfd._output_ring()
+        dfd._slot ^= 1
+        do, dwb, dinfo, _ = dfd._ring[dfd._slot]
+        if self._ring is None:
+            self._output_ring()
+        self._slot ^= 1
+        to, tb = self._ring[self._slot]
+        key = (id(wb), id(dwb), id(tb), att.invalid_action_reward_modifier, att.max_timesteps)
+        call = self._calls.get(key)
+        if call is None:
+            call = self._calls[key] = self.engine.two_agent_train_step_call(att.discrete, att._rows, att._obs_block, wb, att.invalid_action_reward_modifier,
+                                                                            att.max_timesteps, att._keep, att._fresh, dfd._obs_block, dwb, dfd._wc, tb)
+        call(a.data_ptr(), d.data_ptr())
+        dfd._out = do
+        ainfo = dict(info, dones=att._dones, episode_valid_actions=to["attacker_valid_out"], episode_invalid_actions=to["attacker_invalid_out"])
+        dinfo = dict(dinfo, dones=to["defender_dones"], episode_return=to["defender_return_out"], episode_length=to["defender_length_out"],
+                     episode_valid_actions=to["defender_valid_out"], episode_invalid_actions=to["defender_invalid_out"])
+        return ((att.observation, o["rewards"], o["terminated"], o["truncated"], ainfo),
+                (dfd._obs, do["reward"], do["terminated"], do["truncated"], dinfo))
