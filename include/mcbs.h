@@ -1043,6 +1043,48 @@ int  mcbs_defender_wrapper_post(mcbs_batch*, const mcbs_defender_wrapper_buffers
 int  mcbs_defender_wrapper_step(mcbs_batch*, const int64_t* actions, const mcbs_defender_obs* obs, const mcbs_defender_wrapper_buffers* w,
                                 const mcbs_defender_wrapper_cfg* cfg, void* stream);
 
+/* ---- packed defender observations: one bit per MultiBinary element, stored per step, encoded to features later ----
+ * THE PACKED DEFENDER ROW (marlon_amd/features.py DefenderObservationPacking is its host mirror).  With N = n_nodes and S = n_services a
+ * row has F = 6N + N + 6N + S columns, the four fields of mcbs_defender_obs in SORTED KEY order — the order of DefenderVecEnv.features():
+ *     incoming_firewall_status  column 6n + k            infected_nodes   column 6N + n
+ *     outgoing_firewall_status  column 7N + 6n + k       services_status  column 13N + s
+ * and is stored as W_def = ceil(F / 32) uint32_t words: column c is bit c & 31 of word c >> 5 (the packed action masks' convention).
+ * Bits at or past F in the last word are zero, always.  ToyCtf: N = 10, S = 13, F = 143: 5 words = 20 B instead of 143 B.
+ * A dense element packs to 1 when it is not zero (the observation only ever holds 0 and 1) and unpacks to 0 / 1.
+ * Row strides (row_words, in words; out_row_stride, in elements) may exceed the row: every word below W_def / column below F of a
+ * written row is stored whole (the buffers need not be cleared), nothing beyond is touched.  index: optional device int64 [n_rows] into
+ * the n_source_rows source rows (without it n_rows <= n_source_rows: MCBS_EINVAL otherwise) — the gather happens inside the launch; an
+ * index outside [0, n_source_rows) reads nothing and that row comes out all zero.
+ * mcbs_defender_obs_words: W_def; 0 for NULL or a batch not created with MCBS_DEFENDER_EXTERNAL.
+ * mcbs_defender_observe_packed: mcbs_defender_observe for the packed form: the rows of the live state of all envs, one launch.
+ * mcbs_pack_defender_observation: n_rows dense int8 rows (all four arrays required) to packed rows, one launch.
+ * mcbs_unpack_defender_observation: packed rows to int8 fields, one launch; a NULL member of `out` is skipped.
+ * mcbs_encode_defender_features: the float rows DefenderVecEnv.features() builds, 0.0 / 1.0 as float32 / bfloat16 / float16
+ *   (MCBS_FEATURES_*), F columns, from EITHER `dense` (all four arrays, n_source_rows rows; packed NULL) OR `packed` (dense NULL), one
+ *   launch.  bad_rows (optional device int32_t) is INCREASED by the number of rows whose index lay outside the storage.  Rows on 16-byte
+ *   boundaries are written with 16-byte stores, others with narrower ones.
+ * mcbs_defender_wrapper_step_packed: mcbs_defender_wrapper_step with the packed row as its observation output.  On batches whose
+ *   variant has fused_defender_obs (N <= 32, S <= 256) and with packed_out on a 16-byte boundary the turn launch writes the rows itself
+ *   from its LDS stage: ONE launch; otherwise the turn runs without an observation and the kernel of mcbs_defender_observe_packed
+ *   follows: two.  Everything else the call writes (every array of `w`) is bit for bit what mcbs_defender_wrapper_step writes.
+ *   mcbs_defender_wrapper_step_packed_launches: 1 or 2 by the batch (an aligned packed_out assumed); 0 for NULL or a batch without a
+ *   learned defender.
+ * MCBS_EINVAL with a message, nothing launched: a NULL required pointer, a batch not created with MCBS_DEFENDER_EXTERNAL, row_words <
+ * W_def, out_row_stride < F, an unknown dtype, both sources or neither, no index and n_rows > n_source_rows.  n_rows == 0 succeeds
+ * without a launch.  All calls are stream-ordered, allocate nothing and never synchronise with the host. */
+uint32_t mcbs_defender_obs_words(const mcbs_batch*);
+int  mcbs_defender_observe_packed(mcbs_batch*, uint32_t* out, size_t row_words, void* stream);
+int  mcbs_pack_defender_observation(const mcbs_batch*, const mcbs_defender_obs* dense, uint64_t n_rows, uint32_t* out, size_t row_words,
+                                    void* stream);
+int  mcbs_unpack_defender_observation(const mcbs_batch*, const uint32_t* packed, size_t row_words, const int64_t* index,
+                                      uint64_t n_source_rows, uint64_t n_rows, const mcbs_defender_obs* out, void* stream);
+int  mcbs_encode_defender_features(const mcbs_batch*, const mcbs_defender_obs* dense, const uint32_t* packed, size_t row_words,
+                                   const int64_t* index, uint64_t n_source_rows, uint64_t n_rows, void* out, size_t out_row_stride,
+                                   int32_t dtype, int32_t* bad_rows, void* stream);
+int  mcbs_defender_wrapper_step_packed(mcbs_batch*, const int64_t* actions, uint32_t* packed_out, size_t row_words,
+                                       const mcbs_defender_wrapper_buffers* w, const mcbs_defender_wrapper_cfg* cfg, void* stream);
+int32_t mcbs_defender_wrapper_step_packed_launches(const mcbs_batch*);
+
 /* ---- the two-agent turn: marl_algorithm.run_episode's loop body (marlon/baseline_models/multiagent/marl_algorithm.py:197-250) ---- */
 typedef struct mcbs_episode_buffers {   /* 48 bytes: run_episode's per-env bookkeeping (marlon_amd/simulate.py), device arrays of n_envs */
     uint8_t* alive;            /* in/out: the env's episode is still running */

@@ -230,6 +230,16 @@ PROTOTYPES = {
     "mcbs_attacker_wrapper_step_packed": (_int, [_H, _P, _P, _P, _P, _H, _P, _P, _P, _size, _P, _f32, _i32, _i32, _S]),
     "mcbs_defender_wrapper_post": (_int, [_H, _P, _P, _S]),                                   # batch, w, cfg, stream
     "mcbs_defender_wrapper_step": (_int, [_H, _P, _P, _P, _P, _S]),                           # batch, actions, obs, w, cfg, stream
+    "mcbs_defender_obs_words": (_u32, [_H]),
+    "mcbs_defender_observe_packed": (_int, [_H, _P, _size, _S]),                              # batch, out, row_words, stream
+    "mcbs_pack_defender_observation": (_int, [_H, _DOBS, _u64, _P, _size, _S]),               # batch, dense, n_rows, out, row_words, stream
+    # batch, packed, row_words, index, n_source_rows, n_rows, out, stream
+    "mcbs_unpack_defender_observation": (_int, [_H, _P, _size, _P, _u64, _u64, _DOBS, _S]),
+    # batch, dense, packed, row_words, index, n_source_rows, n_rows, out, out_row_stride, dtype, bad_rows, stream
+    "mcbs_encode_defender_features": (_int, [_H, _DOBS, _P, _size, _P, _u64, _u64, _P, _size, _i32, _P, _S]),
+    # batch, actions, packed_out, row_words, w, cfg, stream
+    "mcbs_defender_wrapper_step_packed": (_int, [_H, _P, _P, _size, _P, _P, _S]),
+    "mcbs_defender_wrapper_step_packed_launches": (_i32, [_H]),
     "mcbs_two_agent_step_launches": (_i32, [_H]),
     # batch, multidiscrete, discrete, decoded, info, obs, w, invalid_action_reward_modifier, attacker_max_timesteps, defender_actions,
     # defender_obs, dw, dcfg, ep (an EpisodeBuffers block or NULL), stream

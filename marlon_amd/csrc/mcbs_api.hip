@@ -33,6 +33,7 @@
 #include "mcbs_wrapper_fused.hip"
 #include "mcbs_two_agent.hip"
 #include "mcbs_mask_keys.hip"
+#include "mcbs_defender_obs_packing.hip"
 
 using namespace mcbs;
 
@@ -96,6 +97,7 @@ struct mcbs_batch {
     StepCfg C{};
     StepCfg* C_dev = nullptr;       // device copy read by the step kernel through the scalar cache
     uint32_t* ere_lists_dev = nullptr;
+    DefPackGeom def_pack{};         // MCBS_DEFENDER_EXTERNAL: the packed defender observation's geometry; .svc = the services' bits of a row (device)
     // developer switches, read ONCE at batch creation (getenv on every launch costs more than the launch itself)
     bool no_fused_masks = false, slow_masks = false, no_row_masks = false;
     bool no_quad_obs = false;       // MCBS_NO_QUAD_OBS=1: a wavefront per env for small topologies' observations with mask fields (rounds 1-2)
@@ -611,6 +613,25 @@ extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg
     e = hipMalloc(&b->C_dev, sizeof(StepCfg));
     if (e == hipSuccess) e = hipMemcpy(b->C_dev, &b->C, sizeof(StepCfg), hipMemcpyHostToDevice);
     if (e != hipSuccess) { (void)hipFree(b->arena); delete b; return fail(MCBS_EHIP, "config upload failed: %s", hipGetErrorString(e)); }
+    if (external) {
+        // the packed defender observation (mcbs_defender_obs_packing.hip): services never change state, so their bits of a row are built here, once
+        DefPackGeom& P = b->def_pack;
+        P.N = N; P.S = h->n_services; P.F = 13u * N + P.S; P.W = (P.F + 31u) / 32u;
+        P.dW = fast_div_host(P.W ? P.W : 1u);
+        std::vector<uint32_t> image(P.W ? P.W : 1u, 0u);
+        const mcbs_service* sv = reinterpret_cast<const mcbs_service*>(topo->host.data() + h->off_service);
+        for (uint32_t k = 0; k < P.S; ++k)
+            if (sv[k].running) image[(13u * N + k) >> 5] |= 1u << ((13u * N + k) & 31u);
+        uint32_t* dev = nullptr;
+        e = hipMalloc(&dev, image.size() * sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemcpy(dev, image.data(), image.size() * sizeof(uint32_t), hipMemcpyHostToDevice);
+        if (e != hipSuccess) {
+            if (dev) (void)hipFree(dev);
+            (void)hipFree(b->C_dev); (void)hipFree(b->arena); delete b;
+            return fail(MCBS_EHIP, "services image upload failed: %s", hipGetErrorString(e));
+        }
+        P.svc = dev;
+    }
     launch_step_zero(b, nullptr, 0, nullptr);
     e = hipDeviceSynchronize();
     if (e != hipSuccess) { (void)hipFree(b->arena); delete b; return fail(MCBS_EHIP, "initial reset failed: %s", hipGetErrorString(e)); }
@@ -629,6 +650,7 @@ extern "C" void mcbs_batch_destroy(mcbs_batch* b) {
     if (b->arena) (void)hipFree(b->arena);
     if (b->C_dev) (void)hipFree(b->C_dev);
     if (b->ere_lists_dev) (void)hipFree(b->ere_lists_dev);
+    if (b->def_pack.svc) (void)hipFree(const_cast<uint32_t*>(b->def_pack.svc));
     delete b;
 }
 
@@ -2498,6 +2520,138 @@ extern "C" int mcbs_defender_observe(mcbs_batch* b, const mcbs_defender_obs* obs
     MCBS_ON_DEVICE(b);
     if (const int rc = learned_defender_ok(b)) return rc;
     return launch_defender_obs(b, obs, (hipStream_t)stream);
+}
+
+// ------------------------------------------------------------------ packed defender observations (mcbs_defender_obs_packing.hip)
+// the checks every call on packed defender rows shares: a learned defender's batch, rows of at least W_def words
+static int defender_packing_ok(const mcbs_batch* b, const char* who, size_t row_words) {
+    if (b->cfg.defender_kind != MCBS_DEFENDER_EXTERNAL) return fail(MCBS_EINVAL, "%s: batch was not created with MCBS_DEFENDER_EXTERNAL", who);
+    if (row_words < b->def_pack.W) return fail(MCBS_EINVAL, "%s: row_words %zu is shorter than the %u words of a packed defender row", who, row_words, b->def_pack.W);
+    return MCBS_OK;
+}
+static bool defender_obs_complete(const mcbs_defender_obs* o) {
+    return o->infected_nodes && o->incoming_firewall_status && o->outgoing_firewall_status && o->services_status;
+}
+
+extern "C" uint32_t mcbs_defender_obs_words(const mcbs_batch* b) {
+    return (b && b->cfg.defender_kind == MCBS_DEFENDER_EXTERNAL) ? b->def_pack.W : 0u;
+}
+
+// defender_obs_packed_kernel takes a thread per (env, word) of one launch: checked before anything is launched
+static int defender_live_rows_ok(const mcbs_batch* b) {
+    const uint64_t total = (uint64_t)b->S.E * b->def_pack.W;
+    if (total >= (1ull << 32)) return fail(MCBS_ELIMIT, "packed defender observation: %llu words in one launch", (unsigned long long)total);
+    return MCBS_OK;
+}
+static int launch_defender_obs_packed(mcbs_batch* b, uint32_t* out, size_t row_words, hipStream_t st) {
+    const uint64_t total = (uint64_t)b->S.E * b->def_pack.W;
+    hipLaunchKernelGGL(defender_obs_packed_kernel, dim3((uint32_t)((total + 255u) / 256u)), dim3(256), 0, st, b->S, b->T, b->def_pack, out, row_words);
+    return launch_ok("packed defender observation");
+}
+
+extern "C" int mcbs_defender_observe_packed(mcbs_batch* b, uint32_t* out, size_t row_words, void* stream) {
+    if (!b || !out) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    if (const int rc = defender_packing_ok(b, "mcbs_defender_observe_packed", row_words)) return rc;
+    if (const int rc = defender_live_rows_ok(b)) return rc;
+    return launch_defender_obs_packed(b, out, row_words, (hipStream_t)stream);
+}
+
+// 32 rows per workgroup and pass (pack / unpack kernels), at most `cap` workgroups: the kernels loop over the rows beyond a grid's worth
+static dim3 defender_rows_grid(uint64_t n_rows, uint64_t rows_per_block, uint32_t cap) {
+    const uint64_t blocks = (n_rows + rows_per_block - 1u) / rows_per_block;
+    return dim3(blocks < cap ? (uint32_t)blocks : cap);
+}
+
+extern "C" int mcbs_pack_defender_observation(const mcbs_batch* b, const mcbs_defender_obs* dense, uint64_t n_rows, uint32_t* out, size_t row_words,
+                                              void* stream) {
+    if (!b || !dense || !out) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    if (const int rc = defender_packing_ok(b, "mcbs_pack_defender_observation", row_words)) return rc;
+    if (!defender_obs_complete(dense)) return fail(MCBS_EINVAL, "mcbs_pack_defender_observation: all four int8 fields are packed, one is NULL");
+    if (n_rows == 0) return MCBS_OK;
+    const DefDense src{{dense->incoming_firewall_status, dense->infected_nodes, dense->outgoing_firewall_status, dense->services_status}};
+    hipLaunchKernelGGL(pack_defender_obs_kernel, defender_rows_grid(n_rows, 32u, 16384u), dim3(256), 0, (hipStream_t)stream, b->def_pack, src, n_rows, out, row_words);
+    return launch_ok("pack defender observation");
+}
+
+extern "C" int mcbs_unpack_defender_observation(const mcbs_batch* b, const uint32_t* packed, size_t row_words, const int64_t* index,
+                                                uint64_t n_source_rows, uint64_t n_rows, const mcbs_defender_obs* out, void* stream) {
+    if (!b || !packed || !out) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    if (const int rc = defender_packing_ok(b, "mcbs_unpack_defender_observation", row_words)) return rc;
+    if (!index && n_rows > n_source_rows) return fail(MCBS_EINVAL, "mcbs_unpack_defender_observation: %llu rows asked of %llu stored ones and no index",
+                                                      (unsigned long long)n_rows, (unsigned long long)n_source_rows);
+    if (n_rows == 0) return MCBS_OK;
+    const DefDenseOut dst{{out->incoming_firewall_status, out->infected_nodes, out->outgoing_firewall_status, out->services_status}};
+    hipLaunchKernelGGL(unpack_defender_obs_kernel, defender_rows_grid(n_rows, 32u, 16384u), dim3(256), 0, (hipStream_t)stream, b->def_pack, packed, row_words,
+                       index, n_source_rows, n_rows, dst);
+    return launch_ok("unpack defender observation");
+}
+
+extern "C" int mcbs_encode_defender_features(const mcbs_batch* b, const mcbs_defender_obs* dense, const uint32_t* packed, size_t row_words,
+                                             const int64_t* index, uint64_t n_source_rows, uint64_t n_rows, void* out, size_t out_row_stride,
+                                             int32_t dtype, int32_t* bad_rows, void* stream) {
+    const char* who = "mcbs_encode_defender_features";
+    if (!b || !out) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    if (!dense == !packed) return fail(MCBS_EINVAL, "%s: the source is either the dense fields or packed rows: exactly one of them", who);
+    if (const int rc = defender_packing_ok(b, who, packed ? row_words : b->def_pack.W)) return rc;
+    if (dense && !defender_obs_complete(dense)) return fail(MCBS_EINVAL, "%s: all four int8 fields are read, one is NULL", who);
+    if (dtype != MCBS_FEATURES_F32 && dtype != MCBS_FEATURES_BF16 && dtype != MCBS_FEATURES_F16)
+        return fail(MCBS_EINVAL, "features dtype must be MCBS_FEATURES_F32, MCBS_FEATURES_BF16 or MCBS_FEATURES_F16");
+    const DefPackGeom& G = b->def_pack;
+    if (out_row_stride < G.F) return fail(MCBS_EINVAL, "out_row_stride %zu is shorter than the %u feature columns", out_row_stride, G.F);
+    if (!index && n_rows > n_source_rows) return fail(MCBS_EINVAL, "%s: %llu rows asked of %llu stored ones and no index", who,
+                                                      (unsigned long long)n_rows, (unsigned long long)n_source_rows);
+    if (n_rows == 0) return MCBS_OK;
+    DefDense src{};
+    if (dense) src = DefDense{{dense->incoming_firewall_status, dense->infected_nodes, dense->outgoing_firewall_status, dense->services_status}};
+    const size_t item = dtype == MCBS_FEATURES_F32 ? 4u : 2u;
+    const uint32_t one = dtype == MCBS_FEATURES_F32 ? 0x3F800000u : dtype == MCBS_FEATURES_BF16 ? 0x3F80u : 0x3C00u;      // 1.0 as the dtype's pattern
+    rows_dispatch<1u, 2u>(item, out, out_row_stride, [&](auto es, auto gw, auto vec) {
+        using T = std::conditional_t<decltype(es)::value == 4u, uint32_t, uint16_t>;
+        constexpr uint32_t GW = decltype(gw)::value;
+        constexpr bool VEC = decltype(vec)::value;
+        // rows per pass of a workgroup's 256 threads: as many whole rows of `ngroup` store groups as fit, at least one
+        const uint32_t ngroup = (G.F + GW - 1u) / GW, RB = ngroup <= 256u ? 256u / ngroup : 1u;
+        const dim3 grid = defender_rows_grid(n_rows, RB, 8192u);
+        pick<0, 1>(packed ? 1 : 0, [&](auto pk) {
+            hipLaunchKernelGGL((encode_defender_features_kernel<T, GW, VEC, decltype(pk)::value != 0>), grid, dim3(256), 0, (hipStream_t)stream, G, src, packed,
+                               row_words, index, n_source_rows, n_rows, static_cast<T*>(out), out_row_stride, (T)one, ngroup, RB, fast_div_host(ngroup), bad_rows);
+        });
+    });
+    return launch_ok("encode defender features");
+}
+
+// 1: the turn launch writes the packed rows itself; 2: the turn, then the kernel of mcbs_defender_observe_packed
+extern "C" int32_t mcbs_defender_wrapper_step_packed_launches(const mcbs_batch* b) {
+    if (!b || b->cfg.defender_kind != MCBS_DEFENDER_EXTERNAL) return 0;
+    return b->variant.fused_defender_obs ? 1 : 2;
+}
+
+extern "C" int mcbs_defender_wrapper_step_packed(mcbs_batch* b, const int64_t* actions, uint32_t* packed_out, size_t row_words,
+                                                 const mcbs_defender_wrapper_buffers* w, const mcbs_defender_wrapper_cfg* cfg, void* stream) {
+    if (!b || !actions || !packed_out || !w || !cfg) return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    if (const int rc = defender_packing_ok(b, "mcbs_defender_wrapper_step_packed", row_words)) return rc;
+    if (const int rc = defender_live_rows_ok(b)) return rc;
+    if (!arrays_set(w, 0)) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
+    hipStream_t st = (hipStream_t)stream;
+    const bool fused = b->variant.fused_defender_obs && reinterpret_cast<uintptr_t>(packed_out) % 16 == 0;
+    if (fused) {
+        b->all_fresh = false;
+        pick<1, 2, 4>((int)b->S.WT, [&](auto wt) {
+            hipLaunchKernelGGL((defender_turn_post_packed_kernel<decltype(wt)::value>), dim3((b->S.E + 127) / 128), dim3(128), 0, st, b->S, b->T, b->C_dev, actions,
+                               *w, *cfg, b->def_pack, packed_out, row_words);
+        });
+        return launch_ok("defender turn + reward shaping + packed observation");
+    }
+    const int rc = launch_defender_turn(b, nullptr, st, "defender turn + reward shaping", [&](auto wt, dim3 grid, dim3 block, const DefObs& dob) {
+        hipLaunchKernelGGL((defender_turn_post_kernel<decltype(wt)::value>), grid, block, 0, st, b->S, b->T, b->C_dev, actions, *w, *cfg, dob);
+    });
+    if (rc) return rc;
+    return launch_defender_obs_packed(b, packed_out, row_words, st);
 }
 
 // ------------------------------------------------------------------ the two-agent turn (mcbs_two_agent.hip)

@@ -1449,6 +1449,130 @@ class BatchEngine:
         _check(self.lib, self.lib.mcbs_defender_observe(self._h, C.byref(o), self._stream()), "mcbs_defender_observe")
         return obs
 
+    # -- packed defender observations (include/mcbs.h): int32 tensors [rows, >= W_def], one bit per MultiBinary element --
+    def defender_obs_words(self) -> int:
+        """W_def, the uint32 words of a packed defender row (mcbs_defender_obs_words); 0 for a batch without a learned defender."""
+        return int(self.lib.mcbs_defender_obs_words(self._h))
+
+    def _defender_field_sizes(self) -> dict:
+        N, S = self.topo.n_nodes, int(self.topo.header()["n_services"])
+        return dict(infected_nodes=N, incoming_firewall_status=6 * N, outgoing_firewall_status=6 * N, services_status=S)
+
+    def _defender_packed_rows(self, x, what: str, n=None):
+        """x: int32 rows of at least W_def words, n packed defender observations (None: any count)."""
+        return self._rows(x, (self.torch.int32,), what, n, self.defender_obs_words())
+
+    def _defender_dense(self, obs: dict, what: str, n=None, partial: bool = False):
+        """The four int8 fields of `obs` as contiguous device tensors of n rows (None: taken from the first) -> (DefenderObs block, n);
+        partial: fields may be missing (skipped), but none unknown."""
+        t = self.torch
+        sizes = self._defender_field_sizes()
+        unknown = [k for k in obs if k not in sizes]
+        if unknown or (not partial and len(obs) != len(sizes)):
+            raise ValueError(f"{what} holds the four int8 fields {sorted(sizes)}" + (f", not {unknown}" if unknown else ""))
+        ptrs = {}
+        for k, x in obs.items():
+            if n is None:
+                n = x.shape[0] if isinstance(x, t.Tensor) and x.dim() >= 1 else None
+            self._arr(x, t.int8, (n, sizes[k]), f"{what}[{k!r}]")
+            ptrs[k] = x.data_ptr()
+        return DefenderObs(**ptrs), n
+
+    def defender_observe_packed(self, out=None):
+        """The packed rows of the live state of all envs, one launch (mcbs_defender_observe_packed).  out: device int32 [E, >= W_def]
+        with contiguous rows (words from W_def on are not touched, every word below is written), or None for a new [E, W_def] tensor."""
+        if out is None:
+            out = self.torch.empty((self.E, self.defender_obs_words()), dtype=self.torch.int32, device=self.device)
+        self._defender_packed_rows(out, "out", self.E)
+        _check(self.lib, self.lib.mcbs_defender_observe_packed(self._h, out.data_ptr(), _row_stride(out, self.E), self._stream()),
+               "mcbs_defender_observe_packed")
+        return out
+
+    def pack_defender_observation(self, obs: dict, out=None):
+        """n dense rows of the four int8 fields (a dict as alloc_defender_obs builds it, any n) as packed rows, one launch
+        (mcbs_pack_defender_observation): a bit is set where the element is not zero.  out: device int32 [n, >= W_def] or None."""
+        block, n = self._defender_dense(obs, "obs")
+        if out is None:
+            out = self.torch.empty((n, self.defender_obs_words()), dtype=self.torch.int32, device=self.device)
+        self._defender_packed_rows(out, "out", n)
+        if n:
+            _check(self.lib, self.lib.mcbs_pack_defender_observation(self._h, C.byref(block), n, out.data_ptr(), _row_stride(out, n), self._stream()),
+                   "mcbs_pack_defender_observation")
+        return out
+
+    def unpack_defender_observation(self, packed, index=None, out=None):
+        """Packed rows [m, >= W_def] -> dict of the four int8 fields, 0 / 1 (mcbs_unpack_defender_observation).  index: optional device
+        int64 [n]: output row i is stored row index[i] (an index outside [0, m) reads nothing: that row is all zero); without it n = m.
+        out: dict of contiguous device int8 tensors of n rows for the fields wanted (None: all four, newly allocated)."""
+        t = self.torch
+        self._defender_packed_rows(packed, "packed")
+        m = packed.shape[0]
+        idx, n = self._row_index(index, m)
+        if out is None:
+            out = {k: t.empty((n, s), dtype=t.int8, device=self.device) for k, s in self._defender_field_sizes().items()}
+        block, _ = self._defender_dense(out, "out", n, partial=True)
+        if n and out:
+            _check(self.lib, self.lib.mcbs_unpack_defender_observation(self._h, packed.data_ptr(), _row_stride(packed, m), idx, m, n, C.byref(block),
+                                                                       self._stream()), "mcbs_unpack_defender_observation")
+        return out
+
+    def encode_defender_features(self, dense: Optional[dict] = None, packed=None, index=None, out=None, dtype=None, bad_rows=None):
+        """The float rows DefenderVecEnv.features() builds — the four fields as 0.0 / 1.0 in sorted key order, F = 13 N + S columns —
+        in one launch (mcbs_encode_defender_features), from EITHER dense (the four int8 fields, m rows) OR packed (int32 [m, >= W_def]).
+        index: optional device int64 [n]: output row i is built from source row index[i], read where it is stored; an index outside
+        [0, m) reads nothing: that row is all zero and bad_rows (optional device int32 [1]) grows by one.  out: device float32 /
+        bfloat16 / float16 [n, >= F] with contiguous rows (columns from F on are not touched, every column below is written), or None
+        for a new tensor of `dtype` (default float32) whose rows are padded to whole 16-byte groups; returns the [n, F] view."""
+        t = self.torch
+        if (dense is None) == (packed is None):
+            raise ValueError("exactly one of dense= and packed= is the source")
+        if packed is not None:
+            self._defender_packed_rows(packed, "packed")
+            m, block, src, stride = packed.shape[0], None, packed.data_ptr(), _row_stride(packed, packed.shape[0])
+        else:
+            block, m = self._defender_dense(dense, "dense")
+            block, src, stride = C.byref(block), None, 0
+        idx, n = self._row_index(index, m)
+        F = sum(self._defender_field_sizes().values())
+        if out is None:
+            dtype = dtype or t.float32
+            if dtype not in self._feature_dtypes:
+                raise ValueError("features dtype must be float32, bfloat16 or float16")
+            per = 16 // self._feature_dtypes[dtype][1]
+            out = t.empty((n, (F + per - 1) // per * per), dtype=dtype, device=self.device)
+        if out.dtype not in self._feature_dtypes:
+            raise ValueError("out must be float32, bfloat16 or float16")
+        if dtype is not None and out.dtype != dtype:
+            raise ValueError(f"out is {out.dtype}, dtype asks for {dtype}")
+        self._rows(out, (out.dtype,), "out", n, F)
+        if bad_rows is not None:
+            self._counter(bad_rows, "bad_rows")
+        if n:
+            _check(self.lib, self.lib.mcbs_encode_defender_features(self._h, block, src, stride, idx, m, n, out.data_ptr(), _row_stride(out, n),
+                                                                    self._feature_dtypes[out.dtype][0], _ptr(bad_rows), self._stream()),
+                   "mcbs_encode_defender_features")
+        return out[:, :F]
+
+    def defender_wrapper_step_packed_launches(self) -> int:
+        """Launches of one mcbs_defender_wrapper_step_packed of this batch: 1 (the turn writes the packed rows itself: up to 32 nodes),
+        2, or 0 without a learned defender."""
+        return int(self.lib.mcbs_defender_wrapper_step_packed_launches(self._h))
+
+    def defender_wrapper_step_packed_call(self, packed, bufs, cfg):
+        """callable(actions_ptr): mcbs_defender_wrapper_step_packed — the defender's wrapper step whose observation output is the packed
+        row — with the argument blocks bound once.  packed: device int32 [E, >= W_def] with contiguous rows."""
+        self._defender_packed_rows(packed, "packed", self.E)
+        fn, eng, lib, stream = self.lib.mcbs_defender_wrapper_step_packed, self, self.lib, self._stream
+        refs = (C.byref(bufs), C.byref(cfg))
+        pp, stride = packed.data_ptr(), _row_stride(packed, self.E)
+        alive = (packed, bufs, cfg)
+
+        def call(p: int, _alive=alive) -> None:
+            rc = fn(eng._h, p, pp, stride, refs[0], refs[1], stream())
+            if rc:
+                _check(lib, rc, "mcbs_defender_wrapper_step_packed")
+        return call
+
     def get_state(self):
         rb = state_record_bytes(self.topo.n_nodes, self.spec.maximum_total_credentials)
         assert rb == self.lib.mcbs_state_record_bytes(self._h)

@@ -7,6 +7,8 @@ one-hot of its own width, a `MultiBinary` its values as 0.0 / 1.0 — and the ru
 writes it on the device in one launch from the descriptors this class builds, `encode_host` is the same encoding in NumPy.
 `ObservationPacking` is the host mirror of the packed row format (include/mcbs.h "packed observations"): the same source values as bit
 fields, what a rollout buffer stores per step and `mcbs_encode_features_packed` reads at update time.
+`DefenderObservationPacking` is the same for the learned defender's four MultiBinary fields: one bit per element, in the column order
+of `DefenderVecEnv.features()` (include/mcbs.h "packed defender observations").
 
 Pure Python / NumPy: importable without a GPU and without the native library.
 """
@@ -311,3 +313,47 @@ class ObservationPacking:
         p = (p.view(np.uint32) if p.dtype == np.int32 else p.astype(np.uint32)).astype(np.uint64)
         vals = (p[:, self.word] >> self.shift.astype(np.uint64)) & ((np.uint64(1) << self.bits.astype(np.uint64)) - np.uint64(1))
         return self._fields(vals.astype(np.int64))
+
+
+DEFENDER_KEYS = ("incoming_firewall_status", "infected_nodes", "outgoing_firewall_status", "services_status")     # sorted key order
+
+
+class DefenderObservationPacking:
+    """The packed row of the learned defender's observation of `topo` (include/mcbs.h "packed defender observations"): the host mirror
+    of what `mcbs_defender_observe_packed` / `mcbs_pack_defender_observation` write and `mcbs_unpack_defender_observation` /
+    `mcbs_encode_defender_features` read.
+
+    With N nodes and S services a row has `width` = F = 6N + N + 6N + S columns: the four MultiBinary fields in sorted key order
+    (`DEFENDER_KEYS`, the column order of `DefenderVecEnv.features()`): incoming_firewall_status column 6n + k, infected_nodes 6N + n,
+    outgoing_firewall_status 7N + 6n + k, services_status 13N + s.  `fields[key]` = (offset, size) of each.  Column c is bit c & 31 of
+    word c >> 5 of `words` = ceil(F / 32) uint32 words; bits at or past F are zero, always.
+    Packing rule: a bit is set where the dense element is NOT ZERO (`v != 0`; the observation only ever holds 0 and 1); unpacking gives
+    int8 0 / 1.  Pure NumPy."""
+
+    def __init__(self, topo: FlatTopology):
+        N, S = int(topo.n_nodes), int(topo.header()["n_services"])
+        self.n_nodes, self.n_services = N, S
+        sizes = (6 * N, N, 6 * N, S)
+        self.fields = {}
+        c = 0
+        for k, n in zip(DEFENDER_KEYS, sizes):
+            self.fields[k] = (c, n)
+            c += n
+        self.width = c
+        self.words = (c + 31) // 32
+
+    def pack_host(self, obs: dict) -> np.ndarray:
+        """uint32 [n, words] of a dict of the four fields with a leading row axis (any trailing shape, any integer or bool dtype)."""
+        n = len(np.asarray(obs[DEFENDER_KEYS[0]]))
+        bits = np.zeros((n, self.words * 32), dtype=np.uint64)
+        for k, (off, size) in self.fields.items():
+            bits[:, off:off + size] = np.asarray(obs[k]).reshape(n, size) != 0
+        shifts = np.arange(32, dtype=np.uint64)
+        return (bits.reshape(n, self.words, 32) << shifts).sum(axis=2).astype(np.uint32)       # (distinct bits: adding is OR-ing)
+
+    def unpack_host(self, rows) -> dict:
+        """The four int8 fields (0 / 1, [n, size] each) of uint32 / int32 rows [n, >= words]."""
+        p = np.asarray(rows)
+        p = (p.view(np.uint32) if p.dtype == np.int32 else p.astype(np.uint32))[:, :self.words]
+        bits = ((p[:, :, None] >> np.arange(32, dtype=np.uint32)) & 1).reshape(p.shape[0], self.words * 32).astype(np.int8)
+        return {k: bits[:, off:off + size].copy() for k, (off, size) in self.fields.items()}

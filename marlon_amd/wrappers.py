@@ -669,11 +669,22 @@ class DefenderVecEnv(_MultiDiscreteHead):
     (`mcbs_defender_wrapper_step`).  The shaping (defend_wrapper.py:228-282): invalid-action penalty, minus the attacker's last environment reward, a one-time
     `loss_reward` when availability first drops below `maintain_sla` (terminating if reset_on_constraint_broken), a
     worsening penalty while breached, `winning_reward` on eviction; truncation at max_timesteps.
-    The learned defender always acts on the live environment."""
+    The learned defender always acts on the live environment.
+
+    observation_format="packed": the wrapper keeps no int8 field.  Its observation is `{"packed": rows}`, `packed_observation` int32
+    [n_envs, W_def]: one bit per MultiBinary element in features()' column order (features.DefenderObservationPacking; ToyCtf: 20 B
+    instead of 143 B per row), written by the step itself (`mcbs_defender_wrapper_step_packed`: the turn launch writes the rows on
+    topologies of up to 32 nodes, a second launch elsewhere).  features(), rollout_buffer() and encode_features_packed() read the
+    rows; unpack_observation() rebuilds the int8 fields.  The two-agent turns write the dense form only and refuse such a wrapper."""
 
     def __init__(self, attacker: AttackerVecEnv, max_timesteps: int = 100, invalid_action_reward: float = 0.0,
                  reset_on_constraint_broken: bool = True, loss_reward: float = -5000.0, sla_worsening_penalty_scale: float = 200.0,
-                 use_graph: bool = False):
+                 use_graph: bool = False, observation_format: str = "dense"):
+        if observation_format not in ("dense", "packed"):
+            raise ValueError(f"observation_format must be 'dense' or 'packed', got {observation_format!r}")
+        self.observation_format = observation_format
+        self._packed_mode = observation_format == "packed"
+        self._packing = None
         self.attacker = attacker
         self.engine = attacker.engine
         t = self.torch = attacker.torch
@@ -689,7 +700,12 @@ class DefenderVecEnv(_MultiDiscreteHead):
         N = attacker.topo.n_nodes
         self.nvec = np.array([5, N, N, 6, 2, N, 6, 2, N, 3, N, 3], dtype=np.int64)          # defend_wrapper.py:162-195
         self._nvec = tuple(int(v) for v in self.nvec)
-        self._obs = self.engine.alloc_defender_obs()
+        self._sizes = self.engine._defender_field_sizes()
+        if self._packed_mode:
+            self.packed_observation = t.zeros((E, self.engine.defender_obs_words()), dtype=t.int32, device=dev)
+            self._obs = {"packed": self.packed_observation}
+        else:
+            self._obs = self.engine.alloc_defender_obs()
         self.timesteps = t.zeros(E, dtype=t.int32, device=dev)
         self.has_breached_sla = t.zeros(E, dtype=t.bool, device=dev)
         self.prev_availability = t.ones(E, dtype=t.float64, device=dev)
@@ -713,21 +729,33 @@ class DefenderVecEnv(_MultiDiscreteHead):
     @property
     def feature_width(self) -> int:
         """Columns of a features() row: the four MultiBinary fields' sizes added up."""
-        return sum(int(np.prod(self._obs[k].shape[1:])) for k in self.FEATURE_KEYS)
+        return sum(self._sizes[k] for k in self.FEATURE_KEYS)
 
     def features(self, out=None, dtype=None):
         """The observation this env last returned as the float rows Stable-Baselines3's MultiInputPolicy would build from it
         (preprocess_obs + CombinedExtractor): the four int8 MultiBinary fields as 0.0 / 1.0, flattened and concatenated in sorted key
         order (FEATURE_KEYS) -> [n_envs, feature_width] float32 (or `dtype`).  out=: write into a preallocated [n_envs, >= feature_width]
-        tensor, e.g. buffer[t] of a rollout buffer; columns beyond feature_width are left alone.  Four converting `copy_`s: about 140 bytes
-        per row of plumbing, not a kernel of its own."""
+        tensor, e.g. buffer[t] of a rollout buffer; columns beyond feature_width are left alone.  float32, bfloat16 and float16 rows are
+        ONE launch (mcbs_encode_defender_features), from the int8 fields or, with observation_format="packed", from the packed rows;
+        any other floating dtype takes four converting `copy_`s from the int8 fields (refused in packed mode)."""
         t = self.torch
         E, F = self.num_envs, self.feature_width
+        want = out.dtype if isinstance(out, t.Tensor) else (dtype if dtype is not None else t.float32)
+        kernel = want in (t.float32, t.bfloat16, t.float16)
+        if self._packed_mode and not kernel:
+            raise ValueError(f"features(): {want} rows are built from the int8 fields, which a DefenderVecEnv with observation_format='packed' "
+                             "does not keep (float32, bfloat16 and float16 are encoded from the packed rows)")
         if out is None:
-            out = t.empty((E, F), dtype=dtype if dtype is not None else t.float32, device=self.engine.device)
+            if kernel:
+                return self.engine.encode_defender_features(**self._feature_source(), dtype=want)
+            out = t.empty((E, F), dtype=want, device=self.engine.device)
         elif (not isinstance(out, t.Tensor) or out.dim() != 2 or out.shape[0] != E or out.shape[1] < F or not out.is_floating_point()
               or out.device != self.engine.device or (dtype is not None and out.dtype != dtype)):
             raise ValueError(f"out must be a floating-point device tensor [{E}, >= {F}]" + (f" of {dtype}" if dtype is not None else ""))
+        if kernel and out.stride(1) == 1:
+            return self.engine.encode_defender_features(**self._feature_source(), out=out)
+        if self._packed_mode:
+            raise ValueError("features(out=): the rows of out must be contiguous")
         c = 0
         for k in self.FEATURE_KEYS:
             x = self._obs[k].reshape(E, -1)
@@ -735,18 +763,72 @@ class DefenderVecEnv(_MultiDiscreteHead):
             c += x.shape[1]
         return out[:, :F]
 
-    def rollout_buffer(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, store_observations: bool = True):
+    def _feature_source(self) -> dict:
+        return dict(packed=self.packed_observation) if self._packed_mode else dict(dense=self._obs)
+
+    # -- packed observations (features.DefenderObservationPacking): store 20 B per ToyCtf step, encode features later --
+    def observation_packing(self):
+        """The `features.DefenderObservationPacking` of this topology: `words` is the row width W_def, `fields` the four (offset, size)
+        pairs, `pack_host` / `unpack_host` the same format on the host."""
+        if self._packing is None:
+            from .features import DefenderObservationPacking
+            self._packing = DefenderObservationPacking(self.attacker.topo)
+        return self._packing
+
+    def observation_packed(self, out=None):
+        """The observation this env last returned as packed rows: device int32 [n_envs, W_def].  Dense mode: one pack launch.  Packed
+        mode: the step has written them — without out= the wrapper's persistent `packed_observation` is returned, with out= it is copied.
+        out=: a preallocated [n_envs, >= W_def] buffer, e.g. `buf.observations["packed"][buf.pos]` of rollout_buffer(pack_observations=True);
+        words from W_def on are not touched."""
+        if self._packed_mode:
+            if out is None:
+                return self.packed_observation
+            self.engine._defender_packed_rows(out, "out", self.num_envs)
+            out[:, :self.packed_observation.shape[1]].copy_(self.packed_observation)
+            return out
+        return self.engine.pack_defender_observation(self._obs, out=out)
+
+    def unpack_observation(self, packed, index=None):
+        """Packed rows [m, >= W_def] -> the four int8 fields (0 / 1) of those rows, or of rows index[i] with index (device int64 [n])."""
+        return self.engine.unpack_defender_observation(packed, index=index)
+
+    def encode_features_packed(self, packed, index=None, out=None, dtype=None, bad_rows=None):
+        """features() rows straight from stored packed rows [m, >= W_def], one launch.  With index (device int64 [n]) the rows are read
+        where they are stored, nothing is gathered first:
+            x = dfd.encode_features_packed(buf.observations["packed"].view(T * E, -1), index=batch.index, dtype=torch.bfloat16)
+        An index outside [0, m) gives an all-zero row and adds one to bad_rows (optional device int32 [1])."""
+        return self.engine.encode_defender_features(packed=packed, index=index, out=out, dtype=dtype, bad_rows=bad_rows)
+
+    def rollout_buffer(self, n_steps: int, gamma: float = 0.99, gae_lambda: float = 0.95, store_observations: bool = True,
+                       pack_observations: Optional[bool] = None):
         """A `rollout.DeviceRolloutBuffer` of n_steps x n_envs transitions for the defender: it stores the four int8 observation fields,
         actions [12] and no packed masks (a MultiDiscrete head has none), and computes advantages and returns with one launch.  Its add()
-        takes `observation` as obs.  store_observations=False: no observation storage (a trainer that keeps features() rows of its own)."""
+        takes `observation` as obs.  store_observations=False: no observation storage (a trainer that keeps features() rows of its own).
+        pack_observations=True: the observation storage is ONE key, `observations["packed"]` int32 [T, E, W_def]: fill row `pos` with
+        observation_packed(out=buf.observations["packed"][buf.pos]) and pass obs=None to add(); at update time
+        encode_features_packed(..., index=batch.index) reads the storage itself.  The default is False, and True for a wrapper created
+        with observation_format="packed", which has nothing else to store: False is refused there."""
         from .rollout import DeviceRolloutBuffer
-        return DeviceRolloutBuffer(self.engine, n_steps, self.num_envs, obs=self._obs if store_observations else None, action_shape=(12,),
-                                   mask_words=None, gamma=gamma, gae_lambda=gae_lambda)
+        if pack_observations is None:
+            pack_observations = self._packed_mode
+        if self._packed_mode and store_observations and not pack_observations:
+            raise ValueError("rollout_buffer(pack_observations=False): this DefenderVecEnv was created with observation_format='packed' "
+                             "and keeps no int8 field to store")
+        obs = None
+        if store_observations:
+            obs = self._obs
+            if pack_observations:
+                obs = {"packed": self.torch.zeros((self.num_envs, self.engine.defender_obs_words()), dtype=self.torch.int32, device=self.engine.device)}
+        return DeviceRolloutBuffer(self.engine, n_steps, self.num_envs, obs=obs, action_shape=(12,), mask_words=None, gamma=gamma,
+                                   gae_lambda=gae_lambda)
 
     def reset(self, env_mask=None):
         """Wrapper state of the envs in env_mask (all if None); the environment itself is reset by the attacker side."""
         t = self.torch
-        self.engine.defender_observe(self._obs)
+        if self._packed_mode:
+            self.engine.defender_observe_packed(out=self.packed_observation)
+        else:
+            self.engine.defender_observe(self._obs)
         avail = self.engine.step_info()["network_availability"]
         keep = t.zeros(self.num_envs, dtype=t.bool, device=self.engine.device) if env_mask is None else ~(env_mask != 0)
         self.timesteps *= keep
@@ -790,7 +872,7 @@ class DefenderVecEnv(_MultiDiscreteHead):
         E, dev = self.num_envs, self.engine.device
         from ._abi import DefenderObs, DefenderWrapperBuffers, DefenderWrapperCfg
         self._evicted = t.zeros(E, dtype=t.uint8, device=dev)
-        self._obs_block = DefenderObs(**{k: x.data_ptr() for k, x in self._obs.items()})
+        self._obs_block = None if self._packed_mode else DefenderObs(**{k: x.data_ptr() for k, x in self._obs.items()})
         self._wc = DefenderWrapperCfg(self.invalid_action_penalty, self.loss_reward, self.sla_worsening_penalty_scale, self.maintain_sla,
                                       self.winning_reward, int(self.reset_on_constraint_broken), self.max_timesteps)
         self._ring = []
@@ -805,7 +887,9 @@ class DefenderVecEnv(_MultiDiscreteHead):
                 o["truncated"], o["breached"], o["won"])])
             info = {"valid_action": o["valid"].view(t.bool), "network_availability": o["availability"], "sla_breached": o["breached"].view(t.bool),
                     "defender_won": o["won"].view(t.bool)}
-            self._ring.append((o, wb, info, self.engine.defender_wrapper_step_call(self._obs_block, wb, self._wc)))
+            call = (self.engine.defender_wrapper_step_packed_call(self.packed_observation, wb, self._wc) if self._packed_mode
+                    else self.engine.defender_wrapper_step_call(self._obs_block, wb, self._wc))
+            self._ring.append((o, wb, info, call))
 
 
 class EpisodeState:
@@ -884,6 +968,8 @@ class TwoAgentVecEnv:
             return "the library does not serve this batch with a joint turn (mcbs_two_agent_step_launches: small packed topologies only)"
         if dfd is not None and not (isinstance(dfd, DefenderVecEnv) and dfd.attacker is att and not dfd.use_graph):
             return "the defender side must be the DefenderVecEnv created on this AttackerVecEnv (use_graph=False)"
+        if dfd is not None and dfd.observation_format != "dense":
+            return "the DefenderVecEnv must be created with observation_format='dense' (these turns write the int8 fields, not packed rows)"
         return None
 
     @staticmethod
@@ -985,6 +1071,8 @@ class TwoAgentTrainVecEnv:
             return "the library does not serve this batch with a training turn (mcbs_two_agent_train_step_launches: small packed topologies only)"
         if dfd is not None and not (isinstance(dfd, DefenderVecEnv) and dfd.attacker is att and not dfd.use_graph):
             return "the defender side must be the DefenderVecEnv created on this AttackerVecEnv (use_graph=False)"
+        if dfd is not None and dfd.observation_format != "dense":
+            return "the DefenderVecEnv must be created with observation_format='dense' (these turns write the int8 fields, not packed rows)"
         return None
 
     @staticmethod
