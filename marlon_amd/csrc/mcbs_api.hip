@@ -14,6 +14,7 @@
 
 #include "mcbs.h"
 #include "mcbs_device.h"
+#include "mcbs_extents.h"
 #include "mcbs_step.hip"
 #include "mcbs_step_coop.hip"
 #include "mcbs_obs.hip"
@@ -72,7 +73,60 @@ static int fail(int code, const char* fmt, ...) {
     DeviceGuard _dev_guard((b)->cfg.device);                                                                                   \
     if (_dev_guard.err != hipSuccess) return fail(MCBS_EHIP, "cannot select device %d: %s", (b)->cfg.device, hipGetErrorString(_dev_guard.err))
 
-static FastDiv fast_div_host(uint32_t d);
+static FastDiv fast_div_host(uint32_t d) {   // n / d = (t + ((n - t) >> sh1)) >> sh2 with t = mulhi(n, mul)
+    uint32_t l = 0;
+    while ((1ull << l) < d) ++l;
+    FastDiv f;
+    f.mul = (uint32_t)(((1ull << 32) * ((1ull << l) - d)) / d + 1ull);
+    f.sh1 = l < 1u ? l : 1u;
+    f.sh2 = l > 0u ? l - 1u : 0u;
+    return f;
+}
+
+// "No array this call writes may share a byte with another array it reads or writes" (mcbs_extents.h), as every entry point refuses it
+static int disjoint(const char* who, const Extents& x) {
+    if (x.overflowed) return fail(MCBS_ELIMIT, "%s: more than %zu arrays in one overlap check", who, Extents::kCapacity);
+    const Extents::Pair c = x.overlap();
+    if (c.first) return fail(MCBS_EINVAL, "%s: %s%s overlaps %s%s", who, c.first->prefix, c.first->name, c.second->prefix, c.second->name);
+    return MCBS_OK;
+}
+
+// The arrays of a buffer struct of mcbs.h, one entry per pointer member in the member's order: n_envs rows of
+// bytes + per_node * n_nodes + per_service * n_services bytes each; all three 0: the member is in no overlap check.
+// kind kFreshRow: ONE such row for the whole batch, which the call only ever reads, whatever the struct's other arrays are listed as
+enum ArrayKind : uint32_t { kPerEnv = 0, kFreshRow = 1 };
+struct ArrayDesc { const char* name; uint32_t bytes, per_node, per_service; ArrayKind kind; };
+static const ArrayDesc kWrapperArrays[] = {
+    {"invalid", 1}, {"reward", 4}, {"terminated", 1}, {"timesteps", 4}, {"valid_action_count", 8}, {"invalid_action_count", 8}, {"episode_returns", 8},
+    {"last_cyber_reward", 4}, {"has_cyber_reward", 1}, {"rewards", 4}, {"truncated", 1}, {"dones", 1}, {"episode_return_out", 8},
+    {"episode_length_out", 4}, {"n_done", 0}, {"executed", 1}};
+static const ArrayDesc kInfoArrays[] = {{"network_availability", 8}, {"step_count", 4}, {"truncated", 1}, {"out_of_bound", 1}, {"raw_reward", 4}};
+static const ArrayDesc kDefenderObsArrays[] = {
+    {"infected_nodes", 0, 1}, {"incoming_firewall_status", 0, 6}, {"outgoing_firewall_status", 0, 6}, {"services_status", 0, 0, 1}};
+// (dw->attacker_has_cyber_reward / attacker_last_cyber_reward ARE w->has_cyber_reward / last_cyber_reward: read where the attacker half wrote)
+static const ArrayDesc kDefenderWrapperArrays[] = {
+    {"valid", 1}, {"availability", 8}, {"evicted", 1}, {"attacker_has_cyber_reward", 0}, {"attacker_last_cyber_reward", 0}, {"timesteps", 4},
+    {"valid_action_count", 8}, {"invalid_action_count", 8}, {"has_breached_sla", 1}, {"prev_availability", 8}, {"reward", 8}, {"terminated", 1},
+    {"truncated", 1}, {"breached", 1}, {"won", 1}};
+static const ArrayDesc kTrainingArrays[] = {
+    {"attacker_reset_request", 1}, {"defender_return", 8}, {"attacker_valid_out", 8}, {"attacker_invalid_out", 8}, {"defender_return_out", 8},
+    {"defender_length_out", 4}, {"defender_valid_out", 8}, {"defender_invalid_out", 8}, {"defender_dones", 1}, {"terminal_infected_nodes", 0, 1},
+    {"terminal_incoming_firewall_status", 0, 6}, {"terminal_outgoing_firewall_status", 0, 6}, {"terminal_services_status", 0, 0, 1},
+    {"fresh_infected_nodes", 0, 1, 0, kFreshRow}, {"fresh_incoming_firewall_status", 0, 6, 0, kFreshRow},
+    {"fresh_outgoing_firewall_status", 0, 6, 0, kFreshRow},
+    {"fresh_services_status", 0}};
+// ... appended to an overlap check as prefix + name
+template <class W, size_t K>
+static void add_arrays(Extents& x, const char* prefix, const W* w, const ArrayDesc (&desc)[K], uint64_t E, uint64_t N, uint64_t Sv, bool written) {
+    // (the count is held to the header here; the ORDER only by tests/test_gpu_turn_extents.py, which moves an array of every struct)
+    static_assert(sizeof(W) == K * sizeof(void*), "one descriptor per pointer member of the struct (mcbs.h)");
+    const void* const* p = reinterpret_cast<const void* const*>(w);
+    for (size_t i = 0; w && i < K; ++i) {
+        const bool fresh_row = desc[i].kind == kFreshRow;
+        x.bytes(desc[i].name, p[i], (fresh_row ? 1u : E) * (desc[i].bytes + desc[i].per_node * N + desc[i].per_service * Sv), written && !fresh_row, prefix);
+    }
+}
+
 struct HotLayout {
     uint32_t node, desc, payload, auth, auth_words, triple, avail, fwlist, bytes;
     uint32_t max_leak;   // the largest payload_cnt of any descriptor: no action of this topology leaks more entries (StepCfg::max_leak)
@@ -399,6 +453,20 @@ static mcbs_batch_variant_info batch_variant(const mcbs_batch* b) {
     // and 256 services; MCBS_NO_FUSED_DEFENDER_OBS=1: the separate launch
     v.fused_defender_obs = def == MCBS_DEFENDER_EXTERNAL && S.N <= 32u && b->C.n_services <= 256u && !getenv("MCBS_NO_FUSED_DEFENDER_OBS");
     return v;
+}
+
+extern "C" int mcbs_batch_variant(const mcbs_batch* b, mcbs_batch_variant_info* out) {
+    if (!b || !out) return fail(MCBS_EINVAL, "null argument");
+    *out = b->variant;
+    return MCBS_OK;
+}
+
+extern "C" int32_t mcbs_step_is_lean(const mcbs_batch* b, int32_t with_info) {
+    return (b && b->lean_step && !with_info) ? 1 : 0;
+}
+extern "C" int32_t mcbs_step_topo_traits(const mcbs_batch* b, int32_t with_info, uint32_t* traits) {
+    if (traits) *traits = b ? b->topo->hot.traits : 0u;
+    return (b && b->narrow_step && !with_info) ? 1 : 0;
 }
 
 extern "C" int mcbs_batch_create(const mcbs_topology* topo, const mcbs_batch_cfg* cfg, mcbs_batch** out) {
@@ -971,8 +1039,6 @@ static int launch_obs_inner(mcbs_batch* b, const mcbs_obs_buffers* o, hipStream_
     return launch_masks(b, &rest, st, env_mask, masks_only);
 }
 
-static inline bool getenv_rows_off(const mcbs_batch* b) { return b->no_row_masks; }
-
 template <int REGION>
 static int launch_region(mcbs_batch* b, int8_t* dst, size_t env_stride, size_t region_off, size_t len, hipStream_t st, const uint8_t* env_mask, bool masks_only) {
     const uint32_t Nm = b->cfg.maximum_node_count, Cm = b->cfg.maximum_total_credentials;
@@ -984,7 +1050,7 @@ static int launch_region(mcbs_batch* b, int8_t* dst, size_t env_stride, size_t r
     const dim3 grid(b->S.E, (unsigned)((chunks + 255) / 256));
     if (grid.y > 65535u) return fail(MCBS_ELIMIT, "mask region too large for one launch");
     const uint32_t RL = REGION == 0 ? b->C.P * Cm : (REGION == 1 ? Nm * b->C.R : 0u), Cc = REGION == 0 ? Cm : RL;
-    if (W == 16 && REGION == 0 && RL % 16u == 0 && RL >= 16u && !b->slow_masks && !getenv_rows_off(b)) {
+    if (W == 16 && REGION == 0 && RL % 16u == 0 && RL >= 16u && !b->slow_masks && !b->no_row_masks) {
         // whole rows of 16-byte chunks: pattern row + per-row on/off bytes in LDS (mcbs_obs.hip: mask_connect_rows_kernel)
         const uint32_t cpr = RL / 16u, rows = Nm * Nm;
         uint32_t rpb = 128u;                                          // rows per workgroup: >= 16 KB of output each
@@ -1121,6 +1187,30 @@ static int finish_args(mcbs_batch* b, const mcbs_wrapper_buffers* w, float modif
     return MCBS_OK;
 }
 
+// What every attacker-turn entry point checks first, in the order the refusal tests see (finish_args, the draw tape, exactly one action
+// encoding) -> the turn's StepIO, and in *finish the arguments of the wrapper-finish half where the caller launches it on its own
+static int attacker_turn_io(mcbs_batch* b, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded, const mcbs_info_buffers* info,
+                            const mcbs_wrapper_buffers* w, float modifier, int32_t max_timesteps, int32_t auto_reset, const mcbs_row_copies* keep,
+                            const mcbs_row_copies* fresh, StepIO* io, WrapperFinishArgs* finish = nullptr) {
+    WrapperFinishArgs checked_only;
+    int rc = finish_args(b, w, modifier, max_timesteps, auto_reset, keep, fresh, finish ? finish : &checked_only);
+    if (rc) return rc;
+    if ((rc = draws_ok(b))) return rc;
+    if (!multidiscrete == !discrete) return fail(MCBS_EINVAL, "need exactly one action encoding");
+    *io = make_io(b, decoded, const_cast<float*>(w->reward), const_cast<uint8_t*>(w->terminated), info);
+    return MCBS_OK;
+}
+
+// ... and what it does after its one launch: every env's digest was written (or, for an intercepted action, stands); own_lists: with the
+// discovery order of its own observation (the training turn)
+static int turn_launched(mcbs_batch* b, const char* what, bool own_lists = false) {
+    const int rc = launch_ok(what);
+    if (rc) return rc;
+    if (own_lists) b->digest_lists = true;
+    b->digest_state = 1;
+    return MCBS_OK;
+}
+
 extern "C" int mcbs_attacker_wrapper_finish(mcbs_batch* b, const mcbs_wrapper_buffers* w, float modifier, int32_t max_timesteps, int32_t auto_reset,
                                             const mcbs_row_copies* keep, const mcbs_row_copies* fresh, void* stream) {
     WrapperFinishArgs A;
@@ -1196,10 +1286,8 @@ static int try_fused_wrapper_step(mcbs_batch* b, const int64_t* multidiscrete, c
     pick<MCBS_DEFENDER_SCAN_AND_REIMAGE, MCBS_DEFENDER_EXTERNAL, MCBS_DEFENDER_NONE>((int)b->cfg.defender_kind, [&](auto def) {
         hipLaunchKernelGGL((wrapper_fused_kernel<decltype(def)::value>), grid, block, 0, st, b->S, b->T, b->C_dev, io, A);
     });
-    const int rc = launch_ok("wrapper step (one launch)");
-    if (rc) return rc;
-    b->digest_state = 1;       // every env's digest was written (or, for an intercepted action, stands)
-    return 1;
+    const int rc = turn_launched(b, "wrapper step (one launch)");
+    return rc ? rc : 1;
 }
 
 extern "C" int mcbs_attacker_wrapper_step(mcbs_batch* b, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded,
@@ -1209,12 +1297,11 @@ extern "C" int mcbs_attacker_wrapper_step(mcbs_batch* b, const int64_t* multidis
     if (!b || !w || !decoded || !obs) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
     WrapperFinishArgs A;
-    int rc = finish_args(b, w, modifier, max_timesteps, auto_reset, keep, fresh, &A);      // (all checks before the first launch)
+    StepIO io;
+    // (all checks before the first launch)
+    int rc = attacker_turn_io(b, multidiscrete, discrete, decoded, info, w, modifier, max_timesteps, auto_reset, keep, fresh, &io, &A);
     if (rc) return rc;
-    if ((rc = draws_ok(b))) return rc;
-    if (!multidiscrete == !discrete) return fail(MCBS_EINVAL, "need exactly one action encoding");
     hipStream_t st = (hipStream_t)stream;
-    const StepIO io = make_io(b, decoded, const_cast<float*>(w->reward), const_cast<uint8_t*>(w->terminated), info);
     uint8_t* invalid = const_cast<uint8_t*>(w->invalid);
     if ((rc = try_fused_wrapper_step(b, multidiscrete, discrete, decoded, io, obs, w, modifier, max_timesteps, auto_reset, keep, fresh, st)) != 0)
         return rc < 0 ? rc : MCBS_OK;
@@ -1267,16 +1354,6 @@ extern "C" int mcbs_decode_attacker_actions(mcbs_batch* b, const int64_t* multid
 }
 
 // ------------------------------------------------------------------ action mask -> logits
-static FastDiv fast_div_host(uint32_t d) {   // n / d = (t + ((n - t) >> sh1)) >> sh2 with t = mulhi(n, mul)
-    uint32_t l = 0;
-    while ((1ull << l) < d) ++l;
-    FastDiv f;
-    f.mul = (uint32_t)(((1ull << 32) * ((1ull << l) - d)) / d + 1ull);
-    f.sh1 = l < 1u ? l : 1u;
-    f.sh2 = l > 0u ? l - 1u : 0u;
-    return f;
-}
-
 extern "C" uint64_t mcbs_discrete_action_count(const mcbs_batch* b) {
     if (!b) return 0;
     const uint64_t N = b->cfg.maximum_node_count, C = b->cfg.maximum_total_credentials;
@@ -1688,31 +1765,21 @@ extern "C" int mcbs_masked_linear_categorical_grad(const mcbs_batch* b, const ui
         return fail(MCBS_EINVAL, "%s: the workspace must hold %zu bytes (mcbs_masked_linear_categorical_grad_workspace), got %zu at %p", who, ws.bytes,
                     workspace_bytes, workspace);
 
-    // no output may share a byte with an input, the workspace or another output: the extents [first byte, last byte] are compared
-    struct Extent { const char* name; uintptr_t lo, hi; bool out; };
+    // no output may share a byte with an input, the workspace or another output
     const size_t es = dtype == MCBS_LOGITS_F32 ? 4u : 2u;
-    auto extent = [](const char* name, const void* p, uint64_t rows, size_t stride, size_t width, size_t elem, bool out) {
-        const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-        return Extent{name, lo, p && rows ? lo + (uintptr_t)(((rows - 1u) * stride + width) * elem) : lo, out};
-    };
-    const Extent ext[] = {
-        extent("grad_latent", grad_latent, n_rows, grad_latent_row_stride, H, 4u, true),
-        extent("grad_weight", grad_weight, A, grad_weight_row_stride, H, 4u, true),
-        extent("grad_bias", grad_bias, 1u, 0u, A, 4u, true),
-        extent("workspace", workspace, ws.bytes ? 1u : 0u, 0u, ws.bytes, 1u, true),
-        extent("bits", bits, n_rows, bits_row_words, W, 4u, false),
-        extent("latent", latent, n_rows, latent_row_stride, H, es, false),
-        extent("weight", weight, n_rows ? A : 0u, weight_row_stride, H, es, false),
-        extent("bias", bias, n_rows ? 1u : 0u, 0u, A, es, false),
-        extent("actions", actions, n_rows ? 1u : 0u, 0u, n_rows, 8u, false),
-        extent("grad_log_prob", grad_log_prob, n_rows ? 1u : 0u, 0u, n_rows, 4u, false),
-        extent("grad_entropy", grad_entropy, n_rows ? 1u : 0u, 0u, n_rows, 4u, false),
-    };
-    constexpr size_t NE = sizeof(ext) / sizeof(ext[0]);
-    for (size_t i = 0; i < NE; ++i)
-        for (size_t k = i + 1u; k < NE; ++k)
-            if (ext[i].out && ext[i].lo < ext[i].hi && ext[k].lo < ext[k].hi && ext[i].lo < ext[k].hi && ext[k].lo < ext[i].hi)
-                return fail(MCBS_EINVAL, "%s: %s overlaps %s", who, ext[i].name, ext[k].name);
+    Extents ext;
+    ext.rows("grad_latent", grad_latent, n_rows, grad_latent_row_stride, H, 4u, true);
+    ext.rows("grad_weight", grad_weight, A, grad_weight_row_stride, H, 4u, true);
+    ext.bytes("grad_bias", grad_bias, (uint64_t)A * 4u, true);
+    ext.bytes("workspace", workspace, ws.bytes, true);
+    ext.rows("bits", bits, n_rows, bits_row_words, W, 4u, false);
+    ext.rows("latent", latent, n_rows, latent_row_stride, H, es, false);
+    ext.rows("weight", weight, n_rows ? A : 0u, weight_row_stride, H, es, false);
+    ext.bytes("bias", bias, n_rows ? (uint64_t)A * es : 0u, false);
+    ext.bytes("actions", actions, n_rows * 8u, false);
+    ext.bytes("grad_log_prob", grad_log_prob, n_rows * 4u, false);
+    ext.bytes("grad_entropy", grad_entropy, n_rows * 4u, false);
+    if ((rc = disjoint(who, ext))) return rc;
 
     char* wsp = static_cast<char*>(workspace);
     LinGradIO io{actions, grad_log_prob, grad_entropy, grad_latent, grad_latent_row_stride, grad_weight, grad_weight_row_stride, grad_bias,
@@ -2155,11 +2222,9 @@ extern "C" int mcbs_attacker_wrapper_step_packed(mcbs_batch* b, const int64_t* m
     const char* who = "mcbs_attacker_wrapper_step_packed";
     if (!b || !w || !decoded || !p || !packed) return fail(MCBS_EINVAL, "null argument");
     MCBS_ON_DEVICE(b);
-    WrapperFinishArgs F;
-    int rc = finish_args(b, w, modifier, max_timesteps, auto_reset, nullptr, nullptr, &F);
+    StepIO io;
+    int rc = attacker_turn_io(b, multidiscrete, discrete, decoded, info, w, modifier, max_timesteps, auto_reset, nullptr, nullptr, &io);
     if (rc) return rc;
-    if ((rc = draws_ok(b))) return rc;
-    if (!multidiscrete == !discrete) return fail(MCBS_EINVAL, "need exactly one action encoding");
     if (!b->variant.fused_wrapper)
         return fail(MCBS_EINVAL, "%s: the wrapper step of this batch is not one launch (packed batch, at most 16 nodes and cached credentials, not "
                                  "the random-events defender); there is no multi-launch form of the packed step", who);
@@ -2173,37 +2238,15 @@ extern "C" int mcbs_attacker_wrapper_step_packed(mcbs_batch* b, const int64_t* m
         return fail(MCBS_EINVAL, "%s: auto_reset needs packed_terminal (the rows of the envs that end) and packed_fresh (the row of a reset env)", who);
     if (!auto_reset) packed_terminal = nullptr, packed_fresh = nullptr;                 // (neither is touched)
     // the three arrays this entry point adds may share no byte with each other, with an input or with an array of `w` / `info`, which the
-    // same launch writes
-    {
-        const uint64_t E = b->S.E;
-        struct Extent { const char* name; uintptr_t lo, hi; bool out; };
-        auto extent = [](const char* name, const void* q, uint64_t bytes, bool out) {
-            const uintptr_t lo = reinterpret_cast<uintptr_t>(q);
-            return Extent{name, lo, q ? lo + (uintptr_t)bytes : lo, out};
-        };
-        const uint64_t rows_bytes = ((E - 1u) * row_words + W) * 4u;
-        const Extent ext[] = {
-            extent("packed", packed, rows_bytes, true), extent("packed_terminal", packed_terminal, rows_bytes, true),
-            extent("decoded", decoded, E * 20u, true), extent("packed_fresh", packed_fresh, (uint64_t)W * 4u, false),
-            extent("multidiscrete", multidiscrete, E * 80u, false), extent("discrete", discrete, E * 8u, false),
-            extent("w->invalid", w->invalid, E, false), extent("w->reward", w->reward, E * 4u, false), extent("w->terminated", w->terminated, E, false),
-            extent("w->timesteps", w->timesteps, E * 4u, false), extent("w->valid_action_count", w->valid_action_count, E * 8u, false),
-            extent("w->invalid_action_count", w->invalid_action_count, E * 8u, false), extent("w->episode_returns", w->episode_returns, E * 8u, false),
-            extent("w->last_cyber_reward", w->last_cyber_reward, E * 4u, false), extent("w->has_cyber_reward", w->has_cyber_reward, E, false),
-            extent("w->rewards", w->rewards, E * 4u, false), extent("w->truncated", w->truncated, E, false), extent("w->dones", w->dones, E, false),
-            extent("w->episode_return_out", w->episode_return_out, E * 8u, false), extent("w->episode_length_out", w->episode_length_out, E * 4u, false),
-            extent("w->executed", w->executed, E, false),
-            extent("info->network_availability", info ? info->network_availability : nullptr, E * 8u, false),
-            extent("info->step_count", info ? info->step_count : nullptr, E * 4u, false), extent("info->truncated", info ? info->truncated : nullptr, E, false),
-            extent("info->out_of_bound", info ? info->out_of_bound : nullptr, E, false), extent("info->raw_reward", info ? info->raw_reward : nullptr, E * 4u, false),
-        };
-        constexpr size_t NE = sizeof(ext) / sizeof(ext[0]);
-        for (size_t i = 0; i < NE; ++i)
-            for (size_t k = i + 1u; k < NE; ++k)
-                if (ext[i].out && ext[i].lo < ext[i].hi && ext[k].lo < ext[k].hi && ext[i].lo < ext[k].hi && ext[k].lo < ext[i].hi)
-                    return fail(MCBS_EINVAL, "%s: %s overlaps %s", who, ext[i].name, ext[k].name);
-    }
-    const StepIO io = make_io(b, decoded, const_cast<float*>(w->reward), const_cast<uint8_t*>(w->terminated), info);
+    // same launch writes (those are listed as not written: unlike the training turn, this call does not refuse two of them against each other)
+    const uint64_t E = b->S.E;
+    Extents ext;
+    ext.rows("packed", packed, E, row_words, W, 4u, true); ext.rows("packed_terminal", packed_terminal, E, row_words, W, 4u, true);
+    ext.bytes("decoded", decoded, E * 20u, true); ext.bytes("packed_fresh", packed_fresh, (uint64_t)W * 4u, false);
+    ext.bytes("multidiscrete", multidiscrete, E * 80u, false); ext.bytes("discrete", discrete, E * 8u, false);
+    add_arrays(ext, "w->", w, kWrapperArrays, E, 0u, 0u, false);
+    add_arrays(ext, "info->", info, kInfoArrays, E, 0u, 0u, false);
+    if ((rc = disjoint(who, ext))) return rc;
     const mcbs_obs_buffers none{};
     FusedArgs A;
     if (!fused_wrapper_args(b, multidiscrete, discrete, decoded, &none, w, modifier, max_timesteps, auto_reset, nullptr, nullptr, &A))
@@ -2217,9 +2260,7 @@ extern "C" int mcbs_attacker_wrapper_step_packed(mcbs_batch* b, const int64_t* m
     pick<MCBS_DEFENDER_SCAN_AND_REIMAGE, MCBS_DEFENDER_EXTERNAL, MCBS_DEFENDER_NONE>((int)b->cfg.defender_kind, [&](auto def) {
         hipLaunchKernelGGL((wrapper_fused_packed_kernel<decltype(def)::value>), grid, block, 0, (hipStream_t)stream, b->S, b->T, b->C_dev, io, A, PA);
     });
-    if ((rc = launch_ok("wrapper step (one launch, packed rows)"))) return rc;
-    b->digest_state = 1;       // every env's digest was written (or, for an intercepted action, stands)
-    return MCBS_OK;
+    return turn_launched(b, "wrapper step (one launch, packed rows)");
 }
 
 extern "C" int mcbs_encode_features_packed(const mcbs_batch* b, const mcbs_feature_layout* l, const mcbs_obs_packing* p, const uint32_t* packed,
@@ -2275,27 +2316,12 @@ extern "C" int mcbs_encode_features_packed(const mcbs_batch* b, const mcbs_featu
 }
 
 // ------------------------------------------------------------------ first layer from the observation
-// [first byte, last byte) of an array of `rows` rows `stride` elements apart whose first `width` elements are used; `out`: the call writes it
-struct FlExtent { const char* name; uintptr_t lo, hi; bool out; };
-static FlExtent fl_extent(const char* name, const void* p, uint64_t rows, size_t stride, size_t width, size_t elem, bool out) {
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    return FlExtent{name, lo, p && rows && width ? lo + (uintptr_t)(((rows - 1u) * stride + width) * elem) : lo, out};
-}
-// no output may share a byte with an input or another output
-static int fl_disjoint(const char* who, const std::vector<FlExtent>& ext) {
-    for (size_t i = 0; i < ext.size(); ++i)
-        for (size_t k = 0; k < ext.size(); ++k)
-            if (i != k && ext[i].out && (k > i || !ext[k].out) && ext[i].lo < ext[i].hi && ext[k].lo < ext[k].hi && ext[i].lo < ext[k].hi &&
-                ext[k].lo < ext[i].hi)
-                return fail(MCBS_EINVAL, "%s: %s overlaps %s", who, ext[i].name, ext[k].name);
-    return MCBS_OK;
-}
-
+static const char* const kObsFields[5] = {"scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel"};
 // The checks on (batch, layout, source) the three calls share; fills S and appends the source's extents.  obs: the dense form; else
 // packing + packed (+ index).
 static int fl_source(const char* who, const mcbs_batch* b, const mcbs_feature_layout* l, const mcbs_obs_buffers* obs, const mcbs_obs_packing* p,
                      const uint32_t* packed, size_t packed_row_words, const int64_t* index, uint64_t n_source_rows, uint64_t n_rows, FlSrc& S,
-                     std::vector<FlExtent>& ext) {
+                     Extents& ext) {
     const FeatGeom& G = l->G;
     if (G.n_ranges || G.W) return fail(MCBS_EINVAL, "%s: the layout has mask columns; include_masks is out of scope of the first-layer calls", who);
     uint64_t lens[5];
@@ -2304,13 +2330,12 @@ static int fl_source(const char* who, const mcbs_batch* b, const mcbs_feature_la
     for (int k = 0; k < 5; ++k) same = same && G.len[k] == lens[k];
     if (!same) return fail(MCBS_EINVAL, "%s: the layout was created for a batch of another device or geometry", who);
     S = FlSrc{};
-    static const char* const names[5] = {"scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties", "nodes_privilegelevel"};
     if (obs) {
         S.dense = FeatSrc{{obs->scalars, obs->leaked_credentials, obs->credential_cache_matrix, obs->discovered_nodes_properties, obs->nodes_privilegelevel}};
         for (uint32_t k = 0; k < 5u; ++k) {
             if (!((l->fields_used >> k) & 1u)) { S.dense.f[k] = nullptr; continue; }
-            if (!S.dense.f[k]) return fail(MCBS_EINVAL, "%s: the layout reads obs->%s, which is NULL", who, names[k]);
-            ext.push_back(fl_extent(names[k], S.dense.f[k], n_rows ? 1u : 0u, 0u, (size_t)n_rows * G.len[k], 4u, false));
+            if (!S.dense.f[k]) return fail(MCBS_EINVAL, "%s: the layout reads obs->%s, which is NULL", who, kObsFields[k]);
+            ext.bytes(kObsFields[k], S.dense.f[k], n_rows * G.len[k] * 4u, false);
         }
         return MCBS_OK;
     }
@@ -2323,8 +2348,8 @@ static int fl_source(const char* who, const mcbs_batch* b, const mcbs_feature_la
     if (!index && n_rows > n_source_rows)
         return fail(MCBS_EINVAL, "%s: %llu rows asked of %llu stored ones and no index", who, (unsigned long long)n_rows, (unsigned long long)n_source_rows);
     S.pdesc = p->desc_dev; S.packed = packed; S.packed_row_words = packed_row_words; S.index = index; S.n_source_rows = n_source_rows;
-    ext.push_back(fl_extent("packed", packed, n_source_rows, packed_row_words, p->P.W, 4u, false));
-    ext.push_back(fl_extent("index", index, n_rows ? 1u : 0u, 0u, (size_t)n_rows, 8u, false));
+    ext.rows("packed", packed, n_source_rows, packed_row_words, p->P.W, 4u, false);
+    ext.bytes("index", index, n_rows * 8u, false);
     return MCBS_OK;
 }
 
@@ -2339,15 +2364,15 @@ static int first_layer_forward(const char* who, const mcbs_batch* b, const mcbs_
     if (weight_row_stride < H) return fail(MCBS_EINVAL, "%s: weight_row_stride %zu is shorter than H = %u", who, weight_row_stride, H);
     if (out_row_stride < H) return fail(MCBS_EINVAL, "%s: out_row_stride %zu is shorter than H = %u", who, out_row_stride, H);
     FlSrc S;
-    std::vector<FlExtent> ext;
+    Extents ext;
     const size_t wes = weight_dtype == MCBS_FEATURES_F32 ? 4u : 2u, oes = out_dtype == MCBS_FEATURES_F32 ? 4u : 2u;
-    ext.push_back(fl_extent("out", out, n_rows, out_row_stride, H, oes, true));
-    ext.push_back(fl_extent("weight_t", weight_t, l->G.F, weight_row_stride, H, wes, false));
-    ext.push_back(fl_extent("bias", bias, 1u, 0u, H, wes, false));
-    ext.push_back(fl_extent("out_of_range", out_of_range, 1u, 0u, 1u, 4u, false));
+    ext.rows("out", out, n_rows, out_row_stride, H, oes, true);
+    ext.rows("weight_t", weight_t, l->G.F, weight_row_stride, H, wes, false);
+    ext.bytes("bias", bias, H * wes, false);
+    ext.bytes("out_of_range", out_of_range, 4u, false);
     int rc;
     if ((rc = fl_source(who, b, l, obs, p, packed, packed_row_words, index, n_source_rows, n_rows, S, ext))) return rc;
-    if ((rc = fl_disjoint(who, ext))) return rc;
+    if ((rc = disjoint(who, ext))) return rc;
     if (n_rows == 0) return MCBS_OK;
     const uint64_t groups = (n_rows + FL_ROWS - 1u) / FL_ROWS;
     if (groups > 0x7FFFFFFFull) return fail(MCBS_EINVAL, "%s: too many rows", who);
@@ -2410,18 +2435,18 @@ extern "C" int mcbs_first_layer_grad(const mcbs_batch* b, const mcbs_feature_lay
         if (grad_out_row_stride < H) return fail(MCBS_EINVAL, "%s: grad_out_row_stride %zu is shorter than H = %u", who, grad_out_row_stride, H);
     }
     FlSrc S;
-    std::vector<FlExtent> ext;
+    Extents ext;
     const uint32_t F = l->G.F;
     const size_t need = mcbs_first_layer_grad_workspace(b, l, n_rows, H);
-    ext.push_back(fl_extent("grad_weight_t", grad_weight_t, F, grad_weight_row_stride, H, 4u, true));
-    ext.push_back(fl_extent("grad_bias", grad_bias, 1u, 0u, H, 4u, true));
-    ext.push_back(fl_extent("workspace", workspace, need ? 1u : 0u, 0u, need, 1u, true));
-    ext.push_back(fl_extent("grad_out", grad_out, n_rows, grad_out_row_stride, H, 4u, false));
+    ext.rows("grad_weight_t", grad_weight_t, F, grad_weight_row_stride, H, 4u, true);
+    ext.bytes("grad_bias", grad_bias, H * 4u, true);
+    ext.bytes("workspace", workspace, need, true);
+    ext.rows("grad_out", grad_out, n_rows, grad_out_row_stride, H, 4u, false);
     int rc;
     if ((rc = fl_source(who, b, l, obs, p, packed, packed_row_words, index, n_source_rows, n_rows, S, ext))) return rc;
     if (need && (!workspace || workspace_bytes < need))
         return fail(MCBS_EINVAL, "%s: the workspace must hold %zu bytes (mcbs_first_layer_grad_workspace), got %zu at %p", who, need, workspace_bytes, workspace);
-    if ((rc = fl_disjoint(who, ext))) return rc;
+    if ((rc = disjoint(who, ext))) return rc;
     const uint64_t n_blocks = (n_rows + FLG_ROW_BLOCK - 1u) / FLG_ROW_BLOCK;
     const uint32_t n_slabs = grad_weight_t ? (l->n_elements + FLG_WAVES * FLG_EPW - 1u) / (FLG_WAVES * FLG_EPW) : 1u;
     if (n_blocks * (n_slabs ? n_slabs : 1u) > 0x7FFFFFFFull) return fail(MCBS_EINVAL, "%s: too many rows", who);
@@ -2456,20 +2481,6 @@ static DefObs fused_defender_obs(const mcbs_batch* b, const mcbs_defender_obs* o
     return d;
 }
 
-extern "C" int32_t mcbs_step_is_lean(const mcbs_batch* b, int32_t with_info) {
-    return (b && b->lean_step && !with_info) ? 1 : 0;
-}
-extern "C" int32_t mcbs_step_topo_traits(const mcbs_batch* b, int32_t with_info, uint32_t* traits) {
-    if (traits) *traits = b ? b->topo->hot.traits : 0u;
-    return (b && b->narrow_step && !with_info) ? 1 : 0;
-}
-
-extern "C" int mcbs_batch_variant(const mcbs_batch* b, mcbs_batch_variant_info* out) {
-    if (!b || !out) return fail(MCBS_EINVAL, "null argument");
-    *out = b->variant;
-    return MCBS_OK;
-}
-
 static int launch_defender_obs(mcbs_batch* b, const mcbs_defender_obs* o, hipStream_t st) {
     const uint32_t total = b->S.E * b->S.N;
     hipLaunchKernelGGL(defender_obs_kernel, dim3((total + 255) / 256), dim3(256), 0, st, b->S, b->T, o->infected_nodes,
@@ -2483,7 +2494,8 @@ static int learned_defender_ok(const mcbs_batch* b) {
 }
 
 // One turn of the learned defender: 128 envs per workgroup, launch(WT, grid, block, observation arguments) for the batch's words per set;
-// then the observation as a launch of its own where the turn kernel could not write it
+// then the observation as a launch of its own where the turn kernel could not write it.  obs == nullptr: no dense observation is asked for —
+// also the call of a kernel that writes an observation of its own (the packed rows) and ignores the DefObs it is handed
 template <class Launch>
 static int launch_defender_turn(mcbs_batch* b, const mcbs_defender_obs* obs, hipStream_t st, const char* what, Launch&& launch) {
     b->all_fresh = false;
@@ -2532,6 +2544,9 @@ static int defender_packing_ok(const mcbs_batch* b, const char* who, size_t row_
 static bool defender_obs_complete(const mcbs_defender_obs* o) {
     return o->infected_nodes && o->incoming_firewall_status && o->outgoing_firewall_status && o->services_status;
 }
+// the four fields in the packed row's COLUMN order, as the kernels read (DefDense) or write (DefDenseOut) them
+template <class D = DefDense>
+static D def_dense(const mcbs_defender_obs* o) { return D{{o->incoming_firewall_status, o->infected_nodes, o->outgoing_firewall_status, o->services_status}}; }
 
 extern "C" uint32_t mcbs_defender_obs_words(const mcbs_batch* b) {
     return (b && b->cfg.defender_kind == MCBS_DEFENDER_EXTERNAL) ? b->def_pack.W : 0u;
@@ -2570,8 +2585,8 @@ extern "C" int mcbs_pack_defender_observation(const mcbs_batch* b, const mcbs_de
     if (const int rc = defender_packing_ok(b, "mcbs_pack_defender_observation", row_words)) return rc;
     if (!defender_obs_complete(dense)) return fail(MCBS_EINVAL, "mcbs_pack_defender_observation: all four int8 fields are packed, one is NULL");
     if (n_rows == 0) return MCBS_OK;
-    const DefDense src{{dense->incoming_firewall_status, dense->infected_nodes, dense->outgoing_firewall_status, dense->services_status}};
-    hipLaunchKernelGGL(pack_defender_obs_kernel, defender_rows_grid(n_rows, 32u, 16384u), dim3(256), 0, (hipStream_t)stream, b->def_pack, src, n_rows, out, row_words);
+    hipLaunchKernelGGL(pack_defender_obs_kernel, defender_rows_grid(n_rows, 32u, 16384u), dim3(256), 0, (hipStream_t)stream, b->def_pack, def_dense(dense),
+                       n_rows, out, row_words);
     return launch_ok("pack defender observation");
 }
 
@@ -2583,9 +2598,8 @@ extern "C" int mcbs_unpack_defender_observation(const mcbs_batch* b, const uint3
     if (!index && n_rows > n_source_rows) return fail(MCBS_EINVAL, "mcbs_unpack_defender_observation: %llu rows asked of %llu stored ones and no index",
                                                       (unsigned long long)n_rows, (unsigned long long)n_source_rows);
     if (n_rows == 0) return MCBS_OK;
-    const DefDenseOut dst{{out->incoming_firewall_status, out->infected_nodes, out->outgoing_firewall_status, out->services_status}};
     hipLaunchKernelGGL(unpack_defender_obs_kernel, defender_rows_grid(n_rows, 32u, 16384u), dim3(256), 0, (hipStream_t)stream, b->def_pack, packed, row_words,
-                       index, n_source_rows, n_rows, dst);
+                       index, n_source_rows, n_rows, def_dense<DefDenseOut>(out));
     return launch_ok("unpack defender observation");
 }
 
@@ -2605,8 +2619,7 @@ extern "C" int mcbs_encode_defender_features(const mcbs_batch* b, const mcbs_def
     if (!index && n_rows > n_source_rows) return fail(MCBS_EINVAL, "%s: %llu rows asked of %llu stored ones and no index", who,
                                                       (unsigned long long)n_rows, (unsigned long long)n_source_rows);
     if (n_rows == 0) return MCBS_OK;
-    DefDense src{};
-    if (dense) src = DefDense{{dense->incoming_firewall_status, dense->infected_nodes, dense->outgoing_firewall_status, dense->services_status}};
+    const DefDense src = dense ? def_dense(dense) : DefDense{};
     const size_t item = dtype == MCBS_FEATURES_F32 ? 4u : 2u;
     const uint32_t one = dtype == MCBS_FEATURES_F32 ? 0x3F800000u : dtype == MCBS_FEATURES_BF16 ? 0x3F80u : 0x3C00u;      // 1.0 as the dtype's pattern
     rows_dispatch<1u, 2u>(item, out, out_row_stride, [&](auto es, auto gw, auto vec) {
@@ -2639,14 +2652,11 @@ extern "C" int mcbs_defender_wrapper_step_packed(mcbs_batch* b, const int64_t* a
     if (!arrays_set(w, 0)) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
     hipStream_t st = (hipStream_t)stream;
     const bool fused = b->variant.fused_defender_obs && reinterpret_cast<uintptr_t>(packed_out) % 16 == 0;
-    if (fused) {
-        b->all_fresh = false;
-        pick<1, 2, 4>((int)b->S.WT, [&](auto wt) {
-            hipLaunchKernelGGL((defender_turn_post_packed_kernel<decltype(wt)::value>), dim3((b->S.E + 127) / 128), dim3(128), 0, st, b->S, b->T, b->C_dev, actions,
-                               *w, *cfg, b->def_pack, packed_out, row_words);
+    if (fused)
+        return launch_defender_turn(b, nullptr, st, "defender turn + reward shaping + packed observation", [&](auto wt, dim3 grid, dim3 block, const DefObs&) {
+            hipLaunchKernelGGL((defender_turn_post_packed_kernel<decltype(wt)::value>), grid, block, 0, st, b->S, b->T, b->C_dev, actions, *w, *cfg, b->def_pack,
+                               packed_out, row_words);
         });
-        return launch_ok("defender turn + reward shaping + packed observation");
-    }
     const int rc = launch_defender_turn(b, nullptr, st, "defender turn + reward shaping", [&](auto wt, dim3 grid, dim3 block, const DefObs& dob) {
         hipLaunchKernelGGL((defender_turn_post_kernel<decltype(wt)::value>), grid, block, 0, st, b->S, b->T, b->C_dev, actions, *w, *cfg, dob);
     });
@@ -2675,11 +2685,8 @@ extern "C" int mcbs_two_agent_step(mcbs_batch* b, const int64_t* multidiscrete, 
     MCBS_ON_DEVICE(b);
     // every check before the launch: a refused call launches nothing and changes no state
     if (const char* why = two_agent_batch_reason(b)) return fail(MCBS_EINVAL, "two-agent turn: %s", why);
-    WrapperFinishArgs unused;
-    int rc = finish_args(b, w, modifier, attacker_max_timesteps, 0, nullptr, nullptr, &unused);
-    if (rc) return rc;
-    if ((rc = draws_ok(b))) return rc;
-    if (!multidiscrete == !discrete) return fail(MCBS_EINVAL, "need exactly one action encoding");
+    StepIO io;
+    if (const int rc = attacker_turn_io(b, multidiscrete, discrete, decoded, info, w, modifier, attacker_max_timesteps, 0, nullptr, nullptr, &io)) return rc;
     if (!arrays_set(dw, 0)) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
     if (ep && !arrays_set(ep, 0)) return fail(MCBS_EINVAL, "mcbs_episode_buffers: every array is required");
     TwoAgentArgs D{};
@@ -2691,13 +2698,9 @@ extern "C" int mcbs_two_agent_step(mcbs_batch* b, const int64_t* multidiscrete, 
     if (!fused_wrapper_args(b, multidiscrete, discrete, decoded, obs, w, modifier, attacker_max_timesteps, 0, nullptr, nullptr, &A))
         return fail(MCBS_EINVAL, "two-agent turn: the attacker's request is outside the one-launch wrapper step (a mask field, or an observation "
                                  "array that is not on a 16-byte boundary)");
-    const StepIO io = make_io(b, decoded, const_cast<float*>(w->reward), const_cast<uint8_t*>(w->terminated), info);
     b->all_fresh = false;
     hipLaunchKernelGGL(two_agent_kernel, dim3((b->S.E + 63u) / 64u), dim3(FUSED_THREADS), 0, (hipStream_t)stream, b->S, b->T, b->C_dev, io, A, D);
-    rc = launch_ok("two-agent turn");
-    if (rc) return rc;
-    b->digest_state = 1;       // every env's digest was written (or, for an intercepted action, stands)
-    return MCBS_OK;
+    return turn_launched(b, "two-agent turn");
 }
 
 // ---- the training turn: both auto-resets and the reset_request hand-shake in the same launch (two_agent_train_kernel)
@@ -2715,15 +2718,11 @@ extern "C" int mcbs_two_agent_train_step(mcbs_batch* b, const int64_t* multidisc
     MCBS_ON_DEVICE(b);
     // every check before the launch: a refused call launches nothing and changes no state
     if (const char* why = two_agent_batch_reason(b)) return fail(MCBS_EINVAL, "%s: %s", who, why);
-    WrapperFinishArgs unused;
-    int rc = finish_args(b, w, modifier, attacker_max_timesteps, 1, keep, fresh, &unused);
-    if (rc) return rc;
-    if ((rc = draws_ok(b))) return rc;
-    if (!multidiscrete == !discrete) return fail(MCBS_EINVAL, "need exactly one action encoding");
+    StepIO io;
+    if (const int rc = attacker_turn_io(b, multidiscrete, discrete, decoded, info, w, modifier, attacker_max_timesteps, 1, keep, fresh, &io)) return rc;
     if (!arrays_set(dw, 0)) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
     if (!arrays_set(tr, 0)) return fail(MCBS_EINVAL, "mcbs_training_buffers: every array is required");
-    if (!defender_obs->infected_nodes || !defender_obs->incoming_firewall_status || !defender_obs->outgoing_firewall_status || !defender_obs->services_status)
-        return fail(MCBS_EINVAL, "%s: every field of the defender's observation is required", who);
+    if (!defender_obs_complete(defender_obs)) return fail(MCBS_EINVAL, "%s: every field of the defender's observation is required", who);
     TrainArgs D{};
     D.actions = defender_actions; D.dw = *dw; D.dcfg = *dcfg;
     D.obs = fused_defender_obs(b, defender_obs);
@@ -2742,69 +2741,25 @@ extern "C" int mcbs_two_agent_train_step(mcbs_batch* b, const int64_t* multidisc
         return fail(MCBS_EINVAL, "%s: the attacker's request is outside the one-launch wrapper step (a mask field, an observation array that is "
                                  "not on a 16-byte boundary, or a field without its terminal array in `keep` and its reset row in `fresh`)", who);
     // no array this launch writes may share a byte with another array it reads or writes
-    {
-        const uint64_t E = b->S.E, N = b->S.N, Sv = b->C.n_services;
-        struct Extent { const char* name; uintptr_t lo, hi; bool out; };
-        std::vector<Extent> ext;
-        auto add = [&](const char* name, const void* q, uint64_t bytes, bool out) {
-            const uintptr_t lo = reinterpret_cast<uintptr_t>(q);
-            if (q && bytes) ext.push_back(Extent{name, lo, lo + (uintptr_t)bytes, out});
-        };
-        add("decoded", decoded, E * 20u, true); add("multidiscrete", multidiscrete, E * 80u, false); add("discrete", discrete, E * 8u, false);
-        add("defender_actions", defender_actions, E * 96u, false);
-        static const char* const fields[FUSED_FIELDS] = {"scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties",
-                                                         "nodes_privilegelevel"};
-        for (uint32_t f = 0; f < FUSED_FIELDS; ++f) {
-            add(fields[f], A.obs[f], E * 4u * A.dwords[f], true);
-            add("a terminal observation array (keep)", A.obs[f] ? A.term[f] : nullptr, E * 4u * A.dwords[f], true);
-            add("a reset row (fresh)", A.obs[f] ? A.fresh[f] : nullptr, 4ull * A.dwords[f], false);
-        }
-        add("w->invalid", w->invalid, E, true); add("w->reward", w->reward, E * 4u, true); add("w->terminated", w->terminated, E, true);
-        add("w->timesteps", w->timesteps, E * 4u, true); add("w->valid_action_count", w->valid_action_count, E * 8u, true);
-        add("w->invalid_action_count", w->invalid_action_count, E * 8u, true); add("w->episode_returns", w->episode_returns, E * 8u, true);
-        add("w->last_cyber_reward", w->last_cyber_reward, E * 4u, true); add("w->has_cyber_reward", w->has_cyber_reward, E, true);
-        add("w->rewards", w->rewards, E * 4u, true); add("w->truncated", w->truncated, E, true); add("w->dones", w->dones, E, true);
-        add("w->episode_return_out", w->episode_return_out, E * 8u, true); add("w->episode_length_out", w->episode_length_out, E * 4u, true);
-        add("w->executed", w->executed, E, true);
-        add("info->network_availability", info ? info->network_availability : nullptr, E * 8u, true);
-        add("info->step_count", info ? info->step_count : nullptr, E * 4u, true); add("info->truncated", info ? info->truncated : nullptr, E, true);
-        add("info->out_of_bound", info ? info->out_of_bound : nullptr, E, true); add("info->raw_reward", info ? info->raw_reward : nullptr, E * 4u, true);
-        add("defender_obs->infected_nodes", defender_obs->infected_nodes, E * N, true);
-        add("defender_obs->incoming_firewall_status", defender_obs->incoming_firewall_status, E * N * 6u, true);
-        add("defender_obs->outgoing_firewall_status", defender_obs->outgoing_firewall_status, E * N * 6u, true);
-        add("defender_obs->services_status", defender_obs->services_status, E * Sv, true);
-        add("dw->valid", dw->valid, E, true); add("dw->availability", dw->availability, E * 8u, true); add("dw->evicted", dw->evicted, E, true);
-        // (dw->attacker_has_cyber_reward / attacker_last_cyber_reward ARE w->has_cyber_reward / last_cyber_reward: read where the attacker half wrote)
-        add("dw->timesteps", dw->timesteps, E * 4u, true); add("dw->valid_action_count", dw->valid_action_count, E * 8u, true);
-        add("dw->invalid_action_count", dw->invalid_action_count, E * 8u, true); add("dw->has_breached_sla", dw->has_breached_sla, E, true);
-        add("dw->prev_availability", dw->prev_availability, E * 8u, true); add("dw->reward", dw->reward, E * 8u, true);
-        add("dw->terminated", dw->terminated, E, true); add("dw->truncated", dw->truncated, E, true); add("dw->breached", dw->breached, E, true);
-        add("dw->won", dw->won, E, true);
-        add("tr->attacker_reset_request", tr->attacker_reset_request, E, true); add("tr->defender_return", tr->defender_return, E * 8u, true);
-        add("tr->attacker_valid_out", tr->attacker_valid_out, E * 8u, true); add("tr->attacker_invalid_out", tr->attacker_invalid_out, E * 8u, true);
-        add("tr->defender_return_out", tr->defender_return_out, E * 8u, true); add("tr->defender_length_out", tr->defender_length_out, E * 4u, true);
-        add("tr->defender_valid_out", tr->defender_valid_out, E * 8u, true); add("tr->defender_invalid_out", tr->defender_invalid_out, E * 8u, true);
-        add("tr->defender_dones", tr->defender_dones, E, true);
-        add("tr->terminal_infected_nodes", tr->terminal_infected_nodes, E * N, true);
-        add("tr->terminal_incoming_firewall_status", tr->terminal_incoming_firewall_status, E * N * 6u, true);
-        add("tr->terminal_outgoing_firewall_status", tr->terminal_outgoing_firewall_status, E * N * 6u, true);
-        add("tr->terminal_services_status", tr->terminal_services_status, E * Sv, true);
-        add("tr->fresh_infected_nodes", tr->fresh_infected_nodes, N, false);
-        add("tr->fresh_incoming_firewall_status", tr->fresh_incoming_firewall_status, N * 6u, false);
-        add("tr->fresh_outgoing_firewall_status", tr->fresh_outgoing_firewall_status, N * 6u, false);
-        for (size_t i = 0; i < ext.size(); ++i)
-            for (size_t k = i + 1u; k < ext.size(); ++k)
-                if ((ext[i].out || ext[k].out) && ext[i].lo < ext[k].hi && ext[k].lo < ext[i].hi)
-                    return fail(MCBS_EINVAL, "%s: %s overlaps %s", who, ext[i].name, ext[k].name);
+    const uint64_t E = b->S.E, N = b->S.N, Sv = b->C.n_services;
+    Extents ext;
+    ext.bytes("decoded", decoded, E * 20u, true); ext.bytes("multidiscrete", multidiscrete, E * 80u, false);
+    ext.bytes("discrete", discrete, E * 8u, false); ext.bytes("defender_actions", defender_actions, E * 96u, false);
+    static_assert(FUSED_FIELDS == 5, "kObsFields names the fused step's fields");
+    for (uint32_t f = 0; f < FUSED_FIELDS; ++f) {
+        ext.bytes(kObsFields[f], A.obs[f], E * 4u * A.dwords[f], true);
+        ext.bytes("a terminal observation array (keep)", A.obs[f] ? A.term[f] : nullptr, E * 4u * A.dwords[f], true);
+        ext.bytes("a reset row (fresh)", A.obs[f] ? A.fresh[f] : nullptr, 4ull * A.dwords[f], false);
     }
-    const StepIO io = make_io(b, decoded, const_cast<float*>(w->reward), const_cast<uint8_t*>(w->terminated), info);
+    add_arrays(ext, "w->", w, kWrapperArrays, E, N, Sv, true);
+    add_arrays(ext, "info->", info, kInfoArrays, E, N, Sv, true);
+    add_arrays(ext, "defender_obs->", defender_obs, kDefenderObsArrays, E, N, Sv, true);
+    add_arrays(ext, "dw->", dw, kDefenderWrapperArrays, E, N, Sv, true);
+    add_arrays(ext, "tr->", tr, kTrainingArrays, E, N, Sv, true);
+    if (const int rc = disjoint(who, ext)) return rc;
     b->all_fresh = false;
     hipLaunchKernelGGL(two_agent_train_kernel, dim3((b->S.E + 63u) / 64u), dim3(FUSED_THREADS), 0, (hipStream_t)stream, b->S, b->T, b->C_dev, io, A, D);
-    rc = launch_ok("two-agent training turn");
-    if (rc) return rc;
-    b->digest_lists = true;    // the digests this launch wrote carry their observation's discovery order
-    b->digest_state = 1;       // every env's digest was written (or, for an intercepted action, stands)
-    return MCBS_OK;
+    return turn_launched(b, "two-agent training turn", true);      // (the digests it wrote carry their observation's discovery order)
 }
 
 // ------------------------------------------------------------------ state export / import (debug, synchronous)
