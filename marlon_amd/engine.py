@@ -96,6 +96,15 @@ def _row_stride(x, rows: int) -> int:
     return x.stride(0) if rows > 1 else max(x.stride(0), x.shape[1])
 
 
+# BatchEngine._bound: where the per-call values go in a bound call's argument list
+_ACTIONS, _ACTIONS2, _EPISODE, _STREAM = "<actions>", "<second actions>", "<episode block>", "<stream>"
+
+
+def _attacker_actions(discrete: bool):
+    """The attacker entry points' (MultiDiscrete rows, Discrete indices) pointer pair: the call's actions in the one, NULL in the other."""
+    return (None, _ACTIONS) if discrete else (_ACTIONS, None)
+
+
 def topology_traits(topo: FlatTopology) -> int:
     """The MCBS_TOPO_* bits (_abi.TOPO_*) the native library derives from a topology's blob; computed on the host, no GPU needed."""
     lib = load_library()
@@ -527,38 +536,50 @@ class BatchEngine:
             rc.src[i], rc.dst[i], rc.row_bytes[i] = src.data_ptr(), dst.data_ptr(), dst[0].numel() * dst.element_size()
         return rc
 
-    def wrapper_finish(self, bufs, modifier: float, max_timesteps: int, auto_reset: bool, keep=(), fresh=()) -> None:
-        """mcbs_attacker_wrapper_finish: the wrapper's bookkeeping and — for the envs it flags done — terminal observation (`keep`:
-        (obs, terminal) pairs), env reset, reset observation (`fresh`: ([1, ...] row of a freshly reset env, obs) pairs) and cleared
-        counters, all in one launch.  `keep` / `fresh` may be argument blocks built once with `row_copies()`."""
-        k = keep if isinstance(keep, RowCopies) else self._row_copies(list(keep), False)
-        f = fresh if isinstance(fresh, RowCopies) else self._row_copies(list(fresh), True)
-        _check(self.lib, self.lib.mcbs_attacker_wrapper_finish(self._h, C.byref(bufs), float(modifier), int(max_timesteps), int(bool(auto_reset)),
-                                                               C.byref(k), C.byref(f), self._stream()), "mcbs_attacker_wrapper_finish")
+    def _bound(self, name: str, *args, keep=()):
+        """callable(p), or callable(p, q, ep=None) where args hold _ACTIONS2: the library function `name` on this batch with every argument but
+        the per-call ones bound ONCE — the argument blocks' references and conversions are most of what a per-step call costs on the host next to the launch itself.
+        args: what follows the batch handle, in the prototype's order: numbers and None as they are, a tensor as its device pointer, a
+        ctypes block as a reference to it; and, by position, the per-call values: _ACTIONS <- p, _ACTIONS2 <- q (actions pointers),
+        _EPISODE <- a reference to ep (an _abi.EpisodeBuffers the caller keeps alive) or NULL, _STREAM <- torch's current stream, queried
+        per call.  The batch handle is read per call too (None once the engine is closed: the library refuses it); a failure raises
+        through _check under the entry point's name.  The closure keeps alive every tensor and block it points into, and `keep`."""
+        fn, eng, lib, stream = getattr(self.lib, name), self, self.lib, self._stream
+        Tensor, blocks = self.torch.Tensor, (C.Structure, C.Array)
+        argv = [None] + [x.data_ptr() if isinstance(x, Tensor) else C.byref(x) if isinstance(x, blocks) else x for x in args]
+        ip, iq, ie, ist = (argv.index(m) if m in argv else None for m in (_ACTIONS, _ACTIONS2, _EPISODE, _STREAM))
+        if ie is not None:
+            argv[ie] = None
 
-    def wrapper_step(self, actions, discrete: bool, decoded, obs_struct, bufs, modifier: float, max_timesteps: int, auto_reset: bool, keep, fresh) -> None:
-        """mcbs_attacker_wrapper_step: decode, environment step + observation, bookkeeping / auto-reset — one call, five launches.
-        `actions`: int64 device tensor ([E] Discrete or [E, 10] MultiDiscrete); `obs_struct`: obs_struct(obs) built once; `bufs` /
-        `keep` / `fresh`: argument blocks built once (WrapperBuffers, row_copies())."""
-        p = actions.data_ptr()
-        _check(self.lib, self.lib.mcbs_attacker_wrapper_step(self._h, None if discrete else p, p if discrete else None, decoded.data_ptr(),
-                                                             C.byref(self._info_struct), C.byref(obs_struct), C.byref(bufs), float(modifier),
-                                                             int(max_timesteps), int(bool(auto_reset)), C.byref(keep), C.byref(fresh), self._stream()),
-               "mcbs_attacker_wrapper_step")
+        # one pointer or two: a missing or a surplus actions pointer is a TypeError on the host, as is an episode block handed to an entry
+        # point that has no _EPISODE slot (ie is None).  The two bodies end alike; a shared tail would cost every step a Python call.
+        if iq is None:
+            if ie is not None:
+                raise ValueError(f"{name}: an episode block without second actions")
+
+            def call(p: int, *, _alive=(args, keep)) -> None:
+                a = argv.copy()
+                a[0], a[ip], a[ist] = eng._h, p, stream()
+                rc = fn(*a)
+                if rc:
+                    _check(lib, rc, name)
+        else:
+            def call(p: int, q: int, ep=None, *, _alive=(args, keep)) -> None:
+                a = argv.copy()
+                a[0], a[ip], a[iq], a[ist] = eng._h, p, q, stream()
+                if ep is not None:
+                    a[ie] = C.byref(ep)
+                rc = fn(*a)
+                if rc:
+                    _check(lib, rc, name)
+        return call
 
     def wrapper_step_call(self, discrete: bool, decoded, obs_struct, bufs, modifier: float, max_timesteps: int, auto_reset: bool, keep, fresh):
-        """callable(actions_ptr): wrapper_step with every argument but the actions (and the stream, queried per call) bound ONCE — the
-        argument blocks' references and conversions are most of what a per-step call costs on the host next to the launch itself."""
-        fn, eng, lib, stream = self.lib.mcbs_attacker_wrapper_step, self, self.lib, self._stream       # (eng._h is None once closed: refused)
-        refs = (C.byref(self._info_struct), C.byref(obs_struct), C.byref(bufs), C.byref(keep), C.byref(fresh))
-        rows, mod, mt, ar = decoded.data_ptr(), float(modifier), int(max_timesteps), int(bool(auto_reset))
-        alive = (decoded, obs_struct, bufs, keep, fresh, self._info_struct)       # the blocks the references point into
-
-        def call(p: int, _alive=alive) -> None:
-            rc = fn(eng._h, None if discrete else p, p if discrete else None, rows, refs[0], refs[1], refs[2], mod, mt, ar, refs[3], refs[4], stream())
-            if rc:
-                _check(lib, rc, "mcbs_attacker_wrapper_step")
-        return call
+        """callable(actions_ptr): mcbs_attacker_wrapper_step — decode, environment step + observation, bookkeeping / auto-reset — with every
+        argument but the actions bound once (_bound).  `decoded`: int32 [E, 5]; `obs_struct`: obs_struct(obs); `bufs` / `keep` / `fresh`:
+        argument blocks built once (WrapperBuffers, row_copies())."""
+        return self._bound("mcbs_attacker_wrapper_step", *_attacker_actions(discrete), decoded, self._info_struct, obs_struct, bufs, float(modifier),
+                           int(max_timesteps), int(bool(auto_reset)), keep, fresh, _STREAM)
 
     def wrapper_step_packed_call(self, discrete: bool, decoded, packing: "ObservationPackingHandle", packed, packed_terminal, packed_fresh, bufs,
                                  modifier: float, max_timesteps: int, auto_reset: bool):
@@ -576,29 +597,14 @@ class BatchEngine:
         if packed_fresh is not None:
             if packed_fresh.dtype != t.int32 or packed_fresh.device != self.device or not packed_fresh.is_contiguous() or packed_fresh.numel() < packing.words:
                 raise ValueError(f"packed_fresh must be a contiguous device int32 tensor of at least {packing.words} words, got {_describe(packed_fresh)}")
-        fn, eng, lib, stream = self.lib.mcbs_attacker_wrapper_step_packed, self, self.lib, self._stream
-        refs = (C.byref(self._info_struct), C.byref(bufs))
-        rows, mod, mt, ar = decoded.data_ptr(), float(modifier), int(max_timesteps), int(bool(auto_reset))
-        ph, pp, pt, pf = packing.ptr, packed.data_ptr(), _ptr(packed_terminal), _ptr(packed_fresh)
-        alive = (decoded, packing, packed, packed_terminal, packed_fresh, bufs, self._info_struct)
-
-        def call(p: int, _alive=alive) -> None:
-            rc = fn(eng._h, None if discrete else p, p if discrete else None, rows, refs[0], ph, pp, pt, pf, stride, refs[1], mod, mt, ar, stream())
-            if rc:
-                _check(lib, rc, "mcbs_attacker_wrapper_step_packed")
-        return call
+        return self._bound("mcbs_attacker_wrapper_step_packed", *_attacker_actions(discrete), decoded, self._info_struct, packing.ptr, packed,
+                           packed_terminal, packed_fresh, stride, bufs, float(modifier), int(max_timesteps), int(bool(auto_reset)), _STREAM,
+                           keep=(packing,))
 
     def defender_wrapper_step_call(self, obs_struct, bufs, cfg):
-        """callable(actions_ptr): defender_wrapper_step with the argument blocks bound once."""
-        fn, eng, lib, stream = self.lib.mcbs_defender_wrapper_step, self, self.lib, self._stream
-        refs = (C.byref(obs_struct) if obs_struct is not None else None, C.byref(bufs), C.byref(cfg))
-        alive = (obs_struct, bufs, cfg)
-
-        def call(p: int, _alive=alive) -> None:
-            rc = fn(eng._h, p, refs[0], refs[1], refs[2], stream())
-            if rc:
-                _check(lib, rc, "mcbs_defender_wrapper_step")
-        return call
+        """callable(actions_ptr): mcbs_defender_wrapper_step — the defender's turn + the wrapper's reward shaping in one launch, then the
+        observation — with the argument blocks bound once.  `obs_struct`: a DefenderObs block (or None)."""
+        return self._bound("mcbs_defender_wrapper_step", _ACTIONS, obs_struct, bufs, cfg, _STREAM)
 
     def two_agent_step_launches(self) -> int:
         """1 when mcbs_two_agent_step serves this batch (both wrappers' steps and the episode bookkeeping in one launch), else 0."""
@@ -609,18 +615,8 @@ class BatchEngine:
         """callable(attacker_actions_ptr, defender_actions_ptr, episode_block or None): mcbs_two_agent_step with every argument block but
         the episode's bound once, like wrapper_step_call / defender_wrapper_step_call.  `episode_block`: an _abi.EpisodeBuffers the caller
         keeps alive (its two reward rows move from turn to turn)."""
-        fn, eng, lib, stream = self.lib.mcbs_two_agent_step, self, self.lib, self._stream
-        refs = (C.byref(self._info_struct), C.byref(obs_struct), C.byref(bufs), C.byref(defender_obs_struct), C.byref(defender_bufs),
-                C.byref(defender_cfg))
-        rows, mod, mt = decoded.data_ptr(), float(modifier), int(max_timesteps)
-        alive = (decoded, obs_struct, bufs, defender_obs_struct, defender_bufs, defender_cfg, self._info_struct)
-
-        def call(p: int, q: int, ep=None, _alive=alive) -> None:
-            rc = fn(eng._h, None if discrete else p, p if discrete else None, rows, refs[0], refs[1], refs[2], mod, mt, q, refs[3], refs[4], refs[5],
-                    C.byref(ep) if ep is not None else None, stream())
-            if rc:
-                _check(lib, rc, "mcbs_two_agent_step")
-        return call
+        return self._bound("mcbs_two_agent_step", *_attacker_actions(discrete), decoded, self._info_struct, obs_struct, bufs, float(modifier),
+                           int(max_timesteps), _ACTIONS2, defender_obs_struct, defender_bufs, defender_cfg, _EPISODE, _STREAM)
 
     def two_agent_train_step_launches(self) -> int:
         """1 when mcbs_two_agent_train_step serves this batch (the training turn: both wrappers' steps, both auto-resets and the
@@ -632,29 +628,19 @@ class BatchEngine:
         """callable(attacker_actions_ptr, defender_actions_ptr): mcbs_two_agent_train_step with every argument block bound once, like
         two_agent_step_call.  keep / fresh: row_copies() blocks that pair every observation field with its terminal array and its reset
         row; training_block: an _abi.TrainingBuffers whose arrays the caller keeps alive."""
-        fn, eng, lib, stream = self.lib.mcbs_two_agent_train_step, self, self.lib, self._stream
-        refs = (C.byref(self._info_struct), C.byref(obs_struct), C.byref(bufs), C.byref(keep), C.byref(fresh), C.byref(defender_obs_struct),
-                C.byref(defender_bufs), C.byref(defender_cfg), C.byref(training_block))
-        rows, mod, mt = decoded.data_ptr(), float(modifier), int(max_timesteps)
-        alive = (decoded, obs_struct, bufs, keep, fresh, defender_obs_struct, defender_bufs, defender_cfg, training_block, self._info_struct)
-
-        def call(p: int, q: int, _alive=alive) -> None:
-            rc = fn(eng._h, None if discrete else p, p if discrete else None, rows, refs[0], refs[1], refs[2], mod, mt, refs[3], refs[4], q, refs[5],
-                    refs[6], refs[7], refs[8], stream())
-            if rc:
-                _check(lib, rc, "mcbs_two_agent_train_step")
-        return call
+        return self._bound("mcbs_two_agent_train_step", *_attacker_actions(discrete), decoded, self._info_struct, obs_struct, bufs, float(modifier),
+                           int(max_timesteps), keep, fresh, _ACTIONS2, defender_obs_struct, defender_bufs, defender_cfg, training_block, _STREAM)
 
     def wrapper_step_launches(self, with_masks: bool) -> int:
         """Kernel launches per mcbs_attacker_wrapper_step of this batch (1: the whole wrapper step is one launch; 3 otherwise)."""
         return int(self.lib.mcbs_attacker_wrapper_step_launches(self._h, int(bool(with_masks))))
 
     def obs_struct(self, obs: dict):
-        """Argument block (_abi.ObsBuffers) for wrapper_step, built once for a set of persistent observation tensors."""
+        """Argument block (_abi.ObsBuffers) for wrapper_step_call and the two-agent calls, built once for a set of persistent observation tensors."""
         return self._obs_struct(obs)
 
     def row_copies(self, pairs, one_row_src: bool = False):
-        """Argument block (_abi.RowCopies) for wrapper_finish, built once and reused across steps."""
+        """Argument block (_abi.RowCopies) for wrapper_step_call's keep / fresh lists, built once and reused across steps."""
         return self._row_copies(list(pairs), one_row_src)
 
     def wrapper_clear(self, bufs) -> None:
@@ -1438,12 +1424,6 @@ class BatchEngine:
                                                      C.byref(o) if o is not None else None, self._stream()), "mcbs_defender_step")
         return v, av, ev
 
-    def defender_wrapper_step(self, actions12, obs_struct, bufs, cfg) -> None:
-        """mcbs_defender_wrapper_step: the defender's turn + the wrapper's reward shaping in one launch, then the observation.
-        `actions12`: int64 device tensor [E, 12]; `obs_struct`: a DefenderObs block (or None); `bufs` / `cfg`: argument blocks built once."""
-        _check(self.lib, self.lib.mcbs_defender_wrapper_step(self._h, actions12.data_ptr(), C.byref(obs_struct) if obs_struct is not None else None,
-                                                             C.byref(bufs), C.byref(cfg), self._stream()), "mcbs_defender_wrapper_step")
-
     def defender_observe(self, obs: dict) -> dict:
         o = DefenderObs(**{k: x.data_ptr() for k, x in obs.items()})
         _check(self.lib, self.lib.mcbs_defender_observe(self._h, C.byref(o), self._stream()), "mcbs_defender_observe")
@@ -1562,16 +1542,7 @@ class BatchEngine:
         """callable(actions_ptr): mcbs_defender_wrapper_step_packed — the defender's wrapper step whose observation output is the packed
         row — with the argument blocks bound once.  packed: device int32 [E, >= W_def] with contiguous rows."""
         self._defender_packed_rows(packed, "packed", self.E)
-        fn, eng, lib, stream = self.lib.mcbs_defender_wrapper_step_packed, self, self.lib, self._stream
-        refs = (C.byref(bufs), C.byref(cfg))
-        pp, stride = packed.data_ptr(), _row_stride(packed, self.E)
-        alive = (packed, bufs, cfg)
-
-        def call(p: int, _alive=alive) -> None:
-            rc = fn(eng._h, p, pp, stride, refs[0], refs[1], stream())
-            if rc:
-                _check(lib, rc, "mcbs_defender_wrapper_step_packed")
-        return call
+        return self._bound("mcbs_defender_wrapper_step_packed", _ACTIONS, packed, _row_stride(packed, self.E), bufs, cfg, _STREAM)
 
     def get_state(self):
         rb = state_record_bytes(self.topo.n_nodes, self.spec.maximum_total_credentials)

@@ -38,6 +38,80 @@ from .flatten import FlatTopology, flatten
 FLAT_FIELDS = ["scalars", "leaked_credentials", "credential_cache_matrix", "discovered_nodes_properties",
                "nodes_privilegelevel", "mask_discrete"]
 
+# a step's alternating output sets: name and dtype of each [n_envs] tensor (_output_set)
+_ATTACKER_OUTPUTS = (("invalid", "uint8"), ("executed", "bool"), ("rewards", "float32"), ("truncated", "uint8"), ("ret", "float64"),
+                     ("length", "int32"), ("terminated", "uint8"))
+_DEFENDER_OUTPUTS = (("valid", "uint8"), ("availability", "float64"), ("reward", "float64"), ("terminated", "uint8"), ("truncated", "uint8"),
+                     ("breached", "uint8"), ("won", "uint8"))
+_TRAINING_OUTPUTS = (("attacker_valid_out", "int64"), ("attacker_invalid_out", "int64"), ("defender_return_out", "float64"),
+                     ("defender_length_out", "int32"), ("defender_valid_out", "int64"), ("defender_invalid_out", "int64"), ("defender_dones", "uint8"))
+
+
+def _output_set(venv, table) -> Dict[str, object]:
+    t = venv.torch
+    return {k: t.empty(venv.num_envs, dtype=getattr(t, dtype), device=venv.engine.device) for k, dtype in table}
+
+
+def _as_actions(att, a, shape, wording: str):
+    """Whatever the caller passed as actions -> a contiguous int64 tensor of `shape` on the device of `att` (an AttackerVecEnv).  The
+    common case — the policy's own int64 tensor — is returned as it is.  Another shape is a ValueError opening with the caller's wording."""
+    t = att.torch
+    if not (type(a) is t.Tensor and a.dtype is t.int64 and a.is_cuda and a.get_device() == att._dev_index and a.is_contiguous()):
+        a = a if isinstance(a, t.Tensor) else t.as_tensor(np.asarray(a))
+        a = a.to(device=att.engine.device, dtype=t.int64).contiguous()
+    if a.shape != shape:
+        raise ValueError(f"{wording} {tuple(shape)}, got {tuple(a.shape)}")
+    return a
+
+
+def _stage_actions(venv, actions):
+    """use_graph: the caller's actions copied into the wrapper's persistent action buffer, which the step then reads."""
+    t = venv.torch
+    a = actions if isinstance(actions, t.Tensor) else t.as_tensor(np.asarray(actions))
+    venv._act_in.copy_(a.to(device=venv.engine.device).reshape(venv._act_in.shape), non_blocking=True)
+    return venv._act_in
+
+
+def _observation_storage(venv, store_observations: bool, pack_observations: Optional[bool], fields, words, wrapper: str, kind: str):
+    """What rollout_buffer() hands DeviceRolloutBuffer as obs: None, the wrapper's fields() or one "packed" key of words() words per row
+    (pack_observations; the default for a wrapper with observation_format="packed", which has no `kind` field to store instead;
+    `wrapper`: the class's name in that refusal)."""
+    if pack_observations is None:
+        pack_observations = venv._packed_mode
+    if venv._packed_mode and store_observations and not pack_observations:
+        raise ValueError(f"rollout_buffer(pack_observations=False): this {wrapper} was created with observation_format='packed' "
+                         f"and keeps no {kind} field to store")
+    if not store_observations:
+        return None
+    if pack_observations:
+        return {"packed": venv.torch.zeros((venv.num_envs, words()), dtype=venv.torch.int32, device=venv.engine.device)}
+    return fields()
+
+
+def _two_agent_refusal(att, dfd, turn: str, auto_reset: bool, auto_reset_why: str, launches: str) -> Optional[str]:
+    """Why the `turn` ("joint" / "training") turn does not take this attacker wrapper, or this pair: the first of nine conditions that
+    fails, else None.  launches: the engine's query for the turn's entry point."""
+    from ._abi import DEFENDER_EXTERNAL
+    if not isinstance(att, AttackerVecEnv):
+        return "the attacker side must be an AttackerVecEnv"
+    if att.engine._cfg.defender_kind != DEFENDER_EXTERNAL:
+        return "the AttackerVecEnv must be created with learned_defender=True"
+    if bool(att.auto_reset) != auto_reset:
+        return f"the AttackerVecEnv must be created with auto_reset={auto_reset} ({auto_reset_why})"
+    if att.materialize_masks:
+        return f"the AttackerVecEnv must be created with materialize_masks=False (the {turn} turn writes no mask field)"
+    if att.use_graph:
+        return "the AttackerVecEnv must be created with use_graph=False"
+    if att.observation_format != "fields":
+        return f"the AttackerVecEnv must be created with observation_format='fields' (the {turn} turn writes the int32 fields, not packed rows)"
+    if getattr(att.engine, launches)() != 1:
+        return f"the library does not serve this batch with a {turn} turn (mcbs_{launches}: small packed topologies only)"
+    if dfd is not None and not (isinstance(dfd, DefenderVecEnv) and dfd.attacker is att and not dfd.use_graph):
+        return "the defender side must be the DefenderVecEnv created on this AttackerVecEnv (use_graph=False)"
+    if dfd is not None and dfd.observation_format != "dense":
+        return "the DefenderVecEnv must be created with observation_format='dense' (these turns write the int8 fields, not packed rows)"
+    return None
+
 
 class _MultiDiscreteHead:
     """The MultiDiscrete head (mcbs_multicategorical) for a wrapper with `engine`, `num_envs` and `nvec`: SB3's
@@ -166,7 +240,7 @@ class AttackerVecEnv(_MultiDiscreteHead):
         self._ret_out = t.zeros(n_envs, dtype=t.float64, device=dev)
         self._len_out = t.zeros(n_envs, dtype=t.int32, device=dev)
         self._n_done = t.zeros(1, dtype=t.int32, device=dev)
-        self._wb = self._keep = self._fresh = self._reset_rows = None
+        self._wb = self._keep = self._fresh = self._obs_block = self._reset_rows = None
         self._calls = {}                                   # bound library calls (engine.wrapper_step_call), one per output set and settings
         self._dev_index = self.engine.device.index if self.engine.device.index is not None else t.cuda.current_device()
         self._action_shape = (n_envs,) if self.discrete else (n_envs, 10)
@@ -269,14 +343,14 @@ class AttackerVecEnv(_MultiDiscreteHead):
                                "sample_masked_uniform / evaluate_masked")
 
     # -- the masked categorical head (mcbs_masked_categorical): MaskableCategorical's sample / log_prob / entropy in one launch --
-    def _live_bits(self):
+    def _live_bits(self, caller: str = "the masked categorical head"):
         """None where the live form serves (the mask is rebuilt from the digest); under ExternalRandomEvents, where it cannot be, the
-        materialised mask packed with torch expressions, as features(include_masks=True) does (rows are then keyed by their index)."""
+        materialised mask packed with torch expressions (rows are then keyed by their index).  caller: who asks, for the refusal."""
         from ._abi import DEFENDER_RANDOM_EVENTS
         if self.engine._cfg.defender_kind != DEFENDER_RANDOM_EVENTS:
             return None
         if not self.materialize_masks:
-            raise RuntimeError("the masked categorical head under ExternalRandomEvents needs the materialised masks (the mask cannot be "
+            raise RuntimeError(f"{caller} under ExternalRandomEvents needs the materialised masks (the mask cannot be "
                                "rebuilt from the observation digest there): create the env with materialize_masks=True")
         return self._pack_bits_from_mask(self.action_masks())
 
@@ -364,13 +438,8 @@ class AttackerVecEnv(_MultiDiscreteHead):
         instead (materialize_masks=False then raises).  reference_counts / out_of_range: see FeatureLayout / engine.encode_features."""
         bits = None
         if include_masks:
-            from ._abi import DEFENDER_RANDOM_EVENTS
-            if self.engine._cfg.defender_kind == DEFENDER_RANDOM_EVENTS:
-                if not self.materialize_masks:
-                    raise RuntimeError("features(include_masks=True) under ExternalRandomEvents needs the materialised masks "
-                                       "(the mask cannot be rebuilt from the observation digest there): create the env with materialize_masks=True")
-                bits = self._pack_bits_from_mask(self.action_masks())
-            else:
+            bits = self._live_bits("features(include_masks=True)")
+            if bits is None:
                 if self._feature_bits is None:
                     self._feature_bits = self.torch.zeros((self.num_envs, self.engine.packed_mask_words()[1]), dtype=self.torch.int32,
                                                           device=self.engine.device)
@@ -386,12 +455,16 @@ class AttackerVecEnv(_MultiDiscreteHead):
         fields `scalars` [n, 7] (or the seven named counts [n]), `leaked_credentials`, `credential_cache_matrix`,
         `discovered_nodes_properties`, `nodes_privilegelevel` with a leading row axis; bits = the rows' packed masks [n, >= W]
         (action_masks_packed) adds the mask columns."""
+        return self.engine.encode_features(self._feature_handle(bits is not None, reference_counts), self._stored_fields(obs), bits=bits, out=out,
+                                           dtype=dtype, out_of_range=out_of_range)
+
+    def _stored_fields(self, obs) -> Dict[str, object]:
+        """Stored observation rows as the contiguous int32 fields the engine reads: `scalars` stacked from the seven named counts where
+        it is not there itself."""
         t = self.torch
         if "scalars" not in obs:
             obs = dict(obs, scalars=t.stack([obs[k] for k in SCALAR_KEYS], dim=1).to(t.int32))
-        fields = {k: obs[k].contiguous() for k in FLAT_FIELDS[:5] if k in obs}
-        return self.engine.encode_features(self._feature_handle(bits is not None, reference_counts), fields, bits=bits, out=out, dtype=dtype,
-                                           out_of_range=out_of_range)
+        return {k: obs[k].contiguous() for k in FLAT_FIELDS[:5] if k in obs}
 
     # -- packed observations (features.ObservationPacking, mcbs_pack_observation): store per step, encode features later --
     def _packing_handle(self):
@@ -464,11 +537,8 @@ class AttackerVecEnv(_MultiDiscreteHead):
         """first_layer() for any n stored observation rows: obs as encode_features() takes it (`scalars` [n, 7] or the seven named counts,
         and the four array fields).  differentiable=True: the result carries an autograd graph into weight and bias whose backward is
         one call of engine.first_layer_grad (no feature tensor is kept alive for it)."""
-        t = self.torch
-        if "scalars" not in obs:
-            obs = dict(obs, scalars=t.stack([obs[k] for k in SCALAR_KEYS], dim=1).to(t.int32))
-        fields = {k: obs[k].contiguous() for k in FLAT_FIELDS[:5] if k in obs}
-        return self._first_layer_call(reference_counts, weight, bias, dict(obs=fields), out, dtype, out_of_range, weight_t, differentiable)
+        return self._first_layer_call(reference_counts, weight, bias, dict(obs=self._stored_fields(obs)), out, dtype, out_of_range, weight_t,
+                                      differentiable)
 
     def encode_first_layer_packed(self, packed, weight, bias=None, index=None, out=None, dtype=None, reference_counts: bool = False,
                                   out_of_range=None, weight_t=None, differentiable: bool = False):
@@ -504,14 +574,8 @@ class AttackerVecEnv(_MultiDiscreteHead):
         time encode_features_packed(..., index=batch.index) reads the storage itself.  The default is False, and True for a wrapper
         created with observation_format="packed", which has nothing else to store: False is refused there."""
         from .rollout import DeviceRolloutBuffer
-        if pack_observations is None:
-            pack_observations = self._packed_mode
-        if self._packed_mode and store_observations and not pack_observations:
-            raise ValueError("rollout_buffer(pack_observations=False): this AttackerVecEnv was created with observation_format='packed' "
-                             "and keeps no int32 field to store")
-        obs = self.observation_fields if store_observations and not pack_observations else None
-        if store_observations and pack_observations:
-            obs = {"packed": self.torch.zeros((self.num_envs, self._packing_handle().words), dtype=self.torch.int32, device=self.engine.device)}
+        obs = _observation_storage(self, store_observations, pack_observations, lambda: self.observation_fields, lambda: self._packing_handle().words,
+                                   "AttackerVecEnv", "int32")
         if mask_storage not in ("bits", "keys"):
             raise ValueError(f"mask_storage must be 'bits' or 'keys', got {mask_storage!r}")
         keys = self.discrete and mask_storage == "keys"
@@ -552,55 +616,56 @@ class AttackerVecEnv(_MultiDiscreteHead):
         observation, then — one launch — counters, reward modifier of intercepted actions (attack_wrapper.py:296,354), truncation
         (:350-352), episode returns and what DummyVecEnv.step_wait does for an env that reports done: keep its last observation, reset
         it, return the reset observation (every env resets to the same state, so that is row 0 of reset()'s observation)."""
-        t = self.torch
-        a = actions
-        if not (type(a) is t.Tensor and a.dtype is t.int64 and a.is_cuda and a.get_device() == self._dev_index and a.is_contiguous()):
-            a = a if isinstance(a, t.Tensor) else t.as_tensor(np.asarray(a))       # (the common case — the policy's own int64 tensor — skips this)
-            a = a.to(device=self.engine.device, dtype=t.int64).contiguous()
-        want = self._action_shape
-        if a.shape != want:
-            raise ValueError(f"expected actions of shape {want}, got {tuple(a.shape)}")
-        if self._packed_mode:
-            if self._wb is None:
-                self._wb = self._wrapper_buffers(self._invalid, self.engine.terminated if self.use_graph else self._terminated_out, self._rewards,
-                                                 self._truncated, self._ret_out, self._len_out, self._executed)
-            key = (id(self._wb), self.invalid_action_reward_modifier, self.max_timesteps, self.auto_reset)
-            call = self._calls.get(key)
-            if call is None:
-                call = self._calls[key] = self.engine.wrapper_step_packed_call(
-                    self.discrete, self._rows, self._packing_handle(), self.packed_observation, self.terminal_packed_observation, self._packed_fresh,
-                    self._wb, self.invalid_action_reward_modifier, self.max_timesteps, self.auto_reset)
-            call(a.data_ptr())
-            return
+        a = _as_actions(self, actions, self._action_shape, "expected actions of shape")
+        if self._wb is None:                               # (use_graph: the one persistent set; eager steps install theirs in _next_output_set)
+            self._wb = self._wrapper_buffers(self._persistent_set())
+        # the library call with every argument block bound once per (output set, wrapper settings): engine.wrapper_step_call
+        key = (id(self._wb), self.invalid_action_reward_modifier, self.max_timesteps, self.auto_reset)
+        call = self._calls.get(key)
+        if call is None:
+            settings = (self._wb,) + key[1:]
+            if self._packed_mode:
+                call = self.engine.wrapper_step_packed_call(self.discrete, self._rows, self._packing_handle(), self.packed_observation,
+                                                            self.terminal_packed_observation, self._packed_fresh, *settings)
+            else:
+                obs_block, keep, fresh = self._blocks()
+                call = self.engine.wrapper_step_call(self.discrete, self._rows, obs_block, *settings, keep, fresh)
+            self._calls[key] = call
+        call(a.data_ptr())
+
+    def _blocks(self):
+        """-> (ObsBuffers of the observation, RowCopies observation -> terminal observation, RowCopies reset row -> observation): the
+        argument blocks of the fields form's calls (engine.wrapper_step_call and the two-agent calls), built on first use."""
         if self._keep is None:
             eng = self.engine
             self._keep = eng.row_copies([(self._obs[k], self._terminal[k]) for k in self._obs])
             self._fresh = eng.row_copies([(self._reset_rows[k], self._obs[k]) for k in self._obs], one_row_src=True)
             self._obs_block = eng.obs_struct(self._obs)
-        if self._wb is None:
-            self._wb = self._wrapper_buffers(self._invalid, self.engine.terminated if self.use_graph else self._terminated_out, self._rewards,
-                                             self._truncated, self._ret_out, self._len_out, self._executed)
-        # the library call with every argument block bound once per (output set, wrapper settings): engine.wrapper_step_call
-        key = (id(self._wb), self.invalid_action_reward_modifier, self.max_timesteps, self.auto_reset)
-        call = self._calls.get(key)
-        if call is None:
-            call = self._calls[key] = self.engine.wrapper_step_call(self.discrete, self._rows, self._obs_block, self._wb, self.invalid_action_reward_modifier,
-                                                                    self.max_timesteps, self.auto_reset, self._keep, self._fresh)
-        call(a.data_ptr())
+        return self._obs_block, self._keep, self._fresh
 
-    def _wrapper_buffers(self, invalid, terminated, rewards, truncated, ret_out, len_out, executed):
+    def _persistent_set(self) -> Dict[str, object]:
+        """The wrapper's own output tensors under the names of _ATTACKER_OUTPUTS: what a use_graph step writes, every step."""
+        return dict(invalid=self._invalid, executed=self._executed, rewards=self._rewards, truncated=self._truncated, ret=self._ret_out,
+                    length=self._len_out, terminated=self.engine.terminated)
+
+    def _wrapper_buffers(self, o):
         from ._abi import WrapperBuffers
         return WrapperBuffers(*[x.data_ptr() for x in (
-            invalid, self.engine.reward, terminated, self.timesteps, self.valid_action_count, self.invalid_action_count, self.episode_returns,
-            self.last_cyber_reward, self.has_cyber_reward, rewards, truncated, self._dones, ret_out, len_out, self._n_done, executed)])
+            o["invalid"], self.engine.reward, o["terminated"], self.timesteps, self.valid_action_count, self.invalid_action_count, self.episode_returns,
+            self.last_cyber_reward, self.has_cyber_reward, o["rewards"], o["truncated"], self._dones, o["ret"], o["length"], self._n_done, o["executed"])])
+
+    def _info(self, o) -> Dict[str, object]:
+        """A step's info dict over the output set o."""
+        return {"invalid_action": o["invalid"].view(self.torch.bool), "cyber_step_executed": o["executed"],
+                "network_availability": self.engine.info["network_availability"], "step_count": self.engine.info["step_count"],
+                "episode_return": o["ret"], "episode_length": o["length"]}
 
     def step(self, actions):
         """-> (observation dict, rewards f32 [E], terminated u8 [E], truncated u8 [E], info dict of tensors)."""
         t = self.torch
         if self.use_graph:
             if actions is not self._act_in:                    # a policy may write its actions straight into `action_buffer`: no copy then
-                a = actions if isinstance(actions, t.Tensor) else t.as_tensor(np.asarray(actions))
-                self._act_in.copy_(a.to(device=self.engine.device).reshape(self._act_in.shape), non_blocking=True)
+                _stage_actions(self, actions)
             if self._one_launch is None:
                 self._one_launch = self.engine.wrapper_step_launches(self.materialize_masks) == 1
             if self._one_launch:
@@ -622,10 +687,7 @@ class AttackerVecEnv(_MultiDiscreteHead):
             else:
                 self._graph.replay()
             if self._graph_out is None:                        # the same persistent buffers every step: built once
-                self._graph_out = (self.observation, self._rewards, self.engine.terminated, self._truncated,
-                                   {"invalid_action": self._invalid.view(t.bool), "cyber_step_executed": self._executed,
-                                    "network_availability": self.engine.info["network_availability"], "step_count": self.engine.info["step_count"],
-                                    "episode_return": self._ret_out, "episode_length": self._len_out})
+                self._graph_out = (self.observation, self._rewards, self.engine.terminated, self._truncated, self._info(self._persistent_set()))
             return self._graph_out
         o, _, info = self._next_output_set()
         self._step_device(actions)
@@ -636,20 +698,9 @@ class AttackerVecEnv(_MultiDiscreteHead):
         next; consumers that keep them longer clone them).  Seven allocations and a rebuilt argument block per step cost more host time
         than the device needs for the whole wrapper step (20 us at 65 536 envs).  -> (tensors, WrapperBuffers, info) of the set the
         coming step writes, installed as the wrapper's current outputs."""
-        t = self.torch
-        E, dev = self.num_envs, self.engine.device
         if self._ring is None:
-            self._ring = []
-            for _ in range(2):
-                o = dict(invalid=t.empty(E, dtype=t.uint8, device=dev), executed=t.empty(E, dtype=t.bool, device=dev),
-                         rewards=t.empty(E, dtype=t.float32, device=dev), truncated=t.empty(E, dtype=t.uint8, device=dev),
-                         ret=t.empty(E, dtype=t.float64, device=dev), length=t.empty(E, dtype=t.int32, device=dev),
-                         terminated=t.empty(E, dtype=t.uint8, device=dev))
-                wb = self._wrapper_buffers(o["invalid"], o["terminated"], o["rewards"], o["truncated"], o["ret"], o["length"], o["executed"])
-                info = {"invalid_action": o["invalid"].view(t.bool), "cyber_step_executed": o["executed"],
-                        "network_availability": self.engine.info["network_availability"], "step_count": self.engine.info["step_count"],
-                        "episode_return": o["ret"], "episode_length": o["length"]}
-                self._ring.append((o, wb, info))
+            sets = [_output_set(self, _ATTACKER_OUTPUTS) for _ in range(2)]
+            self._ring = [(o, self._wrapper_buffers(o), self._info(o)) for o in sets]
         self._slot ^= 1
         o, wb, info = self._ring[self._slot]
         self._invalid, self._executed, self._rewards, self._truncated = o["invalid"], o["executed"], o["rewards"], o["truncated"]
@@ -809,16 +860,8 @@ class DefenderVecEnv(_MultiDiscreteHead):
         encode_features_packed(..., index=batch.index) reads the storage itself.  The default is False, and True for a wrapper created
         with observation_format="packed", which has nothing else to store: False is refused there."""
         from .rollout import DeviceRolloutBuffer
-        if pack_observations is None:
-            pack_observations = self._packed_mode
-        if self._packed_mode and store_observations and not pack_observations:
-            raise ValueError("rollout_buffer(pack_observations=False): this DefenderVecEnv was created with observation_format='packed' "
-                             "and keeps no int8 field to store")
-        obs = None
-        if store_observations:
-            obs = self._obs
-            if pack_observations:
-                obs = {"packed": self.torch.zeros((self.num_envs, self.engine.defender_obs_words()), dtype=self.torch.int32, device=self.engine.device)}
+        obs = _observation_storage(self, store_observations, pack_observations, lambda: self._obs, self.engine.defender_obs_words,
+                                   "DefenderVecEnv", "int8")
         return DeviceRolloutBuffer(self.engine, n_steps, self.num_envs, obs=obs, action_shape=(12,), mask_words=None, gamma=gamma,
                                    gae_lambda=gae_lambda)
 
@@ -840,30 +883,24 @@ class DefenderVecEnv(_MultiDiscreteHead):
 
     def step(self, actions):
         """-> (observation dict, reward f64 [E], terminated u8 [E], truncated u8 [E], info)."""
-        t = self.torch
         if self.use_graph:
             # (persistent outputs, actions copied into a persistent buffer — what a captured turn offered; the turn itself is two
             # launches issued directly: replaying them from a hipGraph cost the device more than the launches it wraps, 23 vs 12 us
             # per turn at 16 384 ToyCtf envs)
-            a = actions if isinstance(actions, t.Tensor) else t.as_tensor(np.asarray(actions))
-            self._act_in.copy_(a.to(device=self.engine.device).reshape(self._act_in.shape), non_blocking=True)
-            actions = self._act_in
+            actions = _stage_actions(self, actions)
         # eager: ONE library call per turn (mcbs_defender_wrapper_step: the turn and the reward shaping in one launch, then the observation)
-        E, dev = self.num_envs, self.engine.device
+        o, _, info, call = self._next_output_set()
+        call(_as_actions(self.attacker, actions, (self.num_envs, 12), "defender actions must have shape").data_ptr())
+        return self._obs, o["reward"], o["terminated"], o["truncated"], dict(info)
+
+    def _next_output_set(self):
+        """-> (tensors, DefenderWrapperBuffers, info, bound library call) of the set the coming turn writes: the two sets of _output_ring
+        in turn (a turn's outputs stay valid until the turn after next); under use_graph the first one, every turn."""
         if self._ring is None:
             self._output_ring()
         if not self.use_graph:
             self._slot ^= 1
-        o, wb, info, call = self._ring[self._slot]
-        a = actions
-        if not (type(a) is t.Tensor and a.dtype is t.int64 and a.is_cuda and a.get_device() == self.attacker._dev_index and a.is_contiguous()):
-            a = a if isinstance(a, t.Tensor) else t.as_tensor(np.asarray(a))
-            a = a.to(device=dev, dtype=t.int64).contiguous()
-        if a.shape != (E, 12):
-            raise ValueError(f"defender actions must have shape ({E}, 12), got {tuple(a.shape)}")
-        call(a.data_ptr())
-        self._out = o
-        return self._obs, o["reward"], o["terminated"], o["truncated"], dict(info)
+        return self._ring[self._slot]
 
     def _output_ring(self) -> None:
         """The turn's outputs alternate between two sets of tensors allocated once (valid until the turn after next): per set the tensors,
@@ -877,10 +914,7 @@ class DefenderVecEnv(_MultiDiscreteHead):
                                       self.winning_reward, int(self.reset_on_constraint_broken), self.max_timesteps)
         self._ring = []
         for _ in range(2):
-            o = dict(valid=t.empty(E, dtype=t.uint8, device=dev), availability=t.empty(E, dtype=t.float64, device=dev),
-                     reward=t.empty(E, dtype=t.float64, device=dev), terminated=t.empty(E, dtype=t.uint8, device=dev),
-                     truncated=t.empty(E, dtype=t.uint8, device=dev), breached=t.empty(E, dtype=t.uint8, device=dev),
-                     won=t.empty(E, dtype=t.uint8, device=dev))
+            o = _output_set(self, _DEFENDER_OUTPUTS)
             wb = DefenderWrapperBuffers(*[x.data_ptr() for x in (
                 o["valid"], o["availability"], self._evicted, self.attacker.has_cyber_reward, self.attacker.last_cyber_reward, self.timesteps,
                 self.valid_action_count, self.invalid_action_count, self.has_breached_sla, self.prev_availability, o["reward"], o["terminated"],
@@ -946,31 +980,12 @@ class TwoAgentVecEnv:
             raise ValueError(f"TwoAgentVecEnv: {why}")
         self.att, self.dfd = att, dfd
         self.engine, self.torch, self.num_envs = att.engine, att.torch, att.num_envs
-        self._obs_block = self.engine.obs_struct(att._obs)
         self._calls = {}
 
     @staticmethod
     def _refusal(att, dfd=None) -> Optional[str]:
-        from ._abi import DEFENDER_EXTERNAL
-        if not isinstance(att, AttackerVecEnv):
-            return "the attacker side must be an AttackerVecEnv"
-        if att.engine._cfg.defender_kind != DEFENDER_EXTERNAL:
-            return "the AttackerVecEnv must be created with learned_defender=True"
-        if att.auto_reset:
-            return "the AttackerVecEnv must be created with auto_reset=False (the episode boundary belongs to the caller)"
-        if att.materialize_masks:
-            return "the AttackerVecEnv must be created with materialize_masks=False (the joint turn writes no mask field)"
-        if att.use_graph:
-            return "the AttackerVecEnv must be created with use_graph=False"
-        if att.observation_format != "fields":
-            return "the AttackerVecEnv must be created with observation_format='fields' (the joint turn writes the int32 fields, not packed rows)"
-        if att.engine.two_agent_step_launches() != 1:
-            return "the library does not serve this batch with a joint turn (mcbs_two_agent_step_launches: small packed topologies only)"
-        if dfd is not None and not (isinstance(dfd, DefenderVecEnv) and dfd.attacker is att and not dfd.use_graph):
-            return "the defender side must be the DefenderVecEnv created on this AttackerVecEnv (use_graph=False)"
-        if dfd is not None and dfd.observation_format != "dense":
-            return "the DefenderVecEnv must be created with observation_format='dense' (these turns write the int8 fields, not packed rows)"
-        return None
+        return _two_agent_refusal(att, dfd, "joint", auto_reset=False, auto_reset_why="the episode boundary belongs to the caller",
+                                  launches="two_agent_step_launches")
 
     @staticmethod
     def supported(att) -> bool:
@@ -981,15 +996,6 @@ class TwoAgentVecEnv:
         """Freshly allocated episode bookkeeping: every env alive, nothing counted."""
         return EpisodeState(self.torch, self.num_envs, self.engine.device)
 
-    def _actions(self, a, shape, what: str):
-        t = self.torch
-        if not (type(a) is t.Tensor and a.dtype is t.int64 and a.is_cuda and a.get_device() == self.att._dev_index and a.is_contiguous()):
-            a = a if isinstance(a, t.Tensor) else t.as_tensor(np.asarray(a))
-            a = a.to(device=self.engine.device, dtype=t.int64).contiguous()
-        if a.shape != shape:
-            raise ValueError(f"{what} actions must have shape {tuple(shape)}, got {tuple(a.shape)}")
-        return a
-
     def step(self, attacker_actions, defender_actions, episode: Optional[EpisodeState] = None, reward_rows=None):
         """-> ((obs, rewards, terminated, truncated, info), (dobs, dreward, dterminated, dtruncated, dinfo)): exactly the tuples
         `att.step(attacker_actions)` and `dfd.step(defender_actions)` return.  The defender's turn of an env whose episode is over — `episode.alive`
@@ -997,23 +1003,19 @@ class TwoAgentVecEnv:
         `episode`: an episode_state() to book the turn into (mcbs.h states the rules); `reward_rows` = (attacker row, defender row), float64
         [E] device tensors that receive the turn's two trace rows instead of `episode.attacker_reward` / `.defender_reward`."""
         att, dfd = self.att, self.dfd
-        a = self._actions(attacker_actions, att._action_shape, "attacker")
-        d = self._actions(defender_actions, (self.num_envs, 12), "defender")
+        a = _as_actions(att, attacker_actions, att._action_shape, "attacker actions must have shape")
+        d = _as_actions(att, defender_actions, (self.num_envs, 12), "defender actions must have shape")
         if reward_rows is not None and episode is None:
             raise ValueError("reward_rows go with an episode state")
         block = episode.block(*(reward_rows or ())) if episode is not None else None
         o, wb, info = att._next_output_set()
-        if dfd._ring is None:
-            dfd._output_ring()
-        dfd._slot ^= 1
-        do, dwb, dinfo, _ = dfd._ring[dfd._slot]
+        do, dwb, dinfo, _ = dfd._next_output_set()
         key = (id(wb), id(dwb), att.invalid_action_reward_modifier, att.max_timesteps)
         call = self._calls.get(key)
         if call is None:
-            call = self._calls[key] = self.engine.two_agent_step_call(att.discrete, att._rows, self._obs_block, wb, att.invalid_action_reward_modifier,
+            call = self._calls[key] = self.engine.two_agent_step_call(att.discrete, att._rows, att._blocks()[0], wb, att.invalid_action_reward_modifier,
                                                                       att.max_timesteps, dfd._obs_block, dwb, dfd._wc)
         call(a.data_ptr(), d.data_ptr(), block)
-        dfd._out = do
         return ((att.observation, o["rewards"], o["terminated"], o["truncated"], dict(info)),
                 (dfd._obs, do["reward"], do["terminated"], do["truncated"], dict(dinfo)))
 
@@ -1054,26 +1056,8 @@ class TwoAgentTrainVecEnv:
 
     @staticmethod
     def _refusal(att, dfd=None) -> Optional[str]:
-        from ._abi import DEFENDER_EXTERNAL
-        if not isinstance(att, AttackerVecEnv):
-            return "the attacker side must be an AttackerVecEnv"
-        if att.engine._cfg.defender_kind != DEFENDER_EXTERNAL:
-            return "the AttackerVecEnv must be created with learned_defender=True"
-        if not att.auto_reset:
-            return "the AttackerVecEnv must be created with auto_reset=True (both agents' DummyVecEnv resets are part of the training turn)"
-        if att.materialize_masks:
-            return "the AttackerVecEnv must be created with materialize_masks=False (the training turn writes no mask field)"
-        if att.use_graph:
-            return "the AttackerVecEnv must be created with use_graph=False"
-        if att.observation_format != "fields":
-            return "the AttackerVecEnv must be created with observation_format='fields' (the training turn writes the int32 fields, not packed rows)"
-        if att.engine.two_agent_train_step_launches() != 1:
-            return "the library does not serve this batch with a training turn (mcbs_two_agent_train_step_launches: small packed topologies only)"
-        if dfd is not None and not (isinstance(dfd, DefenderVecEnv) and dfd.attacker is att and not dfd.use_graph):
-            return "the defender side must be the DefenderVecEnv created on this AttackerVecEnv (use_graph=False)"
-        if dfd is not None and dfd.observation_format != "dense":
-            return "the DefenderVecEnv must be created with observation_format='dense' (these turns write the int8 fields, not packed rows)"
-        return None
+        return _two_agent_refusal(att, dfd, "training", auto_reset=True, auto_reset_why="both agents' DummyVecEnv resets are part of the training turn",
+                                  launches="two_agent_train_step_launches")
 
     @staticmethod
     def supported(att) -> bool:
@@ -1108,19 +1092,13 @@ class TwoAgentTrainVecEnv:
 
     def _output_ring(self) -> None:
         from ._abi import training_buffers
-        t, E, dev = self.torch, self.num_envs, self.engine.device
         fixed = dict(attacker_reset_request=self._request.data_ptr(), defender_return=self.defender_returns.data_ptr())
         fixed.update({"terminal_" + k: v.data_ptr() for k, v in self._terminal.items()})       # (the four keys of mcbs_defender_obs)
         fixed.update({"fresh_" + k: v.data_ptr() for k, v in self._fresh_rows.items()})
         self._ring = []
         for _ in range(2):
-            o = dict(attacker_valid_out=t.empty(E, dtype=t.int64, device=dev), attacker_invalid_out=t.empty(E, dtype=t.int64, device=dev),
-                     defender_return_out=t.empty(E, dtype=t.float64, device=dev), defender_length_out=t.empty(E, dtype=t.int32, device=dev),
-                     defender_valid_out=t.empty(E, dtype=t.int64, device=dev), defender_invalid_out=t.empty(E, dtype=t.int64, device=dev),
-                     defender_dones=t.empty(E, dtype=t.uint8, device=dev))
+            o = _output_set(self, _TRAINING_OUTPUTS)
             self._ring.append((o, training_buffers(**fixed, **{k: v.data_ptr() for k, v in o.items()})))
-
-    _actions = TwoAgentVecEnv._actions
 
     def step(self, attacker_actions, defender_actions):
         """-> ((obs, rewards, terminated, truncated, info), (dobs, dreward, dterminated, dtruncated, dinfo)): what the two agents'
@@ -1131,18 +1109,10 @@ class TwoAgentTrainVecEnv:
         `truncated` includes a reset request; the defender's reward on a request step is `-1 * the attacker's reward of this turn`.
         Outputs are valid until the turn after next.  The defender's action of a turn is chosen before the attacker's step of that turn."""
         att, dfd = self.att, self.dfd
-        a = self._actions(attacker_actions, att._action_shape, "attacker")
-        d = self._actions(defender_actions, (self.num_envs, 12), "defender")
-        if att._keep is None:
-            eng = self.engine
-            att._keep = eng.row_copies([(att._obs[k], att._terminal[k]) for k in att._obs])
-            att._fresh = eng.row_copies([(att._reset_rows[k], att._obs[k]) for k in att._obs], one_row_src=True)
-            att._obs_block = eng.obs_struct(att._obs)
+        a = _as_actions(att, attacker_actions, att._action_shape, "attacker actions must have shape")
+        d = _as_actions(att, defender_actions, (self.num_envs, 12), "defender actions must have shape")
         o, wb, info = att._next_output_set()
-        if dfd._ring is None:
-            dfd._output_ring()
-        dfd._slot ^= 1
-        do, dwb, dinfo, _ = dfd._ring[dfd._slot]
+        do, dwb, dinfo, _ = dfd._next_output_set()
         if self._ring is None:
             self._output_ring()
         self._slot ^= 1
@@ -1150,10 +1120,10 @@ class TwoAgentTrainVecEnv:
         key = (id(wb), id(dwb), id(tb), att.invalid_action_reward_modifier, att.max_timesteps)
         call = self._calls.get(key)
         if call is None:
-            call = self._calls[key] = self.engine.two_agent_train_step_call(att.discrete, att._rows, att._obs_block, wb, att.invalid_action_reward_modifier,
-                                                                            att.max_timesteps, att._keep, att._fresh, dfd._obs_block, dwb, dfd._wc, tb)
+            obs_block, keep, fresh = att._blocks()
+            call = self._calls[key] = self.engine.two_agent_train_step_call(att.discrete, att._rows, obs_block, wb, att.invalid_action_reward_modifier,
+                                                                            att.max_timesteps, keep, fresh, dfd._obs_block, dwb, dfd._wc, tb)
         call(a.data_ptr(), d.data_ptr())
-        dfd._out = do
         ainfo = dict(info, dones=att._dones, episode_valid_actions=to["attacker_valid_out"], episode_invalid_actions=to["attacker_invalid_out"])
         dinfo = dict(dinfo, dones=to["defender_dones"], episode_return=to["defender_return_out"], episode_length=to["defender_length_out"],
                      episode_valid_actions=to["defender_valid_out"], episode_invalid_actions=to["defender_invalid_out"])
