@@ -1186,6 +1186,54 @@ int  mcbs_two_agent_train_step(mcbs_batch*, const int64_t* multidiscrete, const 
                                const mcbs_defender_wrapper_buffers* dw, const mcbs_defender_wrapper_cfg* dcfg,
                                const mcbs_training_buffers* tr, void* stream);
 
+/* ---- the training turn for a trainer that stores PACKED observations on both sides ----
+ * mcbs_training_buffers with the defender's packed rows in place of its eight int8 arrays: the nine per-env arrays keep their
+ * order and meaning. */
+typedef struct mcbs_training_packed_buffers {   /* 88 bytes: device arrays of n_envs rows unless stated otherwise */
+    uint8_t* attacker_reset_request;     /* in/out */
+    double*  defender_return;            /* in/out */
+    int64_t* attacker_valid_out;         /* out */
+    int64_t* attacker_invalid_out;       /* out */
+    double*  defender_return_out;        /* out */
+    int32_t* defender_length_out;        /* out */
+    int64_t* defender_valid_out;         /* out */
+    int64_t* defender_invalid_out;       /* out */
+    uint8_t* defender_dones;             /* out */
+    uint32_t* terminal_defender_packed;      /* out [n_envs, defender_row_words]: the defender's packed row after its action — the terminal
+                                                observation of the envs whose defender_dones is set; other rows hold the same row and mean nothing */
+    const uint32_t* fresh_defender_packed;   /* in [W_def]: the defender's packed row of a freshly reset env, ONE row */
+} mcbs_training_packed_buffers;
+
+/* 1: mcbs_two_agent_train_step_packed serves this batch with this packing, in one launch; 0: it does not (NULL: 0). */
+int32_t mcbs_two_agent_train_step_packed_launches(const mcbs_batch*, const mcbs_obs_packing* packing);
+/* mcbs_two_agent_train_step with BOTH observations written as packed rows by the same ONE launch (marlon_amd/csrc/mcbs_two_agent.hip
+ * two_agent_train_packed_kernel): the attacker's as mcbs_attacker_wrapper_step_packed writes them (packing, packed, packed_terminal,
+ * packed_fresh, row_words: see there), the defender's as the W_def words of "packed defender observations" above — defender_packed
+ * [n_envs, defender_row_words] the live rows, tr->terminal_defender_packed the rows after the defender's action, and
+ * tr->fresh_defender_packed the row that becomes the live row of an env the defender ends.  No int32 or int8 observation array exists
+ * in this call, nothing is packed by a second launch, nothing dense is read back.
+ * Contract.  Per env the call equals mcbs_two_agent_train_step bit for bit in every array of w, info, dw, decoded, the digests, the
+ * nine shared members of tr and the env state.  Live and terminal rows equal mcbs_pack_observation of the attacker's rows and
+ * mcbs_pack_defender_observation of the defender's rows as that call writes them: the attacker's live row of an env whose action was
+ * intercepted stands, its terminal rows are written for the envs the attacker's step ends only, and after a defender-side reset the
+ * attacker's rows and digest are not touched; the defender's terminal and live rows are written for every env.  Every word below W
+ * (W_obs, W_def) of a written row is stored whole; words from W on, and rows that stand, are never touched.
+ * Scope: the intersection of mcbs_two_agent_train_step's batches, the packed step's LDS room (W_obs <= 128 and W_obs + 1 + V <= 896) and
+ * the defender turn that writes its own observation (N <= 32, S <= 256: W_def <= 21).  There is no multi-launch form and no mixed
+ * form (one side packed, the other dense).  MCBS_EINVAL with a message naming the reason — nothing launched, no state changed — for:
+ * a batch outside the scope; a packing created for another device or geometry; row_words < W_obs or defender_row_words < W_def;
+ * defender_packed or tr->terminal_defender_packed off a 16-byte boundary, or defender rows that neither follow each other without a gap
+ * (defender_row_words == W_def) nor are a multiple of 4 words apart (the turn kernels' 16-byte store condition); a NULL argument or
+ * member; both action encodings or neither; any written array that shares a byte with another array of the call.  MCBS_ESTATE as for
+ * mcbs_two_agent_train_step. */
+int  mcbs_two_agent_train_step_packed(mcbs_batch*, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded,
+                                      const mcbs_info_buffers* info, const mcbs_obs_packing* packing, uint32_t* packed,
+                                      uint32_t* packed_terminal, const uint32_t* packed_fresh, size_t row_words,
+                                      const mcbs_wrapper_buffers* w, float invalid_action_reward_modifier, int32_t attacker_max_timesteps,
+                                      const int64_t* defender_actions, uint32_t* defender_packed, size_t defender_row_words,
+                                      const mcbs_defender_wrapper_buffers* dw, const mcbs_defender_wrapper_cfg* dcfg,
+                                      const mcbs_training_packed_buffers* tr, void* stream);
+
 /* Parity / debugging: canonical per-env state records (layout: mcbs_state_record below),
  * host buffers, synchronous.  The record does not carry what only MCBS_DEFENDER_RANDOM_EVENTS mutates (vulnerability keys,
  * service flags, firewall rule lists): mcbs_set_state puts those back to the topology's initial ones for the envs it writes. */

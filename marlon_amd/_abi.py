@@ -99,6 +99,19 @@ def training_buffers(**arrays) -> "TrainingBuffers":
     return TrainingBuffers(*[arrays[n] for n in TRAINING_FIELDS])
 
 
+# mcbs_training_packed_buffers (include/mcbs.h): the nine per-env members of mcbs_training_buffers, then the defender's terminal packed
+# rows and its fresh packed row — eleven device pointers, held to the header by tests/test_training_packed_host.py
+TRAINING_PACKED_FIELDS = TRAINING_FIELDS[:9] + ("terminal_defender_packed", "fresh_defender_packed")
+TrainingPackedBuffers = C.c_void_p * len(TRAINING_PACKED_FIELDS)
+
+
+def training_packed_buffers(**arrays) -> "TrainingPackedBuffers":
+    """An mcbs_training_packed_buffers block from device pointers given by member name (every member of TRAINING_PACKED_FIELDS)."""
+    if set(arrays) != set(TRAINING_PACKED_FIELDS):
+        raise ValueError(f"mcbs_training_packed_buffers has exactly the members {TRAINING_PACKED_FIELDS}")
+    return TrainingPackedBuffers(*[arrays[n] for n in TRAINING_PACKED_FIELDS])
+
+
 class BatchVariantInfo(C.Structure):
     """mcbs_batch_variant_info (include/mcbs.h): the compiled variant a batch dispatches to"""
     _fields_ = [(n, C.c_uint32) for n in ("packed", "words_per_set", "wide", "coop", "lds_topo", "defender_kind", "fused_wrapper",
@@ -248,6 +261,11 @@ PROTOTYPES = {
     # batch, multidiscrete, discrete, decoded, info, obs, w, invalid_action_reward_modifier, attacker_max_timesteps, keep, fresh,
     # defender_actions, defender_obs, dw, dcfg, tr (a TrainingBuffers block), stream
     "mcbs_two_agent_train_step": (_int, [_H, _P, _P, _P, _P, _P, _P, _f32, _i32, _P, _P, _P, _P, _P, _P, _P, _S]),
+    "mcbs_two_agent_train_step_packed_launches": (_i32, [_H, _H]),                            # batch, packing
+    # batch, multidiscrete, discrete, decoded, info, packing, packed, packed_terminal, packed_fresh, row_words, w,
+    # invalid_action_reward_modifier, attacker_max_timesteps, defender_actions, defender_packed, defender_row_words, dw, dcfg,
+    # tr (a TrainingPackedBuffers block), stream
+    "mcbs_two_agent_train_step_packed": (_int, [_H, _P, _P, _P, _P, _H, _P, _P, _P, _size, _P, _f32, _i32, _P, _P, _size, _P, _P, _P, _S]),
     "mcbs_state_record_bytes": (_size, [_H]),
     "mcbs_get_state": (_int, [_H, _P, _size]),                                                # batch, host_buf, nbytes
     "mcbs_set_state": (_int, [_H, _P, _size]),                                                # batch, host_buf, nbytes

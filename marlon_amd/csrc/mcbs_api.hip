@@ -115,6 +115,11 @@ static const ArrayDesc kTrainingArrays[] = {
     {"fresh_infected_nodes", 0, 1, 0, kFreshRow}, {"fresh_incoming_firewall_status", 0, 6, 0, kFreshRow},
     {"fresh_outgoing_firewall_status", 0, 6, 0, kFreshRow},
     {"fresh_services_status", 0}};
+// (the two packed members are rows of the caller's stride: mcbs_two_agent_train_step_packed lists them itself)
+static const ArrayDesc kTrainingPackedArrays[] = {
+    {"attacker_reset_request", 1}, {"defender_return", 8}, {"attacker_valid_out", 8}, {"attacker_invalid_out", 8}, {"defender_return_out", 8},
+    {"defender_length_out", 4}, {"defender_valid_out", 8}, {"defender_invalid_out", 8}, {"defender_dones", 1}, {"terminal_defender_packed", 0},
+    {"fresh_defender_packed", 0}};
 // ... appended to an overlap check as prefix + name
 template <class W, size_t K>
 static void add_arrays(Extents& x, const char* prefix, const W* w, const ArrayDesc (&desc)[K], uint64_t E, uint64_t N, uint64_t Sv, bool written) {
@@ -2760,6 +2765,82 @@ extern "C" int mcbs_two_agent_train_step(mcbs_batch* b, const int64_t* multidisc
     b->all_fresh = false;
     hipLaunchKernelGGL(two_agent_train_kernel, dim3((b->S.E + 63u) / 64u), dim3(FUSED_THREADS), 0, (hipStream_t)stream, b->S, b->T, b->C_dev, io, A, D);
     return turn_launched(b, "two-agent training turn", true);      // (the digests it wrote carry their observation's discovery order)
+}
+
+// ---- the training turn with both observations as packed rows (two_agent_train_packed_kernel): no multi-launch form, no mixed form
+// the packed step's LDS room for a row of this packing (mcbs_wrapper_fused.hip FusedPackedStore)
+static bool packed_step_room(const mcbs_obs_packing* p) {
+    return p->P.W <= FUSED_PACKED_MAX_WORDS && p->P.W + 1u + p->P.V <= FUSED_PACKED_TABLE_DWORDS;
+}
+
+extern "C" int32_t mcbs_two_agent_train_step_packed_launches(const mcbs_batch* b, const mcbs_obs_packing* p) {
+    return (b && p && !two_agent_batch_reason(b) && obs_packing_fits(b, p) && packed_step_room(p) && b->def_pack.W <= DEF_WMAX) ? 1 : 0;
+}
+
+extern "C" int mcbs_two_agent_train_step_packed(mcbs_batch* b, const int64_t* multidiscrete, const int64_t* discrete, int32_t* decoded,
+                                                const mcbs_info_buffers* info, const mcbs_obs_packing* p, uint32_t* packed, uint32_t* packed_terminal,
+                                                const uint32_t* packed_fresh, size_t row_words, const mcbs_wrapper_buffers* w, float modifier,
+                                                int32_t attacker_max_timesteps, const int64_t* defender_actions, uint32_t* defender_packed,
+                                                size_t defender_row_words, const mcbs_defender_wrapper_buffers* dw, const mcbs_defender_wrapper_cfg* dcfg,
+                                                const mcbs_training_packed_buffers* tr, void* stream) {
+    const char* who = "two-agent training turn (packed rows)";
+    if (!b || !w || !decoded || !p || !packed || !packed_terminal || !packed_fresh || !defender_actions || !defender_packed || !dw || !dcfg || !tr)
+        return fail(MCBS_EINVAL, "null argument");
+    MCBS_ON_DEVICE(b);
+    // every check before the launch: a refused call launches nothing and changes no state
+    if (const char* why = two_agent_batch_reason(b)) return fail(MCBS_EINVAL, "%s: %s", who, why);
+    StepIO io;
+    if (const int rc = attacker_turn_io(b, multidiscrete, discrete, decoded, info, w, modifier, attacker_max_timesteps, 1, nullptr, nullptr, &io)) return rc;
+    if (!arrays_set(dw, 0)) return fail(MCBS_EINVAL, "mcbs_defender_wrapper_buffers: every array is required");
+    if (!arrays_set(tr, 0)) return fail(MCBS_EINVAL, "mcbs_training_packed_buffers: every array is required");
+    if (!obs_packing_fits(b, p)) return fail(MCBS_EINVAL, "%s: the packing was created for a batch of another device or geometry", who);
+    const uint32_t W = p->P.W, V = p->P.V, Wd = b->def_pack.W;
+    if (row_words < W) return fail(MCBS_EINVAL, "%s: row_words %zu is shorter than the %u words of a packed row", who, row_words, W);
+    if (!packed_step_room(p))
+        return fail(MCBS_EINVAL, "%s: a packed row of %u words and %u values is beyond the LDS room the step keeps for the fresh row (%u words) and "
+                                 "its tables (%u entries)", who, W, V, FUSED_PACKED_MAX_WORDS, FUSED_PACKED_TABLE_DWORDS);
+    if (const int rc = defender_packing_ok(b, who, defender_row_words)) return rc;
+    if (Wd > DEF_WMAX) return fail(MCBS_EINVAL, "%s: a packed defender row of %u words is beyond the %u the turn writes itself", who, Wd, DEF_WMAX);
+    if (reinterpret_cast<uintptr_t>(defender_packed) % 16u || reinterpret_cast<uintptr_t>(tr->terminal_defender_packed) % 16u)
+        return fail(MCBS_EINVAL, "%s: defender_packed and tr->terminal_defender_packed must lie on 16-byte boundaries", who);
+    if (defender_row_words != Wd && defender_row_words % 4u)
+        return fail(MCBS_EINVAL, "%s: defender_row_words %zu is neither the %u words of a packed defender row nor a multiple of 4 (16-byte stores)",
+                    who, defender_row_words, Wd);
+    // no array this launch writes may share a byte with another array it reads or writes
+    const uint64_t E = b->S.E;
+    Extents ext;
+    ext.bytes("decoded", decoded, E * 20u, true); ext.bytes("multidiscrete", multidiscrete, E * 80u, false);
+    ext.bytes("discrete", discrete, E * 8u, false); ext.bytes("defender_actions", defender_actions, E * 96u, false);
+    ext.rows("packed", packed, E, row_words, W, 4u, true); ext.rows("packed_terminal", packed_terminal, E, row_words, W, 4u, true);
+    ext.bytes("packed_fresh", packed_fresh, (uint64_t)W * 4u, false);
+    ext.rows("defender_packed", defender_packed, E, defender_row_words, Wd, 4u, true);
+    ext.rows("tr->terminal_defender_packed", tr->terminal_defender_packed, E, defender_row_words, Wd, 4u, true);
+    ext.bytes("tr->fresh_defender_packed", tr->fresh_defender_packed, (uint64_t)Wd * 4u, false);
+    add_arrays(ext, "w->", w, kWrapperArrays, E, 0u, 0u, true);
+    add_arrays(ext, "info->", info, kInfoArrays, E, 0u, 0u, true);
+    add_arrays(ext, "dw->", dw, kDefenderWrapperArrays, E, 0u, 0u, true);
+    add_arrays(ext, "tr->", tr, kTrainingPackedArrays, E, 0u, 0u, true);
+    if (const int rc = disjoint(who, ext)) return rc;
+    const mcbs_obs_buffers none{};
+    FusedArgs A;
+    if (!fused_wrapper_args(b, multidiscrete, discrete, decoded, &none, w, modifier, attacker_max_timesteps, 1, nullptr, nullptr, &A))
+        return fail(MCBS_EINVAL, "%s: the wrapper step of this batch is not one launch", who);
+    FusedPackedArgs PA{};
+    PA.packed = packed; PA.term = packed_terminal; PA.fresh = packed_fresh; PA.desc = p->desc_dev; PA.word_first = p->word_first_dev;
+    PA.row_words = row_words; PA.W = W; PA.V = V;
+    PA.off1 = p->P.off[1]; PA.off2 = p->P.off[2]; PA.off3 = p->P.off[3]; PA.off4 = p->P.off[4];
+    TrainPackedArgs D{};
+    D.actions = defender_actions; D.dw = *dw; D.dcfg = *dcfg; D.W = Wd;
+    TrainPackedStoreArgs Q{};
+    Q.G = b->def_pack; Q.packed = defender_packed; Q.term = tr->terminal_defender_packed; Q.fresh = tr->fresh_defender_packed;
+    Q.row_words = defender_row_words;
+    D.request = tr->attacker_reset_request; D.dreturn = tr->defender_return;
+    D.a_valid_out = tr->attacker_valid_out; D.a_invalid_out = tr->attacker_invalid_out;
+    D.d_return_out = tr->defender_return_out; D.d_length_out = tr->defender_length_out;
+    D.d_valid_out = tr->defender_valid_out; D.d_invalid_out = tr->defender_invalid_out; D.d_dones = tr->defender_dones;
+    b->all_fresh = false;
+    hipLaunchKernelGGL(two_agent_train_packed_kernel, dim3((b->S.E + 63u) / 64u), dim3(FUSED_THREADS), 0, (hipStream_t)stream, b->S, b->T, b->C_dev, io, A, PA, D, Q);
+    return turn_launched(b, "two-agent training turn (packed rows)", true);      // (the digests it wrote carry their observation's discovery order)
 }
 
 // ------------------------------------------------------------------ state export / import (debug, synchronous)

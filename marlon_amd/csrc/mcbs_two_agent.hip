@@ -21,9 +21,11 @@
 // Not part of the joint turn: attacker auto-reset (the caller owns the episode boundary, as run_episode does), mask fields, anything
 // outside the fused wrapper step's scope.  mcbs_api.hip refuses those; there is no multi-launch fallback.
 // The TRAINING turn (two_agent_train_kernel, at the end of this file) is the same launch with both wrappers' auto-resets and the
-// reset_request hand-shake between them: marl_algorithm.collect_rollouts' turn — mcbs_two_agent_train_step.
+// reset_request hand-shake between them: marl_algorithm.collect_rollouts' turn — mcbs_two_agent_train_step; two_agent_train_packed_kernel
+// behind it is that turn with both observations written as packed rows — mcbs_two_agent_train_step_packed.
 #pragma once
 #include "mcbs_defend.hip"
+#include "mcbs_defender_obs_packing.hip"
 #include "mcbs_wrapper_fused.hip"
 
 namespace mcbs {
@@ -148,10 +150,20 @@ __device__ __forceinline__ void train_reinit(const DevState& S, const StepCfg& C
     S.pending[e] = 0.0;
 }
 
-struct TrainHook : FusedHook {
-    const TrainArgs& D;
+// The defender's store side of a stepping lane, in LDS: park(S, T, e, lane) leaves the env's observation after the defender's action
+// there, ended()[lane] tells the workgroup which envs the defender ended.  TrainDenseSide: the int8 form's raw bits; TrainPackedSide
+// (with two_agent_train_packed_kernel, below): the packed row's finished words.
+struct TrainDenseSide {
     TwoAgentStage& dstage;
     TrainStage& tstage;
+    __device__ __forceinline__ uint8_t* ended() const { return tstage.ended; }
+    __device__ __forceinline__ void park(const DevState& S, const Topo& T, uint32_t e, uint32_t lane) const { defender_park<1>(S, T, e, lane, dstage); }
+};
+
+template <class Args, class Side>
+struct TrainHookT : FusedHook {
+    const Args& D;
+    Side side;
     uint8_t rq;                                // level-1 loads: the request byte, the defender's running return
     double dret;
 
@@ -161,7 +173,7 @@ struct TrainHook : FusedHook {
         dret = D.dreturn[ec];
     }
 
-    // the fresh defender record from the one-row arrays, by the wavefronts that do not step (threads t of nt; N <= DEF_NMAX)
+    // (dense side) the fresh defender record from the one-row arrays, by the wavefronts that do not step (threads t of nt; N <= DEF_NMAX)
     __device__ __forceinline__ void fill_fresh_defender(const DevState& S, uint32_t t, uint32_t nt) const {
         const uint32_t N = S.N;
         for (uint32_t n = t; n < N; n += nt) {
@@ -169,18 +181,18 @@ struct TrainHook : FusedHook {
 #pragma unroll
             for (uint32_t k = 0; k < 6u; ++k)
                 f |= (D.fresh_fw_in[n * 6u + k] ? 1u << k : 0u) | (D.fresh_fw_out[n * 6u + k] ? 1u << (8u + k) : 0u);
-            tstage.fresh_fw[n] = (uint16_t)f;
+            side.tstage.fresh_fw[n] = (uint16_t)f;
         }
         if (t == nt - 1u) {
             uint32_t bits = 0;
             for (uint32_t n = 0; n < N; ++n) bits |= D.fresh_infected[n] ? 1u << n : 0u;
-            tstage.fresh_inst = bits;
+            side.tstage.fresh_inst = bits;
         }
     }
 
     __device__ __forceinline__ void finish(const DevState& S, const StepCfg& C, const Topo& T, uint32_t e, bool active, float reward, bool terminated,
                                            uint32_t episode) {
-        if (!active) { if (lane < 64u) tstage.ended[lane] = 0; return; }
+        if (!active) { if (lane < 64u) side.ended()[lane] = 0; return; }
         const mcbs_wrapper_buffers& w = A.w;
         // ---- the attacker's bookkeeping: FusedHook::finish with auto_reset, truncated |= q ----
         const bool q = rq != 0;
@@ -232,8 +244,8 @@ struct TrainHook : FusedHook {
         D.dreturn[e] = done2 ? 0.0 : dret2;
         D.request[e] = (done2 && !n) ? 1 : 0;
         // the defender's observation after its action (the terminal one where done2), before the second re-initialisation
-        defender_park<1>(S, T, e, lane, dstage);
-        tstage.ended[lane] = done2 ? 1 : 0;
+        side.park(S, T, e, lane);
+        side.ended()[lane] = done2 ? 1 : 0;
         if (done2) {
             train_reinit(S, C, e, episode + (done1 ? 2u : 1u));
             D.dw.timesteps[e] = 0;
@@ -244,7 +256,7 @@ struct TrainHook : FusedHook {
         }
     }
 
-    // FusedHook::stream's five fields (its digest loop is replaced by stream_digests below)
+    // (dense side) FusedHook::stream's five fields (its digest loop is replaced by stream_digests below)
     __device__ __forceinline__ void stream_fields(const DevState& S, uint32_t e0) {
         const uint32_t n_env = S.E - e0 < 64u ? S.E - e0 : 64u;
         const uint32_t* fr = fresh_lds();
@@ -283,13 +295,14 @@ struct TrainHook : FusedHook {
         }
     }
 };
+using TrainHook = TrainHookT<TrainArgs, TrainDenseSide>;
 
 __global__ __launch_bounds__(FUSED_THREADS) void two_agent_train_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, StepIO io, FusedArgs A, TrainArgs D) {
     __shared__ uint32_t lds[64u * (FUSED_STAGE_DWORDS + FUSED_RAW_DWORDS) + FUSED_FRESH_DWORDS + 32u + 16u];
     __shared__ TwoAgentStage dstage;
     __shared__ TrainStage tstage;
     const uint32_t tid = threadIdx.x;
-    TrainHook hook{{A, lds, tid, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, {0, 0, 0, 0, 0}, false}, D, dstage, tstage, 0, 0.0};
+    TrainHook hook{{A, lds, tid, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, {0, 0, 0, 0, 0}, false}, D, {dstage, tstage}, 0, 0.0};
     if (tid < 64u) step_body<0, 0, MCBS_DEFENDER_EXTERNAL, false>(S, T, Cp, io, RollArgs{}, hook);
     else {
         hook.fill_reset_rows(tid - 64u, FUSED_THREADS - 64u);
@@ -316,5 +329,119 @@ __global__ __launch_bounds__(FUSED_THREADS) void two_agent_train_kernel(DevState
 #undef MCBS_LDS_BARRIER
     defender_stream<64u, FUSED_THREADS>(S, D.obs, tid, e0, dstage);
 }
+
+// ------------------------------------------------------------------ the TRAINING turn, both observations as PACKED rows
+// (mcbs_two_agent_train_step_packed; rules in mcbs.h)
+// two_agent_train_kernel with the two packed store sides in place of the dense ones, an instantiation of its own: the same step_body,
+// the same TrainHookT::finish, the same digest stream.
+//   attacker : FusedPackedStore (mcbs_wrapper_fused.hip) builds the W_obs words of a row from the LDS records and stores them as
+//              wrapper_fused_packed_kernel does: live row, terminal row of an env that ended (read back from the live row that stands
+//              when its action was intercepted), the fresh row from LDS.  It builds its words OVER the hand-over records, whose first two
+//              words stream_digests still needs (the discovery order of a written digest): here the digests leave first, a barrier
+//              between.  After a defender-side reset neither row nor digest of the attacker is touched.
+//   defender : the stepping lane parks its env's finished words (defender_park_words, where the dense turn parks the raw bits: after
+//              the defender's action, before the second re-initialisation); the workgroup streams them, OR-ed with the services' words,
+//              to the terminal rows of every env; the lanes whose env the defender ended then replace their words by the caller's fresh
+//              row, and the stage leaves again, to the live rows.  Fresh row and service words are fetched into LDS by the wavefronts
+//              that do not step.
+// FusedPackedArgs is read where it is used (fused_packed_args): it sits at the offset it has in wrapper_fused_packed_kernel's argument
+// segment, and TrainPackedKernArgs with the static_assert behind the kernel holds that.  The defender's store side likewise.
+struct TrainPackedArgs {                       // by value, named members only: what the stepping lane's finish reads
+    const int64_t* actions;                    // the defender's [E, 12] rows (never written)
+    mcbs_defender_wrapper_buffers dw;
+    mcbs_defender_wrapper_cfg dcfg;
+    uint32_t W, pad;                           // words of a packed defender row (W <= DEF_WMAX)
+    uint8_t* request;
+    double* dreturn;
+    int64_t* a_valid_out; int64_t* a_invalid_out;
+    double* d_return_out; int32_t* d_length_out; int64_t* d_valid_out; int64_t* d_invalid_out;
+    uint8_t* d_dones;
+};
+// The defender's store side has an argument block of its own, read WHERE IT IS USED like FusedPackedArgs and for the same reason: as
+// by-value members of TrainPackedArgs its scalar registers stay live across step_body, where scalar registers are what the kernel
+// is short of (it spills 37 of them to vector lanes as it is).
+struct TrainPackedStoreArgs {
+    DefPackGeom G;                             // the batch's own
+    uint32_t* packed;                          // [E, row_words] live rows
+    uint32_t* term;                            // [E, row_words] the rows after the defender's action
+    const uint32_t* fresh;                     // [W] the row of a freshly reset env
+    size_t row_words;
+};
+// restates two_agent_train_packed_kernel's parameter list, member for parameter (the static_assert behind the kernel)
+struct TrainPackedKernArgs { DevState S; Topo T; const StepCfg* Cp; StepIO io; FusedArgs A; FusedPackedArgs P; TrainPackedArgs D; TrainPackedStoreArgs Q; };
+__device__ __forceinline__ TrainPackedStoreArgs train_packed_store_args() {
+    uint64_t q = (uint64_t)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(TrainPackedKernArgs, Q);
+    asm volatile("" : "+s"(q));
+#define MCBS_KARG(T, member) fused_karg<T>(q + offsetof(TrainPackedStoreArgs, member))
+    TrainPackedStoreArgs Q{};                  // (G.N, G.S, G.F: not read by the store side)
+    Q.G.W = MCBS_KARG(uint32_t, G.W); Q.G.svc = MCBS_KARG(const uint32_t*, G.svc);
+    Q.G.dW.mul = MCBS_KARG(uint32_t, G.dW.mul); Q.G.dW.sh1 = MCBS_KARG(uint32_t, G.dW.sh1); Q.G.dW.sh2 = MCBS_KARG(uint32_t, G.dW.sh2);
+    Q.packed = MCBS_KARG(uint32_t*, packed); Q.term = MCBS_KARG(uint32_t*, term); Q.fresh = MCBS_KARG(const uint32_t*, fresh);
+    Q.row_words = MCBS_KARG(size_t, row_words);
+#undef MCBS_KARG
+    return Q;
+}
+struct TrainPackedStage { uint32_t words[64u * DEF_WMAX]; uint32_t svc[DEF_WMAX]; uint32_t fresh[DEF_WMAX]; uint8_t ended[64]; };
+struct TrainPackedSide {
+    TrainPackedStage& ps;
+    uint32_t W;
+    __device__ __forceinline__ uint8_t* ended() const { return ps.ended; }
+    __device__ __forceinline__ void park(const DevState& S, const Topo& T, uint32_t e, uint32_t lane) const {
+        defender_park_words<1>(S, T, e, W, ps.words + lane * W);
+    }
+};
+using TrainPackedHook = TrainHookT<TrainPackedArgs, TrainPackedSide>;
+
+__global__ __launch_bounds__(FUSED_THREADS) void two_agent_train_packed_kernel(DevState S, Topo T, const StepCfg* __restrict__ Cp, StepIO io, FusedArgs A,
+                                                                               FusedPackedArgs P, TrainPackedArgs D, TrainPackedStoreArgs Q) {
+    __shared__ uint32_t lds[64u * (FUSED_STAGE_DWORDS + FUSED_RAW_DWORDS) + FUSED_FRESH_DWORDS + 32u + 16u];
+    __shared__ TrainPackedStage ps;
+    const uint32_t tid = threadIdx.x;
+    (void)P; (void)Q;                                                                    // (read through fused_packed_args / train_packed_store_args)
+    TrainPackedHook hook{{A, lds, tid, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0.0, {0, 0, 0, 0, 0}, false}, D, {ps, D.W}, 0, 0.0};
+    if (tid < 64u) step_body<0, 0, MCBS_DEFENDER_EXTERNAL, false>(S, T, Cp, io, RollArgs{}, hook);
+    else {
+        const uint32_t t = tid - 64u;
+        // (the condition always holds here; it is wrapper_fused_packed_kernel's line: with the call unconditional the compiler left the kernel
+        // a 20-byte private segment that no instruction touched, and with it a scratch set-up per dispatch)
+        if (A.auto_reset) hook.fill_reset_digest(t);
+        FusedPackedStore{hook, fused_packed_args()}.fill(t, FUSED_THREADS - 64u);
+        const TrainPackedStoreArgs q = train_packed_store_args();
+        if (t < q.G.W) { ps.svc[t] = q.G.svc[t]; ps.fresh[t] = q.fresh[t]; }             // (W <= DEF_WMAX < 192)
+    }
+#define MCBS_LDS_BARRIER() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_s_waitcnt(0xC07F); \
+                                __builtin_amdgcn_s_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
+    MCBS_LDS_BARRIER();
+    hook.convert_nodes(S);
+    MCBS_LDS_BARRIER();
+    hook.convert_creds();
+    MCBS_LDS_BARRIER();
+    const uint32_t e0 = blockIdx.x * 64u, n_env = S.E - e0 < 64u ? S.E - e0 : 64u;
+    hook.stream_digests(S, e0);                                                  // reads the hand-over records' discovery order ...
+    MCBS_LDS_BARRIER();                                                          // ... which the attacker's words are now built over
+    FusedPackedStore{hook, fused_packed_args()}.stream(e0, n_env);
+    const TrainPackedStoreArgs q = train_packed_store_args();
+    const uint32_t W = q.G.W;
+    defender_stream_words<64u, FUSED_THREADS>(S.E, q.G, q.term, q.row_words, tid, e0, ps.words, ps.svc);
+    MCBS_LDS_BARRIER();                                                          // every thread has read the words it streams
+    if (tid < 64u && ps.ended[tid])
+        for (uint32_t w = 0; w < W; ++w) ps.words[tid * W + w] = ps.fresh[w];
+    MCBS_LDS_BARRIER();
+#undef MCBS_LDS_BARRIER
+    defender_stream_words<64u, FUSED_THREADS>(S.E, q.G, q.packed, q.row_words, tid, e0, ps.words, ps.svc);
+}
+static_assert(std::is_same<decltype(&two_agent_train_packed_kernel),
+                           void (*)(DevState, Topo, const StepCfg*, StepIO, FusedArgs, FusedPackedArgs, TrainPackedArgs, TrainPackedStoreArgs)>::value &&
+                  std::is_same<decltype(TrainPackedKernArgs::S), DevState>::value && std::is_same<decltype(TrainPackedKernArgs::T), Topo>::value &&
+                  std::is_same<decltype(TrainPackedKernArgs::Cp), const StepCfg*>::value && std::is_same<decltype(TrainPackedKernArgs::io), StepIO>::value &&
+                  std::is_same<decltype(TrainPackedKernArgs::A), FusedArgs>::value && std::is_same<decltype(TrainPackedKernArgs::P), FusedPackedArgs>::value &&
+                  std::is_same<decltype(TrainPackedKernArgs::D), TrainPackedArgs>::value &&
+                  std::is_same<decltype(TrainPackedKernArgs::Q), TrainPackedStoreArgs>::value &&
+                  offsetof(TrainPackedKernArgs, P) == offsetof(FusedPackedKernArgs, P) &&
+                  sizeof(TrainPackedKernArgs) == offsetof(TrainPackedKernArgs, Q) + sizeof(TrainPackedStoreArgs) &&
+                  std::is_trivially_copyable<TrainPackedKernArgs>::value,
+              "fused_packed_args() reads FusedPackedArgs at offsetof(FusedPackedKernArgs, P) of the kernel-argument segment and "
+              "train_packed_store_args() TrainPackedStoreArgs at offsetof(TrainPackedKernArgs, Q): TrainPackedKernArgs must restate this kernel's "
+              "parameter list, with P where it lies in wrapper_fused_packed_kernel's");
 
 } // namespace mcbs

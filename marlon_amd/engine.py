@@ -631,6 +631,30 @@ class BatchEngine:
         return self._bound("mcbs_two_agent_train_step", *_attacker_actions(discrete), decoded, self._info_struct, obs_struct, bufs, float(modifier),
                            int(max_timesteps), keep, fresh, _ACTIONS2, defender_obs_struct, defender_bufs, defender_cfg, training_block, _STREAM)
 
+    def two_agent_train_step_packed_launches(self, packing: "ObservationPackingHandle") -> int:
+        """1 when mcbs_two_agent_train_step_packed serves this batch with this packing (the training turn with both observations written
+        as packed rows by its one launch), else 0."""
+        return int(self.lib.mcbs_two_agent_train_step_packed_launches(self._h, packing.ptr))
+
+    def two_agent_train_step_packed_call(self, discrete: bool, decoded, packing: "ObservationPackingHandle", packed, packed_terminal, packed_fresh,
+                                         bufs, modifier: float, max_timesteps: int, defender_packed, defender_bufs, defender_cfg, training_block):
+        """callable(attacker_actions_ptr, defender_actions_ptr): mcbs_two_agent_train_step_packed with every argument block bound once, like
+        two_agent_train_step_call.  packed / packed_terminal / packed_fresh: the attacker's rows as wrapper_step_packed_call takes them;
+        defender_packed: device int32 [E, >= W_def] with contiguous rows, the defender's live rows — the terminal rows named by
+        training_block (an _abi.TrainingPackedBuffers whose arrays the caller keeps alive) have the same row stride."""
+        t = self.torch
+        for x, what in ((packed, "packed"), (packed_terminal, "packed_terminal")):
+            self._packed_obs_rows(x, packing, what, self.E)
+        stride = _row_stride(packed, self.E)
+        if _row_stride(packed_terminal, self.E) != stride:
+            raise ValueError("packed and packed_terminal must have the same row stride")
+        if packed_fresh.dtype != t.int32 or packed_fresh.device != self.device or not packed_fresh.is_contiguous() or packed_fresh.numel() < packing.words:
+            raise ValueError(f"packed_fresh must be a contiguous device int32 tensor of at least {packing.words} words, got {_describe(packed_fresh)}")
+        self._defender_packed_rows(defender_packed, "defender_packed", self.E)
+        return self._bound("mcbs_two_agent_train_step_packed", *_attacker_actions(discrete), decoded, self._info_struct, packing.ptr, packed,
+                           packed_terminal, packed_fresh, stride, bufs, float(modifier), int(max_timesteps), _ACTIONS2, defender_packed,
+                           _row_stride(defender_packed, self.E), defender_bufs, defender_cfg, training_block, _STREAM, keep=(packing,))
+
     def wrapper_step_launches(self, with_masks: bool) -> int:
         """Kernel launches per mcbs_attacker_wrapper_step of this batch (1: the whole wrapper step is one launch; 3 otherwise)."""
         return int(self.lib.mcbs_attacker_wrapper_step_launches(self._h, int(bool(with_masks))))

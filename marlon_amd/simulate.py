@@ -169,7 +169,12 @@ def collect_rollouts(train, attacker_policy: Callable, defender_policy: Callable
     chosen from — for a Discrete attacker also its packed mask or mask key, the STALE one after a defender-side reset, as the
     reference's policy saw it —, the action, the turn's reward, and `episode_starts` taken from the previous turn's dones (ones after
     `train.reset()`, carried from call to call in `train.last_dones`).  Both buffers are emptied first, as SB3's collect_rollouts does.
-    -> (attacker dones, defender dones) of the last turn, uint8 [E] each, for `buffer.compute_returns_and_advantage(last_values, dones)`."""
+    -> (attacker dones, defender dones) of the last turn, uint8 [E] each, for `buffer.compute_returns_and_advantage(last_values, dones)`.
+
+    Buffers made with `rollout_buffer(n_steps, pack_observations=True)` store packed rows.  With a dense pair each side's row comes from
+    a pack launch per turn (`observation_packed(out=)`), which reads back the dense rows the turn has just written.  With a pair of
+    observation_format="packed" wrappers the turn itself has written the rows and `observation_packed(out=)` is a row copy: no pack
+    kernel is launched on either side, and no dense observation exists anywhere."""
     att, dfd = train.att, train.dfd
     if attacker_buffer.n_steps != n_steps or defender_buffer.n_steps != n_steps:
         raise ValueError(f"both buffers must hold exactly n_steps = {n_steps} steps")
@@ -183,6 +188,7 @@ def collect_rollouts(train, attacker_policy: Callable, defender_policy: Callable
             if set(buf.observations) == {"packed"}:
                 env.observation_packed(out=buf.observations["packed"][p])
             else:
+                fields = fields()
                 for k, dst in buf.observations.items():
                     dst[p].copy_(fields[k].reshape(dst[p].shape))
         if buf.mask_bits is not None:
@@ -197,8 +203,9 @@ def collect_rollouts(train, attacker_policy: Callable, defender_policy: Callable
         a1, v1, lp1 = split(attacker_policy(att))
         a2, v2, lp2 = split(defender_policy(dfd))
         # what each action was chosen from, before the turn overwrites the wrappers' persistent tensors
-        store_inputs(attacker_buffer, att.observation_fields, att)
-        store_inputs(defender_buffer, dfd.observation, dfd)
+        # (the dense fields are asked for only where a buffer stores them: a packed-format attacker keeps none)
+        store_inputs(attacker_buffer, lambda: att.observation_fields, att)
+        store_inputs(defender_buffer, lambda: dfd.observation, dfd)
         (_, r1, term1, trunc1, _), (_, r2, term2, trunc2, _) = train.step(a1, a2)
         attacker_buffer.add(None, att.torch.as_tensor(a1, device=att.engine.device), r1, starts_a, v1, lp1)
         defender_buffer.add(None, att.torch.as_tensor(a2, device=att.engine.device), r2, starts_d, v2, lp2)

@@ -88,9 +88,11 @@ def _observation_storage(venv, store_observations: bool, pack_observations: Opti
     return fields()
 
 
-def _two_agent_refusal(att, dfd, turn: str, auto_reset: bool, auto_reset_why: str, launches: str) -> Optional[str]:
+def _two_agent_refusal(att, dfd, turn: str, auto_reset: bool, auto_reset_why: str, launches: str, packed_launches: Optional[str] = None) -> Optional[str]:
     """Why the `turn` ("joint" / "training") turn does not take this attacker wrapper, or this pair: the first of nine conditions that
-    fails, else None.  launches: the engine's query for the turn's entry point."""
+    fails, else None.  launches: the engine's query for the turn's entry point.  packed_launches: the query for the entry point that
+    writes BOTH observations as packed rows, where the turn has one — a packed attacker is then taken together with a packed defender
+    (with dfd None: asked about), and only the mixed pairs are refused."""
     from ._abi import DEFENDER_EXTERNAL
     if not isinstance(att, AttackerVecEnv):
         return "the attacker side must be an AttackerVecEnv"
@@ -102,13 +104,20 @@ def _two_agent_refusal(att, dfd, turn: str, auto_reset: bool, auto_reset_why: st
         return f"the AttackerVecEnv must be created with materialize_masks=False (the {turn} turn writes no mask field)"
     if att.use_graph:
         return "the AttackerVecEnv must be created with use_graph=False"
-    if att.observation_format != "fields":
+    # a packed attacker is one half of a packed pair where the turn has an entry point that writes packed rows and that entry point
+    # serves this batch (an engine without the query serves none); everywhere else the fields form is what to ask for
+    packed_query = getattr(att.engine, packed_launches, None) if packed_launches is not None and att.observation_format == "packed" else None
+    packed_pair = packed_query is not None and packed_query(att._packing_handle()) == 1
+    if att.observation_format != "fields" and not packed_pair:
         return f"the AttackerVecEnv must be created with observation_format='fields' (the {turn} turn writes the int32 fields, not packed rows)"
-    if getattr(att.engine, launches)() != 1:
+    if not packed_pair and getattr(att.engine, launches)() != 1:
         return f"the library does not serve this batch with a {turn} turn (mcbs_{launches}: small packed topologies only)"
     if dfd is not None and not (isinstance(dfd, DefenderVecEnv) and dfd.attacker is att and not dfd.use_graph):
         return "the defender side must be the DefenderVecEnv created on this AttackerVecEnv (use_graph=False)"
-    if dfd is not None and dfd.observation_format != "dense":
+    if dfd is not None and packed_pair and dfd.observation_format != "packed":
+        return ("both wrappers of a pair must have the same observation_format: this AttackerVecEnv writes packed rows, so the DefenderVecEnv "
+                f"must be created with observation_format='packed' too (the {turn} turn has no mixed form)")
+    if dfd is not None and not packed_pair and dfd.observation_format != "dense":
         return "the DefenderVecEnv must be created with observation_format='dense' (these turns write the int8 fields, not packed rows)"
     return None
 
@@ -726,7 +735,8 @@ class DefenderVecEnv(_MultiDiscreteHead):
     [n_envs, W_def]: one bit per MultiBinary element in features()' column order (features.DefenderObservationPacking; ToyCtf: 20 B
     instead of 143 B per row), written by the step itself (`mcbs_defender_wrapper_step_packed`: the turn launch writes the rows on
     topologies of up to 32 nodes, a second launch elsewhere).  features(), rollout_buffer() and encode_features_packed() read the
-    rows; unpack_observation() rebuilds the int8 fields.  The two-agent turns write the dense form only and refuse such a wrapper."""
+    rows; unpack_observation() rebuilds the int8 fields.  TwoAgentTrainVecEnv takes such a wrapper together with an AttackerVecEnv of
+    observation_format="packed"; the joint turn (TwoAgentVecEnv) writes the dense form only and refuses it."""
 
     def __init__(self, attacker: AttackerVecEnv, max_timesteps: int = 100, invalid_action_reward: float = 0.0,
                  reset_on_constraint_broken: bool = True, loss_reward: float = -5000.0, sla_worsening_penalty_scale: float = 200.0,
@@ -1037,7 +1047,12 @@ class TwoAgentTrainVecEnv:
     the `DefenderVecEnv` on it; anything else is a ValueError naming the reason (`supported(att)` asks first).  The turn writes into the
     two wrappers' own persistent state, so `att.mask_logits`, `att.features()`, `dfd.features()`, `sample_masked*` ... work as after
     separate steps.  But separate `att.step` / `dfd.step` calls must NOT be mixed with this class's `step`: they know nothing of the
-    request byte, of the defender's running return, or of the defender-side reset."""
+    request byte, of the defender's running return, or of the defender-side reset.
+
+    A pair in which BOTH wrappers were created with observation_format="packed" is taken as well: the same launch then writes both
+    observations as packed rows (mcbs_two_agent_train_step_packed) into `att.packed_observation` / `att.terminal_packed_observation` and
+    `dfd.packed_observation`, no int32 or int8 field exists, and `terminal_observation` is `{"packed": rows}` like the attacker's.  A
+    mixed pair (one side packed, the other not) is refused."""
 
     def __init__(self, att: AttackerVecEnv, dfd: "DefenderVecEnv"):
         why = self._refusal(att, dfd)
@@ -1048,7 +1063,8 @@ class TwoAgentTrainVecEnv:
         t, E, dev = self.torch, self.num_envs, self.engine.device
         self._request = t.zeros(E, dtype=t.uint8, device=dev)
         self.defender_returns = t.zeros(E, dtype=t.float64, device=dev)
-        self._terminal = {k: t.zeros_like(v) for k, v in dfd._obs.items()}
+        self._packed_mode = att._packed_mode                # (both sides: _refusal has refused a mixed pair)
+        self._terminal = {k: t.zeros_like(v) for k, v in dfd._obs.items()}      # (packed mode: the one key "packed")
         self._fresh_rows = None
         self._ring, self._slot = None, 0
         self._calls = {}
@@ -1057,11 +1073,13 @@ class TwoAgentTrainVecEnv:
     @staticmethod
     def _refusal(att, dfd=None) -> Optional[str]:
         return _two_agent_refusal(att, dfd, "training", auto_reset=True, auto_reset_why="both agents' DummyVecEnv resets are part of the training turn",
-                                  launches="two_agent_train_step_launches")
+                                  launches="two_agent_train_step_launches", packed_launches="two_agent_train_step_packed_launches")
 
     @staticmethod
     def supported(att) -> bool:
-        """Whether TwoAgentTrainVecEnv(att, DefenderVecEnv(att)) would be accepted."""
+        """Whether TwoAgentTrainVecEnv(att, dfd) would be accepted with the DefenderVecEnv on att of the same observation format:
+        DefenderVecEnv(att) for an attacker with observation_format="fields", DefenderVecEnv(att, observation_format="packed") for one with
+        observation_format="packed"."""
         return TwoAgentTrainVecEnv._refusal(att) is None
 
     @property
@@ -1074,7 +1092,7 @@ class TwoAgentTrainVecEnv:
     def terminal_observation(self) -> Dict[str, object]:
         """The defender's observation after its action of the last turn: its episode's last observation for the envs whose defender
         `dones` was set (SB3's infos[e]["terminal_observation"]); rows of other envs mean nothing.  The attacker's is
-        `att.terminal_observation`."""
+        `att.terminal_observation`.  A packed pair: `{"packed": int32 [E, W_def]}`."""
         return self._terminal
 
     def reset(self):
@@ -1087,18 +1105,23 @@ class TwoAgentTrainVecEnv:
         # (attacker, defender) dones of the last turn: the next turn's episode_starts (simulate.collect_rollouts carries them here)
         self.last_dones = (t.ones(self.num_envs, dtype=t.uint8, device=self.engine.device), t.ones(self.num_envs, dtype=t.uint8, device=self.engine.device))
         if self._fresh_rows is None:
-            self._fresh_rows = {k: v[0:1].clone() for k, v in dobs.items()}     # every env resets to the same state
+            self._fresh_rows = {k: v[0:1].clone() for k, v in dobs.items()}     # every env resets to the same state (packed mode:
+                                                                                 # dfd.packed_observation[0:1])
         return obs, dobs
 
     def _output_ring(self) -> None:
-        from ._abi import training_buffers
+        from ._abi import training_buffers, training_packed_buffers
         fixed = dict(attacker_reset_request=self._request.data_ptr(), defender_return=self.defender_returns.data_ptr())
-        fixed.update({"terminal_" + k: v.data_ptr() for k, v in self._terminal.items()})       # (the four keys of mcbs_defender_obs)
-        fixed.update({"fresh_" + k: v.data_ptr() for k, v in self._fresh_rows.items()})
+        if self._packed_mode:
+            fixed.update(terminal_defender_packed=self._terminal["packed"].data_ptr(), fresh_defender_packed=self._fresh_rows["packed"].data_ptr())
+        else:
+            fixed.update({"terminal_" + k: v.data_ptr() for k, v in self._terminal.items()})       # (the four keys of mcbs_defender_obs)
+            fixed.update({"fresh_" + k: v.data_ptr() for k, v in self._fresh_rows.items()})
+        block = training_packed_buffers if self._packed_mode else training_buffers
         self._ring = []
         for _ in range(2):
             o = _output_set(self, _TRAINING_OUTPUTS)
-            self._ring.append((o, training_buffers(**fixed, **{k: v.data_ptr() for k, v in o.items()})))
+            self._ring.append((o, block(**fixed, **{k: v.data_ptr() for k, v in o.items()})))
 
     def step(self, attacker_actions, defender_actions):
         """-> ((obs, rewards, terminated, truncated, info), (dobs, dreward, dterminated, dtruncated, dinfo)): what the two agents'
@@ -1119,7 +1142,11 @@ class TwoAgentTrainVecEnv:
         to, tb = self._ring[self._slot]
         key = (id(wb), id(dwb), id(tb), att.invalid_action_reward_modifier, att.max_timesteps)
         call = self._calls.get(key)
-        if call is None:
+        if call is None and self._packed_mode:
+            call = self._calls[key] = self.engine.two_agent_train_step_packed_call(
+                att.discrete, att._rows, att._packing_handle(), att.packed_observation, att.terminal_packed_observation, att._packed_fresh, wb,
+                att.invalid_action_reward_modifier, att.max_timesteps, dfd.packed_observation, dwb, dfd._wc, tb)
+        elif call is None:
             obs_block, keep, fresh = att._blocks()
             call = self._calls[key] = self.engine.two_agent_train_step_call(att.discrete, att._rows, obs_block, wb, att.invalid_action_reward_modifier,
                                                                             att.max_timesteps, keep, fresh, dfd._obs_block, dwb, dfd._wc, tb)
